@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X: decoded shots/sec, [[144,12,12]] code capacity, p = 0.005, 50 BP iterations
-(BASELINE.json), plus the circuit-level trial pipeline (BASELINE config 5) in the same run.
+(BASELINE.json); with --full also the circuit-level trial pipeline (BASELINE config 5) in the same run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run times the headline leg alone (`value` below) and prints its JSON line; `--full` adds every other leg, the CPU
+baselines and the checks against the oracle (`--p-sweep`, `--circuit`, `--legs`, `--no-cpu-baseline` shape what it adds).
+`--dump-outputs DIR` writes what the headline leg's plan returned after its last timed step -- the int64[16] tally of the
+timed steps, all ranks summed -- as DIR/tally.npy (float64); with the same arguments the shots are the same in every run.
 
 One process per GPU.  `--gpus N` with WORLD_SIZE unset starts the N ranks itself (children, before anything touches the
 GPU); under `torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE.  Shots are sharded by global shot index
@@ -56,21 +61,41 @@ def parse_args(argv=None):
     ap.add_argument("--min-launch", type=int, default=0, help="launch granule of the code-capacity plan (0 = --batch taken literally; qldpc_cc_plan_create)")
     ap.add_argument("--code", default="bb144", help="bb72 = BASELINE config 2, bb144 = config 3 (headline), bb288 = config 4")
     ap.add_argument("--p", type=float, default=0.005)
-    ap.add_argument("--p-sweep", default="", help="comma-separated error rates (BASELINE config 4: --code bb288 --p-sweep 0.004,0.005,0.006): the headline leg once "
-                                                  "per point, one tally and one all-reduce per point, every point in the JSON line; `value` is the rate over all points")
+    ap.add_argument("--p-sweep", default="", help="(--full) comma-separated error rates (BASELINE config 4: --code bb288 --p-sweep 0.004,0.005,0.006): the headline leg "
+                                                  "once per point, one tally and one all-reduce per point, every point in the JSON line; `value` is the rate over all points")
     ap.add_argument("--max-iter", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baselines and the oracle checks")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work per baseline (each of the two legs)")
     ap.add_argument("--kernel", choices=["auto", "resident", "stream"], default="auto")
     ap.add_argument("--legs", choices=["both", "fixed"], default="both",
-                    help="'fixed' runs only the headline fixed-work leg (every launch in a rocprofv3 --stats summary is then the timed kernel)")
-    ap.add_argument("--circuit", default="circ144", help="circuit-level leg: decoding matrices tag (circ72 / circ144 / circ288) or 'none'")
+                    help="(--full) 'fixed' runs only the headline fixed-work leg (every launch in a rocprofv3 --stats summary is then the timed kernel)")
+    ap.add_argument("--circuit", default=None, help="(--full) circuit-level leg: decoding matrices tag (circ72 / circ144 / circ288, default circ144) or 'none'")
     ap.add_argument("--circuit-batch", type=int, default=16384, help="trials per step per GPU")
     ap.add_argument("--circuit-steps", type=int, default=4)
     ap.add_argument("--circuit-warmup", type=int, default=1)
     ap.add_argument("--circuit-flags", type=lambda x: int(x, 0), default=0)
-    ap.add_argument("--no-code-capacity", action="store_true", help="run only the circuit-level leg (profiling)")
-    return ap.parse_args(argv)
+    ap.add_argument("--no-code-capacity", action="store_true", help="(--full) run only the circuit-level leg (profiling)")
+    ap.add_argument("--full", action="store_true", help="every leg, CPU baseline and oracle check besides the headline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the headline leg's tally of the timed steps to DIR/tally.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full:
+        args.circuit = "circ144" if args.circuit is None else args.circuit
+    else:
+        extra = [f for f, on in (("--p-sweep", bool(args.p_sweep)), ("--no-code-capacity", args.no_code_capacity),
+                                 ("--circuit " + str(args.circuit), args.circuit not in (None, "none"))) if on]
+        if extra:
+            ap.error(f"{', '.join(extra)} measures beyond the headline leg: add --full")
+        args.legs, args.circuit, args.no_cpu_baseline = "fixed", "none", True      # the plain run: the headline leg alone
+    return args
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array the timed path returned."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64))
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
@@ -341,6 +366,8 @@ def worker(args):
                                  "kernel_ms_per_launch": round(ms_p / max(nl_p, 1), 4), "logical_error_rate": round(float(tot_p[T["total_err"]]) / max(1, int(tot_p[T["trials"]])), 8),
                                  "tally": {k: int(tot_p[v]) for k, v in T.items() if k.endswith("_z") or k in ("trials", "total_err")}, **leg_extra[f"p={ps:g}"]})
         dt_fixed, tally_fixed, local_fixed, ms_fixed, nl_fixed, clk_fixed, _ = run_leg(_lib.FLAG_FIXED_ITERS)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tally": tally_fixed})       # the plan's running tally after the last timed step
         if args.legs == "fixed":
             dt_ref, tally_ref, ms_ref, nl_ref, clk_ref, ms_first = dt_fixed, tally_fixed, ms_fixed, nl_fixed, clk_fixed, 0.0
         else:
@@ -556,6 +583,8 @@ def circuit_leg(args, _lib, rank, world, local_rank, stream, barrier, reduce_tal
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     phases, nb = plan.phase_times()        # both sectors run on the caller's stream: the hipEvent spans are exclusive and sum to the step
+    if rank == 0 and args.dump_outputs and args.no_code_capacity:          # this leg is the headline
+        dump_outputs(args.dump_outputs, {"tally": total})
     solo_tally = tally
     clk_bp, clk_osd = plan.clock(stream)
     trials = world * K * B

@@ -210,6 +210,21 @@ def test_bench_launcher_fails_loudly():
     assert r.returncode != 0 and r.stderr.count("no HIP device") >= 1 and "{" not in r.stdout
 
 
+def test_bench_plain_and_full_arguments():
+    """A plain bench run is the headline leg alone; every other leg needs --full, and asking for one without it is an error, not a silent no-op."""
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "3", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.dump_outputs, a.full) == (7, 3, "d", False)
+    assert (a.legs, a.circuit, a.no_cpu_baseline) == ("fixed", "none", True)
+    f = bench.parse_args(["--full"])
+    assert (f.legs, f.circuit, f.no_cpu_baseline) == ("both", "circ144", False)
+    assert bench.parse_args(["--full", "--circuit", "circ72", "--p-sweep", "0.004"]).circuit == "circ72"
+    assert bench.parse_args(["--circuit", "none"]).circuit == "none"
+    for bad in (["--p-sweep", "0.004"], ["--circuit", "circ72"], ["--no-code-capacity"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_collective_device_rule():
     """RCCL reduces device tensors, gloo host tensors: one rule for the tally all-reduce and the verdict gather."""
     import qldpc_amd  # noqa: F401

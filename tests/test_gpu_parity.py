@@ -1484,7 +1484,7 @@ def test_bench_starts_its_own_ranks(L, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["QLDPC_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "65536", "--p-sweep", "0.004,0.006",
-                        "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", "2", "--no-cpu-baseline"],
+                        "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", "2", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1498,13 +1498,37 @@ def test_bench_starts_its_own_ranks(L, tmp_path):
     assert len(out["per_rank"]["per_rank_ms_per_step"]) == 2 and len(out["per_rank"]["tally_allreduce_ms"]) == 2
     # the same shots on one rank give the same tally (the Philox streams are keyed by the global shot index)
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "65536",
-                         "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", "4", "--no-cpu-baseline"],
+                         "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", "4", "--no-cpu-baseline", "--full"],
                         env=env, capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-2000:]
     one = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][0])
     assert one["tally"] == out["tally"] and one["circuit_level"]["tally"] == out["circuit_level"]["tally"]
     assert set(one["circuit_level"]["phases_ms_per_step"]) == set(L.CIRCUIT_PHASES)
     assert one["roofline"]["clock_mhz"] is None or 500 < one["roofline"]["clock_mhz"] < 3000
+
+
+def test_bench_plain_run_times_the_headline_leg_and_dumps_its_tally(L, tmp_path):
+    """`python bench.py` without --full: the headline leg alone (no other leg, baseline or check in the line), exactly --steps timed steps, and
+    --dump-outputs DIR writes that leg's tally as DIR/tally.npy -- the same numbers in the line and in a second run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    tallies = []
+    for run in range(2):
+        d = tmp_path / f"dump{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "65536",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["tally"]["trials"] == 3 * 65536
+        assert not any(k in out for k in ("reference_semantics", "circuit_level", "cpu_baseline", "llr_check", "p_sweep"))
+        t = np.load(d / "tally.npy")
+        assert t.dtype == np.float64 and t.shape == (L.TALLY_SLOTS,)
+        assert all(t[v] == out["tally"][k] for k, v in L.TALLY.items() if k in out["tally"])
+        tallies.append(t)
+    assert np.array_equal(tallies[0], tallies[1])
 
 
 def test_native_rccl_tally_allreduce(L):
@@ -1627,7 +1651,8 @@ def test_two_gpus_bench_over_rccl(L):
     outs = []
     for gpus, steps in ((2, 2), (1, 4)):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", "1", "--batch", "65536", "--code", "bb288",
-                            "--p-sweep", "0.004,0.006", "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", str(steps), "--no-cpu-baseline"],
+                            "--p-sweep", "0.004,0.006", "--circuit", "circ72", "--circuit-batch", "1024", "--circuit-steps", str(steps), "--no-cpu-baseline",
+                            "--full"],
                            env=env, capture_output=True, text=True, timeout=1200)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
