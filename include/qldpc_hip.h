@@ -24,6 +24,10 @@
  *     QLDPC_ERR_NO_DEVICE.
  *   - matrices over GF(2) are CSR with sorted column indices (int32 indptr[m+1], indices[nnz]).
  *   - batched arrays are shot-major: syndromes[B][m], errors[B][n], llr[B][n].
+ *
+ * Changelog (qldpc_version)
+ *   100  the C ABI of the BP+OSD decoder and the Monte-Carlo plans
+ *   101  Relay-BP: qldpc_relay_decode_batch[_dev], qldpc_circuit_plan_use_relay; tally slots QLDPC_TALLY_LEGS_Z / _X
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -90,6 +94,8 @@ extern "C" {
 #define QLDPC_TALLY_ZERO_SYND_X 11
 #define QLDPC_TALLY_UNSAT_Z 12    /* decoder output (after OSD if enabled) does not reproduce the syndrome */
 #define QLDPC_TALLY_UNSAT_X 13
+#define QLDPC_TALLY_LEGS_Z 14     /* Relay-BP circuit plans: sum over trials of the legs run (0 on every other path) */
+#define QLDPC_TALLY_LEGS_X 15
 
 typedef struct qldpc_graph qldpc_graph; /* Tanner graph: host CSR + CSC (ascending check order) + device copies */
 
@@ -151,6 +157,28 @@ int qldpc_bp_check_pass(const qldpc_graph *g, int64_t B, const double *Q, const 
 /* a5 driver: performBeliefPropagationFast (src/decoding/dense.py:75-96), batched */
 int qldpc_bp_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior, int max_iter,
                           int8_t *out_err, double *out_llr, uint8_t *out_conv, int32_t *out_iter);
+
+/* Relay-BP (Mueller et al. 2025): normalised min-sum (constant alpha, messages clipped to +-clip_llr) with a per-variable memory
+ * term, run in legs.  The variable pass of a leg writes V_j = sum_R + ((1 - gamma_j) * prior_j + gamma_j * V_j)
+ * (a V_j that is not finite, as the +-inf messages of degree-1 checks make it, enters that term as 0.0).  Leg 0 runs t0
+ * iterations from V = prior with gamma_j = gamma0; leg r = 1..max_legs runs tr iterations from the previous leg's final marginals
+ * with gamma_j = gamma_min + (gamma_max - gamma_min) * (w / 2^16), w = the top 16 bits of word (j & 3) of
+ * Philox4x32-10(ctr = {lo32(shot), hi32(shot), j >> 2, 0x52000000 | tag << 20 | r}, key = {lo32(seed), hi32(seed)}), shot = shot_begin + b.
+ * Every converged leg is a solution of weight sum_{j: e_j = 1} floor(prior_j * 2^20 + 0.5) (int64; the product clamped to +-2^40);
+ * the lightest one is kept (the earlier leg wins ties); the decoder stops after stop_after solutions or after leg max_legs.
+ * Outputs per shot: err int8[n] (the best solution, else the last leg's hard decision), conv (>= 1 solution), legs (1..1 + max_legs),
+ * iters (sum over legs of the iteration counts: it if the leg converged at it, else its length), solutions (converged legs).
+ * Arguments: prior finite; alpha, clip_llr finite > 0; gammas finite with gamma_min <= gamma_max; t0, tr >= 1; 0 <= max_legs < 2^20;
+ * stop_after >= 1; tag in 0..15; B = 0 is a no-op.  QLDPC_ERR_UNSUPPORTED for graphs with a row degree above 56 or whose check
+ * state does not fit in LDS.  Results depend only on (seed, shot, tag, inputs): not on batch splits or the grid. */
+int qldpc_relay_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior, double alpha, double clip_llr,
+                             double gamma0, double gamma_min, double gamma_max, int t0, int tr, int max_legs, int stop_after, uint64_t seed,
+                             int64_t shot_begin, int tag, int8_t *err, uint8_t *conv, int32_t *legs, int32_t *iters, int32_t *solutions);
+/* same on device pointers; only enqueues on `stream`.  Precondition: every d_prior entry is finite (not checked: it lives on the device). */
+int qldpc_relay_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_prior, double alpha,
+                                 double clip_llr, double gamma0, double gamma_min, double gamma_max, int t0, int tr, int max_legs,
+                                 int stop_after, uint64_t seed, int64_t shot_begin, int tag, int8_t *d_err, uint8_t *d_conv, int32_t *d_legs,
+                                 int32_t *d_iters, int32_t *d_solutions, void *stream);
 
 /* a6: GF(2) syndrome SpMV  s = H e (kernels.py:222-231, 352-359; H_csr.dot(e)%2 in alpha.py:128): vectors[B][n] -> out[B][m] */
 int qldpc_gf2_spmv_batch(const qldpc_graph *g, int64_t B, const int8_t *vectors, int8_t *out);
@@ -314,6 +342,12 @@ int qldpc_circuit_plan_clock(qldpc_circuit_plan *plan, void *stream, double *mhz
 int qldpc_circuit_plan_sample(qldpc_circuit_plan *plan, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z,
                               int8_t *true_z, int8_t *sparse_x, int8_t *true_x);
 void qldpc_circuit_plan_destroy(qldpc_circuit_plan *plan);
+/* Switches the plan's decoder to Relay-BP (one-way): both sectors are decoded by qldpc_relay_decode_batch's kernel with the plan's
+ * priors, the seed of the run call and the global trial index as `shot` (tag 0 for sector Z, 1 for sector X); no OSD stage follows.
+ * The tally keeps its meaning: bp_conv = Relay-BP converged, iters = sum of Relay-BP iterations, OSD slots 0, legs in
+ * QLDPC_TALLY_LEGS_Z / _X.  Arguments as in qldpc_relay_decode_batch. */
+int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *plan, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
+                                 int max_legs, int stop_after);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

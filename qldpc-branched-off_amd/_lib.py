@@ -27,7 +27,7 @@ ALPHA_CONST, ALPHA_DYNAMIC, ALPHA_SEQ = 0, 1, 2
 FLAG_FIXED_ITERS, FLAG_KERNEL_STREAM, FLAG_KERNEL_RESIDENT, FLAG_KERNEL_GENERIC, FLAG_MC_UNFUSED = 0x1, 0x10, 0x20, 0x40, 0x80
 TALLY_SLOTS = 16
 TALLY = {"trials": 0, "z_err": 1, "x_err": 2, "total_err": 3, "bp_conv_z": 4, "bp_conv_x": 5, "osd_z": 6, "osd_x": 7,
-         "iters_z": 8, "iters_x": 9, "zero_synd_z": 10, "zero_synd_x": 11, "unsat_z": 12, "unsat_x": 13}
+         "iters_z": 8, "iters_x": 9, "zero_synd_z": 10, "zero_synd_x": 11, "unsat_z": 12, "unsat_x": 13, "legs_z": 14, "legs_x": 15}
 
 FLAG_WG_EDGE_LANES, FLAG_OSD_LDS, FLAG_WG_IDXLOAD = 0x2, 0x20000, 0x40000
 FLAG_OSD_REFORDER, FLAG_OSD_QUEUE, FLAG_WG_TABLES = 0x80000, 0x100000, 0x200000
@@ -353,6 +353,67 @@ def gf2_spmv_batch(graph, vectors):
     return out
 
 
+# Relay-BP defaults: the published gross-code setting (a starting point; qldpc_relay_decode_batch in include/qldpc_hip.h)
+RELAY_DEFAULTS = {"alpha": 1.0, "clip_llr": 20.0, "gamma0": 0.125, "gamma_min": -0.24, "gamma_max": 0.66, "t0": 80, "tr": 60, "max_legs": 300,
+                  "stop_after": 5}
+
+
+def relay_params(params, with_clip=True):
+    """RELAY_DEFAULTS updated by `params` and validated: ValueError for an unknown name or a value the C ABI rejects."""
+    unknown = set(params) - set(RELAY_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown Relay-BP parameter(s): {sorted(unknown)}")
+    p = dict(RELAY_DEFAULTS, **params)
+    for k in ("alpha", "clip_llr", "gamma0", "gamma_min", "gamma_max"):
+        p[k] = float(p[k])
+        if not np.isfinite(p[k]):
+            raise ValueError(f"{k} must be finite")
+    for k in ("t0", "tr", "max_legs", "stop_after"):
+        if int(p[k]) != p[k]:
+            raise ValueError(f"{k} must be an integer")
+        p[k] = int(p[k])
+    if p["alpha"] <= 0 or p["clip_llr"] <= 0:
+        raise ValueError("alpha and clip_llr must be > 0")
+    if p["gamma_min"] > p["gamma_max"]:
+        raise ValueError(f"gamma_min ({p['gamma_min']}) > gamma_max ({p['gamma_max']})")
+    if p["t0"] < 1 or p["tr"] < 1:
+        raise ValueError("t0 and tr must be >= 1")
+    if not 0 <= p["max_legs"] < 2 ** 20:
+        raise ValueError("max_legs must be in [0, 2**20)")
+    if p["stop_after"] < 1:
+        raise ValueError("stop_after must be >= 1")
+    if not with_clip:
+        p.pop("clip_llr")
+    return p
+
+
+def relay_check_inputs(prior, tag):
+    """ValueError unless every prior is finite and 0 <= tag <= 15."""
+    if not np.all(np.isfinite(prior)):
+        raise ValueError("Relay-BP needs a finite prior")
+    if int(tag) != tag or not 0 <= int(tag) <= 15:
+        raise ValueError("tag must be an integer in 0..15")
+
+
+def relay_decode_batch(graph, syndromes, prior, seed, shot_begin=0, tag=0, **params):
+    """qldpc_relay_decode_batch on host arrays -> (err int8[B, n], conv uint8[B], legs int32[B], iters int32[B], solutions int32[B])."""
+    p = relay_params(params)
+    prior = f64(prior)
+    if prior.size != graph.n:
+        raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+    relay_check_inputs(prior, tag)
+    syndromes = i8(syndromes).reshape(-1, graph.m)
+    B = syndromes.shape[0]
+    err = np.zeros((B, graph.n), np.int8)
+    conv = np.zeros(B, np.uint8)
+    legs, iters, sols = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    check(lib().qldpc_relay_decode_batch(graph.handle, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(prior, C.c_double), p["alpha"], p["clip_llr"],
+                                         p["gamma0"], p["gamma_min"], p["gamma_max"], p["t0"], p["tr"], p["max_legs"], p["stop_after"],
+                                         C.c_uint64(int(seed)), C.c_int64(int(shot_begin)), int(tag), ptr(err, C.c_int8), ptr(conv, C.c_uint8),
+                                         ptr(legs, C.c_int32), ptr(iters, C.c_int32), ptr(sols, C.c_int32)))
+    return err, conv, legs, iters, sols
+
+
 def osd_timers(reset=True):
     """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/osd_common.h) -> uint64[32]."""
     out = np.zeros(32, np.uint64)
@@ -586,6 +647,15 @@ class CircuitPlan:
                                               C.c_double(az), C.c_double(ax), ptr(sz, C.c_double), C.c_int(sz.size), ptr(sx, C.c_double),
                                               C.c_int(sx.size), C.c_double(damping), C.c_double(clip_llr), C.c_int(int(use_osd)), C.c_int(flags),
                                               C.c_int64(batch), C.byref(self._h)))
+
+    def use_relay(self, **params):
+        """Decode both sectors with Relay-BP from now on (one-way; qldpc_circuit_plan_use_relay).  The plan's clip_llr applies."""
+        if "clip_llr" in params:
+            raise ValueError("a circuit plan's clip_llr is set when the plan is created")
+        p = relay_params(params, with_clip=False)
+        check(lib().qldpc_circuit_plan_use_relay(self._h, p["alpha"], p["gamma0"], p["gamma_min"], p["gamma_max"], p["t0"], p["tr"], p["max_legs"],
+                                                 p["stop_after"]))
+        self.relay = p
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))

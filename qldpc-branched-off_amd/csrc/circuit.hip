@@ -14,6 +14,7 @@
 #include "minsum_common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -259,10 +260,14 @@ struct qldpc_circuit_plan {
     std::vector<hipEvent_t> pool;
     double phase_ms[QLDPC_CIRCUIT_PHASES] = {0, 0, 0, 0, 0, 0};
     int64_t batches = 0;
+    // qldpc_circuit_plan_use_relay: both sectors go through the Relay-BP kernel instead of BP + OSD-0 (relay_bp.hip)
+    bool relay = false;
+    RelayParams rp{};
+    DevBuf d_legs_z, d_legs_x;
     std::vector<DevBuf *> all() {
         return {&d_loc_type, &d_zptr, &d_zidx, &d_zlog, &d_xptr, &d_xidx, &d_xlog, &d_alpha_z, &d_alpha_x, &d_prior_z, &d_prior_x, &d_lm_z, &d_lm_x,
                 &d_syn_z, &d_syn_x, &d_true_z, &d_true_x, &d_det_z, &d_det_x, &d_llr_z, &d_llr_x, &d_conv_z, &d_conv_x, &d_iter_z, &d_iter_x,
-                &d_list_z, &d_list_x, &d_count, &d_tally, &d_outcome, &d_clk};
+                &d_list_z, &d_list_x, &d_count, &d_tally, &d_outcome, &d_clk, &d_legs_z, &d_legs_x};
     }
 };
 
@@ -508,11 +513,22 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
 }
 
 static int decode_sector(qldpc_circuit_plan *P, const qldpc_graph *g, int64_t B, DevBuf &syn, DevBuf &prior, DevBuf &alpha, DevBuf &det, DevBuf &llr,
-                         DevBuf &conv, DevBuf &iter, DevBuf &list, int sector, hipStream_t s) {
+                         DevBuf &conv, DevBuf &iter, DevBuf &list, int sector, hipStream_t s, uint64_t seed, int64_t trial_begin) {
     const std::vector<double> &hp = sector ? P->h_prior_x : P->h_prior_z;
     int rc;
     int32_t *count = P->d_count.as<int32_t>() + 4 * sector;
     const int ph_bp = sector ? QLDPC_PHASE_BP_X : QLDPC_PHASE_BP_Z, ph_osd = sector ? QLDPC_PHASE_OSD_X : QLDPC_PHASE_OSD_Z;
+    if (P->relay) {                    // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
+        if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            // iter_bias -1: the judge adds one per trial, so the ITERS slots sum the Relay-BP iterations
+            rc = relay_decode_launch(g, B, syn.as<int8_t>(), prior.as<double>(), P->rp, seed, trial_begin, sector, -1, det.as<int8_t>(), conv.as<uint8_t>(),
+                                     (sector ? P->d_legs_x : P->d_legs_z).as<int32_t>(), iter.as<int32_t>(), nullptr, s);
+        }
+        if (rc != QLDPC_OK) return rc;
+        return phase_mark(P, ph_bp, s, false);
+    }
     unsigned long long *clk = (P->flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr;
     if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
     {
@@ -556,8 +572,10 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
             QLDPC_HIP_TRY(hipEventRecord(P->ev_sampled, s));
             QLDPC_HIP_TRY(hipStreamWaitEvent(sx, P->ev_sampled, 0));
         }
-        if ((rc = decode_sector(P, P->gz, B, P->d_syn_z, P->d_prior_z, P->d_alpha_z, P->d_det_z, P->d_llr_z, P->d_conv_z, P->d_iter_z, P->d_list_z, 0, s)) != QLDPC_OK) return rc;
-        if ((rc = decode_sector(P, P->gx, B, P->d_syn_x, P->d_prior_x, P->d_alpha_x, P->d_det_x, P->d_llr_x, P->d_conv_x, P->d_iter_x, P->d_list_x, 1, sx)) != QLDPC_OK) return rc;
+        if ((rc = decode_sector(P, P->gz, B, P->d_syn_z, P->d_prior_z, P->d_alpha_z, P->d_det_z, P->d_llr_z, P->d_conv_z, P->d_iter_z, P->d_list_z, 0, s,
+                                seed, trial_begin + off)) != QLDPC_OK) return rc;
+        if ((rc = decode_sector(P, P->gx, B, P->d_syn_x, P->d_prior_x, P->d_alpha_x, P->d_det_x, P->d_llr_x, P->d_conv_x, P->d_iter_x, P->d_list_x, 1, sx,
+                                seed, trial_begin + off)) != QLDPC_OK) return rc;
         if (sx != s) {
             QLDPC_HIP_TRY(hipEventRecord(P->ev_x_done, sx));
             QLDPC_HIP_TRY(hipStreamWaitEvent(s, P->ev_x_done, 0));
@@ -569,11 +587,13 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
                       P->d_conv_x.as<uint8_t>(), P->d_iter_x.as<int32_t>(), P->d_true_x.as<unsigned long long>()};
         if (P->gz->m <= 4096 && P->gx->m <= 4096 && P->gz->d_colptr && P->gx->d_colptr)
             hipLaunchKernelGGL(circuit_judge_kernel<true>, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
-                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->use_osd ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
+                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, (P->use_osd && !P->relay) ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         else
             hipLaunchKernelGGL(circuit_judge_kernel<false>, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
-                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->use_osd ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
+                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, (P->use_osd && !P->relay) ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
+        if (P->relay && (rc = relay_legs_tally_launch(B, P->d_legs_z.as<int32_t>(), P->d_legs_x.as<int32_t>(), P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
+            return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
         P->batches++;           // (the next batch's sampler follows the judge on s, which already waited for sector X)
         if (outcome) {
@@ -660,6 +680,23 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
     std::vector<unsigned long long> h(4 * kClkSlots);
     QLDPC_HIP_TRY(hipMemcpy(h.data(), P->d_clk.p, h.size() * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < 2; k++) mhz[k] = clock_probe_median(h.data() + 2 * kClkSlots * k, kClkSlots);
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
+                                             int max_legs, int stop_after) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
+    int rc = relay_check_params(rp);
+    if (rc != QLDPC_OK) return rc;
+    for (double v : P->h_prior_z) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-Z prior is not finite");
+    for (double v : P->h_prior_x) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-X prior is not finite");
+    if (relay_mode(P->gz) == 0) return relay_unsupported(P->gz);
+    if (relay_mode(P->gx) == 0) return relay_unsupported(P->gx);
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_legs_z.ensure((size_t)P->batch * 4)) != QLDPC_OK || (rc = P->d_legs_x.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    P->rp = rp;
+    P->relay = true;
     return QLDPC_OK;
 }
 

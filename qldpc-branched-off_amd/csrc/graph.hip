@@ -134,7 +134,7 @@ int qldpc_graph::alpha_table(const std::vector<double> &tab, hipStream_t stream,
 }
 
 QLDPC_EXPORT const char *qldpc_last_error(void) { return g_last_error.c_str(); }
-QLDPC_EXPORT int qldpc_version(void) { return 100; }
+QLDPC_EXPORT int qldpc_version(void) { return 101; }
 
 QLDPC_EXPORT int qldpc_device_count(void) {
     int count = 0;

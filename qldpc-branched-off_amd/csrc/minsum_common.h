@@ -89,6 +89,16 @@ void wg2_cache_free(void *cache);
 // "clean" decoder inputs, verified on the host: every prior finite and not -0.0, clip finite > 0, every alpha finite > 0.
 // Then no message or posterior can be -0.0 and no |q| NaN, which the regular and lean kernels exploit (see their headers).
 bool inputs_clean(const double *prior, int n, double clip, const double *alpha, int n_alpha);
+// Relay-BP (relay_bp.hip): memory min-sum in legs.  Parameters as in qldpc_relay_decode_batch; callers validate them with relay_check_params.
+struct RelayParams { double alpha, clip, gamma0, gamma_min, gamma_max; int t0, tr, max_legs, stop_after; };
+int relay_check_params(const RelayParams &P);
+int relay_mode(const qldpc_graph *g);            // 0: not supported, 1: V in LDS, 2: V in a per-workgroup HBM/L2 slab
+int relay_unsupported(const qldpc_graph *g);     // sets the error text, returns QLDPC_ERR_UNSUPPORTED
+// callers hold g->mu.  iter_bias is added to every iteration count written to d_iters; d_legs / d_sol may be NULL
+int relay_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, const RelayParams &P, uint64_t seed,
+                        int64_t shot_begin, int tag, int iter_bias, int8_t *d_err, uint8_t *d_conv, int32_t *d_legs, int32_t *d_iters,
+                        int32_t *d_sol, hipStream_t stream);
+int relay_legs_tally_launch(int64_t B, const int32_t *d_legs_z, const int32_t *d_legs_x, unsigned long long *d_tally, hipStream_t stream);
 // h_prior: the same prior on the host when the caller has it (a circuit plan, the host-pointer entry point), else NULL
 int minsum_decode_dispatch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter,
                            const double *d_alpha, double damping, double clip, int flags, bool nanfree, int8_t *d_err, double *d_llr,

@@ -21,6 +21,11 @@ Differences that are deliberate and documented:
   * one process per GPU also works: under a ``torch.distributed`` launch a rank drives ``device`` = LOCAL_RANK alone (``num_workers`` then counts
     the plans of that rank, default 1) and one all-reduce of the tally follows; with the RCCL backend it runs on device tensors;
   * ``target_logical_errors`` stops at the exact trial the reference would (in-order prefix cut over per-trial verdicts).
+
+``decoder="relay_bp"`` (an extension; ``"bp_osd"`` is the default) decodes both sectors with Relay-BP (``decoding/relay.py``) instead of
+min-sum + OSD-0, with ``relay_params`` over ``_lib.RELAY_DEFAULTS``.  Relay-BP uses its own constant alpha, so the alpha / beta estimators do not run,
+and the arguments that only mean something for BP+OSD (``alpha_mode``, ``alvarado_alpha``, ``scopt=True``, ``osd_order > 0``) raise ValueError.
+The result then also holds ``decoder``, ``relay_params`` and ``mean_legs_z`` / ``mean_legs_x`` (legs per trial).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -50,9 +55,23 @@ def _estimation_trials(requested, n_cols, error_rate):
 def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
-                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, **bb_params):
+                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
+    if decoder not in ("bp_osd", "relay_bp"):
+        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd' or 'relay_bp')")
+    relay = decoder == "relay_bp"
+    if relay:
+        bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None), ("scopt", bool(scopt)),
+                                        ("osd_order", osd_order > 0)) if given]
+        if bad:
+            raise ValueError(f"decoder='relay_bp' does not use {', '.join(bad)} (Relay-BP has its own constant alpha and no OSD stage)")
+        relay_params = dict(relay_params or {})
+        if "clip_llr" in relay_params:
+            raise ValueError("relay_params: the circuit plan's clip_llr is fixed (20)")
+        relay_params = _lib.relay_params(relay_params, with_clip=False)
+    elif relay_params is not None:
+        raise ValueError("relay_params is for decoder='relay_bp'")
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
     rank, world = 0, 1
@@ -79,7 +98,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if base_seed is None:
         base_seed = int(np.random.randint(0, 2 ** 31))
     if alpha_mode is None:
-        alpha_mode = "dynamical" if use_dynamic_alpha else "alvarado"
+        alpha_mode = "dynamical" if (use_dynamic_alpha or relay) else "alvarado"
     if alpha_mode not in ("dynamical", "alvarado", "alvarado-autoregressive"):
         raise ValueError(f"Unsupported alpha_mode: {alpha_mode}")
     if alpha_mode == "alvarado-autoregressive" and alvarado_alpha is not None:
@@ -150,6 +169,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
             self.stream = _lib.Stream(dev)
             self.plan = _lib.CircuitPlan(compiled, Lx, Lz, self.graphs[0], self.graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
                                          alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
+            if relay:
+                self.plan.use_relay(**relay_params)
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -280,5 +301,9 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     else:
         result = parallel.tally_to_result(total)
     result.update(extra)
+    if relay:
+        trials = max(int(total[T["trials"]]), 1)
+        result.update(decoder=decoder, relay_params=dict(relay_params), mean_legs_z=float(total[T["legs_z"]]) / trials,
+                      mean_legs_x=float(total[T["legs_x"]]) / trials)
     result["tally"] = total
     return result
