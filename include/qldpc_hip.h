@@ -28,6 +28,7 @@
  * Changelog (qldpc_version)
  *   100  the C ABI of the BP+OSD decoder and the Monte-Carlo plans
  *   101  Relay-BP: qldpc_relay_decode_batch[_dev], qldpc_circuit_plan_use_relay; tally slots QLDPC_TALLY_LEGS_Z / _X
+ *        additive, same version: OSD-CS, qldpc_osdcs_batch[_dev] and qldpc_circuit_plan_use_osd_cs
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -214,6 +215,26 @@ int qldpc_osd_timers_read(uint64_t *out32, int reset);
  * (QLDPC_ERR_UNSUPPORTED beyond, use max_combinations).  Ties of |llr|: ascending index (see qldpc_osd0_batch). */
 int qldpc_osdw_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard,
                      const int32_t *ordering, int order, int64_t max_combinations, int8_t *solution);
+/* OSD-CS: OSD-0 followed by a combination sweep (Roffe et al. 2020), batched over B shots of one graph.  Per shot, with the BP posteriors
+ * llr and their hard decision hard (the OSD-0 hand-over) and per-column weights w[n] (finite, the same for every shot):
+ *   q_j = floor(w_j * 2^20 + 0.5) (the product clamped to +-2^40) as int64; the cost of x is W(x) = sum_{j : x_j = 1} q_j, exact.
+ *   1. order: columns by ascending |llr|, NaN as +inf, ties by ascending index (qldpc_osd0_batch with ordering = NULL);
+ *   2. pivots: S = the columns independent of the columns before them in that order, rank = |S|; T = the other n - rank columns in the
+ *      same order, T[0] the least reliable;
+ *   3. candidates: corrections c with H c = s + H hard, fixed by t = c_T (c_S the unique solution on S).  Candidate 0 is t = {} (its
+ *      solution hard ^ c is qldpc_osd0_batch's, bit for bit); candidates 1 .. n - rank are t = {T[i]} for EVERY i; then the pairs
+ *      t = {T[a], T[b]}, a < b < order, in lexicographic order of (a, b);
+ *   4. selection: the candidate of least W(hard ^ c); ties go to the earlier candidate (so OSD-0 wins every tie);
+ *   5. s + H hard outside the column space of H (only a caller's own syndrome can be): exactly qldpc_osd0_batch's answer;
+ *   6. flips int32[B][2]: the original column indices of the winner's t (pair: T[a], T[b]), padded with -1; (-1, -1) = OSD-0 kept.
+ * 0 <= order <= 64 (order <= 1: no pairs).  m <= 1024 and n <= 65535, else QLDPC_ERR_UNSUPPORTED.  solution int8[B][n]. */
+int qldpc_osdcs_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard,
+                      const double *weights, int order, int8_t *solution, int32_t *flips);
+/* same on device pointers; only enqueues on `stream` (weights are not checked for finiteness here).  d_select / d_select_count as in
+ * qldpc_osd0_batch_dev: shots not listed keep whatever d_solution and d_flips hold.  d_solution may alias d_hard. */
+int qldpc_osdcs_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
+                          const double *d_weights, int order, const int32_t *d_select, const int32_t *d_select_count,
+                          int8_t *d_solution, int32_t *d_flips, void *stream);
 
 /* a10: generate_noisy_circuit_jit (src/noise/kernels.py:175-353), batched over B draws of explicit random
  * arrays rv/rp/rt [B][n_locs]; out_* [B][cap]; out_len int64[B]. */
@@ -348,6 +369,11 @@ void qldpc_circuit_plan_destroy(qldpc_circuit_plan *plan);
  * QLDPC_TALLY_LEGS_Z / _X.  Arguments as in qldpc_relay_decode_batch. */
 int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *plan, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
                                  int max_legs, int stop_after);
+/* Switches the plan's OSD stage to OSD-CS of `order` (one-way; qldpc_osdcs_batch with the plan's priors as the weights): the same
+ * unconverged trials, the same phase brackets, the same tally slots.  QLDPC_ERR_INVALID on a plan created with use_osd = 0 or switched to
+ * Relay-BP (and qldpc_circuit_plan_use_relay after this call returns QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is
+ * outside the range of qldpc_osdcs_batch. */
+int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *plan, int order);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

@@ -345,6 +345,30 @@ def osdw_batch(graph, syndromes, llr, hard, order, max_combinations=None, orderi
     return sol
 
 
+OSDCS_MAX_ORDER = 64
+
+
+def osdcs_batch(graph, syndromes, llr, hard, weights, order):
+    """qldpc_osdcs_batch on host arrays: OSD-0 followed by a combination sweep of `order` (semantics in include/qldpc_hip.h)
+    -> (solution int8[B, n], flips int32[B, 2]); flips holds the non-pivot columns the winner flips, -1 padded."""
+    order = int(order)
+    if not 0 <= order <= OSDCS_MAX_ORDER:
+        raise ValueError(f"OSD-CS order must be in 0..{OSDCS_MAX_ORDER}, got {order}")
+    syndromes = i8(syndromes).reshape(-1, graph.m) if graph.m else np.zeros((np.asarray(hard).reshape(-1, graph.n).shape[0], 0), np.int8)
+    B = syndromes.shape[0]
+    llr, hard = f64(llr).reshape(B, graph.n), i8(hard).reshape(B, graph.n)
+    weights = f64(weights)
+    if weights.size != graph.n:
+        raise ValueError(f"weights has {weights.size} entries, H has {graph.n} columns")
+    if not np.isfinite(weights).all():
+        raise ValueError("weights must be finite")
+    sol = np.zeros((B, graph.n), np.int8)
+    flips = np.full((B, 2), -1, np.int32)
+    check(lib().qldpc_osdcs_batch(graph.handle, B, ptr(syndromes, C.c_int8), ptr(llr, C.c_double), ptr(hard, C.c_int8), ptr(weights, C.c_double),
+                                  order, ptr(sol, C.c_int8), ptr(flips, C.c_int32)))
+    return sol, flips
+
+
 def gf2_spmv_batch(graph, vectors):
     """s = H e over GF(2) for B vectors (qldpc_gf2_spmv_batch, kernels.py:222-231): int8[B, n] -> int8[B, m]."""
     vectors = i8(vectors).reshape(-1, graph.n)
@@ -656,6 +680,14 @@ class CircuitPlan:
         check(lib().qldpc_circuit_plan_use_relay(self._h, p["alpha"], p["gamma0"], p["gamma_min"], p["gamma_max"], p["t0"], p["tr"], p["max_legs"],
                                                  p["stop_after"]))
         self.relay = p
+
+    def use_osd_cs(self, order):
+        """Run OSD-CS of `order` in the OSD stage from now on, with the plan's priors as the weights (one-way; qldpc_circuit_plan_use_osd_cs)."""
+        order = int(order)
+        if not 0 <= order <= OSDCS_MAX_ORDER:
+            raise ValueError(f"OSD-CS order must be in 0..{OSDCS_MAX_ORDER}, got {order}")
+        check(lib().qldpc_circuit_plan_use_osd_cs(self._h, order))
+        self.osd_cs_order = order
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))

@@ -264,10 +264,13 @@ struct qldpc_circuit_plan {
     bool relay = false;
     RelayParams rp{};
     DevBuf d_legs_z, d_legs_x;
+    // qldpc_circuit_plan_use_osd_cs: the OSD stage runs OSD-CS of this order (osd_cs.hip) instead of OSD-0; -1 = OSD-0
+    int cs_order = -1;
+    DevBuf d_flips_z, d_flips_x;
     std::vector<DevBuf *> all() {
         return {&d_loc_type, &d_zptr, &d_zidx, &d_zlog, &d_xptr, &d_xidx, &d_xlog, &d_alpha_z, &d_alpha_x, &d_prior_z, &d_prior_x, &d_lm_z, &d_lm_x,
                 &d_syn_z, &d_syn_x, &d_true_z, &d_true_x, &d_det_z, &d_det_x, &d_llr_z, &d_llr_x, &d_conv_z, &d_conv_x, &d_iter_z, &d_iter_x,
-                &d_list_z, &d_list_x, &d_count, &d_tally, &d_outcome, &d_clk, &d_legs_z, &d_legs_x};
+                &d_list_z, &d_list_x, &d_count, &d_tally, &d_outcome, &d_clk, &d_legs_z, &d_legs_x, &d_flips_z, &d_flips_x};
     }
 };
 
@@ -546,8 +549,12 @@ static int decode_sector(qldpc_circuit_plan *P, const qldpc_graph *g, int64_t B,
     {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk + 2 * kClkSlots : nullptr;
-        rc = osd0_listed_launch(g, list.as<int32_t>(), count, B, syn.as<int8_t>(), llr.as<double>(), det.as<int8_t>(), nullptr,
-                                det.as<int8_t>(), P->flags, s);
+        if (P->cs_order >= 0)
+            rc = osdcs_listed_launch(g, list.as<int32_t>(), count, B, syn.as<int8_t>(), llr.as<double>(), det.as<int8_t>(), prior.as<double>(),
+                                     P->cs_order, det.as<int8_t>(), (sector ? P->d_flips_x : P->d_flips_z).as<int32_t>(), s);
+        else
+            rc = osd0_listed_launch(g, list.as<int32_t>(), count, B, syn.as<int8_t>(), llr.as<double>(), det.as<int8_t>(), nullptr,
+                                    det.as<int8_t>(), P->flags, s);
         g->clk_probe = nullptr;
     }
     if (rc != QLDPC_OK) return rc;
@@ -686,6 +693,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
                                              int max_legs, int stop_after) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->cs_order < 0, "the plan's OSD stage was switched to OSD-CS: Relay-BP replaces BP + OSD and cannot follow");
     const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
     int rc = relay_check_params(rp);
     if (rc != QLDPC_OK) return rc;
@@ -697,6 +705,21 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alph
     if ((rc = P->d_legs_z.ensure((size_t)P->batch * 4)) != QLDPC_OK || (rc = P->d_legs_x.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
     P->rp = rp;
     P->relay = true;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: there is no OSD stage to switch");
+    QLDPC_REQUIRE(!P->relay, "the plan was switched to Relay-BP, which has no OSD stage");
+    int rc = osdcs_check_order(order);
+    if (rc != QLDPC_OK) return rc;
+    for (double v : P->h_prior_z) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-Z prior is not finite");
+    for (double v : P->h_prior_x) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-X prior is not finite");
+    if ((rc = osdcs_supported(P->gz)) != QLDPC_OK || (rc = osdcs_supported(P->gx)) != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_flips_z.ensure((size_t)P->batch * 8)) != QLDPC_OK || (rc = P->d_flips_x.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
+    P->cs_order = order;
     return QLDPC_OK;
 }
 

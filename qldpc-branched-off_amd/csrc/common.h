@@ -133,6 +133,7 @@ struct qldpc_graph {
     // launch on another stream first waits (hipStreamWaitEvent) for the previous user of the workspaces to finish.
     mutable std::mutex mu;
     mutable qldpc::DevBuf ws_msg, ws_qold, ws_vals, ws_misc, ws_queue, ws_list, ws_prior, ws_redo;
+    mutable qldpc::DevBuf ws_cs;      // OSD-CS (osd_cs.hip): [0] count, [4..] shots whose right-hand side is outside the column space
     mutable qldpc::DevBuf ws_squeue;  // work queue of the one-wave OSD-0 kernels (osd_small.hip): zeroed once, the kernels reset it themselves
     mutable bool ws_private = false;  // the handle is used from ONE stream only (a private copy owned by a plan lane): no hand-over events
     mutable hipEvent_t ws_event = nullptr;

@@ -67,5 +67,12 @@ int gf2_spmv_launch(const qldpc_graph *g, int64_t B, const int8_t *d_vec, int8_t
 struct OsdJudge { const int8_t *err; const uint64_t *Lmask; unsigned long long *tally; int32_t *count; int64_t max_listed; bool fused; };
 int osd0_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
                        const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, OsdJudge *judge = nullptr);
+// OSD-CS (osd_cs.hip) on the listed shots, weights on the device; the shots whose right-hand side lies outside the column space go through
+// osd0_listed_launch behind it.  Callers hold g->mu and have checked order (osdcs_check_order) and the graph (osdcs_supported).
+int osdcs_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd,
+                        const double *d_llr, const int8_t *d_hard, const double *d_weights, int order, int8_t *d_solution, int32_t *d_flips,
+                        hipStream_t stream);
+int osdcs_check_order(int order);
+int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
 
 }  // namespace qldpc

@@ -8,6 +8,15 @@ struct qldpc_graph;
 
 namespace qldpc {
 
+// Integer column weights of Relay-BP (relay_bp.hip) and OSD-CS (osd_cs.hip).
+// q_j = floor(prior_j * 2^20 + 0.5) as int64, the product clamped to +-2^40 so that a sum over any column count fits
+__host__ __device__ __forceinline__ long long relay_weight(double p) {
+    double x = p * 1048576.0;
+    if (x > 1099511627776.0) x = 1099511627776.0;
+    if (x < -1099511627776.0) x = -1099511627776.0;
+    return (long long)floor(x + 0.5);
+}
+
 // reference src/decoding/kernels.py:328-333: NaN -> 0, else clip to [-clip, clip]
 __device__ __forceinline__ double clip_nan(double q, double clip) {
     if (q != q) return 0.0;

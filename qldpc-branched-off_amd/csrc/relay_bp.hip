@@ -43,14 +43,6 @@ struct RelayArgs {
     int *queue;                    // next shot (zeroed before the launch)
 };
 
-// q_j = floor(prior_j * 2^20 + 0.5) as int64, the product clamped to +-2^40 so that a sum over any column count fits
-__host__ __device__ __forceinline__ long long relay_weight(double p) {
-    double x = p * 1048576.0;
-    if (x > 1099511627776.0) x = 1099511627776.0;
-    if (x < -1099511627776.0) x = -1099511627776.0;
-    return (long long)floor(x + 0.5);
-}
-
 template <bool VG>
 __global__ __launch_bounds__(1024) void relay_bp_kernel(RelayArgs A) {
     extern __shared__ unsigned char lds[];

@@ -26,6 +26,12 @@ Differences that are deliberate and documented:
 min-sum + OSD-0, with ``relay_params`` over ``_lib.RELAY_DEFAULTS``.  Relay-BP uses its own constant alpha, so the alpha / beta estimators do not run,
 and the arguments that only mean something for BP+OSD (``alpha_mode``, ``alvarado_alpha``, ``scopt=True``, ``osd_order > 0``) raise ValueError.
 The result then also holds ``decoder``, ``relay_params`` and ``mean_legs_z`` / ``mean_legs_x`` (legs per trial).
+
+``decoder="bp_osd_cs"`` (an extension) runs OSD-CS (``decoding/osd_cs.py``: OSD-0 followed by a combination sweep, Roffe et al. 2020) in the
+plan's OSD stage, with the plan's priors as the weights.  Here ``osd_order`` is the sweep's order lambda (0..64; pairs among the lambda least
+reliable non-pivot columns), not the reference's OSD-w order.  The alpha / SCOPT estimators run as for ``"bp_osd"``; ``relay_params`` raises
+ValueError.  OSD-CS returns OSD-0's answer wherever the syndrome is not reproducible, so no OSD-w pass follows.  The result also holds
+``decoder`` and ``osd_order``.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -58,9 +64,15 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
-    if decoder not in ("bp_osd", "relay_bp"):
-        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd' or 'relay_bp')")
+    if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs"):
+        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp' or 'bp_osd_cs')")
     relay = decoder == "relay_bp"
+    osd_cs = decoder == "bp_osd_cs"
+    if osd_cs:
+        if relay_params is not None:
+            raise ValueError("relay_params is for decoder='relay_bp'")
+        if not 0 <= int(osd_order) <= _lib.OSDCS_MAX_ORDER:
+            raise ValueError(f"decoder='bp_osd_cs': osd_order is the combination-sweep order, 0..{_lib.OSDCS_MAX_ORDER} (got {osd_order})")
     if relay:
         bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None), ("scopt", bool(scopt)),
                                         ("osd_order", osd_order > 0)) if given]
@@ -159,6 +171,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
 
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
+    osdw_pass = osd_order > 0 and not osd_cs          # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
     class Worker:
         """One worker = the reference's pool process (engine.py:433-435) as a device plan: graphs, masks, buffers and a stream of its own on one GPU."""
@@ -171,6 +184,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                                          alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
             if relay:
                 self.plan.use_relay(**relay_params)
+            if osd_cs:
+                self.plan.use_osd_cs(int(osd_order))
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -205,7 +220,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                 return np.zeros(0, np.uint8), np.zeros(_lib.TALLY_SLOTS, np.int64)
             local = self.plan.run_outcomes(base_seed, begin, count, self.stream.ptr)
             tally = self.plan.read(self.stream.ptr, clear=True)
-            if osd_order > 0 and (tally[T["unsat_z"]] or tally[T["unsat_x"]]):
+            if osdw_pass and (tally[T["unsat_z"]] or tally[T["unsat_x"]]):
                 local, tally = self.osdw_batch(begin, count)
             return local, tally
 
@@ -217,7 +232,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
             if count:
                 self.plan.run(base_seed, begin, count, self.stream.ptr)
             tally = self.plan.read(self.stream.ptr, clear=True)
-            if osd_order > 0 and (tally[T["unsat_z"]] or tally[T["unsat_x"]]):
+            if osdw_pass and (tally[T["unsat_z"]] or tally[T["unsat_x"]]):
                 tally = np.zeros(_lib.TALLY_SLOTS, np.int64)
                 for off in range(0, count, batch):
                     nb = min(batch, count - off)
@@ -305,5 +320,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         trials = max(int(total[T["trials"]]), 1)
         result.update(decoder=decoder, relay_params=dict(relay_params), mean_legs_z=float(total[T["legs_z"]]) / trials,
                       mean_legs_x=float(total[T["legs_x"]]) / trials)
+    if osd_cs:
+        result.update(decoder=decoder, osd_order=int(osd_order))
     result["tally"] = total
     return result
