@@ -65,6 +65,21 @@ def save(name, **arrs):
     print(f"  wrote {name}.npz  {os.path.getsize(path) / 1024:.1f} KiB")
 
 
+def save_fixed(name, **arrs):
+    """save() with fixed zip member times, so that a rerun of the generator writes byte-identical files (np.savez stamps the current time)."""
+    import io
+    import zipfile
+    path = os.path.join(HERE, name + ".npz")
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrs.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, buf.getvalue())
+    print(f"  wrote {name}.npz  {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 def csr_of(H):
     c = csr_matrix(np.asarray(H))
     c.sort_indices()
@@ -637,11 +652,245 @@ def gen_osdw():
     save("osdw", **out)
 
 
+# --------------------------------------------------------------------------- whole circuit-level trials
+# The decoder settings of the trial fixtures.  Alpha values are fixed inputs (the reference's estimators are too slow in pure
+# Python, and _run_single_trial_fast takes alpha as given).  Config B is main.py's operating point; its X sequence is
+# shorter than maxIter, so iterations 7..19 reuse its last value (dense.py:62, kernels.py minsum_decoder_full_autoregressive).
+TRIAL_CONFIGS = {
+    "A": dict(max_iter=50, osd_order=0, alpha_mode="dynamical", alpha_z=1.0, alpha_x=1.0),
+    "B": dict(max_iter=20, osd_order=2, alpha_mode="alvarado-autoregressive",
+              alpha_z=np.round(np.linspace(0.62, 0.95, 20), 6),
+              alpha_x=np.array([0.58, 0.66, 0.72, 0.78, 0.82, 0.86, 0.88])),
+    "C": dict(max_iter=30, osd_order=0, alpha_mode="alvarado", alpha_z=0.75, alpha_x=0.85),
+}
+# (tag) -> list of (config, [(error_rate, base_seed, trials, want_z_only, want_x_only, want_osd)])
+TRIAL_PLAN = {
+    "circ72": [(c, [(0.005, 7200, 12, 1, 1, 4), (0.01, 7201, 12, 3, 3, 2)]) for c in "ABC"],
+    "circ144": [(c, [(0.005, 14400, 8, 2, 2, 2)]) for c in "AB"],
+    "circ288": [("B", [(0.005, 28800, 2, 0, 0, 0)])],
+}
+
+
+def _oracle():
+    sys.path.insert(0, REPO)
+    from oracle import oracle as orc
+    orc.build()
+    return orc
+
+
+def _trial_shared_data(tag, cfg, error_rate, base_seed):
+    """shared_data of engine.py:391-419 for precomputed matrices (load_matrices) and fixed alpha values."""
+    from src.utils.caching import load_matrices
+    path, code, cycles, _ = CACHE[tag]
+    key = os.path.basename(path)[len("matrices_"):-len(".npz")]
+    matrices = load_matrices(os.path.join(REF, "matrix_cache"), key)
+    d, cb, comp = build_circuit(tag)
+    Lx, Lz = d["Lx"], d["Lz"]
+    with np.errstate(divide='ignore', invalid='ignore'):                      # engine.py:210-212
+        llrs_z = np.clip(np.nan_to_num(np.log((1 - matrices['channel_probsZ']) / matrices['channel_probsZ'])), -50, 50)
+        llrs_x = np.clip(np.nan_to_num(np.log((1 - matrices['channel_probsX']) / matrices['channel_probsX'])), -50, 50)
+    use_sparse = matrices['HdecZ'].shape[1] > 5000                            # engine.py:214
+    sd = {
+        'error_rate': error_rate, 'Lx': Lx, 'Lz': Lz,
+        'HdecZ': np.asarray(matrices['HdecZ'], dtype=np.float64, order='C'),
+        'HdecX': np.asarray(matrices['HdecX'], dtype=np.float64, order='C'), 'llrs_z': llrs_z, 'llrs_x': llrs_x,
+        'HZ_logical': np.ascontiguousarray(matrices['HZ_full'][matrices['first_logical_rowZ']:matrices['first_logical_rowZ'] + Lx.shape[0]]),
+        'HX_logical': np.ascontiguousarray(matrices['HX_full'][matrices['first_logical_rowX']:matrices['first_logical_rowX'] + Lx.shape[0]]),
+        'alpha_mode': cfg["alpha_mode"], 'alpha_z': cfg["alpha_z"], 'alpha_x': cfg["alpha_x"],
+        'maxIter': cfg["max_iter"], 'osd_order': cfg["osd_order"],
+        'base_seed': base_seed, 'use_sparse': use_sparse,
+        'HdecZ_csr': csr_matrix(matrices['HdecZ']) if use_sparse else None,
+        'HdecX_csr': csr_matrix(matrices['HdecX']) if use_sparse else None,
+        'compiled_circuit': comp,
+    }
+    return sd
+
+
+def _screen_trials(orc, sd, base_seed, count):
+    """Seed selection only (nothing of it is stored): the oracle's verdicts for trials base_seed + 0 .. count-1, so the fixture can
+    pick trials that exercise the hard cases.  Returns int arrays (z_err, x_err, osd_z, osd_x)."""
+    comp = sd["compiled_circuit"]
+    fx = {k: getattr(comp, k) for k in ("base_ops", "base_q1", "base_q2", "suffix_ops", "suffix_q1", "suffix_q2", "total_qubits",
+                                        "max_circuit_size", "max_syndromes_x", "max_syndromes_z", "x_syn_positions", "x_syn_ptrs",
+                                        "z_syn_positions", "z_syn_ptrs", "num_x_checks", "num_z_checks", "data_qubit_indices")}
+    fx["Lx"], fx["Lz"] = sd["Lx"], sd["Lz"]
+    n_locs = comp.num_error_locs
+    SZ, TZ, SX, TX = [], [], [], []
+    for i in range(count):
+        np.random.seed(base_seed + i)
+        rv = np.random.random(n_locs)
+        rp = np.random.randint(0, 3, n_locs, dtype=np.int32)
+        rt = np.random.randint(0, 15, n_locs, dtype=np.int32)
+        a, b, c, e = orc.run_trial(fx, sd["error_rate"], rv, rp, rt)
+        SZ.append(a); TZ.append(b); SX.append(c); TX.append(e)
+    res = []
+    for s, S, T, al in (("Z", SZ, TZ, sd["alpha_z"]), ("X", SX, TX, sd["alpha_x"])):
+        Hc = csr_of(sd[f"Hdec{s}"])
+        ip, ix, n = Hc.indptr.astype(np.int32), Hc.indices.astype(np.int32), Hc.shape[1]
+        E, C, V, _ = orc.minsum_decode_batch(ip, ix, n, np.array(S), sd[f"llrs_{s.lower()}"], max_iter=sd["maxIter"], alpha=al,
+                                             alpha_mode=sd["alpha_mode"], threads=0)
+        Lg = sd[f"H{s}_logical"].astype(np.int64)
+        err = np.zeros(count, np.int64)
+        for i in range(count):
+            det = E[i] if C[i] else orc.osd0(ip, ix, n, S[i], V[i], E[i])
+            err[i] = not np.array_equal((Lg @ det.astype(np.int64)) % 2, T[i])
+        res += [err, 1 - C.astype(np.int64)]
+    return res[0], res[2], res[1], res[3]
+
+
+def _pick_trials(screen, total, want_z, want_x, want_osd):
+    z, x, oz, ox = screen
+    picked = []
+    for cond, k in ((z & ~x & 1, want_z), (x & ~z & 1, want_x), ((oz | ox) & ~(z | x) & 1, want_osd)):
+        picked += [int(i) for i in np.flatnonzero(cond) if i not in picked][:k]
+    picked += [i for i in range(len(z)) if i not in picked][:total - len(picked)]
+    return sorted(picked[:total])
+
+
+def _packbits(a):
+    return np.packbits(np.asarray(a, np.uint8) % 2, axis=-1, bitorder="little")
+
+
+def gen_trials(tag, screen_count=None, posteriors_per_sector=2):
+    """Whole circuit-level trials by the reference's own _run_single_trial_fast (engine.py:68-122), imported, not re-composed.
+
+    engine.py imports rich and multiprocessing; both import here, no stub is needed.  The decoder and OSD calls the trial makes
+    are observed (not altered) by wrapping the names engine.py imported: each BP call's hard decision, success flag, final
+    iteration and (for a few decodes) posteriors; each OSD call's np.argsort order (osd.py:12) and solution.  Every OSD call is
+    then repeated with np.argsort forced to kind="stable" -- the device's tie rule -- and that solution and the verdict it leads to
+    are stored too.  One file per (tag, config): {tag}_trials_{config}.npz."""
+    import src.simulation.engine as ENG
+    orc = _oracle()
+    real = {k: getattr(ENG, k) for k in ("performMinSum_Symmetric", "performMinSum_Symmetric_Sparse", "performOSD_enhanced")}
+    real_argsort = np.argsort
+    for cname, groups in TRIAL_PLAN[tag]:
+        cfg = TRIAL_CONFIGS[cname]
+        t_start = time.time()
+        rows = []                      # one dict per trial
+        for error_rate, base_seed, total, wz, wx, wo in groups:
+            sd = _trial_shared_data(tag, cfg, error_rate, base_seed)
+            scount = (screen_count or (400 if tag == "circ72" else 1500)) if wz or wx or wo else total
+            t0 = time.time()
+            scr = _screen_trials(orc, sd, base_seed, scount)
+            idxs = _pick_trials(scr, total, wz, wx, wo)
+            print(f"    {tag} {cname} p={error_rate}: screened {scount} trials in {time.time() - t0:.0f}s "
+                  f"(z-only {int((scr[0] & ~scr[1] & 1).sum())}, x-only {int((scr[1] & ~scr[0] & 1).sum())}) -> {idxs}")
+            for idx in idxs:
+                calls = []
+
+                def bp_spy(name):
+                    def f(*a, **k):
+                        r = real[name](*a, **k)
+                        calls.append(("bp", np.asarray(r[0], np.int8).copy(), bool(r[1]), np.asarray(r[2], np.float64).copy(), int(r[3])))
+                        return r
+                    return f
+
+                def osd_spy(H, syndrome, llr, hard, order=0, max_combinations=None):
+                    seen = []
+
+                    def spy(a, *aa, **kk):
+                        r = real_argsort(a, *aa, **kk)
+                        if seen:               # the order-w sweep's second sort (osd.py:40) must be tie free, else the fixture is ambiguous
+                            assert np.array_equal(r, real_argsort(a, kind="stable"))
+                        seen.append(r.copy())
+                        return r
+
+                    def stable(a, *aa, **kk):
+                        kk["kind"] = "stable"
+                        return real_argsort(a, *aa, **kk)
+                    ENG.np.argsort = spy
+                    try:
+                        sol = real["performOSD_enhanced"](H, syndrome, llr, hard, order=order, max_combinations=max_combinations)
+                    finally:
+                        ENG.np.argsort = real_argsort
+                    ENG.np.argsort = stable
+                    try:
+                        sol_st = real["performOSD_enhanced"](H, syndrome, llr, hard, order=order, max_combinations=max_combinations)
+                    finally:
+                        ENG.np.argsort = real_argsort
+                    calls.append(("osd", seen[0].copy(), np.asarray(sol, np.int64) % 2, np.asarray(sol_st, np.int64) % 2, len(seen) > 1))
+                    return sol
+
+                ENG.performMinSum_Symmetric = bp_spy("performMinSum_Symmetric")
+                ENG.performMinSum_Symmetric_Sparse = bp_spy("performMinSum_Symmetric_Sparse")
+                ENG.performOSD_enhanced = osd_spy
+                try:
+                    t0 = time.time()
+                    verdict = ENG._run_single_trial_fast(idx, sd)
+                finally:
+                    for k, v in real.items():
+                        setattr(ENG, k, v)
+                np.random.seed(base_seed + idx)          # the same draws once more, for the stored syndromes / logicals
+                spz, tz, spx, tx = run_trial_fast(sd["compiled_circuit"], error_rate, sd["Lx"], sd["Lz"])
+                row = dict(error_rate=error_rate, base_seed=base_seed, trial=idx, verdict=np.array(verdict, np.uint8),
+                           use_sparse=sd["use_sparse"], Z_syndrome=np.asarray(spz, np.int8), X_syndrome=np.asarray(spx, np.int8),
+                           Z_true=np.asarray(tz, np.int8), X_true=np.asarray(tx, np.int8))
+                it = iter(calls)
+                for s in "ZX":
+                    bp = next(it)
+                    assert bp[0] == "bp"
+                    row[f"{s}_hard"], row[f"{s}_succ"], row[f"{s}_post"], row[f"{s}_iter"] = bp[1], bp[2], bp[3], bp[4]
+                    det = bp[1].astype(np.int64)
+                    row[f"{s}_osd"] = None
+                    if not bp[2]:
+                        o = next(it)
+                        assert o[0] == "osd"
+                        row[f"{s}_osd"] = dict(ordering=o[1], solution=o[2], stable=o[3], swept=o[4])
+                        det = o[2]
+                    row[f"{s}_det"] = det
+                    Lg = sd[f"H{s}_logical"]
+                    stable_det = row[f"{s}_osd"]["stable"] if row[f"{s}_osd"] else det
+                    row[f"{s}_err_stable"] = not np.array_equal((Lg @ stable_det) % 2, row[f"{s}_true"])
+                    assert (not np.array_equal((Lg @ det) % 2, row[f"{s}_true"])) == bool(verdict["ZX".index(s)])
+                assert next(it, None) is None
+                row["verdict_stable"] = np.array([row["Z_err_stable"], row["X_err_stable"], row["Z_err_stable"] or row["X_err_stable"]], np.uint8)
+                print(f"      trial {base_seed}+{idx}: {time.time() - t0:.1f}s verdict={tuple(int(v) for v in verdict)} "
+                      f"succ=({row['Z_succ']},{row['X_succ']}) iters=({row['Z_iter']},{row['X_iter']})")
+                rows.append(row)
+        save_fixed(f"{tag}_trials_{cname}", **_pack_trials(cfg, rows, posteriors_per_sector))
+        print(f"    {tag} {cname}: {len(rows)} trials in {time.time() - t_start:.0f}s")
+
+
+def _pack_trials(cfg, rows, per_sector):
+    out = dict(max_iter=np.int64(cfg["max_iter"]), osd_order=np.int64(cfg["osd_order"]), alpha_mode=np.array(cfg["alpha_mode"]),
+               alpha_Z=np.asarray(cfg["alpha_z"], np.float64), alpha_X=np.asarray(cfg["alpha_x"], np.float64),
+               use_sparse=np.uint8(rows[0]["use_sparse"]),
+               error_rate=np.array([r["error_rate"] for r in rows]), base_seed=np.array([r["base_seed"] for r in rows], np.int64),
+               trial=np.array([r["trial"] for r in rows], np.int64), verdict=np.array([r["verdict"] for r in rows]),
+               verdict_stable=np.array([r["verdict_stable"] for r in rows]))
+    for s in "ZX":
+        out[f"{s}_syndrome"] = _packbits([r[f"{s}_syndrome"] for r in rows])
+        out[f"{s}_true"] = np.array([r[f"{s}_true"] for r in rows], np.uint8)
+        out[f"{s}_hard"] = _packbits([r[f"{s}_hard"] for r in rows])
+        out[f"{s}_succ"] = np.array([r[f"{s}_succ"] for r in rows], np.uint8)
+        out[f"{s}_iter"] = np.array([r[f"{s}_iter"] for r in rows], np.int32)
+        out[f"{s}_det"] = _packbits([r[f"{s}_det"] for r in rows])
+        osd = [t for t, r in enumerate(rows) if r[f"{s}_osd"] is not None]
+        n = rows[0][f"{s}_hard"].size
+        assert n < 2 ** 15
+        out[f"{s}_osd_trials"] = np.array(osd, np.int64)
+        out[f"{s}_osd_ordering"] = np.array([rows[t][f"{s}_osd"]["ordering"] for t in osd], np.int16).reshape(len(osd), n)
+        out[f"{s}_osd_swept"] = np.array([rows[t][f"{s}_osd"]["swept"] for t in osd], np.uint8)
+        out[f"{s}_osd_stable"] = _packbits([rows[t][f"{s}_osd"]["stable"] for t in osd]).reshape(len(osd), -1)
+        out[f"{s}_osd_tie_changes_solution"] = np.array([not np.array_equal(rows[t][f"{s}_osd"]["stable"], rows[t][f"{s}_osd"]["solution"])
+                                                         for t in osd], np.uint8)
+        # posteriors of a few decodes: OSD'd ones first (all maxIter iterations, so the whole alpha sequence is used), and for X one
+        # with +-inf entries if the OSD'd ones have none
+        post = osd[:per_sector]
+        if s == "X" and not any(np.isinf(rows[t]["X_post"]).any() for t in post):
+            post += [t for t, r in enumerate(rows) if np.isinf(r["X_post"]).any() and t not in post][:1]
+        out[f"{s}_post_trials"] = np.array(post, np.int64)
+        out[f"{s}_post"] = np.array([rows[t][f"{s}_post"] for t in post], np.float64).reshape(len(post), n)
+    out["tie_changes_verdict"] = np.array([not np.array_equal(r["verdict"], r["verdict_stable"]) for r in rows], np.uint8)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
+    ap.add_argument("--trial-tags", default=",".join(TRIAL_PLAN), help="circuits of --only trials")
     a = ap.parse_args()
-    todo = a.only.split(",") if a.only else ["data", "steane", "bb", "core", "gf2", "circ72", "circ144", "estimators", "osdw", "bb256", "gf2big"]
+    todo = a.only.split(",") if a.only else ["data", "steane", "bb", "core", "gf2", "circ72", "circ144", "estimators", "osdw", "bb256", "gf2big", "trials"]
     t0 = time.time()
     if "data" in todo:
         print("[data]"); pack_data()
@@ -668,6 +917,9 @@ def main():
         print("[bb256]"); gen_bb256()
     if "gf2big" in todo:
         print("[gf2big]"); gen_gf2_big()
+    if "trials" in todo:
+        for tag in a.trial_tags.split(","):
+            print(f"[trials {tag}]"); gen_trials(tag)
     print(f"done in {time.time() - t0:.0f}s")
 
 

@@ -1128,8 +1128,8 @@ def test_osd0_with_row_transform_in_global_memory(L, oracle, golden, monkeypatch
             sol = L.osd0_batch(graph, synd, llr, hard, flags=fl)
             for b in range(B):
                 assert np.array_equal(sol[b], want[b]), (cycles, fl, b, int((sol[b] != want[b]).sum()))
-            if b < B - 1:
-                assert np.array_equal(oracle.syndrome_check(ip, ix, sol[b]), synd[b])
+                if b < B - 1:                                            # every consistent shot's solution reproduces its syndrome
+                    assert np.array_equal(oracle.syndrome_check(ip, ix, sol[b]), synd[b]), (cycles, fl, b)
 
 
 def test_random_irregular_graphs_all_kernels(Lb, oracle, monkeypatch):
@@ -1714,3 +1714,193 @@ def test_run_simulation_osd_order_on_unsatisfiable_trials(L, oracle):
     stop = run_simulation(c["Hx"], c["Hz"], c["Lx"], c["Lz"], p, num_trials=N, num_cycles=6, maxIter=20, osd_order=2, precomputed_matrices=F,
                           base_seed=seed, batch=32, target_logical_errors=5, **bb)
     assert stop["logical_errors"] == 5 and stop["num_trials"] <= N
+
+
+# ---- whole circuit-level trials the reference ran (tests/golden/{tag}_trials_{config}.npz: _run_single_trial_fast, engine.py:68-122) -----------------
+from trial_fixtures import TRIAL_SETS  # noqa: E402
+
+
+def _trial_device_setup(L, tag):
+    from trial_fixtures import compiled_circuit, sectors
+    from qldpc_amd.simulation.engine import prior_llrs
+    from qldpc_amd.data import load_circuit_matrices
+    d = load_circuit_matrices(tag)
+    S = sectors(tag)
+    out = {}
+    for s in "ZX":
+        sec = S[s]
+        prior = prior_llrs(np.asarray(d[f"channel_probs{s}"], dtype=np.float64))
+        assert np.array_equal(prior, sec["prior"])
+        out[s] = dict(sec, graph=L.Graph(sec["indptr"], sec["indices"], sec["n"]), prior=prior,
+                      mask=L.logical_column_masks(sec["logical_csr"], sec["n"]))
+    return compiled_circuit(tag), out
+
+
+def _mask_verdict(mask, det, true):
+    """logical compare through the column masks the plans use: bit r of the XOR over det's ones == row r of H*_logical @ det"""
+    acc = np.bitwise_xor.reduce(mask[np.flatnonzero(det)]) if np.any(det) else np.uint64(0)
+    k = np.asarray(true).size
+    return any(((int(acc) >> r) & 1) != int(true[r]) for r in range(k))
+
+
+@pytest.mark.parametrize("tag,config", TRIAL_SETS)
+def test_reference_trials_pieces(L, tag, config):
+    """The reference's trials through the C ABI, stage by stage: the noise kernels on the regenerated random arrays; min-sum under the trial's alpha
+    mode and maxIter in every decode variant that runs at the size (workgroup kernel with LDS tables = default, tables in HBM, posteriors in HBM, the
+    streaming kernel; circ288: the default); OSD (order 0 or 2) with the reference's np.argsort order and with the device's stable order, under the
+    default, the global-memory row transform and the reference-order kernel, a sorted head of 40 columns and the full sort; the logical compare through
+    logical_column_masks.  Reference order: every stage and verdict equals the reference.  Stable order: the reference run under that tie rule; and the
+    reference's verdict wherever the fixture records that the tie rule changes nothing."""
+    from trial_fixtures import load_trials, trial_randoms, tie_sensitive
+    from qldpc_amd.noise.simulation import run_trial_with_randoms
+    F = load_trials(tag, config)
+    (comp, Lx, Lz, fx), secs = _trial_device_setup(L, tag)
+    big = tag == "circ288"
+    T = F["trials"]
+    for t, tr in enumerate(T):
+        rv, rp, rt = trial_randoms(tr["base_seed"], tr["trial"], int(fx["num_error_locs"]))
+        spz, tz, spx, tx = run_trial_with_randoms(comp, tr["error_rate"], Lx, Lz, rv, rp, rt)
+        for s, sp, tl in (("Z", spz, tz), ("X", spx, tx)):
+            assert np.array_equal(sp, tr[s]["syndrome"]) and np.array_equal(tl, tr[s]["true"]), (tag, config, t, s, "sampler")
+    dets = {s: np.stack([tr[s]["hard"] for tr in T]) for s in "ZX"}
+    stable_dets = {s: dets[s].copy() for s in "ZX"}
+    for s in "ZX":
+        sec = secs[s]
+        synd = np.stack([tr[s]["syndrome"] for tr in T])
+        flag_set = (0,) if big else (0, L.FLAG_WG_TABLES, L.FLAG_WG_VGLOBAL, L.FLAG_KERNEL_STREAM)
+        for fl in flag_set:
+            err, conv, llr, it = L.minsum_decode_batch(sec["graph"], synd, sec["prior"], F["max_iter"], F["alpha_mode"], F["alpha"][s], flags=fl)
+            for t, tr in enumerate(T):
+                where = (tag, config, t, s, fl)
+                assert np.array_equal(err[t], tr[s]["hard"]) and bool(conv[t]) == tr[s]["succ"] and int(it[t]) == tr[s]["iter"], where
+                if tr[s]["post"] is not None:
+                    assert np.array_equal(llr[t], tr[s]["post"], equal_nan=True), where + ("posteriors",)
+        bad = [t for t, tr in enumerate(T) if not tr[s]["succ"]]
+        if not bad:
+            continue
+        order = np.stack([T[t][s]["osd"]["ordering"] for t in bad])
+
+        def osd(ordering, flags=0):
+            if F["osd_order"] > 0:
+                return L.osdw_batch(sec["graph"], synd[bad], llr[bad], err[bad], F["osd_order"], ordering=ordering)
+            return L.osd0_batch(sec["graph"], synd[bad], llr[bad], err[bad], ordering=ordering, flags=flags)
+        ref = np.stack([T[t][s]["det"] for t in bad])
+        stable = np.stack([T[t][s]["osd"]["stable"] for t in bad])
+        for fl in ((0,) if big or F["osd_order"] > 0 else (0, L.FLAG_OSD_UG, L.FLAG_OSD_REFORDER)):
+            assert np.array_equal(osd(order, fl), ref), (tag, config, s, fl, "reference order")
+            if not big:
+                assert np.array_equal(osd(None, fl), stable), (tag, config, s, fl, "stable order")
+        if not big:
+            try:
+                for presort in (40, 0):
+                    L.set_option("osd_presort", presort)
+                    assert np.array_equal(osd(None), stable), (tag, config, s, presort)
+                    assert np.array_equal(osd(order), ref), (tag, config, s, presort)
+            finally:
+                L.set_option("osd_presort", -1)
+        dets[s][bad] = ref
+        stable_dets[s][bad] = stable
+    for t, tr in enumerate(T):
+        for s in "ZX":
+            assert np.array_equal(dets[s][t], tr[s]["det"]), (tag, config, t, s)
+        v = [_mask_verdict(secs[s]["mask"], dets[s][t], tr[s]["true"]) for s in "ZX"]
+        assert tuple(v + [v[0] or v[1]]) == tr["verdict"], (tag, config, t)
+        if not big:
+            vs = [_mask_verdict(secs[s]["mask"], stable_dets[s][t], tr[s]["true"]) for s in "ZX"]
+            assert tuple(vs + [vs[0] or vs[1]]) == tr["verdict_stable"], (tag, config, t)
+            if not tie_sensitive(tr):
+                assert tuple(vs + [vs[0] or vs[1]]) == tr["verdict"], (tag, config, t)
+
+
+@pytest.mark.parametrize("tag,config", TRIAL_SETS)
+def test_reference_trials_drop_in_loop(L, tag, config):
+    """engine.py:68-122 line by line with the reference-named API: np.random.seed(base_seed + trial), noise.simulation.run_trial_fast, the dense or
+    the sparse min-sum entry point by the rule of engine.py:214, performOSD_enhanced(order=osd_order) when BP fails, H*_logical @ det % 2.  Every
+    verdict of a tie-insensitive trial is the reference's; every OSD solution is the reference's or the stable-rule one (the host's NumPy picks the tie
+    order of the drop-in call)."""
+    import scipy.sparse as sp
+    from trial_fixtures import load_trials, tie_sensitive
+    from qldpc_amd.noise.simulation import run_trial_fast
+    from qldpc_amd.decoding.dense import performMinSum_Symmetric
+    from qldpc_amd.decoding.sparse import performMinSum_Symmetric_Sparse
+    from qldpc_amd.decoding.osd import performOSD_enhanced
+    F = load_trials(tag, config)
+    (comp, Lx, Lz, fx), secs = _trial_device_setup(L, tag)
+    use_sparse = secs["Z"]["n"] > 5000                                        # engine.py:214
+    assert use_sparse == F["use_sparse"]
+    Hd, Hc = {}, {}
+    for s in "ZX":
+        sec = secs[s]
+        Hc[s] = sp.csr_matrix((np.ones(sec["indices"].size, np.int8), sec["indices"], sec["indptr"]), shape=(sec["m"], sec["n"]))
+        Hd[s] = None if use_sparse else sec["H"].astype(np.float64)
+    for t, tr in enumerate(F["trials"]):
+        np.random.seed(tr["base_seed"] + tr["trial"])
+        sparse_z, true_z, sparse_x, true_x = run_trial_fast(comp, tr["error_rate"], Lx, Lz)
+        verdict = []
+        for s, synd, true in (("Z", sparse_z, true_z), ("X", sparse_x, true_x)):
+            sec, x = secs[s], tr[s]
+            if use_sparse:
+                det, succ, llrs, _ = performMinSum_Symmetric_Sparse(Hc[s], synd, sec["prior"], maxIter=F["max_iter"], alpha=F["alpha"][s],
+                                                                    alpha_mode=F["alpha_mode"])
+            else:
+                det, succ, llrs, _ = performMinSum_Symmetric(Hd[s], synd, sec["prior"], maxIter=F["max_iter"], alpha=F["alpha"][s],
+                                                             alpha_mode=F["alpha_mode"])
+            assert np.array_equal(det, x["hard"]) and bool(succ) == x["succ"], (tag, config, t, s)
+            if not succ:
+                det = performOSD_enhanced(Hc[s] if use_sparse else Hd[s], synd, llrs, det, order=F["osd_order"])
+                assert np.array_equal(det, x["det"]) or np.array_equal(det, x["osd"]["stable"]), (tag, config, t, s)
+            dec = (sec["logical"] @ np.asarray(det, np.int64)) % 2
+            verdict.append(not np.array_equal(dec, true))
+        if not tie_sensitive(tr):
+            assert tuple(verdict + [verdict[0] or verdict[1]]) == tr["verdict"], (tag, config, t)
+
+
+@pytest.mark.parametrize("tag,config,count", [("circ72", "B", 2048), ("circ72", "C", 2048), ("circ144", "B", 256), ("circ144", "C", 256)])
+def test_circuit_plan_under_fixture_alpha_matches_the_pieces(L, oracle, tag, config, count):
+    """The fused plan created with a fixture's alpha sequences (config B: main.py's operating point, a Z sequence of maxIter values and an X sequence that
+    ends early) or per-sector constants (config C) and its maxIter gives the verdicts of the pieces chain (sampler -> min-sum -> OSD-0 -> logical compare)
+    on the plan's own Philox trials, and the same tally.  With test_reference_trials_pieces this ties the plan to the reference for these alpha modes; the
+    first trials' decodes are also held to the oracle, whose alpha rule test_reference_trials pins, so an alpha table the plan and the pieces share is checked too.
+    (The plan runs OSD-0; OSD-2 of config B returns the OSD-0 solution whenever that satisfies the syndrome, osd.py:27-29 -- unsat == 0 below.)"""
+    from trial_fixtures import load_trials
+    F = load_trials("circ72", config)                 # the decoder settings of a config are the same for every circuit (make_golden.py TRIAL_CONFIGS)
+    if (tag, config) in TRIAL_SETS:
+        G = load_trials(tag, config)
+        assert G["max_iter"] == F["max_iter"] and all(np.array_equal(G["alpha"][s], F["alpha"][s]) for s in "ZX")
+    (comp, Lx, Lz, fx), secs = _trial_device_setup(L, tag)
+    seed = 24680
+    kw = dict(max_iter=F["max_iter"], alpha_z=F["alpha"]["Z"], alpha_x=F["alpha"]["X"], alpha_mode=F["alpha_mode"])
+    plan = L.CircuitPlan(comp, Lx, Lz, secs["Z"]["graph"], secs["X"]["graph"], secs["Z"]["prior"], secs["X"]["prior"], secs["Z"]["mask"],
+                         secs["X"]["mask"], 0.005, batch=count, **kw)
+    spz, tz, spx, tx = plan.sample(seed, 0, count)
+    got = plan.run_outcomes(seed, 0, count)
+    tally = plan.read(clear=True)
+    plan.close()
+    verdict = np.zeros(count, np.uint8)
+    conv_sum, osd_sum, unsat = [], [], []
+    for b, (s, synd, true) in enumerate((("Z", spz, tz), ("X", spx, tx))):
+        sec = secs[s]
+        det, conv, llr, it = L.minsum_decode_batch(sec["graph"], synd, sec["prior"], F["max_iter"], F["alpha_mode"], F["alpha"][s])
+        head = 64
+        ref = oracle.minsum_decode_batch(sec["indptr"], sec["indices"], sec["n"], synd[:head], sec["prior"], max_iter=F["max_iter"], alpha=F["alpha"][s],
+                                         alpha_mode=F["alpha_mode"], threads=0)
+        for a, r, what in zip((det[:head], conv[:head], llr[:head], it[:head]), ref, ("err", "conv", "llr", "iter")):
+            assert np.array_equal(a, r, equal_nan=True), (tag, config, s, what)
+        assert (ref[1] == 0).any()
+        bad = np.flatnonzero(conv == 0)
+        if bad.size:
+            det[bad] = L.osd0_batch(sec["graph"], synd[bad], llr[bad], det[bad])
+        dec = (det.astype(np.int64) @ sec["logical"].T) % 2
+        verdict |= (np.any(dec != true.astype(np.int64), axis=1).astype(np.uint8) << b)
+        conv_sum.append(int(conv.sum())); osd_sum.append(int(bad.size))
+        unsat.append(int((L.gf2_spmv_batch(sec["graph"], det) != (synd & 1)).any(axis=1).sum()))
+        if config == "B" and s == "X":
+            assert F["alpha"][s].size < F["max_iter"] and (it == F["max_iter"] - 1).any()     # decodes that run past the end of the sequence
+    T = L.TALLY
+    assert np.array_equal(got, verdict), np.flatnonzero(got != verdict)[:10]
+    assert tally[T["trials"]] == count and tally[T["total_err"]] == np.count_nonzero(verdict)
+    assert tally[T["z_err"]] == np.count_nonzero(verdict & 1) and tally[T["x_err"]] == np.count_nonzero(verdict & 2)
+    assert [tally[T["bp_conv_z"]], tally[T["bp_conv_x"]]] == conv_sum
+    assert [tally[T["osd_z"]], tally[T["osd_x"]]] == osd_sum
+    assert [tally[T["unsat_z"]], tally[T["unsat_x"]]] == unsat == [0, 0]
+    assert np.count_nonzero(verdict & 1) > 0 and np.count_nonzero(verdict & 2) > 0 and min(osd_sum) > 0

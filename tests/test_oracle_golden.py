@@ -341,3 +341,87 @@ def test_osd0_sweep_may_end_when_the_residual_is_gone(oracle):
             assert not stopped, (trial, m, n)                    # a one in an unused row survives to the end
             assert np.array_equal(sol, ref), (trial, m, n)       # (the full sweep, literally)
     assert fired > 150 and early > 100
+
+
+# ---- whole circuit-level trials the reference ran (tests/golden/{tag}_trials_{config}.npz, engine.py:68-122) ---------------------------------
+from trial_fixtures import TRIAL_SETS  # noqa: E402
+
+
+def _oracle_osd(oracle, sec, syndrome, llr, hard, order, ordering):
+    ip, ix, n = sec["indptr"], sec["indices"], sec["n"]
+    if order > 0:
+        return oracle.osdw(ip, ix, n, syndrome, llr, hard, order, ordering=ordering)
+    return oracle.osd0(ip, ix, n, syndrome, llr, hard, ordering=ordering)
+
+
+@pytest.mark.parametrize("tag,config", TRIAL_SETS)
+def test_reference_trials(oracle, tag, config):
+    """Every trial of the fixture, stage by stage: the oracle's trial on the regenerated random arrays == the reference's syndromes and logicals;
+    oracle BP under the trial's alpha mode and maxIter == the reference's hard decision, success flag, final iteration and (where stored) posteriors bit for
+    bit -- through the dense driver too where the reference took the dense path (engine.py:214); OSD (order 0 or 2) with the np.argsort order the reference
+    used == its solution; the logical compare == its verdict.  With the stable tie rule the oracle reproduces the reference run under that rule."""
+    from trial_fixtures import compiled_circuit, load_trials, logical_error, sectors, trial_randoms
+    F = load_trials(tag, config)
+    S = sectors(tag)
+    fx = compiled_circuit(tag)[3]
+    priors = {}
+    from qldpc_amd.data import load_circuit_matrices
+    d = load_circuit_matrices(tag)
+    for s in "ZX":
+        priors[s] = oracle.prior_llrs(d[f"channel_probs{s}"])
+        assert np.array_equal(priors[s], S[s]["prior"])                     # engine.py:210-212
+    assert F["use_sparse"] == (S["Z"]["n"] > 5000)
+    for t, tr in enumerate(F["trials"]):
+        rv, rp, rt = trial_randoms(tr["base_seed"], tr["trial"], int(fx["num_error_locs"]))
+        spz, tz, spx, tx = oracle.run_trial(fx, tr["error_rate"], rv, rp, rt)
+        for s, sp, tl in (("Z", spz, tz), ("X", spx, tx)):
+            assert np.array_equal(sp, tr[s]["syndrome"]) and np.array_equal(tl, tr[s]["true"]), (tag, config, t, s, "sampler")
+        verdict, verdict_stable = [], []
+        for s in "ZX":
+            sec, x = S[s], tr[s]
+            kw = dict(max_iter=F["max_iter"], alpha=F["alpha"][s], alpha_mode=F["alpha_mode"])
+            e, c, v, it = oracle.minsum_decode_batch(sec["indptr"], sec["indices"], sec["n"], x["syndrome"][None], priors[s], **kw)
+            e, c, v, it = e[0], bool(c[0]), v[0], int(it[0])
+            where = (tag, config, t, s)
+            assert np.array_equal(e, x["hard"]) and c == x["succ"] and it == x["iter"], where
+            if x["post"] is not None:
+                assert np.array_equal(v, x["post"], equal_nan=True), where
+            if not F["use_sparse"]:                                         # what the reference ran: dense.py:5-73
+                ed, cd, vd, itd = oracle.minsum_dense_driver(sec["H"], x["syndrome"], priors[s], **kw)
+                assert np.array_equal(ed, e) and cd == c and itd == it and np.array_equal(vd, v, equal_nan=True), where + ("dense",)
+            det = det_stable = e
+            assert (x["osd"] is None) == c, where
+            if not c:
+                # the stable rule itself (ascending |llr|, ties by ascending index): the posteriors of a failed decode hold long runs of equal keys
+                assert np.array_equal(oracle.argsort_abs(v), np.argsort(np.abs(v), kind="stable")), where
+                det = _oracle_osd(oracle, sec, x["syndrome"], v, e, F["osd_order"], x["osd"]["ordering"])
+                det_stable = _oracle_osd(oracle, sec, x["syndrome"], v, e, F["osd_order"], None)
+                assert np.array_equal(det_stable, x["osd"]["stable"]), where + ("stable rule",)
+            assert np.array_equal(det, x["det"]), where + ("osd",)
+            verdict.append(logical_error(sec["logical"], det, x["true"]))
+            verdict_stable.append(logical_error(sec["logical"], det_stable, x["true"]))
+        assert tuple(verdict + [verdict[0] or verdict[1]]) == tr["verdict"], (tag, config, t)
+        assert tuple(verdict_stable + [verdict_stable[0] or verdict_stable[1]]) == tr["verdict_stable"], (tag, config, t)
+
+
+@pytest.mark.parametrize("tag,config", TRIAL_SETS)
+def test_trial_fixtures_exercise_hard_cases(tag, config):
+    """The trial fixtures hold the cases that move a logical-error count: z_err only, x_err only and neither; >= 5 sector decodes that reach OSD; in
+    config B a sector that runs all maxIter iterations past the end of its short alpha sequence; an HdecX decode with +-inf posteriors, stored.
+    circ288 holds 2 trials: the verdict mix and the OSD floor are relaxed there to what 2 trials can hold."""
+    from trial_fixtures import load_trials
+    F = load_trials(tag, config)
+    V = np.array([tr["verdict"] for tr in F["trials"]])
+    n_osd = sum(tr[s]["osd"] is not None for tr in F["trials"] for s in "ZX")
+    if tag == "circ288":
+        assert len(F["trials"]) == 2 and n_osd >= 1
+    else:
+        assert (V[:, 0] & ~V[:, 1]).any() and (V[:, 1] & ~V[:, 0]).any() and (~V[:, 2]).any()
+        assert n_osd >= 5
+    if config == "B":
+        short = [s for s in "ZX" if F["alpha"][s].size < F["max_iter"]]
+        assert short and any(tr[s]["iter"] == F["max_iter"] - 1 for tr in F["trials"] for s in short)
+    assert any(tr["X"]["post"] is not None and np.isinf(tr["X"]["post"]).any() for tr in F["trials"])
+    if tag == "circ72":
+        assert not F["use_sparse"]           # the dense path of engine.py:214
+        assert {tr["error_rate"] for tr in F["trials"]} == {0.005, 0.01}
