@@ -29,6 +29,7 @@
  *   100  the C ABI of the BP+OSD decoder and the Monte-Carlo plans
  *   101  Relay-BP: qldpc_relay_decode_batch[_dev], qldpc_circuit_plan_use_relay; tally slots QLDPC_TALLY_LEGS_Z / _X
  *        additive, same version: OSD-CS, qldpc_osdcs_batch[_dev] and qldpc_circuit_plan_use_osd_cs
+ *        additive, same version: qldpc_minsum_decode_path (which decoder form a call takes), QLDPC_PATH_* and QLDPC_DETAIL_*
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -147,6 +148,30 @@ int qldpc_minsum_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t 
                                   double damping, double clip_llr, int flags,
                                   int8_t *d_out_err, double *d_out_llr, uint8_t *d_out_conv, int32_t *d_out_iter,
                                   void *stream);
+
+/* Which decoder form qldpc_minsum_decode_batch (host prior != NULL) resp. qldpc_minsum_decode_batch_dev (prior == NULL) runs for these arguments.
+ * Launches no kernel, but builds and caches the same tables the decode call would: with a host prior the handle has not seen it may upload the tables
+ * of the LDS-resident form, and on the fifth distinct prior it waits for the device (hipDeviceSynchronize) and drops the four cached sets first, exactly
+ * as the decode call does.  Returns what the decode call would return for arguments it refuses (QLDPC_ERR_UNSUPPORTED).  The query and the launchers
+ * share one selection function, and results never depend on the form.  New here (the reference has no counterpart).
+ *   path    QLDPC_PATH_*: REGULAR csrc/minsum_regular.hip, RESIDENT minsum_resident.hip, WG2 minsum_wg2.hip (workgroup per shot, every table in LDS),
+ *           WG minsum_wg.hip (workgroup per shot, tables in HBM / L2), STREAM minsum_stream.hip, WAVE minsum_wave.hip (experiments build only)
+ *   detail  QLDPC_DETAIL_* bits of the two workgroup forms (0 for the others) */
+#define QLDPC_PATH_REGULAR 0
+#define QLDPC_PATH_RESIDENT 1
+#define QLDPC_PATH_WG2 2
+#define QLDPC_PATH_WG 3
+#define QLDPC_PATH_STREAM 4
+#define QLDPC_PATH_WAVE 5
+#define QLDPC_DETAIL_LEAN 0x1            /* the clean-input kernel (WG2: always) */
+#define QLDPC_DETAIL_REG_INDICES 0x2     /* a thread keeps its row's column indices in registers (WG2: always) */
+#define QLDPC_DETAIL_VGLOBAL 0x4         /* posteriors in global memory, by size or by QLDPC_FLAG_WG_VGLOBAL */
+#define QLDPC_DETAIL_DAMPING 0x8         /* damping != 1: the previous messages in a global-memory slab */
+#define QLDPC_DETAIL_BLOCK_1024 0x10     /* 1024 threads per workgroup (else 512; WG2: always) */
+#define QLDPC_DETAIL_DEG1 0x20           /* the graph has degree-1 checks: the kernel instance that carries their +-inf messages */
+#define QLDPC_DETAIL_NAN_DEG1_ONLY 0x40  /* no column meets two degree-1 checks: only they can make a NaN, and only their waves test for it */
+int qldpc_minsum_decode_path(const qldpc_graph *g, const double *prior, int max_iter, int alpha_mode, double alpha_val, const double *alpha_seq,
+                             int alpha_len, double damping, double clip_llr, int flags, int *path, int *detail);
 
 /* a3: minsum_core_sparse (kernels.py:138-169): one check-node pass; Q[B][nnz], syndrome_sign[B][m] (+-1.0)
  * -> R[B][nnz], R_sum[B][n].  B = 1 is the reference call. */

@@ -32,6 +32,9 @@ TALLY = {"trials": 0, "z_err": 1, "x_err": 2, "total_err": 3, "bp_conv_z": 4, "b
 FLAG_WG_EDGE_LANES, FLAG_OSD_LDS, FLAG_WG_IDXLOAD = 0x2, 0x20000, 0x40000
 FLAG_OSD_REFORDER, FLAG_OSD_QUEUE, FLAG_WG_TABLES = 0x80000, 0x100000, 0x200000
 FLAG_WG_VGLOBAL, FLAG_WG_GENERIC, FLAG_OSD_UG, FLAG_OSD_GLOBAL, FLAG_CLOCK_PROBE, FLAG_WG_ROWMAJOR = 0x100, 0x200, 0x400, 0x800, 0x4000, 0x8000
+# qldpc_minsum_decode_path: the decoder form a call takes (QLDPC_PATH_*) and the QLDPC_DETAIL_* bits of the workgroup forms
+PATH_REGULAR, PATH_RESIDENT, PATH_WG2, PATH_WG, PATH_STREAM, PATH_WAVE = 0, 1, 2, 3, 4, 5
+DETAIL_LEAN, DETAIL_REG_INDICES, DETAIL_VGLOBAL, DETAIL_DAMPING, DETAIL_BLOCK_1024, DETAIL_DEG1, DETAIL_NAN_DEG1_ONLY = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 CIRCUIT_PHASES = ("sample", "bp_z", "osd_z", "bp_x", "osd_x", "judge")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "qldpc_hip.h")
 
@@ -314,6 +317,21 @@ def minsum_decode_batch(graph, syndromes, prior, max_iter, alpha_mode, alpha, da
                                           ptr(err, C.c_int8), ptr(llr, C.c_double) if want_llr else None, ptr(conv, C.c_uint8),
                                           ptr(iters, C.c_int32)))
     return err, conv, llr, iters
+
+
+def minsum_decode_path(graph, prior, max_iter, alpha_mode, alpha, damping=1.0, clip_llr=20.0, flags=0):
+    """qldpc_minsum_decode_path -> (path, detail): the decoder form minsum_decode_batch takes for these arguments (PATH_*, DETAIL_* bits);
+    prior=None asks for the device-pointer entry point, which does not know the prior.  Launches nothing."""
+    mode, aval, seq = alpha_args(alpha_mode, alpha)
+    if prior is not None:
+        prior = f64(prior)
+        if prior.size != graph.n:
+            raise ValueError(f"initialBelief has {prior.size} entries, H has {graph.n} columns")
+    path, detail = C.c_int(-1), C.c_int(0)
+    check(lib().qldpc_minsum_decode_path(graph.handle, ptr(prior, C.c_double) if prior is not None else None, C.c_int(int(max_iter)), C.c_int(mode),
+                                         C.c_double(aval), ptr(seq, C.c_double), C.c_int(seq.size), C.c_double(float(damping)),
+                                         C.c_double(float(clip_llr)), C.c_int(flags), C.byref(path), C.byref(detail)))
+    return path.value, detail.value
 
 
 def osd0_batch(graph, syndromes, llr, hard, ordering=None, flags=0):

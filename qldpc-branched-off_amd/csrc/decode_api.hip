@@ -32,40 +32,62 @@ bool inputs_clean(const double *prior, int n, double clip, const double *alpha, 
     return true;
 }
 
-static int dispatch_kernel(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter,
-                           const double *d_alpha, double damping, double clip, int flags, bool nanfree, int8_t *d_err, double *d_llr,
-                           uint8_t *d_conv, int32_t *d_iter, hipStream_t stream, const double *h_prior) {
+// The one predicate of kernel selection: which decoder form serves these arguments.  dispatch_kernel launches what it returns and
+// qldpc_minsum_decode_path reports it, so the query cannot drift from what runs.  May build and cache the tables of the LDS-resident
+// workgroup form (callers hold g->mu).
+int select_decode_path(const qldpc_graph *g, int max_iter, double damping, double clip, int flags, bool nanfree, const double *h_prior, DecodePath &out) {
+    out.path = QLDPC_PATH_STREAM; out.detail = 0; out.prep = nullptr;
     const bool want_stream = flags & QLDPC_FLAG_KERNEL_STREAM;
     const bool want_res = flags & (QLDPC_FLAG_KERNEL_RESIDENT | QLDPC_FLAG_KERNEL_GENERIC);
     const bool can_res = resident_supported(g, damping);
     if (!want_stream && !(flags & QLDPC_FLAG_KERNEL_GENERIC) && regular_supported(g, clip, max_iter)) {
+        out.path = QLDPC_PATH_REGULAR;
 #ifdef QLDPC_EXPERIMENTS
         const bool clean = nanfree && (flags & QLDPC_FLAG_INTERNAL_PRIOR_LE_CLIP);
-        if (wave_kernel_choice() == 2 && wave_supported(g, damping, clean))
-            return minsum_wave_launch(g, B, d_synd, d_prior, max_iter, d_alpha, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+        if (wave_kernel_choice() == 2 && wave_supported(g, damping, clean)) out.path = QLDPC_PATH_WAVE;
 #endif
-        return minsum_regular_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, nanfree, d_err, d_llr, d_conv, d_iter, stream);
+        return QLDPC_OK;
     }
     if (want_res && !can_res) {
         set_error("resident kernel does not support this graph (m=%d n=%d max row degree %d, max column degree %d)", g->m, g->n,
                   g->max_row_deg, g->max_col_deg);
         return QLDPC_ERR_UNSUPPORTED;
     }
-    if (!want_stream && can_res)
-        return minsum_resident_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+    if (!want_stream && can_res) { out.path = QLDPC_PATH_RESIDENT; return QLDPC_OK; }
     if (!want_stream && wg_supported(g, damping)) {
         // the prior is known on the host and the inputs are clean: the form with every table in LDS (minsum_wg2.hip), unless a flag asks for a form of the
         // table kernel (QLDPC_FLAG_WG_TABLES and the layout / experiment selectors)
         if (h_prior && nanfree && damping == 1.0 && !(flags & (QLDPC_FLAG_WG_TABLES | QLDPC_FLAG_WG_VGLOBAL | QLDPC_FLAG_WG_GENERIC | QLDPC_FLAG_WG_ROWMAJOR |
                                                                   QLDPC_FLAG_WG_EDGE_LANES | QLDPC_FLAG_WG_IDXLOAD))) {
-            const Wg2Prep *prep = nullptr;
-            const int rcp = wg2_prepare(g, h_prior, &prep);
+            const int rcp = wg2_prepare(g, h_prior, &out.prep);
             if (rcp != QLDPC_OK) return rcp;
-            if (prep) return minsum_wg2_launch(g, prep, B, d_synd, max_iter, d_alpha, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+            if (out.prep) { out.path = QLDPC_PATH_WG2; out.detail = wg2_detail(out.prep); return QLDPC_OK; }
         }
-        return minsum_wg_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, nanfree, d_err, d_llr, d_conv, d_iter, stream);
+        const int rcx = wg_check_variant(flags);
+        if (rcx != QLDPC_OK) return rcx;
+        out.path = QLDPC_PATH_WG;
+        out.detail = wg_choose(g, damping, flags, nanfree).detail();
+        return QLDPC_OK;
     }
-    return minsum_stream_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+    return QLDPC_OK;
+}
+
+static int dispatch_kernel(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter,
+                           const double *d_alpha, double damping, double clip, int flags, bool nanfree, int8_t *d_err, double *d_llr,
+                           uint8_t *d_conv, int32_t *d_iter, hipStream_t stream, const double *h_prior) {
+    DecodePath P;
+    const int rc = select_decode_path(g, max_iter, damping, clip, flags, nanfree, h_prior, P);
+    if (rc != QLDPC_OK) return rc;
+    switch (P.path) {
+#ifdef QLDPC_EXPERIMENTS
+    case QLDPC_PATH_WAVE: return minsum_wave_launch(g, B, d_synd, d_prior, max_iter, d_alpha, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+#endif
+    case QLDPC_PATH_REGULAR: return minsum_regular_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, nanfree, d_err, d_llr, d_conv, d_iter, stream);
+    case QLDPC_PATH_RESIDENT: return minsum_resident_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+    case QLDPC_PATH_WG2: return minsum_wg2_launch(g, P.prep, B, d_synd, max_iter, d_alpha, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+    case QLDPC_PATH_WG: return minsum_wg_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, nanfree, d_err, d_llr, d_conv, d_iter, stream);
+    default: return minsum_stream_launch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip, flags, d_err, d_llr, d_conv, d_iter, stream);
+    }
 }
 
 // callers hold g->mu; the graph's device workspaces are handed over in stream order (common.h)
@@ -97,6 +119,22 @@ static int check_decode_args(const qldpc_graph *g, int64_t B, const void *synd, 
     return QLDPC_OK;
 }
 
+// What the host knows about a decode call's inputs: nanfree ("clean": host-verified clean prior -- finite, no -0.0 -- and clip, alphas, damping
+// checked the same way) and the internal flag bits that carry the prior's facts to the launchers.
+static bool decode_facts(bool prior_finite, bool prior_le_clip, double damping, double clip_llr, const std::vector<double> &tab, int max_iter, int &flags) {
+    flags = (flags & QLDPC_FLAG_PUBLIC_MASK) | (prior_finite ? QLDPC_FLAG_INTERNAL_PRIOR_FINITE : 0) |
+            ((prior_finite && prior_le_clip) ? QLDPC_FLAG_INTERNAL_PRIOR_LE_CLIP : 0);
+    return prior_finite && std::isfinite(damping) && inputs_clean(nullptr, 0, clip_llr, tab.data(), max_iter);
+}
+
+// the facts of a host prior (the *_dev entry points know neither)
+static void host_prior_facts(const double *prior, size_t n, double clip_llr, bool &finite, bool &le_clip) {
+    const double one = 1.0;
+    finite = inputs_clean(prior, (int)n, 1.0, &one, 1);
+    le_clip = finite;
+    for (size_t j = 0; j < n && le_clip; j++) le_clip = std::fabs(prior[j]) <= clip_llr;
+}
+
 static int decode_dev_impl(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior,
                                                int max_iter, int alpha_mode, double alpha_val, const double *alpha_seq,
                                                int alpha_len, double damping, double clip_llr, int flags, bool prior_finite, bool prior_le_clip, int8_t *d_err,
@@ -111,10 +149,7 @@ static int decode_dev_impl(const qldpc_graph *g, int64_t B, const int8_t *d_synd
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const double *d_alpha = nullptr;          // per-graph cache of alpha tables: a new schedule is uploaded once, nothing synchronises
     if ((rc = g->alpha_table(tab, s, &d_alpha)) != QLDPC_OK) return rc;
-    // prior_finite here means "host-verified clean prior" (finite, no -0.0); clip and alphas are checked the same way
-    bool nanfree = prior_finite && std::isfinite(damping) && inputs_clean(nullptr, 0, clip_llr, tab.data(), max_iter);
-    flags = (flags & QLDPC_FLAG_PUBLIC_MASK) | (prior_finite ? QLDPC_FLAG_INTERNAL_PRIOR_FINITE : 0) |
-            ((prior_finite && prior_le_clip) ? QLDPC_FLAG_INTERNAL_PRIOR_LE_CLIP : 0);
+    const bool nanfree = decode_facts(prior_finite, prior_le_clip, damping, clip_llr, tab, max_iter, flags);
     return minsum_decode_dispatch(g, B, d_synd, d_prior, max_iter, d_alpha, damping, clip_llr, flags, nanfree, d_err,
                                   d_llr, d_conv, d_iter, s, h_prior);
 }
@@ -126,6 +161,26 @@ QLDPC_EXPORT int qldpc_minsum_decode_batch_dev(const qldpc_graph *g, int64_t B, 
     // the prior lives on the device: its finiteness is unknown here, so the NaN test of kernels.py:328 stays in
     return decode_dev_impl(g, B, d_synd, d_prior, max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, damping, clip_llr, flags, false, false,
                            d_err, d_llr, d_conv, d_iter, stream);
+}
+
+QLDPC_EXPORT int qldpc_minsum_decode_path(const qldpc_graph *g, const double *prior, int max_iter, int alpha_mode, double alpha_val, const double *alpha_seq,
+                                          int alpha_len, double damping, double clip_llr, int flags, int *path, int *detail) {
+    QLDPC_REQUIRE(g != nullptr, "graph is NULL");
+    QLDPC_REQUIRE(path != nullptr && detail != nullptr, "an output pointer is NULL");
+    QLDPC_REQUIRE(max_iter >= 0, "negative max_iter");
+    QLDPC_REQUIRE(!(clip_llr != clip_llr), "clip_llr is NaN");
+    QLDPC_USE_DEVICE(g->device);
+    std::vector<double> tab;
+    int rc = build_alpha_table(max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, tab);
+    if (rc != QLDPC_OK) return rc;
+    bool prior_finite = false, prior_le_clip = false;            // prior == NULL: the *_dev entry point, which knows neither
+    if (prior) host_prior_facts(prior, (size_t)g->n, clip_llr, prior_finite, prior_le_clip);
+    const bool nanfree = decode_facts(prior_finite, prior_le_clip, damping, clip_llr, tab, max_iter, flags);
+    std::lock_guard<std::mutex> lk(g->mu);
+    DecodePath P;
+    if ((rc = select_decode_path(g, max_iter, damping, clip_llr, flags, nanfree, prior, P)) != QLDPC_OK) return rc;
+    *path = P.path; *detail = P.detail;
+    return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_minsum_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior,
@@ -149,10 +204,8 @@ QLDPC_EXPORT int qldpc_minsum_decode_batch(const qldpc_graph *g, int64_t B, cons
     unsigned char *base = g->ws_io.as<unsigned char>();
     if (m) QLDPC_HIP_TRY(hipMemcpyAsync(base + o_synd, syndromes, B * m, hipMemcpyHostToDevice, nullptr));
     if (n) QLDPC_HIP_TRY(hipMemcpyAsync(base + o_prior, prior, n * 8, hipMemcpyHostToDevice, nullptr));
-    const double one = 1.0;
-    const bool prior_finite = inputs_clean(prior, (int)n, 1.0, &one, 1);
-    bool prior_le_clip = prior_finite;
-    for (size_t j = 0; j < n && prior_le_clip; j++) prior_le_clip = std::fabs(prior[j]) <= clip_llr;
+    bool prior_finite, prior_le_clip;
+    host_prior_facts(prior, n, clip_llr, prior_finite, prior_le_clip);
     rc = decode_dev_impl(g, B, reinterpret_cast<int8_t *>(base + o_synd), reinterpret_cast<double *>(base + o_prior), max_iter, alpha_mode,
                          alpha_val, alpha_seq, alpha_len, damping, clip_llr, flags, prior_finite, prior_le_clip, reinterpret_cast<int8_t *>(base + o_err),
                          reinterpret_cast<double *>(base + o_llr), reinterpret_cast<uint8_t *>(base + o_conv),

@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/qldpc_hip.h"
+
 struct qldpc_graph;
 
 namespace qldpc {
@@ -89,12 +91,27 @@ int mc_wave_launch(const qldpc_graph *g, int64_t B, const double *d_prior, int m
 bool wg_supported(const qldpc_graph *g, double damping);
 int minsum_wg_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter, const double *d_alpha,
                      double damping, double clip, int flags, bool clean, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t stream);
+// which form of that kernel a call gets: decided once here, launched by minsum_wg_launch and reported by qldpc_minsum_decode_path
+struct WgChoice {
+    bool vg, damp, lean, ridx, has_deg1;   // posteriors in global memory; damping slab; lean kernel; row indices in registers; degree-1 template
+    int nan_deg1_only, block, edge_lanes;
+    int detail() const {
+        return (lean ? QLDPC_DETAIL_LEAN : 0) | (ridx ? QLDPC_DETAIL_REG_INDICES : 0) | (vg ? QLDPC_DETAIL_VGLOBAL : 0) | (damp ? QLDPC_DETAIL_DAMPING : 0) |
+               (block == 1024 ? QLDPC_DETAIL_BLOCK_1024 : 0) | (has_deg1 ? QLDPC_DETAIL_DEG1 : 0) | (nan_deg1_only ? QLDPC_DETAIL_NAN_DEG1_ONLY : 0);
+    }
+};
+WgChoice wg_choose(const qldpc_graph *g, double damping, int flags, bool clean);
+int wg_check_variant(int flags);                 // QLDPC_ERR_UNSUPPORTED for an experiment selector in the product library
 // LDS-resident form of that kernel for callers whose prior is known on the host (minsum_wg2.hip); *out = NULL when the input is not eligible
 struct Wg2Prep;
 int wg2_prepare(const qldpc_graph *g, const double *h_prior, const Wg2Prep **out);
 int minsum_wg2_launch(const qldpc_graph *g, const Wg2Prep *P, int64_t B, const int8_t *d_synd, int max_iter, const double *d_alpha, double clip, int flags,
                       int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t stream);
 void wg2_cache_free(void *cache);
+int wg2_detail(const Wg2Prep *P);                // QLDPC_DETAIL_* bits of a launch with these tables
+// the decoder form a call takes (QLDPC_PATH_*, QLDPC_DETAIL_*) and, for QLDPC_PATH_WG2, its tables; callers hold g->mu
+struct DecodePath { int path, detail; const Wg2Prep *prep; };
+int select_decode_path(const qldpc_graph *g, int max_iter, double damping, double clip, int flags, bool nanfree, const double *h_prior, DecodePath &out);
 // "clean" decoder inputs, verified on the host: every prior finite and not -0.0, clip finite > 0, every alpha finite > 0.
 // Then no message or posterior can be -0.0 and no |q| NaN, which the regular and lean kernels exploit (see their headers).
 bool inputs_clean(const double *prior, int n, double clip, const double *alpha, int n_alpha);

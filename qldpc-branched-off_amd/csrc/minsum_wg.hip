@@ -561,6 +561,38 @@ static int wg_mode(const qldpc_graph *g, double damping, int flags) {
 
 bool wg_supported(const qldpc_graph *g, double damping) { return wg_mode(g, damping, 0) != 0; }
 
+// the product library has no kernel behind the two experiment selectors: the launch and the path query refuse them alike
+int wg_check_variant(int flags) {
+#ifndef QLDPC_EXPERIMENTS
+    if (flags & (QLDPC_FLAG_WG_EDGE_LANES | QLDPC_FLAG_WG_IDXLOAD)) {
+        set_error("this decoder variant (flags %#x) is a measured-and-rejected experiment: it exists in libqldpc_hip_experiments.so only (make experiments)", flags);
+        return QLDPC_ERR_UNSUPPORTED;
+    }
+#else
+    (void)flags;
+#endif
+    return QLDPC_OK;
+}
+
+WgChoice wg_choose(const qldpc_graph *g, double damping, int flags, bool clean) {
+    WgChoice C;
+    C.vg = (wg_mode(g, damping, flags) == 2); C.damp = (damping != 1.0);
+    C.has_deg1 = false;
+    for (int i = 0; i < g->m; i++) C.has_deg1 = C.has_deg1 || (g->indptr[i + 1] - g->indptr[i] == 1);
+    C.nan_deg1_only = 1;
+    if (C.has_deg1) {
+        std::vector<uint8_t> hit(g->n, 0);
+        for (int i = 0; i < g->m && C.nan_deg1_only; i++)
+            if (g->indptr[i + 1] - g->indptr[i] == 1) { const int j = g->indices[g->indptr[i]]; if (hit[j]++) C.nan_deg1_only = 0; }
+    }
+    C.block = (g->m > 512 || g->n > 4096) ? 1024 : 512;
+    C.edge_lanes = ((flags & QLDPC_FLAG_WG_EDGE_LANES) && g->max_row_deg <= 48) ? 1 : 0;
+    C.lean = clean && std::isfinite(damping) && !(flags & QLDPC_FLAG_WG_GENERIC);
+    // a thread owns one row for the whole launch: its column indices stay in registers (QLDPC_FLAG_WG_IDXLOAD keeps the per-iteration index loads)
+    C.ridx = C.lean && !C.vg && !C.damp && !C.edge_lanes && !(flags & QLDPC_FLAG_WG_IDXLOAD) && g->m <= C.block && g->max_row_deg <= 8 * kIdxChunks;
+    return C;
+}
+
 int minsum_wg_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter, const double *d_alpha,
                      double damping, double clip, int flags, bool clean, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t stream) {
     WgArgs A;
@@ -574,26 +606,16 @@ int minsum_wg_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, cons
     A.ell_col = natural ? g->d_ell_col : g->d_ell_col_s;
     A.ell_var = natural ? g->d_ell_var : g->d_ell_var_s;
     A.indptr = g->d_indptr; A.indices = g->d_indices;
-#ifndef QLDPC_EXPERIMENTS
-    if (flags & (QLDPC_FLAG_WG_EDGE_LANES | QLDPC_FLAG_WG_IDXLOAD)) {
-        set_error("this decoder variant (flags %#x) is a measured-and-rejected experiment: it exists in libqldpc_hip_experiments.so only (make experiments)", flags);
-        return QLDPC_ERR_UNSUPPORTED;
-    }
-#endif
-    A.edge_lanes = ((flags & QLDPC_FLAG_WG_EDGE_LANES) && g->max_row_deg <= 48) ? 1 : 0;
+    const int rcx = wg_check_variant(flags);
+    if (rcx != QLDPC_OK) return rcx;
+    const WgChoice C = wg_choose(g, damping, flags, clean);
+    A.edge_lanes = C.edge_lanes;
     A.B = B; A.synd = d_synd; A.prior = d_prior; A.alpha = d_alpha; A.clip = clip;
     A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
-    const bool vg = (wg_mode(g, damping, flags) == 2), damp = (damping != 1.0);
+    const bool vg = C.vg, damp = C.damp, has_deg1 = C.has_deg1, lean = C.lean;
     const size_t lds = wg_lds_bytes(g, vg, A.offP, A.offI, A.offF);
-    bool has_deg1 = false;
-    for (int i = 0; i < g->m; i++) has_deg1 = has_deg1 || (g->indptr[i + 1] - g->indptr[i] == 1);
-    A.nan_deg1_only = 1;
-    if (has_deg1) {
-        std::vector<uint8_t> hit(g->n, 0);
-        for (int i = 0; i < g->m && A.nan_deg1_only; i++)
-            if (g->indptr[i + 1] - g->indptr[i] == 1) { const int j = g->indices[g->indptr[i]]; if (hit[j]++) A.nan_deg1_only = 0; }
-    }
-    const int block = (g->m > 512 || g->n > 4096) ? 1024 : 512;
+    A.nan_deg1_only = C.nan_deg1_only;
+    const int block = C.block;
     const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 2);
     int rcq = g->ws_queue.ensure(16);
     if (rcq != QLDPC_OK) return rcq;
@@ -614,7 +636,6 @@ int minsum_wg_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, cons
         if ((rcq = g->ws_qold.ensure((size_t)grid * A.qstride * 8)) != QLDPC_OK) return rcq;
         A.qold = g->ws_qold.as<double>();
     }
-    const bool lean = clean && std::isfinite(damping) && !(flags & QLDPC_FLAG_WG_GENERIC);
     using K = void (*)(WgArgs);
     // [lean][nansel][vg][damp]
     static const K table[2][2][2][2] = {
@@ -625,8 +646,7 @@ int minsum_wg_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, cons
          {{minsum_wg_lean_kernel<true, false, false>, minsum_wg_lean_kernel<true, false, true>},
           {minsum_wg_lean_kernel<true, true, false>, minsum_wg_lean_kernel<true, true, true>}}}};
     K kern = table[lean ? 1 : 0][has_deg1 ? 1 : 0][vg ? 1 : 0][damp ? 1 : 0];
-    // a thread owns one row for the whole launch: its column indices stay in registers (QLDPC_FLAG_WG_IDXLOAD keeps the per-iteration index loads)
-    if (lean && !vg && !damp && !A.edge_lanes && !(flags & QLDPC_FLAG_WG_IDXLOAD) && g->m <= block && g->max_row_deg <= 8 * kIdxChunks)
+    if (C.ridx)
         kern = has_deg1 ? minsum_wg_lean_kernel<true, false, false, true> : minsum_wg_lean_kernel<false, false, false, true>;
     if ((rcq = ensure_max_lds(g->device, reinterpret_cast<const void *>(kern), 160 * 1024)) != QLDPC_OK) return rcq;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, A);

@@ -499,6 +499,12 @@ int wg2_prepare(const qldpc_graph *g, const double *h_prior, const Wg2Prep **out
     return QLDPC_OK;
 }
 
+// always 1024 threads with the row's column slots in registers, clean inputs only
+int wg2_detail(const Wg2Prep *P) {
+    return QLDPC_DETAIL_LEAN | QLDPC_DETAIL_REG_INDICES | QLDPC_DETAIL_BLOCK_1024 | (P->has_deg1 ? QLDPC_DETAIL_DEG1 : 0) |
+           (P->nan_deg1_only ? QLDPC_DETAIL_NAN_DEG1_ONLY : 0);
+}
+
 int minsum_wg2_launch(const qldpc_graph *g, const Wg2Prep *P, int64_t B, const int8_t *d_synd, int max_iter, const double *d_alpha, double clip, int flags,
                       int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t stream) {
     Wg2Args A;

@@ -885,12 +885,37 @@ def _pack_trials(cfg, rows, per_sector):
     return out
 
 
+# --------------------------------------------------------------------------- graph shapes beyond the BB matrices
+def gen_wg_shapes():
+    """Six small families of tests/graph_shapes.py (rows of degree 40 and 57, column degrees 0 .. 8, two degree-1 checks on one column, odd nnz,
+    eleven 64-column chunks) through the reference's own decoder: 8 syndromes each, max_iter = 12.  The fixture stores the graph, prior and
+    syndromes the generator returned and the reference's (error, converged, values, final_iter)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import graph_shapes as GS
+    out, names = {}, []
+    for c in GS.families():
+        if not c.golden:
+            continue
+        names.append(c.name)
+        pn = next(iter(c.priors))
+        prior = c.priors[pn]
+        S = GS.syndromes(c, 8)
+        Hc = csr_matrix((np.ones(c.nnz, np.int8), c.indices, c.indptr), shape=(c.m, c.n))
+        E, C, V, I = batch_sparse(Hc, S, prior, maxIter=12, alpha_mode="dynamical")
+        for k, v in (("indptr", c.indptr), ("indices", c.indices), ("n", np.int64(c.n)), ("prior_name", np.array(pn)), ("prior", prior), ("syndromes", S),
+                     ("max_iter", np.int64(12)), ("err", E), ("conv", C), ("llr", V), ("iter", I)):
+            out[f"{c.name}__{k}"] = v
+        print(f"  {c.name}: {c.m} x {c.n}, nnz {c.nnz}, converged {int(C.sum())}/8, NaN {bool(np.isnan(V).any())}")
+    out["families"] = np.array(names)
+    save_fixed("wg_shapes", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
     ap.add_argument("--trial-tags", default=",".join(TRIAL_PLAN), help="circuits of --only trials")
     a = ap.parse_args()
-    todo = a.only.split(",") if a.only else ["data", "steane", "bb", "core", "gf2", "circ72", "circ144", "estimators", "osdw", "bb256", "gf2big", "trials"]
+    todo = a.only.split(",") if a.only else ["data", "steane", "bb", "core", "gf2", "circ72", "circ144", "estimators", "osdw", "bb256", "gf2big", "wgshapes", "trials"]
     t0 = time.time()
     if "data" in todo:
         print("[data]"); pack_data()
@@ -917,6 +942,8 @@ def main():
         print("[bb256]"); gen_bb256()
     if "gf2big" in todo:
         print("[gf2big]"); gen_gf2_big()
+    if "wgshapes" in todo:
+        print("[wgshapes]"); gen_wg_shapes()
     if "trials" in todo:
         for tag in a.trial_tags.split(","):
             print(f"[trials {tag}]"); gen_trials(tag)

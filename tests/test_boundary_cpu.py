@@ -256,3 +256,23 @@ def test_flag_constants_follow_the_header():
         assert v & (v - 1) == 0 and v not in seen, (name, seen.get(v))
         assert v < 0x10000000                      # the public mask (csrc/minsum_common.h: QLDPC_FLAG_PUBLIC_MASK)
         seen[v] = name
+
+
+def test_path_and_detail_constants_follow_the_header():
+    """Every QLDPC_PATH_* / QLDPC_DETAIL_* of include/qldpc_hip.h (qldpc_minsum_decode_path) has a `_lib.PATH_*` / `_lib.DETAIL_*` twin with the same
+    value, and the other way round; paths are distinct small integers, detail bits distinct single bits."""
+    import re
+    import qldpc_amd  # noqa: F401
+    from qldpc_amd import _lib
+    with open(_lib.HEADER_PATH) as fh:
+        text = fh.read()
+    paths = {k: int(v) for k, v in re.findall(r"#define\s+QLDPC_PATH_(\w+)\s+(\d+)\b", text)}
+    bits = {k: int(v, 16) for k, v in re.findall(r"#define\s+QLDPC_DETAIL_(\w+)\s+(0x[0-9a-fA-F]+)", text)}
+    assert set(paths) == {"REGULAR", "RESIDENT", "WG2", "WG", "STREAM", "WAVE"} and sorted(paths.values()) == list(range(6))
+    assert len(bits) == 7 and all(v & (v - 1) == 0 and v for v in bits.values()) and len(set(bits.values())) == 7
+    for name, v in paths.items():
+        assert getattr(_lib, "PATH_" + name) == v, name
+    for name, v in bits.items():
+        assert getattr(_lib, "DETAIL_" + name) == v, name
+    assert {k[5:] for k in vars(_lib) if k.startswith("PATH_")} == set(paths)
+    assert {k[7:] for k in vars(_lib) if k.startswith("DETAIL_")} == set(bits)

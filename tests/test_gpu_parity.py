@@ -190,7 +190,8 @@ def test_workgroup_kernel_lds_resident_form(L, oracle, tag):
     tables in HBM / L2 (csrc/minsum_wg.hip) -- against the oracle and each other on inputs that take different paths through the first one: the real
     priors (11 - 15 classes, a few chunks that mix classes), a two-valued prior scattered at random, a uniform prior, a prior of all-distinct values (not
     eligible: falls back to the table kernel whatever the flag), ragged batches, few and many iterations, the fixed-work mode, and both sectors (HdecX has
-    degree-1 checks: +-inf messages and the NaN -> 0 rule of kernels.py:328)."""
+    degree-1 checks: +-inf messages and the NaN -> 0 rule of kernels.py:328).  Which form each prior takes is asserted below: on circ72 only the uniform
+    prior reaches the first form."""
     from qldpc_amd.data import load_circuit_matrices
     from qldpc_amd.simulation.engine import prior_llrs
     d = load_circuit_matrices(tag)
@@ -208,6 +209,12 @@ def test_workgroup_kernel_lds_resident_form(L, oracle, tag):
                 synd = np.stack([oracle.syndrome_check(ip, ix, e) for e in E])
                 synd[0] = rng.random(m) < 0.4                      # an unrealisable syndrome: never converges
                 ref = oracle.minsum_decode_batch(ip, ix, n, synd, pr, max_iter=iters, threads=0)
+                # which form runs is asserted, not assumed.  circ144 (138 / 139 chunks): the LDS-resident form for the four eligible priors.  circ72 has
+                # 35 / 36 chunks and six degree classes, so its real, two-valued and negative-class priors mix 10 - 13 chunks, more than the
+                # (nch + 3) / 4 = 9 the form admits: there only the uniform prior (5 mixed chunks) takes it, the others the table kernel.
+                wg2 = name != "all distinct" and (tag == "circ144" or name == "uniform")
+                assert L.minsum_decode_path(graph, pr, iters, "dynamical", 1.0)[0] == (L.PATH_WG2 if wg2 else L.PATH_WG), (tag, sct, name)
+                assert L.minsum_decode_path(graph, pr, iters, "dynamical", 1.0, flags=L.FLAG_WG_TABLES)[0] == L.PATH_WG
                 for fl in (0, L.FLAG_FIXED_ITERS, L.FLAG_WG_TABLES):
                     got = L.minsum_decode_batch(graph, synd, pr, iters, "dynamical", 1.0, flags=fl)
                     for x, y, what in zip(got, ref, ("err", "conv", "llr", "iter")):
@@ -1134,8 +1141,10 @@ def test_osd0_with_row_transform_in_global_memory(L, oracle, golden, monkeypatch
 
 def test_random_irregular_graphs_all_kernels(Lb, oracle, monkeypatch):
     """Differential sweep over seeded random Tanner graphs (ragged degrees, empty rows, isolated and degree-1 columns, duplicate rows) of
-    sizes that select every decoder: resident (small), workgroup-per-shot generic / lean in LDS and with posteriors in HBM/L2, streaming;
-    random alpha mode, iteration cap, clip, damping and priors (some zero, some negative).  Everything bit-identical to the oracle."""
+    sizes that select every decoder: resident (small), the table form of the workgroup-per-shot decoder (csrc/minsum_wg.hip) generic / lean in LDS
+    and with posteriors in HBM/L2, streaming; random alpha mode, iteration cap, clip, damping and priors (some zero, some negative).  Everything
+    bit-identical to the oracle.  What ran is counted through qldpc_minsum_decode_path.  The priors are all distinct, so the LDS-resident form
+    (csrc/minsum_wg2.hip) never runs here, and row degrees stop at 20: tests/test_wg_shapes_gpu.py covers both."""
     L = Lb
     rng = np.random.default_rng(2026)
     shapes = [(5, 9, 3), (12, 30, 4), (40, 90, 5), (64, 200, 7), (150, 600, 6), (300, 2100, 9), (700, 5000, 12), (1100, 9000, 20)]
@@ -1172,11 +1181,20 @@ def test_random_irregular_graphs_all_kernels(Lb, oracle, monkeypatch):
             for flags, vg in for_build(L, variants, key=lambda v: v[0]):
                 if vg:
                     ran["vg"] += 1
+                path, detail = L.minsum_decode_path(graph, prior, iters, mode, alpha, damping=damping, clip_llr=clip, flags=flags)
+                form = {L.PATH_RESIDENT: "resident", L.PATH_STREAM: "path stream", L.PATH_WG2: "wg2", L.PATH_REGULAR: "regular"}.get(path)
+                if path == L.PATH_WG:
+                    form = "wg " + ("lean" if detail & L.DETAIL_LEAN else "generic") + (" vglobal" if detail & L.DETAIL_VGLOBAL else "")
+                ran[form] = ran.get(form, 0) + 1
+                assert (path == L.PATH_STREAM) == (flags == L.FLAG_KERNEL_STREAM) and bool(detail & L.DETAIL_VGLOBAL) == bool(vg), (gi, trial, flags, path, detail)
                 out = L.minsum_decode_batch(graph, synd, prior, iters, mode, alpha, damping=damping, clip_llr=clip, flags=flags)
                 ran["stream"] += flags == L.FLAG_KERNEL_STREAM
                 for name, a, b in zip(("err", "conv", "llr", "iter"), (out[0], out[1].astype(bool), out[2], out[3]), (ref[0], ref[1].astype(bool), ref[2], ref[3])):
                     assert np.array_equal(a, b, equal_nan=True), (gi, trial, flags, vg, name, mode, damping, clip, iters)
     assert L.BUILD == "experiments" or (ran["vg"] >= 6 and ran["stream"] >= 20)
+    assert "wg2" not in ran and "regular" not in ran, ran
+    for form in ("wg lean", "wg generic") + (() if L.BUILD == "experiments" else ("resident", "wg lean vglobal", "wg generic vglobal", "path stream")):
+        assert ran.get(form, 0) >= 1, (form, ran)
 
 
 def test_degree_one_checks_and_nan_posteriors(Lb, oracle):
