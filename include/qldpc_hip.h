@@ -30,6 +30,8 @@
  *   101  Relay-BP: qldpc_relay_decode_batch[_dev], qldpc_circuit_plan_use_relay; tally slots QLDPC_TALLY_LEGS_Z / _X
  *        additive, same version: OSD-CS, qldpc_osdcs_batch[_dev] and qldpc_circuit_plan_use_osd_cs
  *        additive, same version: qldpc_minsum_decode_path (which decoder form a call takes), QLDPC_PATH_* and QLDPC_DETAIL_*
+ *        additive, same version (the suites pin 101): sliding-window decoding, qldpc_window_decoder_*, qldpc_window_decode_batch[_dev],
+ *        qldpc_circuit_plan_use_window
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -261,6 +263,44 @@ int qldpc_osdcs_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndr
                           const double *d_weights, int order, const int32_t *d_select, const int32_t *d_select_count,
                           int8_t *d_solution, int32_t *d_flips, void *stream);
 
+/* Sliding-window decoding over the row layers of a space-time decoding matrix: min-sum + OSD-0 on W layers at a time, the first C layers
+ * of every window committed.  New here (the reference decodes the whole matrix).  The window graphs do not grow with the number of layers,
+ * so an experiment of any length runs on the kernels a W-layer matrix takes.
+ * Inputs: H = the graph g (m x n), layer_rows (must divide m; Lyr = m / layer_rows), prior[n] (finite, the same for every shot),
+ * window = W >= 1, commit = C with 1 <= C <= W, and max_iter, the alpha mode and clip_llr of qldpc_minsum_decode_batch (damping is 1).
+ *   1. column layers: tau(j) = the smallest row / layer_rows over the rows of column j; a column without rows has tau = 0;
+ *   2. layer span: a column whose rows span more than two consecutive layers (last layer - first layer > 1) is rejected at creation
+ *      with QLDPC_ERR_INVALID;
+ *   3. windows: window k starts at layer a_k = k C and covers the layers [a_k, min(a_k + W, Lyr)); the last window is the first one with
+ *      a_k + W >= Lyr;
+ *   4. window graph: the rows of the covered layers and the columns with tau in the covered range, in ascending original index; entries
+ *      in rows beyond the window are dropped (only columns of the window's top layer can lose entries); the window prior is the prior of
+ *      those columns.  Windows whose CSR and prior slice are equal share one graph handle (compared, not assumed);
+ *   5. per shot, running syndrome r = s; for window k in order: (a) qldpc_minsum_decode_batch of the window graph on r restricted to
+ *      its rows (the reference's early exit); (b) if it did not converge, qldpc_osd0_batch (ordering = NULL) on its posteriors, including
+ *      OSD-0's defined answer for a right-hand side outside the column space -- an earlier commit that differs from the true faults can
+ *      leave such a residual; (c) commit the columns with tau in [a_k, a_k + C), in the last window all of its columns: err[j] = the
+ *      window's decision; (d) r ^= H[:, committed] e_committed over the FULL columns (at most one layer above the commit region);
+ *   6. outputs per shot: err int8[n]; conv = windows in which min-sum converged; iters = sum over windows of (final_iter + 1), what the
+ *      circuit plan's judge counts per decode; osd = windows sent to OSD-0; unsat = 1 iff H err != s;
+ *   7. with W >= Lyr there is one window, the whole graph: err is qldpc_minsum_decode_batch + qldpc_osd0_batch bit for bit.
+ * QLDPC_ERR_UNSUPPORTED for a window without columns.  flags: the QLDPC_FLAG_* selectors of the decode and OSD-0 calls (results never
+ * depend on them).  The decoder owns its window graphs and device workspaces; calls on one decoder serialise (a mutex while enqueuing, an
+ * event between streams).  qldpc_window_decoder_info: number of windows, of distinct graph handles, rows and columns of the largest window,
+ * and how many windows take the LDS-resident workgroup decoder (QLDPC_PATH_WG2); any output may be NULL. */
+typedef struct qldpc_window_decoder qldpc_window_decoder;
+int qldpc_window_decoder_create(const qldpc_graph *g, int layer_rows, int window, int commit, const double *prior, int max_iter,
+                                int alpha_mode, double alpha_val, const double *alpha_seq, int alpha_len, double clip_llr, int flags,
+                                qldpc_window_decoder **out);
+void qldpc_window_decoder_destroy(qldpc_window_decoder *wd);
+int qldpc_window_decoder_info(const qldpc_window_decoder *wd, int *windows, int *graphs, int *max_rows, int *max_cols, int *wg2_windows);
+/* host pointers: syndromes int8[B][m] -> err int8[B][n], conv / iters / osd int32[B], unsat uint8[B]; returns when they are complete */
+int qldpc_window_decode_batch(qldpc_window_decoder *wd, int64_t B, const int8_t *syndromes, int8_t *err, int32_t *conv, int32_t *iters,
+                              int32_t *osd, uint8_t *unsat);
+/* same on device pointers; only enqueues on `stream` (the first call for a larger B than any before allocates workspaces) */
+int qldpc_window_decode_batch_dev(qldpc_window_decoder *wd, int64_t B, const int8_t *d_syndromes, int8_t *d_err, int32_t *d_conv,
+                                  int32_t *d_iters, int32_t *d_osd, uint8_t *d_unsat, void *stream);
+
 /* a10: generate_noisy_circuit_jit (src/noise/kernels.py:175-353), batched over B draws of explicit random
  * arrays rv/rp/rt [B][n_locs]; out_* [B][cap]; out_len int64[B]. */
 int qldpc_noisy_circuit_batch(int64_t B, int64_t len, const int32_t *ops, const int32_t *q1, const int32_t *q2, double p,
@@ -399,6 +439,14 @@ int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *plan, double alpha, double 
  * Relay-BP (and qldpc_circuit_plan_use_relay after this call returns QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is
  * outside the range of qldpc_osdcs_batch. */
 int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *plan, int order);
+/* Switches the BP + OSD-0 stage of both sectors to sliding-window decoding (one-way): a qldpc_window_decoder per sector with the plan's
+ * prior, alpha schedule, max_iter and clip_llr, layer_rows = the sector's number of checks (num_x_checks for sector Z, num_z_checks for
+ * sector X: one layer per syndrome cycle).  Sampler, judge and tally are unchanged; bp_conv_* counts the trials in which every window
+ * converged, osd_* the trials with at least one OSD-0 window, iters_* and unsat_* as before.  The phase times keep their brackets: BP_* sums
+ * gather + min-sum over the windows, OSD_* collect + OSD-0 + commit.  QLDPC_ERR_INVALID on a plan created with use_osd = 0 or damping != 1,
+ * switched to Relay-BP or OSD-CS, or already windowed (and qldpc_circuit_plan_use_relay / _use_osd_cs after this call return
+ * QLDPC_ERR_INVALID); otherwise what qldpc_window_decoder_create returns. */
+int qldpc_circuit_plan_use_window(qldpc_circuit_plan *plan, int window, int commit);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

@@ -456,6 +456,68 @@ def relay_decode_batch(graph, syndromes, prior, seed, shot_begin=0, tag=0, **par
     return err, conv, legs, iters, sols
 
 
+def check_window_args(layer_rows, window, commit, m=None):
+    """ValueError unless window >= 1, 1 <= commit <= window and layer_rows >= 1 (dividing m when m is given) -> the three as ints."""
+    for name, v in (("layer_rows", layer_rows), ("window", window), ("commit", commit)):
+        if int(v) != v:
+            raise ValueError(f"{name} must be an integer")
+    layer_rows, window, commit = int(layer_rows), int(window), int(commit)
+    if window < 1 or not 1 <= commit <= window:
+        raise ValueError(f"need window >= 1 and 1 <= commit <= window (got window={window}, commit={commit})")
+    if layer_rows < 1 or (m is not None and (m < 1 or m % layer_rows)):
+        raise ValueError(f"layer_rows={layer_rows} does not divide the {m} rows")
+    return layer_rows, window, commit
+
+
+class WindowDecoder:
+    """Owning wrapper of a qldpc_window_decoder (sliding-window min-sum + OSD-0 over the row layers of `graph`; semantics in include/qldpc_hip.h)."""
+
+    def __init__(self, graph, layer_rows, window, commit, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, flags=0):
+        layer_rows, window, commit = check_window_args(layer_rows, window, commit, graph.m)
+        mode, aval, seq = alpha_args(alpha_mode, alpha)
+        prior = f64(prior).reshape(-1)
+        if prior.size != graph.n:
+            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        if not np.isfinite(prior).all():
+            raise ValueError("sliding-window decoding needs a finite prior")
+        self.graph = graph                     # keeps the full graph alive as long as the decoder
+        self._h = C.c_void_p()
+        check(lib().qldpc_window_decoder_create(graph.handle, layer_rows, window, commit, ptr(prior, C.c_double), int(max_iter), mode, aval,
+                                                ptr(seq, C.c_double), seq.size, float(clip_llr), int(flags), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        """{windows, graphs (distinct handles), max_rows, max_cols (of the largest window), wg2_windows (windows on the LDS-resident decoder)}"""
+        v = [C.c_int(0) for _ in range(5)]
+        check(lib().qldpc_window_decoder_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("windows", "graphs", "max_rows", "max_cols", "wg2_windows"), (x.value for x in v)))
+
+    def decode(self, syndromes):
+        """int8[B, m] -> (err int8[B, n], conv int32[B], iters int32[B], osd int32[B], unsat uint8[B])"""
+        syndromes = i8(syndromes).reshape(-1, self.graph.m)
+        B = syndromes.shape[0]
+        err = np.zeros((B, self.graph.n), np.int8)
+        conv, iters, osd = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        unsat = np.zeros(B, np.uint8)
+        check(lib().qldpc_window_decode_batch(self._h, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(err, C.c_int8), ptr(conv, C.c_int32),
+                                              ptr(iters, C.c_int32), ptr(osd, C.c_int32), ptr(unsat, C.c_uint8)))
+        return err, conv, iters, osd, unsat
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib().qldpc_window_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def osd_timers(reset=True):
     """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/osd_common.h) -> uint64[32]."""
     out = np.zeros(32, np.uint64)
@@ -706,6 +768,13 @@ class CircuitPlan:
             raise ValueError(f"OSD-CS order must be in 0..{OSDCS_MAX_ORDER}, got {order}")
         check(lib().qldpc_circuit_plan_use_osd_cs(self._h, order))
         self.osd_cs_order = order
+
+    def use_window(self, window, commit):
+        """Decode both sectors window by window from now on: `window` syndrome cycles at a time, the first `commit` of them committed
+        (one-way; qldpc_circuit_plan_use_window)."""
+        _, window, commit = check_window_args(1, window, commit)
+        check(lib().qldpc_circuit_plan_use_window(self._h, window, commit))
+        self.window = (window, commit)
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))

@@ -267,6 +267,10 @@ struct qldpc_circuit_plan {
     // qldpc_circuit_plan_use_osd_cs: the OSD stage runs OSD-CS of this order (osd_cs.hip) instead of OSD-0; -1 = OSD-0
     int cs_order = -1;
     DevBuf d_flips_z, d_flips_x;
+    // qldpc_circuit_plan_use_window: both sectors go through a sliding-window decoder (window.hip) instead of one BP + OSD-0 over the whole matrix
+    qldpc_window_decoder *win[2] = {nullptr, nullptr};
+    int layer_rows[2] = {0, 0};                    // rows per syndrome cycle of sector Z / X
+    std::vector<double> h_alpha_z, h_alpha_x;      // the alpha tables on the host (the window decoders take them at the switch)
     std::vector<DevBuf *> all() {
         return {&d_loc_type, &d_zptr, &d_zidx, &d_zlog, &d_xptr, &d_xidx, &d_xlog, &d_alpha_z, &d_alpha_x, &d_prior_z, &d_prior_x, &d_lm_z, &d_lm_x,
                 &d_syn_z, &d_syn_x, &d_true_z, &d_true_x, &d_det_z, &d_det_x, &d_llr_z, &d_llr_x, &d_conv_z, &d_conv_x, &d_iter_z, &d_iter_x,
@@ -469,12 +473,14 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
     P->gz = gz; P->gx = gx; P->device = gz->device; P->k = D->k; P->n_locs = (int)loc_op.size(); P->nsx = nsx; P->nsz = nsz;
     P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->p = p; P->damping = damping; P->clip = clip_llr; P->batch = batch;
     P->thr = bernoulli_threshold(p);
+    P->layer_rows[0] = D->num_x_checks; P->layer_rows[1] = D->num_z_checks;
     std::vector<double> az, ax;
     if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val_z, alpha_seq_z, alpha_len_z, az)) != QLDPC_OK) return fail(rc);
     if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val_x, alpha_seq_x, alpha_len_x, ax)) != QLDPC_OK) return fail(rc);
     // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
     // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
     P->nanfree = inputs_clean(prior_z, gz->n, clip_llr, az.data(), max_iter) && inputs_clean(prior_x, gx->n, clip_llr, ax.data(), max_iter);
+    P->h_alpha_z = az; P->h_alpha_x = ax;
     std::vector<int32_t> zp, xp;
     std::vector<uint16_t> zi, xi;
     std::vector<uint64_t> zl, xl;
@@ -531,6 +537,11 @@ static int decode_sector(qldpc_circuit_plan *P, const qldpc_graph *g, int64_t B,
         }
         if (rc != QLDPC_OK) return rc;
         return phase_mark(P, ph_bp, s, false);
+    }
+    if (P->win[sector]) {              // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
+        const WindowPlanSlots slots{conv.as<uint8_t>(), iter.as<int32_t>(), count};
+        const std::function<int(int, bool)> mark = [&](int part, bool open) { return phase_mark(P, part ? ph_osd : ph_bp, s, open); };
+        return window_decoder_lock_and_launch(P->win[sector], B, syn.as<int8_t>(), det.as<int8_t>(), &slots, &mark, s);
     }
     unsigned long long *clk = (P->flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr;
     if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
@@ -694,6 +705,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alph
                                              int max_legs, int stop_after) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(P->cs_order < 0, "the plan's OSD stage was switched to OSD-CS: Relay-BP replaces BP + OSD and cannot follow");
+    QLDPC_REQUIRE(!P->win[0], "the plan was switched to sliding-window decoding: Relay-BP replaces BP + OSD and cannot follow");
     const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
     int rc = relay_check_params(rp);
     if (rc != QLDPC_OK) return rc;
@@ -712,6 +724,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order)
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: there is no OSD stage to switch");
     QLDPC_REQUIRE(!P->relay, "the plan was switched to Relay-BP, which has no OSD stage");
+    QLDPC_REQUIRE(!P->win[0], "the plan was switched to sliding-window decoding, whose windows end in OSD-0");
     int rc = osdcs_check_order(order);
     if (rc != QLDPC_OK) return rc;
     for (double v : P->h_prior_z) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-Z prior is not finite");
@@ -723,9 +736,28 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order)
     return QLDPC_OK;
 }
 
+QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window, int commit) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: a window that does not converge needs the OSD stage");
+    QLDPC_REQUIRE(!P->relay, "the plan was switched to Relay-BP: windows decode with BP + OSD-0");
+    QLDPC_REQUIRE(P->cs_order < 0, "the plan's OSD stage was switched to OSD-CS: windows decode with BP + OSD-0");
+    QLDPC_REQUIRE(!P->win[0], "the plan is already windowed");
+    QLDPC_REQUIRE(P->damping == 1.0, "sliding-window decoding needs damping = 1 (the plan has %g)", P->damping);
+    QLDPC_USE_DEVICE(P->device);
+    qldpc_window_decoder *w[2] = {nullptr, nullptr};
+    for (int sector = 0; sector < 2; sector++) {
+        const int rc = window_decoder_create_tab(sector ? P->gx : P->gz, P->layer_rows[sector], window, commit, (sector ? P->h_prior_x : P->h_prior_z).data(),
+                                                 P->max_iter, sector ? P->h_alpha_x : P->h_alpha_z, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &w[sector]);
+        if (rc != QLDPC_OK) { qldpc_window_decoder_destroy(w[0]); return rc; }
+    }
+    P->win[0] = w[0]; P->win[1] = w[1];
+    return QLDPC_OK;
+}
+
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {
     if (!P) return;
     (void)hipSetDevice(P->device);
+    for (int sector = 0; sector < 2; sector++) qldpc_window_decoder_destroy(P->win[sector]);
     if (P->side) { (void)hipStreamSynchronize(P->side); (void)hipStreamDestroy(P->side); }
     if (P->ev_sampled) (void)hipEventDestroy(P->ev_sampled);
     if (P->ev_x_done) (void)hipEventDestroy(P->ev_x_done);

@@ -8,9 +8,11 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <functional>
 #include <vector>
 
 struct qldpc_graph;
+struct qldpc_window_decoder;
 
 namespace qldpc {
 
@@ -73,6 +75,14 @@ int osdcs_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32
                         const double *d_llr, const int8_t *d_hard, const double *d_weights, int order, int8_t *d_solution, int32_t *d_flips,
                         hipStream_t stream);
 int osdcs_check_order(int order);
+// Sliding-window decoding (window.hip) inside a circuit plan.  create_tab: qldpc_window_decoder_create on a ready alpha table.  lock_and_launch enqueues
+// the window loop for B shots; the last window's commit fills the plan's per-trial slots: conv = 1 iff every window converged, iter = iterations - 1 (the
+// judge adds one per trial), *osd_count += 1 per trial with an OSD-0 window.  mark(0 / 1, open) brackets the BP and the OSD + commit part of every window.
+struct WindowPlanSlots { uint8_t *conv; int32_t *iter; int32_t *osd_count; };
+int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, int commit, const double *prior, int max_iter,
+                              const std::vector<double> &tab, double clip_llr, int flags, qldpc_window_decoder **out);
+int window_decoder_lock_and_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, const WindowPlanSlots *plan,
+                                   const std::function<int(int, bool)> *mark, hipStream_t s);
 int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
 
 }  // namespace qldpc

@@ -32,6 +32,10 @@ plan's OSD stage, with the plan's priors as the weights.  Here ``osd_order`` is 
 reliable non-pivot columns), not the reference's OSD-w order.  The alpha / SCOPT estimators run as for ``"bp_osd"``; ``relay_params`` raises
 ValueError.  OSD-CS returns OSD-0's answer wherever the syndrome is not reproducible, so no OSD-w pass follows.  The result also holds
 ``decoder`` and ``osd_order``.
+
+``window=(W, C)`` (an extension; ``decoder="bp_osd"`` with ``osd_order=0`` only, anything else raises ValueError) decodes both sectors with the
+sliding-window decoder (``decoding/window.py``): W syndrome cycles at a time, the first C of them committed, min-sum + OSD-0 per window.  The
+window graphs do not grow with ``num_cycles``.  The result also holds ``window``.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -61,9 +65,15 @@ def _estimation_trials(requested, n_cols, error_rate):
 def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
-                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, **bb_params):
+                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
+    if window is not None:
+        if decoder != "bp_osd" or osd_order != 0:
+            raise ValueError("window=(W, C) goes with decoder='bp_osd' and osd_order=0 only")
+        if not isinstance(window, (tuple, list)) or len(window) != 2:
+            raise ValueError("window must be a pair (W, C)")
+        window = _lib.check_window_args(1, window[0], window[1])[1:]
     if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs"):
         raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp' or 'bp_osd_cs')")
     relay = decoder == "relay_bp"
@@ -186,6 +196,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                 self.plan.use_relay(**relay_params)
             if osd_cs:
                 self.plan.use_osd_cs(int(osd_order))
+            if window is not None:
+                self.plan.use_window(*window)
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -322,5 +334,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                       mean_legs_x=float(total[T["legs_x"]]) / trials)
     if osd_cs:
         result.update(decoder=decoder, osd_order=int(osd_order))
+    if window is not None:
+        result.update(window=tuple(window))
     result["tally"] = total
     return result
