@@ -411,8 +411,8 @@ int qldpc_circuit_plan_run_outcomes(qldpc_circuit_plan *plan, uint64_t seed, int
                                     uint8_t *outcome);
 int qldpc_circuit_plan_read(qldpc_circuit_plan *plan, void *stream, int clear, int64_t *tally);
 /* hipEvent time (ms, summed over the batches enqueued since the last call) of each phase of the per-trial pipeline of
- * src/simulation/engine.py:68-122, and the number of batches.  Sector X runs on the plan's own stream beside sector Z (unless the plan
- * was created with QLDPC_FLAG_MC_UNFUSED), so the phase spans overlap and their sum exceeds the wall time. */
+ * src/simulation/engine.py:68-122, and the number of batches.  The phases of a batch run back to back on the caller's stream (sample, sector Z,
+ * sector X, judge), so their spans do not overlap. */
 #define QLDPC_CIRCUIT_PHASES 6
 #define QLDPC_PHASE_SAMPLE 0   /* run_trial_fast, engine.py:75 */
 #define QLDPC_PHASE_BP_Z 1     /* engine.py:84-94 */

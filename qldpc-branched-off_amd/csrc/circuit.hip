@@ -238,45 +238,51 @@ __global__ void collect_failed2_kernel(int64_t B, const uint8_t *__restrict__ co
 
 using namespace qldpc;
 
+// A DevBuf that the plan owns: released when the plan is deleted, so a buffer added below needs no line anywhere else.
+struct PlanBuf : DevBuf {
+    PlanBuf() = default;
+    PlanBuf(const PlanBuf &) = delete;
+    PlanBuf &operator=(const PlanBuf &) = delete;
+    ~PlanBuf() { release(); }
+};
+
+// The decoder of both sectors.  A plan is created as BP_OSD0 (BP alone with use_osd = 0); qldpc_circuit_plan_use_* moves it (switch_allowed).
+enum class Decoder { BP_OSD0, BP_OSD_CS, RELAY, WINDOW };
+
 struct qldpc_circuit_plan {
-    const qldpc_graph *gz = nullptr, *gx = nullptr;
-    int device = 0, k = 0, n_locs = 0, nsx = 0, nsz = 0, max_iter = 0, use_osd = 0, flags = 0;
+    // Everything that exists once per sector: sec[0] = Z, sec[1] = X.  A batch decodes Z, then X, on the caller's stream.
+    struct Sector {
+        const qldpc_graph *g = nullptr;
+        int nsyn = 0, layer_rows = 0;              // detectors (= rows of g); rows per syndrome cycle
+        // on the host: the prior lets the decode dispatch pick the LDS-resident workgroup kernel (minsum_wg2.hip), the window decoder takes both at the switch
+        std::vector<double> h_prior, h_alpha;
+        qldpc_window_decoder *win = nullptr;       // Decoder::WINDOW (window.hip)
+        PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
+        PlanBuf d_alpha, d_prior, d_lm;
+        PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
+        PlanBuf d_legs;                            // Decoder::RELAY: legs per trial
+        PlanBuf d_flips;                           // Decoder::BP_OSD_CS: workspace of the sweep
+    } sec[2];
+    int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
     double p = 0, damping = 1, clip = 20;
     uint32_t thr = 0;
     int64_t batch = 0;
     bool nanfree = false;
-    std::vector<double> h_prior_z, h_prior_x;      // the priors on the host: what lets the decode dispatch pick the LDS-resident workgroup kernel (minsum_wg2.hip)
-    DevBuf d_loc_type, d_zptr, d_zidx, d_zlog, d_xptr, d_xidx, d_xlog;
-    DevBuf d_alpha_z, d_alpha_x, d_prior_z, d_prior_x, d_lm_z, d_lm_x;
-    DevBuf d_syn_z, d_syn_x, d_true_z, d_true_x, d_det_z, d_det_x, d_llr_z, d_llr_x, d_conv_z, d_conv_x, d_iter_z, d_iter_x;
-    DevBuf d_list_z, d_list_x, d_count, d_tally, d_outcome, d_clk;    // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
-    // The two sectors are independent between the sampler and the judge: sector X runs on the plan's own stream so its decode fills the CUs the
-    // tail of sector Z's OSD launch leaves idle (and vice versa); QLDPC_FLAG_MC_UNFUSED keeps everything on the caller's stream.
-    hipStream_t side = nullptr;
-    hipEvent_t ev_sampled = nullptr, ev_x_done = nullptr;
+    PlanBuf d_loc_type, d_count, d_tally, d_outcome, d_clk;    // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
+    Decoder decoder = Decoder::BP_OSD0;
+    RelayParams rp{};                              // Decoder::RELAY (relay_bp.hip)
+    int cs_order = 0;                              // Decoder::BP_OSD_CS (osd_cs.hip)
     // hipEvent brackets of the phases of every batch not yet read by qldpc_circuit_plan_phase_times
     struct Bracket { int phase; hipEvent_t a, b; };
     std::vector<Bracket> pending;
     std::vector<hipEvent_t> pool;
     double phase_ms[QLDPC_CIRCUIT_PHASES] = {0, 0, 0, 0, 0, 0};
     int64_t batches = 0;
-    // qldpc_circuit_plan_use_relay: both sectors go through the Relay-BP kernel instead of BP + OSD-0 (relay_bp.hip)
-    bool relay = false;
-    RelayParams rp{};
-    DevBuf d_legs_z, d_legs_x;
-    // qldpc_circuit_plan_use_osd_cs: the OSD stage runs OSD-CS of this order (osd_cs.hip) instead of OSD-0; -1 = OSD-0
-    int cs_order = -1;
-    DevBuf d_flips_z, d_flips_x;
-    // qldpc_circuit_plan_use_window: both sectors go through a sliding-window decoder (window.hip) instead of one BP + OSD-0 over the whole matrix
-    qldpc_window_decoder *win[2] = {nullptr, nullptr};
-    int layer_rows[2] = {0, 0};                    // rows per syndrome cycle of sector Z / X
-    std::vector<double> h_alpha_z, h_alpha_x;      // the alpha tables on the host (the window decoders take them at the switch)
-    std::vector<DevBuf *> all() {
-        return {&d_loc_type, &d_zptr, &d_zidx, &d_zlog, &d_xptr, &d_xidx, &d_xlog, &d_alpha_z, &d_alpha_x, &d_prior_z, &d_prior_x, &d_lm_z, &d_lm_x,
-                &d_syn_z, &d_syn_x, &d_true_z, &d_true_x, &d_det_z, &d_det_x, &d_llr_z, &d_llr_x, &d_conv_z, &d_conv_x, &d_iter_z, &d_iter_x,
-                &d_list_z, &d_list_x, &d_count, &d_tally, &d_outcome, &d_clk, &d_legs_z, &d_legs_x, &d_flips_z, &d_flips_x};
-    }
+    int32_t *fail_count(int sector) { return d_count.as<int32_t>() + 4 * sector; }
+    bool osd_stage() const { return use_osd && decoder != Decoder::RELAY; }      // the judge then adds d_count to the OSD tally slots
 };
+using Sector = qldpc_circuit_plan::Sector;
+static const int kPhaseBp[2] = {QLDPC_PHASE_BP_Z, QLDPC_PHASE_BP_X}, kPhaseOsd[2] = {QLDPC_PHASE_OSD_Z, QLDPC_PHASE_OSD_X};
 
 static hipEvent_t plan_event(qldpc_circuit_plan *P) {
     if (!P->pool.empty()) { hipEvent_t e = P->pool.back(); P->pool.pop_back(); return e; }
@@ -325,24 +331,31 @@ static int up(DevBuf &b, const std::vector<T> &v) {
     return QLDPC_OK;
 }
 
+// What the descriptor holds for one sector (0 = Z: the X checks measure it; 1 = X): the checks' measurements, checks, detectors, logicals.
+struct SectorDesc { const int32_t *spos, *sptr; int nchk, nsyn; const uint8_t *L; };
+static SectorDesc sector_desc(const qldpc_circuit_desc *D, int sector) {
+    if (sector) return {D->z_syn_positions, D->z_syn_ptrs, D->num_z_checks, D->z_syn_ptrs[D->num_z_checks], D->Lz};
+    return {D->x_syn_positions, D->x_syn_ptrs, D->num_x_checks, D->x_syn_ptrs[D->num_x_checks], D->Lx};
+}
+
 // Builds the per-(location, slot) signatures of one sector with the batched single-fault frame simulation.
-static int build_signatures(const qldpc_circuit_desc *D, bool xsector, const std::vector<int32_t> &loc_op, const std::vector<int32_t> &ops,
-                            const std::vector<int32_t> &q1, const std::vector<int32_t> &q2, std::vector<int32_t> &ptr, std::vector<uint16_t> &idx,
-                            std::vector<uint64_t> &logm) {
-    const int n_locs = (int)loc_op.size(), nl = 2 * n_locs, tq = D->total_qubits;
-    const int32_t *spos = xsector ? D->z_syn_positions : D->x_syn_positions, *sptr = xsector ? D->z_syn_ptrs : D->x_syn_ptrs;
-    const int nchk = xsector ? D->num_z_checks : D->num_x_checks;
-    const int nsyn = sptr[nchk];
-    const uint8_t *L = xsector ? D->Lz : D->Lx;
+// Every base op is an error location (kernels.py:206-351 visits them in order); the frames run through the base circuit and its suffix.
+static int build_signatures(const qldpc_circuit_desc *D, int sector, std::vector<int32_t> &ptr, std::vector<uint16_t> &idx, std::vector<uint64_t> &logm) {
+    std::vector<int32_t> ops(D->base_ops, D->base_ops + D->base_len), q1(D->base_q1, D->base_q1 + D->base_len), q2(D->base_q2, D->base_q2 + D->base_len);
+    ops.insert(ops.end(), D->suffix_ops, D->suffix_ops + D->suffix_len);
+    q1.insert(q1.end(), D->suffix_q1, D->suffix_q1 + D->suffix_len);
+    q2.insert(q2.end(), D->suffix_q2, D->suffix_q2 + D->suffix_len);
+    const int n_locs = (int)D->base_len, nl = 2 * n_locs, tq = D->total_qubits;
+    const auto [spos, sptr, nchk, nsyn, L] = sector_desc(D, sector);
     std::vector<int32_t> lane_pos(nl), lane_q(nl);
     std::vector<int8_t> lane_after(nl);
     for (int l = 0; l < n_locs; l++) {
-        const int i = loc_op[l], op = D->base_ops[i];
+        const int op = D->base_ops[l];
         for (int s = 0; s < 2; s++) {
             const int e = 2 * l + s;
-            lane_pos[e] = i;
+            lane_pos[e] = l;
             lane_after[e] = (op == C_OP_PREP_X || op == C_OP_PREP_Z || op == C_OP_CNOT) ? 1 : 0;      // Meas: before; Idle: either
-            lane_q[e] = (s == 0) ? D->base_q1[i] : (op == C_OP_CNOT ? D->base_q2[i] : -1);
+            lane_q[e] = (s == 0) ? D->base_q1[l] : (op == C_OP_CNOT ? D->base_q2[l] : -1);
         }
     }
     DevTmp dpos, dafter, dq, dops, dq1, dq2, dstate, dhist;
@@ -359,7 +372,7 @@ static int build_signatures(const qldpc_circuit_desc *D, bool xsector, const std
     QLDPC_HIP_TRY(hipMemcpy(dq2.p, q2.data(), len * 4, hipMemcpyHostToDevice));
     QLDPC_HIP_TRY(zero_now(dhist.p, (size_t)nsyn * nl));
     const unsigned grid = (unsigned)((nl + 255) / 256);
-    if (xsector)
+    if (sector)
         hipLaunchKernelGGL(fault_signature_kernel<true>, dim3(grid), dim3(256), 0, nullptr, nl, dpos.as<int32_t>(), dafter.as<int8_t>(), dq.as<int32_t>(),
                            (int64_t)len, dops.as<int32_t>(), dq1.as<int32_t>(), dq2.as<int32_t>(), tq, nsyn, dstate.as<int8_t>(), dhist.as<int8_t>());
     else
@@ -424,16 +437,10 @@ QLDPC_EXPORT int qldpc_circuit_fault_signatures(const qldpc_circuit_desc *D, int
     if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(ptr && logmask && idx_needed && (idx || idx_cap == 0), "NULL output");
     QLDPC_USE_DEVICE(0);
-    std::vector<int32_t> ops(D->base_ops, D->base_ops + D->base_len), q1(D->base_q1, D->base_q1 + D->base_len), q2(D->base_q2, D->base_q2 + D->base_len);
-    ops.insert(ops.end(), D->suffix_ops, D->suffix_ops + D->suffix_len);
-    q1.insert(q1.end(), D->suffix_q1, D->suffix_q1 + D->suffix_len);
-    q2.insert(q2.end(), D->suffix_q2, D->suffix_q2 + D->suffix_len);
-    std::vector<int32_t> loc_op(D->base_len);
-    for (int64_t i = 0; i < D->base_len; i++) loc_op[i] = (int32_t)i;
     std::vector<int32_t> p;
     std::vector<uint16_t> ix;
     std::vector<uint64_t> lm;
-    if ((rc = build_signatures(D, sector_is_x != 0, loc_op, ops, q1, q2, p, ix, lm)) != QLDPC_OK) return rc;
+    if ((rc = build_signatures(D, sector_is_x != 0, p, ix, lm)) != QLDPC_OK) return rc;
     *idx_needed = (int64_t)ix.size();
     QLDPC_REQUIRE((int64_t)ix.size() <= idx_cap, "idx buffer too small: need %lld entries", (long long)ix.size());
     std::memcpy(ptr, p.data(), p.size() * sizeof(int32_t));
@@ -455,117 +462,107 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
     QLDPC_REQUIRE(p > 0.0 && p < 1.0, "error rate must be in (0,1)");
     QLDPC_REQUIRE(batch > 0 && batch <= (1 << 24), "batch out of range");
     QLDPC_REQUIRE(gz->device == gx->device, "both sector graphs must live on the same device");
-    const int nsx = D->x_syn_ptrs[D->num_x_checks], nsz = D->z_syn_ptrs[D->num_z_checks];
-    QLDPC_REQUIRE(gz->m == nsx && gx->m == nsz, "decoding matrices have %d / %d rows but the circuit measures %d X / %d Z syndromes", gz->m, gx->m, nsx, nsz);
-    QLDPC_REQUIRE(nsx < 65536 && nsz < 65536, "too many detectors for 16-bit signature indices");
+    const SectorDesc sd[2] = {sector_desc(D, 0), sector_desc(D, 1)};
+    QLDPC_REQUIRE(gz->m == sd[0].nsyn && gx->m == sd[1].nsyn, "decoding matrices have %d / %d rows but the circuit measures %d X / %d Z syndromes", gz->m,
+                  gx->m, sd[0].nsyn, sd[1].nsyn);
+    QLDPC_REQUIRE(sd[0].nsyn < 65536 && sd[1].nsyn < 65536, "too many detectors for 16-bit signature indices");
     QLDPC_USE_DEVICE(gz->device);
-
-    std::vector<int32_t> ops(D->base_ops, D->base_ops + D->base_len), q1(D->base_q1, D->base_q1 + D->base_len), q2(D->base_q2, D->base_q2 + D->base_len);
-    ops.insert(ops.end(), D->suffix_ops, D->suffix_ops + D->suffix_len);
-    q1.insert(q1.end(), D->suffix_q1, D->suffix_q1 + D->suffix_len);
-    q2.insert(q2.end(), D->suffix_q2, D->suffix_q2 + D->suffix_len);
-    std::vector<int32_t> loc_op;               // every base op is an error location (kernels.py:206-351 visits them in order)
-    std::vector<uint8_t> loc_type;
-    for (int64_t i = 0; i < D->base_len; i++) { loc_op.push_back((int32_t)i); loc_type.push_back((uint8_t)D->base_ops[i]); }
+    const std::vector<uint8_t> loc_type(D->base_ops, D->base_ops + D->base_len);      // error location l = base op l
 
     qldpc_circuit_plan *P = new qldpc_circuit_plan();
     auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
-    P->gz = gz; P->gx = gx; P->device = gz->device; P->k = D->k; P->n_locs = (int)loc_op.size(); P->nsx = nsx; P->nsz = nsz;
+    P->device = gz->device; P->k = D->k; P->n_locs = (int)loc_type.size();
     P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->p = p; P->damping = damping; P->clip = clip_llr; P->batch = batch;
     P->thr = bernoulli_threshold(p);
-    P->layer_rows[0] = D->num_x_checks; P->layer_rows[1] = D->num_z_checks;
-    std::vector<double> az, ax;
-    if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val_z, alpha_seq_z, alpha_len_z, az)) != QLDPC_OK) return fail(rc);
-    if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val_x, alpha_seq_x, alpha_len_x, ax)) != QLDPC_OK) return fail(rc);
-    // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
-    // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
-    P->nanfree = inputs_clean(prior_z, gz->n, clip_llr, az.data(), max_iter) && inputs_clean(prior_x, gx->n, clip_llr, ax.data(), max_iter);
-    P->h_alpha_z = az; P->h_alpha_x = ax;
-    std::vector<int32_t> zp, xp;
-    std::vector<uint16_t> zi, xi;
-    std::vector<uint64_t> zl, xl;
-    if ((rc = build_signatures(D, false, loc_op, ops, q1, q2, zp, zi, zl)) != QLDPC_OK) return fail(rc);
-    if ((rc = build_signatures(D, true, loc_op, ops, q1, q2, xp, xi, xl)) != QLDPC_OK) return fail(rc);
-    if ((rc = up(P->d_loc_type, loc_type)) || (rc = up(P->d_zptr, zp)) || (rc = up(P->d_zidx, zi)) || (rc = up(P->d_zlog, zl)) || (rc = up(P->d_xptr, xp)) ||
-        (rc = up(P->d_xidx, xi)) || (rc = up(P->d_xlog, xl)) || (rc = up(P->d_alpha_z, az)) || (rc = up(P->d_alpha_x, ax)))
-        return fail(rc);
-    std::vector<double> pz(prior_z, prior_z + gz->n), px(prior_x, prior_x + gx->n);
-    P->h_prior_z = pz; P->h_prior_x = px;
-    std::vector<uint64_t> lz(logmask_z, logmask_z + gz->n), lx(logmask_x, logmask_x + gx->n);
-    if ((rc = up(P->d_prior_z, pz)) || (rc = up(P->d_prior_x, px)) || (rc = up(P->d_lm_z, lz)) || (rc = up(P->d_lm_x, lx))) return fail(rc);
+    const qldpc_graph *const graph[2] = {gz, gx};
+    const double *const prior[2] = {prior_z, prior_x}, *const alpha_seq[2] = {alpha_seq_z, alpha_seq_x};
+    const double alpha_val[2] = {alpha_val_z, alpha_val_x};
+    const uint64_t *const logmask[2] = {logmask_z, logmask_x};
+    const int alpha_len[2] = {alpha_len_z, alpha_len_x};
     const size_t Bz = (size_t)batch;
-    if ((rc = P->d_syn_z.ensure(Bz * nsx)) || (rc = P->d_syn_x.ensure(Bz * nsz)) || (rc = P->d_true_z.ensure(Bz * 8)) || (rc = P->d_true_x.ensure(Bz * 8)) ||
-        (rc = P->d_det_z.ensure(Bz * gz->n)) || (rc = P->d_det_x.ensure(Bz * gx->n)) || (rc = P->d_llr_z.ensure(Bz * gz->n * 8)) ||
-        (rc = P->d_llr_x.ensure(Bz * gx->n * 8)) || (rc = P->d_conv_z.ensure(Bz)) || (rc = P->d_conv_x.ensure(Bz)) || (rc = P->d_iter_z.ensure(Bz * 4)) ||
-        (rc = P->d_iter_x.ensure(Bz * 4)) || (rc = P->d_list_z.ensure(Bz * 4)) || (rc = P->d_list_x.ensure(Bz * 4)) || (rc = P->d_count.ensure(64)) ||
-        (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) || (rc = P->d_clk.ensure(2 * kClkSlots * 16)))
+    P->nanfree = true;
+    for (int i = 0; i < 2; i++) {
+        Sector &S = P->sec[i];
+        const size_t n = (size_t)graph[i]->n;
+        S.g = graph[i]; S.nsyn = sd[i].nsyn; S.layer_rows = sd[i].nchk;
+        if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], S.h_alpha)) != QLDPC_OK) return fail(rc);
+        S.h_prior.assign(prior[i], prior[i] + n);
+        // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
+        // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
+        P->nanfree = P->nanfree && inputs_clean(prior[i], (int)n, clip_llr, S.h_alpha.data(), max_iter);
+        std::vector<int32_t> sp;
+        std::vector<uint16_t> si;
+        std::vector<uint64_t> sl;
+        if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK) return fail(rc);
+        const std::vector<uint64_t> lm(logmask[i], logmask[i] + n);
+        if ((rc = up(S.d_ptr, sp)) || (rc = up(S.d_idx, si)) || (rc = up(S.d_log, sl)) || (rc = up(S.d_alpha, S.h_alpha)) || (rc = up(S.d_prior, S.h_prior)) ||
+            (rc = up(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
+            (rc = S.d_llr.ensure(Bz * n * 8)) || (rc = S.d_conv.ensure(Bz)) || (rc = S.d_iter.ensure(Bz * 4)) || (rc = S.d_list.ensure(Bz * 4)))
+            return fail(rc);
+    }
+    if ((rc = up(P->d_loc_type, loc_type)) || (rc = P->d_count.ensure(64)) || (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) ||
+        (rc = P->d_clk.ensure(2 * kClkSlots * 16)))
         return fail(rc);
     if (zero_now(P->d_clk.p, 2 * kClkSlots * 16) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
-    // (round 2 ran sector X on a second stream beside sector Z: two persistent kernels that each own every CU do not overlap -- 177.9 vs 178.7 ms
-    // per step -- and the small launches queued behind them polluted the profile; everything runs on the caller's stream now)
     if (zero_now(P->d_tally.p, QLDPC_TALLY_SLOTS * 8) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
     *out = P;
     return QLDPC_OK;
 }
 
 static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, int64_t B, hipStream_t s, bool zero_counts = false) {
-    SigTab Z{P->d_zptr.as<int32_t>(), P->d_zidx.as<uint16_t>(), P->d_zlog.as<uint64_t>()};
-    SigTab X{P->d_xptr.as<int32_t>(), P->d_xidx.as<uint16_t>(), P->d_xlog.as<uint64_t>()};
-    const int wz = (P->nsx + 31) / 32, wx = (P->nsz + 31) / 32;
+    const Sector &Z = P->sec[0], &X = P->sec[1];
+    const auto sig = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
+    const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
     const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
     const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
     hipLaunchKernelGGL(circuit_sample_kernel, dim3(grid), dim3(256), lds, s, B, begin, (uint32_t)seed, (uint32_t)(seed >> 32), P->thr, P->n_locs,
-                       P->d_loc_type.as<uint8_t>(), Z, X, P->nsx, P->nsz, P->d_syn_z.as<int8_t>(), P->d_syn_x.as<int8_t>(),
-                       P->d_true_z.as<unsigned long long>(), P->d_true_x.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr);
+                       P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(),
+                       Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }
 
-static int decode_sector(qldpc_circuit_plan *P, const qldpc_graph *g, int64_t B, DevBuf &syn, DevBuf &prior, DevBuf &alpha, DevBuf &det, DevBuf &llr,
-                         DevBuf &conv, DevBuf &iter, DevBuf &list, int sector, hipStream_t s, uint64_t seed, int64_t trial_begin) {
-    const std::vector<double> &hp = sector ? P->h_prior_x : P->h_prior_z;
+// enqueues the decode of sector `sector` (0 = Z, 1 = X) of a batch on s, inside that sector's phase brackets
+static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s, uint64_t seed, int64_t trial_begin) {
+    Sector &S = P->sec[sector];
+    const qldpc_graph *g = S.g;
     int rc;
-    int32_t *count = P->d_count.as<int32_t>() + 4 * sector;
-    const int ph_bp = sector ? QLDPC_PHASE_BP_X : QLDPC_PHASE_BP_Z, ph_osd = sector ? QLDPC_PHASE_OSD_X : QLDPC_PHASE_OSD_Z;
-    if (P->relay) {                    // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
-        if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
-        {
-            std::lock_guard<std::mutex> lk(g->mu);
-            // iter_bias -1: the judge adds one per trial, so the ITERS slots sum the Relay-BP iterations
-            rc = relay_decode_launch(g, B, syn.as<int8_t>(), prior.as<double>(), P->rp, seed, trial_begin, sector, -1, det.as<int8_t>(), conv.as<uint8_t>(),
-                                     (sector ? P->d_legs_x : P->d_legs_z).as<int32_t>(), iter.as<int32_t>(), nullptr, s);
-        }
-        if (rc != QLDPC_OK) return rc;
-        return phase_mark(P, ph_bp, s, false);
-    }
-    if (P->win[sector]) {              // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
-        const WindowPlanSlots slots{conv.as<uint8_t>(), iter.as<int32_t>(), count};
+    int32_t *count = P->fail_count(sector);
+    const int ph_bp = kPhaseBp[sector], ph_osd = kPhaseOsd[sector];
+    if (P->decoder == Decoder::WINDOW) {  // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
+        const WindowPlanSlots slots{S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), count};
         const std::function<int(int, bool)> mark = [&](int part, bool open) { return phase_mark(P, part ? ph_osd : ph_bp, s, open); };
-        return window_decoder_lock_and_launch(P->win[sector], B, syn.as<int8_t>(), det.as<int8_t>(), &slots, &mark, s);
+        return window_decoder_lock_and_launch(S.win, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), &slots, &mark, s);
     }
     unsigned long long *clk = (P->flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr;
     if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
-    {
+    if (P->decoder == Decoder::RELAY) {   // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
+        std::lock_guard<std::mutex> lk(g->mu);
+        // iter_bias -1: the judge adds one per trial, so the ITERS slots sum the Relay-BP iterations
+        rc = relay_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->rp, seed, trial_begin, sector, -1, S.d_det.as<int8_t>(),
+                                 S.d_conv.as<uint8_t>(), S.d_legs.as<int32_t>(), S.d_iter.as<int32_t>(), nullptr, s);
+    } else {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk : nullptr;                  // sector Z carries the probe (one writer per buffer)
-        rc = minsum_decode_dispatch(g, B, syn.as<int8_t>(), prior.as<double>(), P->max_iter, alpha.as<double>(), P->damping, P->clip,
-                                    (P->flags & QLDPC_FLAG_PUBLIC_MASK) | (P->nanfree ? QLDPC_FLAG_INTERNAL_PRIOR_FINITE : 0),
-                                    P->nanfree, det.as<int8_t>(), llr.as<double>(), conv.as<uint8_t>(), iter.as<int32_t>(), s, hp.empty() ? nullptr : hp.data());
+        rc = minsum_decode_dispatch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->max_iter, S.d_alpha.as<double>(), P->damping, P->clip,
+                                    (P->flags & QLDPC_FLAG_PUBLIC_MASK) | (P->nanfree ? QLDPC_FLAG_INTERNAL_PRIOR_FINITE : 0), P->nanfree,
+                                    S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s,
+                                    S.h_prior.empty() ? nullptr : S.h_prior.data());
         g->clk_probe = nullptr;
     }
     if (rc != QLDPC_OK) return rc;
-    if ((rc = phase_mark(P, ph_bp, s, false)) != QLDPC_OK || !P->use_osd) return rc;
+    if ((rc = phase_mark(P, ph_bp, s, false)) != QLDPC_OK || !P->osd_stage()) return rc;
     if ((rc = phase_mark(P, ph_osd, s, true)) != QLDPC_OK) return rc;
-    hipLaunchKernelGGL(collect_failed2_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, conv.as<uint8_t>(), list.as<int32_t>(), count);
+    hipLaunchKernelGGL(collect_failed2_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, S.d_conv.as<uint8_t>(), S.d_list.as<int32_t>(), count);
     {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk + 2 * kClkSlots : nullptr;
-        if (P->cs_order >= 0)
-            rc = osdcs_listed_launch(g, list.as<int32_t>(), count, B, syn.as<int8_t>(), llr.as<double>(), det.as<int8_t>(), prior.as<double>(),
-                                     P->cs_order, det.as<int8_t>(), (sector ? P->d_flips_x : P->d_flips_z).as<int32_t>(), s);
+        if (P->decoder == Decoder::BP_OSD_CS)
+            rc = osdcs_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(),
+                                     S.d_prior.as<double>(), P->cs_order, S.d_det.as<int8_t>(), S.d_flips.as<int32_t>(), s);
         else
-            rc = osd0_listed_launch(g, list.as<int32_t>(), count, B, syn.as<int8_t>(), llr.as<double>(), det.as<int8_t>(), nullptr,
-                                    det.as<int8_t>(), P->flags, s);
+            rc = osd0_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), nullptr,
+                                    S.d_det.as<int8_t>(), P->flags, s);
         g->clk_probe = nullptr;
     }
     if (rc != QLDPC_OK) return rc;
@@ -573,47 +570,36 @@ static int decode_sector(qldpc_circuit_plan *P, const qldpc_graph *g, int64_t B,
     return phase_mark(P, ph_osd, s, false);                      // (the judge kernel adds the two failure counts to the OSD tally slots)
 }
 
+static JudgeSector judge_view(const Sector &S) {
+    const qldpc_graph *g = S.g;
+    return {g->m, g->n, g->d_indptr, g->d_indices, g->d_colptr, g->d_rowidx, S.d_lm.as<uint64_t>(), S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(),
+            S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), S.d_true.as<unsigned long long>()};
+}
+
 // one pass over [trial_begin, trial_begin + count); `outcome` (host, may be NULL) receives bit0 = z_err, bit1 = x_err per trial
 static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, hipStream_t s, uint8_t *outcome) {
     QLDPC_USE_DEVICE(P->device);
     int rc = QLDPC_OK; (void)rc;
     if (outcome && (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK) return rc;
+    const JudgeSector Z = judge_view(P->sec[0]), X = judge_view(P->sec[1]);
+    const auto judge = (Z.m <= 4096 && X.m <= 4096 && Z.colptr && X.colptr) ? circuit_judge_kernel<true> : circuit_judge_kernel<false>;
     for (int64_t off = 0; off < count; off += P->batch) {
         const int64_t B = std::min<int64_t>(P->batch, count - off);
         if (P->pending.size() > 256) drain_phases(P, false);         // a caller that never reads phase times: recycle finished brackets (bounded event count)
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, s, true)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
-        hipStream_t sx = s;
-        if (P->side && P->gz != P->gx) {                // sector X on the plan's own stream, joined again before the judge
-            sx = P->side;
-            QLDPC_HIP_TRY(hipEventRecord(P->ev_sampled, s));
-            QLDPC_HIP_TRY(hipStreamWaitEvent(sx, P->ev_sampled, 0));
-        }
-        if ((rc = decode_sector(P, P->gz, B, P->d_syn_z, P->d_prior_z, P->d_alpha_z, P->d_det_z, P->d_llr_z, P->d_conv_z, P->d_iter_z, P->d_list_z, 0, s,
-                                seed, trial_begin + off)) != QLDPC_OK) return rc;
-        if ((rc = decode_sector(P, P->gx, B, P->d_syn_x, P->d_prior_x, P->d_alpha_x, P->d_det_x, P->d_llr_x, P->d_conv_x, P->d_iter_x, P->d_list_x, 1, sx,
-                                seed, trial_begin + off)) != QLDPC_OK) return rc;
-        if (sx != s) {
-            QLDPC_HIP_TRY(hipEventRecord(P->ev_x_done, sx));
-            QLDPC_HIP_TRY(hipStreamWaitEvent(s, P->ev_x_done, 0));
-        }
+        for (int sector = 0; sector < 2; sector++)
+            if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, true)) != QLDPC_OK) return rc;
-        JudgeSector Z{P->gz->m, P->gz->n, P->gz->d_indptr, P->gz->d_indices, P->gz->d_colptr, P->gz->d_rowidx, P->d_lm_z.as<uint64_t>(), P->d_syn_z.as<int8_t>(), P->d_det_z.as<int8_t>(),
-                      P->d_conv_z.as<uint8_t>(), P->d_iter_z.as<int32_t>(), P->d_true_z.as<unsigned long long>()};
-        JudgeSector X{P->gx->m, P->gx->n, P->gx->d_indptr, P->gx->d_indices, P->gx->d_colptr, P->gx->d_rowidx, P->d_lm_x.as<uint64_t>(), P->d_syn_x.as<int8_t>(), P->d_det_x.as<int8_t>(),
-                      P->d_conv_x.as<uint8_t>(), P->d_iter_x.as<int32_t>(), P->d_true_x.as<unsigned long long>()};
-        if (P->gz->m <= 4096 && P->gx->m <= 4096 && P->gz->d_colptr && P->gx->d_colptr)
-            hipLaunchKernelGGL(circuit_judge_kernel<true>, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
-                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, (P->use_osd && !P->relay) ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(circuit_judge_kernel<false>, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
-                               outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, (P->use_osd && !P->relay) ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
+        hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
+                           outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
-        if (P->relay && (rc = relay_legs_tally_launch(B, P->d_legs_z.as<int32_t>(), P->d_legs_x.as<int32_t>(), P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
+        if (P->decoder == Decoder::RELAY &&
+            (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), P->sec[1].d_legs.as<int32_t>(), P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
             return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
-        P->batches++;           // (the next batch's sampler follows the judge on s, which already waited for sector X)
+        P->batches++;
         if (outcome) {
             QLDPC_HIP_TRY(hipMemcpyAsync(outcome + off, P->d_outcome.p, (size_t)B, hipMemcpyDeviceToHost, s));
             QLDPC_HIP_TRY(hipStreamSynchronize(s));
@@ -641,7 +627,6 @@ QLDPC_EXPORT int qldpc_circuit_plan_read(qldpc_circuit_plan *P, void *stream, in
     QLDPC_USE_DEVICE(P->device);
     int rc = QLDPC_OK; (void)rc;
     QLDPC_HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-    if (P->side) QLDPC_HIP_TRY(hipStreamSynchronize(P->side));
     drain_phases(P, true);                                           // everything enqueued has finished: fold the brackets, recycle their events
     QLDPC_HIP_TRY(hipMemcpy(tally, P->d_tally.p, QLDPC_TALLY_SLOTS * 8, hipMemcpyDeviceToHost));
     if (clear) QLDPC_HIP_TRY(zero_now(P->d_tally.p, QLDPC_TALLY_SLOTS * 8));
@@ -656,27 +641,26 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed,
     QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x), "NULL output");
     QLDPC_USE_DEVICE(P->device);
     int rc = QLDPC_OK; (void)rc;
-    std::vector<unsigned long long> tz, tx;
+    int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
+    std::vector<unsigned long long> t;
     for (int64_t off = 0; off < count; off += P->batch) {
         const int64_t B = std::min<int64_t>(P->batch, count - off);
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
         QLDPC_HIP_TRY(hipDeviceSynchronize());
-        QLDPC_HIP_TRY(hipMemcpy(sparse_z + off * P->nsx, P->d_syn_z.p, (size_t)B * P->nsx, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(sparse_x + off * P->nsz, P->d_syn_x.p, (size_t)B * P->nsz, hipMemcpyDeviceToHost));
-        tz.resize(B); tx.resize(B);
-        QLDPC_HIP_TRY(hipMemcpy(tz.data(), P->d_true_z.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(tx.data(), P->d_true_x.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-        for (int64_t b = 0; b < B; b++)
-            for (int r = 0; r < P->k; r++) {
-                true_z[(off + b) * P->k + r] = (int8_t)((tz[b] >> r) & 1);
-                true_x[(off + b) * P->k + r] = (int8_t)((tx[b] >> r) & 1);
-            }
+        t.resize(B);
+        for (int i = 0; i < 2; i++) {
+            const Sector &S = P->sec[i];
+            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
+            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+            for (int64_t b = 0; b < B; b++)
+                for (int r = 0; r < P->k; r++) truth[i][(off + b) * P->k + r] = (int8_t)((t[b] >> r) & 1);
+        }
     }
     return QLDPC_OK;
 }
 
-// Sums (ms) of the hipEvent brackets of each phase over the batches enqueued since the last call, and the number of batches.  With the
-// two sectors on two streams the brackets overlap in time: their sum exceeds the wall time, each is the span of that phase on its stream.
+// Sums (ms) of the hipEvent brackets of each phase over the batches enqueued since the last call, and the number of batches.  The phases of
+// a batch run back to back on the caller's stream, so the brackets do not overlap.
 QLDPC_EXPORT int qldpc_circuit_plan_phase_times(qldpc_circuit_plan *P, double *ms, int64_t *batches) {
     QLDPC_REQUIRE(P != nullptr && ms != nullptr, "NULL argument");
     QLDPC_USE_DEVICE(P->device);
@@ -694,75 +678,88 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
     QLDPC_REQUIRE(P->flags & QLDPC_FLAG_CLOCK_PROBE, "the plan was created without QLDPC_FLAG_CLOCK_PROBE");
     QLDPC_USE_DEVICE(P->device);
     QLDPC_HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-    if (P->side) QLDPC_HIP_TRY(hipStreamSynchronize(P->side));
     std::vector<unsigned long long> h(4 * kClkSlots);
     QLDPC_HIP_TRY(hipMemcpy(h.data(), P->d_clk.p, h.size() * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < 2; k++) mhz[k] = clock_probe_median(h.data() + 2 * kClkSlots * k, kClkSlots);
     return QLDPC_OK;
 }
 
+// May a plan that decodes with P->decoder switch to `to`?  (QLDPC_OK, or QLDPC_ERR_INVALID with the error text set)
+//
+//   from \ to      RELAY                   BP_OSD_CS                  WINDOW
+//   BP_OSD0        yes, also use_osd = 0   yes, needs use_osd         yes, needs use_osd
+//   RELAY          yes: new parameters     no                         no
+//   BP_OSD_CS      no                      yes: new order             no
+//   WINDOW         no                      no                         no
+//
+// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS), damping = 1 (WINDOW).
+static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
+    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(to == Decoder::RELAY || P->use_osd, "the plan was created with use_osd = 0: %s needs its OSD stage", name[(int)to]);
+    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || (P->decoder == to && to != Decoder::WINDOW), "the plan was switched to %s: %s cannot follow",
+                  name[(int)P->decoder], name[(int)to]);
+    return QLDPC_OK;
+}
+
+static int priors_finite(const qldpc_circuit_plan *P) {
+    for (int i = 0; i < 2; i++)
+        for (double v : P->sec[i].h_prior) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-%c prior is not finite", "ZX"[i]);
+    return QLDPC_OK;
+}
+
 QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
                                              int max_legs, int stop_after) {
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->cs_order < 0, "the plan's OSD stage was switched to OSD-CS: Relay-BP replaces BP + OSD and cannot follow");
-    QLDPC_REQUIRE(!P->win[0], "the plan was switched to sliding-window decoding: Relay-BP replaces BP + OSD and cannot follow");
-    const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
-    int rc = relay_check_params(rp);
+    int rc = switch_allowed(P, Decoder::RELAY);
     if (rc != QLDPC_OK) return rc;
-    for (double v : P->h_prior_z) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-Z prior is not finite");
-    for (double v : P->h_prior_x) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-X prior is not finite");
-    if (relay_mode(P->gz) == 0) return relay_unsupported(P->gz);
-    if (relay_mode(P->gx) == 0) return relay_unsupported(P->gx);
+    const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
+    if ((rc = relay_check_params(rp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
+    for (const Sector &S : P->sec)
+        if (relay_mode(S.g) == 0) return relay_unsupported(S.g);
     QLDPC_USE_DEVICE(P->device);
-    if ((rc = P->d_legs_z.ensure((size_t)P->batch * 4)) != QLDPC_OK || (rc = P->d_legs_x.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    for (Sector &S : P->sec)
+        if ((rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
     P->rp = rp;
-    P->relay = true;
+    P->decoder = Decoder::RELAY;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order) {
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: there is no OSD stage to switch");
-    QLDPC_REQUIRE(!P->relay, "the plan was switched to Relay-BP, which has no OSD stage");
-    QLDPC_REQUIRE(!P->win[0], "the plan was switched to sliding-window decoding, whose windows end in OSD-0");
-    int rc = osdcs_check_order(order);
+    int rc = switch_allowed(P, Decoder::BP_OSD_CS);
     if (rc != QLDPC_OK) return rc;
-    for (double v : P->h_prior_z) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-Z prior is not finite");
-    for (double v : P->h_prior_x) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-X prior is not finite");
-    if ((rc = osdcs_supported(P->gz)) != QLDPC_OK || (rc = osdcs_supported(P->gx)) != QLDPC_OK) return rc;
+    if ((rc = osdcs_check_order(order)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
+    for (const Sector &S : P->sec)
+        if ((rc = osdcs_supported(S.g)) != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(P->device);
-    if ((rc = P->d_flips_z.ensure((size_t)P->batch * 8)) != QLDPC_OK || (rc = P->d_flips_x.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
+    for (Sector &S : P->sec)
+        if ((rc = S.d_flips.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
     P->cs_order = order;
+    P->decoder = Decoder::BP_OSD_CS;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window, int commit) {
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: a window that does not converge needs the OSD stage");
-    QLDPC_REQUIRE(!P->relay, "the plan was switched to Relay-BP: windows decode with BP + OSD-0");
-    QLDPC_REQUIRE(P->cs_order < 0, "the plan's OSD stage was switched to OSD-CS: windows decode with BP + OSD-0");
-    QLDPC_REQUIRE(!P->win[0], "the plan is already windowed");
+    int rc = switch_allowed(P, Decoder::WINDOW);
+    if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(P->damping == 1.0, "sliding-window decoding needs damping = 1 (the plan has %g)", P->damping);
     QLDPC_USE_DEVICE(P->device);
     qldpc_window_decoder *w[2] = {nullptr, nullptr};
-    for (int sector = 0; sector < 2; sector++) {
-        const int rc = window_decoder_create_tab(sector ? P->gx : P->gz, P->layer_rows[sector], window, commit, (sector ? P->h_prior_x : P->h_prior_z).data(),
-                                                 P->max_iter, sector ? P->h_alpha_x : P->h_alpha_z, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &w[sector]);
+    for (int i = 0; i < 2; i++) {
+        const Sector &S = P->sec[i];
+        rc = window_decoder_create_tab(S.g, S.layer_rows, window, commit, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK,
+                                       &w[i]);
         if (rc != QLDPC_OK) { qldpc_window_decoder_destroy(w[0]); return rc; }
     }
-    P->win[0] = w[0]; P->win[1] = w[1];
+    for (int i = 0; i < 2; i++) P->sec[i].win = w[i];
+    P->decoder = Decoder::WINDOW;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {
     if (!P) return;
     (void)hipSetDevice(P->device);
-    for (int sector = 0; sector < 2; sector++) qldpc_window_decoder_destroy(P->win[sector]);
-    if (P->side) { (void)hipStreamSynchronize(P->side); (void)hipStreamDestroy(P->side); }
-    if (P->ev_sampled) (void)hipEventDestroy(P->ev_sampled);
-    if (P->ev_x_done) (void)hipEventDestroy(P->ev_x_done);
+    for (Sector &S : P->sec) qldpc_window_decoder_destroy(S.win);
     for (auto &br : P->pending) { (void)hipEventDestroy(br.a); if (br.b) (void)hipEventDestroy(br.b); }
     for (auto e : P->pool) (void)hipEventDestroy(e);
-    for (DevBuf *b : P->all()) b->release();
-    delete P;
+    delete P;                                      // every PlanBuf releases itself
 }

@@ -304,6 +304,30 @@ def test_plan_switch_rules(L):
         p.use_relay()
     p.close()
 
+    # the switches that stay open: the same decoder again replaces its parameters, and Relay-BP needs no OSD stage
+    def tally(p):
+        p.run(11, 0, 512)
+        t = p.read()
+        p.close()
+        return t
+
+    one_leg = dict(max_legs=1, stop_after=1)
+    p, q, r = plan(batch=256), plan(batch=256), plan(batch=256)
+    p.use_relay(**one_leg)
+    p.use_relay()
+    q.use_relay()
+    r.use_relay(**one_leg)
+    relay = tally(q)
+    assert np.array_equal(tally(p), relay) and not np.array_equal(tally(r), relay)
+    p = plan(batch=256, use_osd=False)
+    p.use_relay()
+    assert np.array_equal(tally(p), relay)
+    p, q = plan(batch=256), plan(batch=256)
+    p.use_osd_cs(0)
+    p.use_osd_cs(7)
+    q.use_osd_cs(7)
+    assert np.array_equal(tally(p), tally(q))
+
 
 def test_run_simulation_lowers_the_logical_error_count(L):
     from qldpc_amd.data import load_code, load_precomputed_matrices

@@ -21,7 +21,8 @@ ap.add_argument("--batch", type=int, default=16384)
 ap.add_argument("--max-iter", type=int, default=50)
 ap.add_argument("--no-osd", action="store_true")
 ap.add_argument("--flags", type=lambda x: int(x, 0), default=0)
-ap.add_argument("--serial", action="store_true", help="both sectors on one stream (QLDPC_FLAG_MC_UNFUSED): per-phase times are then exclusive")
+ap.add_argument("--serial", action="store_true", help="adds QLDPC_FLAG_MC_UNFUSED to --flags; a circuit plan runs its phases back to back on one stream with or without it, so the "
+                "per-phase times are exclusive either way")
 ap.add_argument("--reps", type=int, default=1)
 ap.add_argument("--counts-out", default="", help="with --timers: write the OSD-0 workload counts per shot (pivots, columns, touched row updates) as JSON")
 ap.add_argument("--cpu-trials", type=int, default=0, help="also time the CPU checker (C port of the reference loop, all host threads) on this many trials")
