@@ -32,6 +32,8 @@
  *        additive, same version: qldpc_minsum_decode_path (which decoder form a call takes), QLDPC_PATH_* and QLDPC_DETAIL_*
  *        additive, same version (the suites pin 101): sliding-window decoding, qldpc_window_decoder_*, qldpc_window_decode_batch[_dev],
  *        qldpc_circuit_plan_use_window
+ *        additive, same version: layered-schedule min-sum, qldpc_layered_decoder_*, qldpc_layered_decode_batch[_dev], qldpc_check_layers,
+ *        qldpc_circuit_plan_use_layered, QLDPC_FLAG_LAYERED_* and QLDPC_LAYERED_FORM_*
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -75,6 +77,12 @@ extern "C" {
                                           even when the prior is known on the host and the LDS-resident form (csrc/minsum_wg2.hip) applies */
 #define QLDPC_FLAG_WG_ROWMAJOR 0x8000   /* workgroup-per-shot decoder: natural row / column order instead of the degree-sorted assignment */
 #define QLDPC_FLAG_CLOCK_PROBE 0x4000   /* plans: workgroups stamp s_memtime / s_memrealtime around their work (see *_plan_clock) */
+/* layered decoder (qldpc_layered_decoder_create): form selectors for tools/ and the parity tests; results never depend on them */
+#define QLDPC_FLAG_LAYERED_BLOCK_256 0x400000    /* threads per workgroup (default: by the edges of an average layer); at most one of the three */
+#define QLDPC_FLAG_LAYERED_BLOCK_512 0x800000
+#define QLDPC_FLAG_LAYERED_BLOCK_1024 0x1000000
+#define QLDPC_FLAG_LAYERED_GLOBAL_IDX 0x2000000  /* column indices in HBM/L2 even when they fit LDS */
+#define QLDPC_FLAG_LAYERED_VGLOBAL 0x4000000     /* posteriors in HBM/L2 even when they fit LDS */
 /* measured-and-rejected kernels: libqldpc_hip_experiments.so only (make -C csrc experiments; same ABI, loaded by the parity tests).  The product
  * library answers these with QLDPC_ERR_UNSUPPORTED.  Numbers: profiles/r02_osd_experiments.txt, r02_bp_lane_mapping.txt, r03_wave_kernel.txt */
 #define QLDPC_FLAG_WG_EDGE_LANES 0x2     /* workgroup-per-shot decoder: check pass with 16 lanes per check and shuffle reductions (SURVEY 7-6 option B) */
@@ -301,6 +309,53 @@ int qldpc_window_decode_batch(qldpc_window_decoder *wd, int64_t B, const int8_t 
 int qldpc_window_decode_batch_dev(qldpc_window_decoder *wd, int64_t B, const int8_t *d_syndromes, int8_t *d_err, int32_t *d_conv,
                                   int32_t *d_iters, int32_t *d_osd, uint8_t *d_unsat, void *stream);
 
+/* Normalised min-sum with a LAYERED (serial) schedule.  New here: the reference and every other decoder of this library use the flooding
+ * schedule.  Inputs: the graph g (m x n), prior[n] (any values, as in qldpc_minsum_decode_batch), row_layer int32[m] or NULL, max_iter >= 1,
+ * the alpha mode, value and sequence of qldpc_minsum_decode_batch, clip_llr > 0.  There is no damping argument: damping is 1.
+ *   Layers.  row_layer == NULL: rows are taken in ascending index and a row gets the smallest layer number >= 0 that no earlier row sharing a
+ *     column with it holds; a row without entries gets layer 0 (qldpc_check_layers returns this colouring).  A caller's row_layer must be
+ *     >= 0 everywhere and two rows of one layer must share no column: otherwise creation returns QLDPC_ERR_INVALID and qldpc_last_error names
+ *     the two rows.  Layers run in ascending number, empty numbers are skipped.  row_layer[i] = i is the literal serial schedule.
+ *   State.  V = prior; every check-to-variable message R_ij = 0.0.
+ *   Iteration k = 0 .. max_iter - 1, alpha_k as in qldpc_minsum_decode_batch.  For every layer in order, for every check i of it with at
+ *     least one entry, over its columns j in ascending order:
+ *       Q_ij = V_j - R_ij;  a NaN becomes 0.0;  then clip to +-clip_llr (the reference's rules, src/decoding/kernels.py:325-333);
+ *       the sign of Q is + for Q >= 0;  sign_prod = the syndrome sign (+1 for s_i = 0, -1 for s_i = 1) times the product of the signs;
+ *       min1, min2 over |Q| by the reference's strict-< scan (min2 is the second smallest of the multiset), min1_pos = the FIRST position
+ *       of the minimum in ascending column order;  a degree-1 check has min2 = +inf;
+ *       R_ij = alpha_k * (sign_prod * sign_ij) * (min2 if j is at min1_pos else min1);   V_j = Q_ij + R_ij.
+ *     Every operation is one correctly rounded f64 operation (the multiply and the add are not contracted into an FMA).
+ *     After the last layer e_j = (V_j < 0); if H e = s (over every row, those without entries included) the shot stops: converged,
+ *     final_iter = k.
+ *   Outputs per shot, exactly those of qldpc_minsum_decode_batch: err int8[n], llr f64[n] (= V), conv, final_iter (max_iter - 1 when not
+ *     converged), so qldpc_osd0_batch and qldpc_osdcs_batch take them unchanged.
+ *   Results do not depend on batch splits, the grid or any flag; the order of the checks inside a layer cannot matter by construction.
+ * Limits (QLDPC_ERR_UNSUPPORTED): 1 <= m, n < 2^24; row degree <= 56; 29 bytes per row with entries + 4 per layer + 48 must fit 163 328 bytes of LDS
+ * (160 KB less 512 the kernel keeps for itself; about 5600 rows).  The posteriors and the column indices (u16, n <= 65535) live in LDS when they fit beside that, else in HBM/L2.
+ * flags: QLDPC_FLAG_LAYERED_* (other bits are ignored).  The decoder owns its tables; it keeps a pointer to g, which must outlive it.  Calls on
+ * one decoder serialise (a mutex while enqueuing, an event between streams).
+ * qldpc_layered_decoder_info: number of layers (with at least one non-empty row), rows and edges of the largest layer, LDS bytes of a
+ * workgroup, and the form that runs: threads per workgroup | QLDPC_LAYERED_FORM_* bits; any output may be NULL.
+ * qldpc_layered_decoder_layers: the row_layer in use, int32[m]. */
+#define QLDPC_LAYERED_FORM_BLOCK_MASK 0xFFFF
+#define QLDPC_LAYERED_FORM_VGLOBAL 0x10000       /* posteriors in a per-workgroup slab in HBM/L2 */
+#define QLDPC_LAYERED_FORM_LDS_INDICES 0x20000   /* column indices as u16 in LDS */
+typedef struct qldpc_layered_decoder qldpc_layered_decoder;
+int qldpc_check_layers(const qldpc_graph *g, int32_t *row_layer, int *layers);
+int qldpc_layered_decoder_create(const qldpc_graph *g, const int32_t *row_layer, const double *prior, int max_iter, int alpha_mode,
+                                 double alpha_val, const double *alpha_seq, int alpha_len, double clip_llr, int flags,
+                                 qldpc_layered_decoder **out);
+void qldpc_layered_decoder_destroy(qldpc_layered_decoder *ld);
+int qldpc_layered_decoder_info(const qldpc_layered_decoder *ld, int *layers, int *max_layer_rows, int *max_layer_edges, int *lds_bytes,
+                               int *form);
+int qldpc_layered_decoder_layers(const qldpc_layered_decoder *ld, int32_t *row_layer);
+/* host pointers: syndromes int8[B][m] -> err int8[B][n], llr f64[B][n], conv uint8[B], iter int32[B]; returns when they are complete.  B = 0: a no-op */
+int qldpc_layered_decode_batch(qldpc_layered_decoder *ld, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
+                               int32_t *iter);
+/* same on device pointers; only enqueues on `stream` */
+int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *ld, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
+                                   uint8_t *d_conv, int32_t *d_iter, void *stream);
+
 /* a10: generate_noisy_circuit_jit (src/noise/kernels.py:175-353), batched over B draws of explicit random
  * arrays rv/rp/rt [B][n_locs]; out_* [B][cap]; out_len int64[B]. */
 int qldpc_noisy_circuit_batch(int64_t B, int64_t len, const int32_t *ops, const int32_t *q1, const int32_t *q2, double p,
@@ -447,6 +502,13 @@ int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *plan, int order);
  * switched to Relay-BP or OSD-CS, or already windowed (and qldpc_circuit_plan_use_relay / _use_osd_cs after this call return
  * QLDPC_ERR_INVALID); otherwise what qldpc_window_decoder_create returns. */
 int qldpc_circuit_plan_use_window(qldpc_circuit_plan *plan, int window, int commit);
+/* Switches the BP launch of both sectors to the layered schedule: a qldpc_layered_decoder per sector with the plan's prior, alpha schedule,
+ * max_iter (>= 1) and clip_llr; row_layer_z / row_layer_x as in qldpc_layered_decoder_create (NULL = the greedy colouring).  Only the launch
+ * inside the BP bracket changes: sampler, unconverged list, the OSD-0 / OSD-CS stage, judge and tally slots are untouched, and
+ * qldpc_circuit_plan_use_osd_cs may come before or after.  A second call replaces the layers.  QLDPC_ERR_INVALID on a plan with damping != 1
+ * or switched to Relay-BP or to windows (and qldpc_circuit_plan_use_relay / _use_window after this call return QLDPC_ERR_INVALID); otherwise
+ * what qldpc_layered_decoder_create returns. */
+int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *plan, const int32_t *row_layer_z, const int32_t *row_layer_x);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

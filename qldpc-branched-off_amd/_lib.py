@@ -35,6 +35,9 @@ FLAG_WG_VGLOBAL, FLAG_WG_GENERIC, FLAG_OSD_UG, FLAG_OSD_GLOBAL, FLAG_CLOCK_PROBE
 # qldpc_minsum_decode_path: the decoder form a call takes (QLDPC_PATH_*) and the QLDPC_DETAIL_* bits of the workgroup forms
 PATH_REGULAR, PATH_RESIDENT, PATH_WG2, PATH_WG, PATH_STREAM, PATH_WAVE = 0, 1, 2, 3, 4, 5
 DETAIL_LEAN, DETAIL_REG_INDICES, DETAIL_VGLOBAL, DETAIL_DAMPING, DETAIL_BLOCK_1024, DETAIL_DEG1, DETAIL_NAN_DEG1_ONLY = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+# layered decoder: form selectors (results never depend on them) and the bits qldpc_layered_decoder_info reports beside the threads per workgroup
+FLAG_LAYERED_BLOCK_256, FLAG_LAYERED_BLOCK_512, FLAG_LAYERED_BLOCK_1024, FLAG_LAYERED_GLOBAL_IDX, FLAG_LAYERED_VGLOBAL = 0x400000, 0x800000, 0x1000000, 0x2000000, 0x4000000
+LAYERED_FORM_BLOCK_MASK, LAYERED_FORM_VGLOBAL, LAYERED_FORM_LDS_INDICES = 0xFFFF, 0x10000, 0x20000
 CIRCUIT_PHASES = ("sample", "bp_z", "osd_z", "bp_x", "osd_x", "judge")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "qldpc_hip.h")
 
@@ -518,6 +521,95 @@ class WindowDecoder:
             pass
 
 
+def check_layered_args(max_iter, clip_llr):
+    """ValueError unless max_iter is an integer >= 1 and clip_llr > 0 -> (int, float)."""
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"the layered decoder needs an integer max_iter >= 1, got {max_iter}")
+    clip_llr = float(clip_llr)
+    if not clip_llr > 0:
+        raise ValueError(f"clip_llr must be > 0, got {clip_llr}")
+    return int(max_iter), clip_llr
+
+
+def check_row_layer(row_layer, m):
+    """ValueError unless row_layer is m integers >= 0 -> int32[m] (None stays None: the greedy colouring)."""
+    if row_layer is None:
+        return None
+    a = np.asarray(row_layer)
+    if a.ndim != 1 or a.size != m:
+        raise ValueError(f"layers has shape {a.shape}, H has {m} rows")
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        if not np.all(np.isfinite(a.astype(np.float64))) or not np.array_equal(a, np.floor(a.astype(np.float64))):
+            raise ValueError("layers must be integers")
+    if a.size and (a.min() < 0 or a.max() > np.iinfo(np.int32).max):
+        bad = int(np.flatnonzero((a < 0) | (a > np.iinfo(np.int32).max))[0])
+        raise ValueError(f"layers[{bad}] = {a[bad]} is outside 0 .. 2^31 - 1")
+    return i32(a)
+
+
+def graph_check_layers(graph):
+    """qldpc_check_layers: the greedy colouring of the rows of `graph` -> (row_layer int32[m], number of layers)."""
+    lay = np.zeros(max(graph.m, 1), np.int32)
+    nl = C.c_int(0)
+    check(lib().qldpc_check_layers(graph.handle, ptr(lay, C.c_int32), C.byref(nl)))
+    return lay[:graph.m], nl.value
+
+
+class LayeredDecoder:
+    """Owning wrapper of a qldpc_layered_decoder (normalised min-sum with a layered schedule on `graph`; semantics in include/qldpc_hip.h)."""
+
+    def __init__(self, graph, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, layers=None, flags=0):
+        max_iter, clip_llr = check_layered_args(max_iter, clip_llr)
+        mode, aval, seq = alpha_args(alpha_mode, alpha)
+        prior = f64(prior).reshape(-1)
+        if prior.size != graph.n:
+            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        layers = check_row_layer(layers, graph.m)
+        self.graph = graph                     # the decoder keeps a pointer to the graph handle
+        self._h = C.c_void_p()
+        check(lib().qldpc_layered_decoder_create(graph.handle, ptr(layers, C.c_int32) if layers is not None else None, ptr(prior, C.c_double), max_iter,
+                                                 mode, aval, ptr(seq, C.c_double), seq.size, clip_llr, int(flags), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        """{layers, max_layer_rows, max_layer_edges, lds_bytes, block (threads per workgroup), v_global, lds_indices}"""
+        v = [C.c_int(0) for _ in range(5)]
+        check(lib().qldpc_layered_decoder_info(self._h, *[C.byref(x) for x in v]))
+        form = v[4].value
+        return dict(layers=v[0].value, max_layer_rows=v[1].value, max_layer_edges=v[2].value, lds_bytes=v[3].value, block=form & LAYERED_FORM_BLOCK_MASK,
+                    v_global=bool(form & LAYERED_FORM_VGLOBAL), lds_indices=bool(form & LAYERED_FORM_LDS_INDICES))
+
+    def layers(self):
+        """the row_layer in use, int32[m]"""
+        lay = np.zeros(max(self.graph.m, 1), np.int32)
+        check(lib().qldpc_layered_decoder_layers(self._h, ptr(lay, C.c_int32)))
+        return lay[:self.graph.m]
+
+    def decode(self, syndromes):
+        """int8[B, m] -> (err int8[B, n], conv uint8[B], llr f64[B, n], iters int32[B]): the outputs of minsum_decode_batch"""
+        syndromes = i8(syndromes).reshape(-1, self.graph.m)
+        B = syndromes.shape[0]
+        err, llr = np.zeros((B, self.graph.n), np.int8), np.zeros((B, self.graph.n), np.float64)
+        conv, iters = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        check(lib().qldpc_layered_decode_batch(self._h, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(err, C.c_int8), ptr(llr, C.c_double),
+                                               ptr(conv, C.c_uint8), ptr(iters, C.c_int32)))
+        return err, conv, llr, iters
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib().qldpc_layered_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def osd_timers(reset=True):
     """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/osd_common.h) -> uint64[32]."""
     out = np.zeros(32, np.uint64)
@@ -775,6 +867,13 @@ class CircuitPlan:
         _, window, commit = check_window_args(1, window, commit)
         check(lib().qldpc_circuit_plan_use_window(self._h, window, commit))
         self.window = (window, commit)
+
+    def use_layered(self, layers_z=None, layers_x=None):
+        """Run the BP stage of both sectors with the layered schedule from now on (qldpc_circuit_plan_use_layered); layers_*: a row_layer per
+        sector, None = the greedy colouring.  Goes with OSD-0 and OSD-CS; not with Relay-BP or windows."""
+        lz, lx = check_row_layer(layers_z, self.graph_z.m), check_row_layer(layers_x, self.graph_x.m)
+        check(lib().qldpc_circuit_plan_use_layered(self._h, ptr(lz, C.c_int32) if lz is not None else None, ptr(lx, C.c_int32) if lx is not None else None))
+        self.layered = True
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))

@@ -257,6 +257,7 @@ struct qldpc_circuit_plan {
         // on the host: the prior lets the decode dispatch pick the LDS-resident workgroup kernel (minsum_wg2.hip), the window decoder takes both at the switch
         std::vector<double> h_prior, h_alpha;
         qldpc_window_decoder *win = nullptr;       // Decoder::WINDOW (window.hip)
+        qldpc_layered_decoder *lay = nullptr;      // the layered schedule in the BP bracket (minsum_layered.hip); both sectors or neither
         PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
         PlanBuf d_alpha, d_prior, d_lm;
         PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
@@ -541,6 +542,8 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
         // iter_bias -1: the judge adds one per trial, so the ITERS slots sum the Relay-BP iterations
         rc = relay_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->rp, seed, trial_begin, sector, -1, S.d_det.as<int8_t>(),
                                  S.d_conv.as<uint8_t>(), S.d_legs.as<int32_t>(), S.d_iter.as<int32_t>(), nullptr, s);
+    } else if (S.lay) {                   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
+        rc = layered_lock_and_launch(S.lay, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
     } else {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk : nullptr;                  // sector Z carries the probe (one writer per buffer)
@@ -692,10 +695,13 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 //   BP_OSD_CS      no                      yes: new order             no
 //   WINDOW         no                      no                         no
 //
-// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS), damping = 1 (WINDOW).
+// The layered schedule (qldpc_circuit_plan_use_layered) replaces the launch inside the BP bracket and leaves the mode alone: it goes with BP_OSD0 and
+// BP_OSD_CS in either order, and a plan that has it moves to neither RELAY nor WINDOW (nor gets it once there).
+// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS), damping = 1 (WINDOW, layered).
 static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
     static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(!P->sec[0].lay || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to the layered schedule: %s cannot follow", name[(int)to]);
     QLDPC_REQUIRE(to == Decoder::RELAY || P->use_osd, "the plan was created with use_osd = 0: %s needs its OSD stage", name[(int)to]);
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || (P->decoder == to && to != Decoder::WINDOW), "the plan was switched to %s: %s cannot follow",
                   name[(int)P->decoder], name[(int)to]);
@@ -755,10 +761,28 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window
     return QLDPC_OK;
 }
 
+QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int32_t *row_layer_z, const int32_t *row_layer_x) {
+    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: the layered schedule cannot follow",
+                  name[(int)P->decoder]);
+    QLDPC_REQUIRE(P->damping == 1.0, "the layered schedule needs damping = 1 (the plan has %g)", P->damping);
+    QLDPC_USE_DEVICE(P->device);
+    const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
+    qldpc_layered_decoder *d[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; i++) {
+        const Sector &S = P->sec[i];
+        const int rc = layered_decoder_create_tab(S.g, row_layer[i], S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
+        if (rc != QLDPC_OK) { qldpc_layered_decoder_destroy(d[0]); return rc; }
+    }
+    for (int i = 0; i < 2; i++) { qldpc_layered_decoder_destroy(P->sec[i].lay); P->sec[i].lay = d[i]; }
+    return QLDPC_OK;
+}
+
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {
     if (!P) return;
     (void)hipSetDevice(P->device);
-    for (Sector &S : P->sec) qldpc_window_decoder_destroy(S.win);
+    for (Sector &S : P->sec) { qldpc_window_decoder_destroy(S.win); qldpc_layered_decoder_destroy(S.lay); }
     for (auto &br : P->pending) { (void)hipEventDestroy(br.a); if (br.b) (void)hipEventDestroy(br.b); }
     for (auto e : P->pool) (void)hipEventDestroy(e);
     delete P;                                      // every PlanBuf releases itself

@@ -13,6 +13,7 @@
 
 struct qldpc_graph;
 struct qldpc_window_decoder;
+struct qldpc_layered_decoder;
 
 namespace qldpc {
 
@@ -83,6 +84,12 @@ int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, 
                               const std::vector<double> &tab, double clip_llr, int flags, qldpc_window_decoder **out);
 int window_decoder_lock_and_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, const WindowPlanSlots *plan,
                                    const std::function<int(int, bool)> *mark, hipStream_t s);
+// Layered-schedule min-sum (minsum_layered.hip) inside a circuit plan.  create_tab: qldpc_layered_decoder_create on a ready alpha table (row_layer NULL = the
+// greedy colouring).  lock_and_launch enqueues the decode of B shots with the outputs of minsum_decode_dispatch.
+int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, const double *prior, int max_iter, const std::vector<double> &tab,
+                               double clip_llr, int flags, qldpc_layered_decoder **out);
+int layered_lock_and_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
+                            hipStream_t s);
 int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
 
 }  // namespace qldpc

@@ -1,0 +1,452 @@
+// Layered-schedule normalised min-sum (semantics: include/qldpc_hip.h, qldpc_layered_decoder_create).
+//
+// The flooding decoders read every posterior, then update every posterior.  Here the checks are cut into layers whose members share no column;
+// a layer reads the posteriors the layers before it left, so one iteration carries information across the whole graph.  The state is the one
+// minsum_wg*.hip keep: the posteriors V[n] and a 24-byte record per check (alpha*min1, alpha*min2, argmin, sign bits) from which the old
+// message of an edge is rebuilt.  Inside a layer every V_j is touched by one check at most, so no floating-point sum has an order to choose and
+// the kernel equals the numpy model (tests/layered_model.py) bit for bit whatever the lane assignment.
+//
+// One workgroup per shot, persistent grid over an atomic shot queue.  The host orders the non-empty rows by (layer, row) into SLOTS and gives
+// every layer 2^lg lanes per check (at most 8 edges per lane, so a row's 56 edges need lg >= 3; more lanes while the layer still fits the
+// workgroup).  A lane scans its edges k = sub, sub + 2^lg, ... with the reference's strict-< rule; the lanes of a check combine
+// (min1, position) lexicographically through wave shuffles, so the argmin is the FIRST position of the minimum in ascending column order.
+// One workgroup barrier per layer; the syndrome test after the last layer is one more (__syncthreads_or).
+// LDS: V (or a per-workgroup slab in HBM/L2 when it does not fit: VG), the records, the slot edge offsets, the shot's syndrome bits by slot,
+// the layer table and -- when n <= 65535 and they still fit -- the column indices as u16 in slot order (else int32 in L2).
+// Every loop is bounded by the host tables and max_iter.
+#include "common.h"
+#include "mc_common.h"
+#include "minsum_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <vector>
+
+namespace qldpc {
+
+constexpr int kLayeredLds = 160 * 1024 - 512;   // dynamic LDS of a workgroup: a CU's 160 KB less the kernel's static 256 bytes (__syncthreads_or), rounded
+constexpr int kLayeredRowDeg = 56;        // sign bits of a record
+constexpr int kLayeredLaneEdges = 8;      // edges a lane holds in registers
+
+struct LayeredArgs {
+    int m, n, nslots, nlayers, nnz;
+    const uint32_t *layer;         // [nlayers + 1] first slot of the layer | lg << 24 (the last entry: nslots)
+    const int32_t *slot_row;       // [m] row of slot s; the rows without entries follow the nslots others
+    const uint32_t *estart;        // [nslots + 1] edge offsets in slot order
+    const uint16_t *idx16;         // [nnz] columns in slot order (n <= 65535), copied to LDS by the IDXL form
+    const int32_t *idx32;          // [nnz] the same as int32: read from HBM/L2 by the other form
+    int64_t B;
+    const int8_t *synd;
+    const double *prior, *alpha;
+    int max_iter;
+    double clip;
+    int8_t *out_err; double *out_llr; uint8_t *out_conv; int32_t *out_iter;
+    int offP, offI, offE, offL, offS, offX, offF;
+    double *vglobal;               // VG: V[n] per workgroup
+    int *queue;                    // next shot (zeroed before the launch)
+};
+
+template <bool VG, bool IDXL>
+__global__ __launch_bounds__(1024) void minsum_layered_kernel(LayeredArgs A) {
+    extern __shared__ unsigned char lds[];
+    double *V;
+    if (VG) V = A.vglobal + (size_t)blockIdx.x * A.n; else V = reinterpret_cast<double *>(lds);
+    double2 *SP = reinterpret_cast<double2 *>(lds + A.offP);                       // (alpha*min1, alpha*min2) per slot
+    unsigned long long *SI = reinterpret_cast<unsigned long long *>(lds + A.offI); // bits 0-55 input signs, 56-62 argmin (127 = none), 63 total sign
+    uint32_t *ES = reinterpret_cast<uint32_t *>(lds + A.offE);
+    uint32_t *LY = reinterpret_cast<uint32_t *>(lds + A.offL);
+    uint8_t *SY = lds + A.offS;
+    const uint16_t *IX = reinterpret_cast<const uint16_t *>(lds + A.offX);
+    int *F = reinterpret_cast<int *>(lds + A.offF);                                // [0] shot, [1] a row without entries has syndrome 1
+    const int n = A.n, m = A.m, ns = A.nslots, tid = threadIdx.x, NT = blockDim.x;
+    const double clip = A.clip;
+    auto col_of = [&](uint32_t e) -> int { return IDXL ? (int)IX[e] : A.idx32[e]; };
+
+    for (int i = tid; i <= ns; i += NT) ES[i] = A.estart[i];
+    for (int i = tid; i <= A.nlayers; i += NT) LY[i] = A.layer[i];
+    if (IDXL) {
+        uint16_t *W = reinterpret_cast<uint16_t *>(lds + A.offX);
+        for (int e = tid; e < A.nnz; e += NT) W[e] = A.idx16[e];
+    }
+    for (;;) {
+        if (tid == 0) { F[0] = atomicAdd(A.queue, 1); F[1] = 0; }
+        __syncthreads();
+        const int64_t b = F[0];
+        if (b >= A.B) break;
+        const int8_t *syn = A.synd + b * m;
+        for (int j = tid; j < n; j += NT) V[j] = A.prior[j];
+        for (int i = tid; i < m; i += NT) {
+            const int s = syn[A.slot_row[i]] & 1;
+            if (i < ns) { SY[i] = (uint8_t)s; SP[i] = make_double2(0.0, 0.0); SI[i] = 0ull; }          // R = +0.0 on every edge
+            else if (s) F[1] = 1;
+        }
+        __syncthreads();
+        bool conv = false;
+        int itc = A.max_iter - 1;
+        for (int it = 0; it < A.max_iter; it++) {
+            const double alpha = A.alpha[it];
+            for (int L = 0; L < A.nlayers; L++) {
+                const uint32_t w = LY[L];
+                const int first = (int)(w & 0xFFFFFFu), cnt = (int)(LY[L + 1] & 0xFFFFFFu) - first, lg = (int)(w >> 24);
+                const int lpc = 1 << lg, sub = tid & (lpc - 1), ngrp = NT >> lg;
+                for (int c = tid >> lg; c < cnt; c += ngrp) {                        // (the lanes of a check share c)
+                    const int slot = first + c;
+                    const uint32_t e0 = ES[slot];
+                    const int deg = (int)(ES[slot + 1] - e0);
+                    const double2 old = SP[slot];
+                    const unsigned long long ip = SI[slot];
+                    const int argp = (int)((ip >> 56) & 127);
+                    const bool spp = (ip >> 63) & 1;
+                    double q[kLayeredLaneEdges];
+                    int cols[kLayeredLaneEdges];
+                    double min1 = INFINITY, min2 = INFINITY;
+                    int pos = 127;
+                    unsigned long long negbits = 0ull;
+#pragma unroll
+                    for (int t = 0; t < kLayeredLaneEdges; t++) {
+                        const int k = sub + (t << lg);
+                        if (k < deg) {
+                            const int col = col_of(e0 + k);
+                            const double mag = (k == argp) ? old.y : old.x;
+                            const double rr = (spp != (bool)((ip >> k) & 1)) ? -mag : mag;
+                            const double x = clip_nan(V[col] - rr, clip);
+                            cols[t] = col; q[t] = x;
+                            negbits |= (unsigned long long)(x < 0.0) << k;
+                            const double a = fabs(x);
+                            if (a < min1) { min2 = min1; min1 = a; pos = k; }
+                            else if (a < min2) { min2 = a; }
+                        }
+                    }
+                    for (int off = lpc >> 1; off > 0; off >>= 1) {                   // lexicographic (|Q|, position) over the check's lanes
+                        const double o1 = __shfl_xor(min1, off, 64), o2 = __shfl_xor(min2, off, 64);
+                        const int op = __shfl_xor(pos, off, 64);
+                        negbits |= __shfl_xor(negbits, off, 64);
+                        const bool take = o1 < min1 || (o1 == min1 && op < pos);
+                        const double lose = take ? min1 : o1, w2 = take ? o2 : min2;
+                        min1 = take ? o1 : min1;
+                        pos = take ? op : pos;
+                        min2 = lose < w2 ? lose : w2;
+                    }
+                    const bool sp = (bool)SY[slot] != (bool)(__popcll(negbits) & 1);
+                    const double a1 = alpha * min1, a2 = alpha * min2;
+                    if (sub == 0) {
+                        SP[slot] = make_double2(a1, a2);
+                        SI[slot] = negbits | ((unsigned long long)pos << 56) | ((unsigned long long)sp << 63);
+                    }
+#pragma unroll
+                    for (int t = 0; t < kLayeredLaneEdges; t++) {
+                        const int k = sub + (t << lg);
+                        if (k < deg) {
+                            const double mag = (k == pos) ? a2 : a1;
+                            const double r = (sp != (bool)((negbits >> k) & 1)) ? -mag : mag;
+                            V[cols[t]] = q[t] + r;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            int bad = F[1];
+            for (int slot = tid; slot < ns; slot += NT) {
+                int par = SY[slot];
+                for (uint32_t e = ES[slot]; e < ES[slot + 1]; e++) par ^= (int)(V[col_of(e)] < 0.0);
+                bad |= par;
+            }
+            if (!__syncthreads_or(bad)) { conv = true; itc = it; break; }
+        }
+        for (int j = tid; j < n; j += NT) {
+            const double v = V[j];
+            A.out_llr[b * n + j] = v;
+            A.out_err[b * n + j] = (v < 0.0) ? 1 : 0;
+        }
+        if (tid == 0) { A.out_conv[b] = conv ? 1 : 0; A.out_iter[b] = itc; }
+        __syncthreads();
+    }
+}
+
+// Greedy colouring in ascending row order: the smallest layer no earlier row sharing a column holds (a row without entries: layer 0).
+static int greedy_layers(const qldpc_graph *g, std::vector<int32_t> &layer) {
+    const int m = g->m;
+    layer.assign(m, 0);
+    std::vector<int32_t> stamp(m + 1, -1);
+    int layers = 0;
+    for (int i = 0; i < m; i++) {
+        for (int e = g->indptr[i]; e < g->indptr[i + 1]; e++) {
+            const int j = g->indices[e];
+            for (int k = g->colptr[j]; k < g->colptr[j + 1] && g->rowidx[k] < i; k++) stamp[layer[g->rowidx[k]]] = i;
+        }
+        int c = 0;
+        while (stamp[c] == i) c++;
+        layer[i] = c;
+        layers = std::max(layers, c + 1);
+    }
+    return layers;
+}
+
+}  // namespace qldpc
+
+using namespace qldpc;
+
+struct qldpc_layered_decoder {
+    const qldpc_graph *g = nullptr;
+    int device = 0, m = 0, n = 0, nnz = 0, max_iter = 0, flags = 0;
+    double clip = 20;
+    int nlayers = 0, nslots = 0, max_rows = 0, max_edges = 0, block = 0, lds = 0, grid_cap = 0;
+    bool vg = false, idxl = false;
+    int offP = 0, offI = 0, offE = 0, offL = 0, offS = 0, offX = 0, offF = 0;
+    std::vector<int32_t> row_layer;
+    DevBuf d_prior, d_alpha, d_layer, d_slot_row, d_estart, d_idx16, d_idx32, d_queue, d_vglobal;
+    // the queue word and the VG slab are handed from stream to stream through an event like a graph handle's workspaces (common.h)
+    std::mutex mu;
+    hipEvent_t ws_event = nullptr;
+    hipStream_t ws_stream = nullptr;
+    bool ws_used = false;
+};
+
+namespace qldpc {
+
+static int ceil_log2(int x) { int l = 0; while ((1 << l) < x) l++; return l; }
+
+template <class T>
+static int upload(DevBuf &b, const std::vector<T> &v) {
+    int rc = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (rc != QLDPC_OK) return rc;
+    if (!v.empty()) QLDPC_HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return QLDPC_OK;
+}
+
+// Creation on a ready alpha table (the circuit plan holds one per sector); the exported form builds the table from the alpha mode.
+int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, const double *prior, int max_iter, const std::vector<double> &tab,
+                               double clip_llr, int flags, qldpc_layered_decoder **out) {
+    QLDPC_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    QLDPC_REQUIRE(g != nullptr && prior != nullptr, "NULL argument");
+    QLDPC_REQUIRE(max_iter >= 1, "max_iter must be >= 1 (got %d)", max_iter);
+    QLDPC_REQUIRE(clip_llr > 0.0, "clip_llr must be > 0 (got %g)", clip_llr);
+    const int m = g->m, n = g->n;
+    const int fb = flags & (QLDPC_FLAG_LAYERED_BLOCK_256 | QLDPC_FLAG_LAYERED_BLOCK_512 | QLDPC_FLAG_LAYERED_BLOCK_1024);
+    QLDPC_REQUIRE((fb & (fb - 1)) == 0, "more than one QLDPC_FLAG_LAYERED_BLOCK_* flag");
+    std::unique_ptr<qldpc_layered_decoder> D(new qldpc_layered_decoder());
+    // ---- layers: the caller's (validated) or the greedy colouring, then compressed to 0 .. nlayers - 1 in ascending order
+    if (row_layer) {
+        for (int i = 0; i < m; i++) QLDPC_REQUIRE(row_layer[i] >= 0, "row_layer[%d] = %d is negative", i, row_layer[i]);
+        D->row_layer.assign(row_layer, row_layer + m);
+    } else {
+        greedy_layers(g, D->row_layer);
+    }
+    std::vector<int32_t> order;                                     // the rows with entries by (layer, row)
+    for (int i = 0; i < m; i++) if (g->indptr[i + 1] > g->indptr[i]) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return D->row_layer[a] < D->row_layer[b]; });
+    if (row_layer) {                                                // two rows of one layer share no column
+        std::vector<int32_t> seen_layer(n, -1), seen_row(n, -1);
+        for (int i : order)
+            for (int e = g->indptr[i]; e < g->indptr[i + 1]; e++) {
+                const int j = g->indices[e];
+                QLDPC_REQUIRE(seen_layer[j] != row_layer[i], "rows %d and %d are both in layer %d and share column %d", seen_row[j], i, row_layer[i], j);
+                seen_layer[j] = row_layer[i]; seen_row[j] = i;
+            }
+    }
+    // ---- what the kernel holds
+    if (m < 1 || n < 1 || n >= (1 << 24) || m >= (1 << 24)) { set_error("the layered decoder needs 1 <= m, n < 2^24 (m=%d n=%d)", m, n); return QLDPC_ERR_UNSUPPORTED; }
+    if (g->max_row_deg > kLayeredRowDeg) {
+        set_error("the layered decoder supports row degree <= %d (this graph: %d)", kLayeredRowDeg, g->max_row_deg);
+        return QLDPC_ERR_UNSUPPORTED;
+    }
+    const int ns = (int)order.size(), nnz = g->nnz;
+    std::vector<int32_t> slot_row(order);
+    for (int i = 0; i < m; i++) if (g->indptr[i + 1] == g->indptr[i]) slot_row.push_back(i);
+    std::vector<uint32_t> estart(ns + 1, 0), layer;
+    std::vector<int32_t> idx32;
+    std::vector<uint16_t> idx16;
+    idx32.reserve(nnz);
+    std::vector<int> lfirst, lmaxdeg;
+    for (int s = 0; s < ns; s++) {
+        const int i = order[s], deg = g->indptr[i + 1] - g->indptr[i];
+        if (s == 0 || D->row_layer[i] != D->row_layer[order[s - 1]]) { lfirst.push_back(s); lmaxdeg.push_back(0); }
+        lmaxdeg.back() = std::max(lmaxdeg.back(), deg);
+        idx32.insert(idx32.end(), g->indices.begin() + g->indptr[i], g->indices.begin() + g->indptr[i + 1]);
+        estart[s + 1] = (uint32_t)idx32.size();
+    }
+    const int nl = (int)lfirst.size();
+    lfirst.push_back(ns);
+    for (int L = 0; L < nl; L++) {
+        const int cnt = lfirst[L + 1] - lfirst[L];
+        D->max_rows = std::max(D->max_rows, cnt);
+        D->max_edges = std::max(D->max_edges, (int)(estart[lfirst[L + 1]] - estart[lfirst[L]]));
+    }
+    D->g = g; D->device = g->device; D->m = m; D->n = n; D->nnz = nnz; D->max_iter = max_iter; D->flags = flags & QLDPC_FLAG_PUBLIC_MASK; D->clip = clip_llr;
+    D->nlayers = nl; D->nslots = ns;
+    // workgroup size: by the edges of an average layer (a small layer leaves most of a large workgroup at the barrier for nothing)
+    const int mean_edges = nl ? nnz / nl : 0;
+    D->block = fb == QLDPC_FLAG_LAYERED_BLOCK_256 ? 256 : fb == QLDPC_FLAG_LAYERED_BLOCK_512 ? 512 : fb == QLDPC_FLAG_LAYERED_BLOCK_1024 ? 1024
+               : mean_edges <= 512 ? 256 : mean_edges <= 1024 ? 512 : 1024;
+    for (int L = 0; L < nl; L++) {      // lanes per check: at most 8 edges per lane; more lanes while the layer fits the workgroup and a lane has an edge
+        const int cnt = lfirst[L + 1] - lfirst[L], lgmax = ceil_log2(std::max(lmaxdeg[L], 1));
+        int lg = ceil_log2((lmaxdeg[L] + kLayeredLaneEdges - 1) / kLayeredLaneEdges);
+        while (lg < lgmax && lg < 6 && ((int64_t)cnt << (lg + 1)) <= D->block) lg++;
+        layer.push_back((uint32_t)lfirst[L] | ((uint32_t)lg << 24));
+    }
+    layer.push_back((uint32_t)ns);
+    // LDS layout: [V] | records | edge offsets | layer table | syndrome bits | [column indices] | flags
+    auto layout = [&](bool vg, bool idxl) {
+        D->offP = vg ? 0 : (int)round_up((int64_t)n * 8, 16);
+        int64_t o = D->offP;
+        D->offI = (int)(o += (int64_t)ns * 16);
+        D->offE = (int)(o += (int64_t)ns * 8);
+        D->offL = (int)(o += (int64_t)(ns + 1) * 4);
+        D->offS = (int)(o += (int64_t)(nl + 1) * 4);
+        D->offX = (int)(o = round_up(o + ns, 16));
+        D->offF = (int)(o = round_up(o + (idxl ? (int64_t)nnz * 2 : 0), 16));
+        return o + 16;
+    };
+    const bool want_idxl = n <= 65535 && !(flags & QLDPC_FLAG_LAYERED_GLOBAL_IDX);
+    int64_t bytes = 0;
+    bool placed = false;
+    for (int form = 0; form < 4 && !placed; form++) {               // V and indices in LDS; V only; indices only (VG); neither
+        const bool vg = form >= 2, idxl = (form & 1) == 0;
+        if ((idxl && !want_idxl) || (!vg && (flags & QLDPC_FLAG_LAYERED_VGLOBAL))) continue;
+        bytes = layout(vg, idxl);
+        if (bytes <= kLayeredLds) { D->vg = vg; D->idxl = idxl; placed = true; }
+    }
+    if (!placed) {
+        set_error("the layered decoder keeps 29 bytes per non-empty row and 4 per layer in LDS: %d rows in %d layers need %lld bytes, more than %d", ns, nl,
+                  (long long)bytes, kLayeredLds);
+        return QLDPC_ERR_UNSUPPORTED;
+    }
+    D->lds = (int)bytes;
+    QLDPC_USE_DEVICE(g->device);
+    auto fail = [&](int code) { qldpc_layered_decoder_destroy(D.release()); return code; };
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    D->grid_cap = cus * (int)std::max<int64_t>(1, std::min<int64_t>(kLayeredLds / D->lds, 2048 / D->block));
+    int rc;
+    if (D->idxl) { idx16.assign(idx32.begin(), idx32.end()); if ((rc = upload(D->d_idx16, idx16)) != QLDPC_OK) return fail(rc); }
+    const std::vector<double> pv(prior, prior + n), av(tab.begin(), tab.begin() + max_iter);
+    if ((rc = upload(D->d_prior, pv)) || (rc = upload(D->d_alpha, av)) || (rc = upload(D->d_layer, layer)) || (rc = upload(D->d_slot_row, slot_row)) ||
+        (rc = upload(D->d_estart, estart)) || (rc = upload(D->d_idx32, idx32)) || (rc = D->d_queue.ensure(16)) ||
+        (D->vg && (rc = D->d_vglobal.ensure((size_t)D->grid_cap * n * 8))))
+        return fail(rc);
+    *out = D.release();
+    return QLDPC_OK;
+}
+
+// Enqueues the decode of B shots on `s`.  Callers hold D->mu.
+static int layered_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
+                          hipStream_t s) {
+    if (D->ws_used && s != D->ws_stream && D->ws_event) QLDPC_HIP_TRY(hipStreamWaitEvent(s, D->ws_event, 0));
+    LayeredArgs A;
+    A.m = D->m; A.n = D->n; A.nslots = D->nslots; A.nlayers = D->nlayers; A.nnz = D->nnz;
+    A.layer = D->d_layer.as<uint32_t>(); A.slot_row = D->d_slot_row.as<int32_t>(); A.estart = D->d_estart.as<uint32_t>();
+    A.idx16 = D->d_idx16.as<uint16_t>(); A.idx32 = D->d_idx32.as<int32_t>();
+    A.B = B; A.synd = d_synd; A.prior = D->d_prior.as<double>(); A.alpha = D->d_alpha.as<double>(); A.max_iter = D->max_iter; A.clip = D->clip;
+    A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
+    A.offP = D->offP; A.offI = D->offI; A.offE = D->offE; A.offL = D->offL; A.offS = D->offS; A.offX = D->offX; A.offF = D->offF;
+    A.vglobal = D->d_vglobal.as<double>(); A.queue = D->d_queue.as<int>();
+    QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
+    void (*kern)(LayeredArgs) = D->vg ? (D->idxl ? minsum_layered_kernel<true, true> : minsum_layered_kernel<true, false>)
+                                      : (D->idxl ? minsum_layered_kernel<false, true> : minsum_layered_kernel<false, false>);
+    const int rc = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kLayeredLds);
+    if (rc != QLDPC_OK) return rc;
+    const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
+    QLDPC_HIP_TRY(hipGetLastError());
+    if (!D->ws_event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&D->ws_event, hipEventDisableTiming));
+    QLDPC_HIP_TRY(hipEventRecord(D->ws_event, s));
+    D->ws_stream = s; D->ws_used = true;
+    return QLDPC_OK;
+}
+
+int layered_lock_and_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
+                            hipStream_t s) {
+    std::lock_guard<std::mutex> lk(D->mu);
+    return layered_launch(D, B, d_synd, d_err, d_llr, d_conv, d_iter, s);
+}
+
+}  // namespace qldpc
+
+QLDPC_EXPORT int qldpc_check_layers(const qldpc_graph *g, int32_t *row_layer, int *layers) {
+    QLDPC_REQUIRE(g != nullptr && row_layer != nullptr, "NULL argument");
+    std::vector<int32_t> lay;
+    const int nl = greedy_layers(g, lay);
+    std::copy(lay.begin(), lay.end(), row_layer);
+    if (layers) *layers = nl;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_layered_decoder_create(const qldpc_graph *g, const int32_t *row_layer, const double *prior, int max_iter, int alpha_mode,
+                                              double alpha_val, const double *alpha_seq, int alpha_len, double clip_llr, int flags,
+                                              qldpc_layered_decoder **out) {
+    QLDPC_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    QLDPC_REQUIRE(max_iter >= 1, "max_iter must be >= 1 (got %d)", max_iter);
+    std::vector<double> tab;
+    const int rc = build_alpha_table(max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, tab);
+    if (rc != QLDPC_OK) return rc;
+    return layered_decoder_create_tab(g, row_layer, prior, max_iter, tab, clip_llr, flags, out);
+}
+
+QLDPC_EXPORT void qldpc_layered_decoder_destroy(qldpc_layered_decoder *D) {
+    if (!D) return;
+    (void)hipSetDevice(D->device);
+    if (D->ws_used) (void)hipDeviceSynchronize();
+    if (D->ws_event) (void)hipEventDestroy(D->ws_event);
+    for (DevBuf *b : {&D->d_prior, &D->d_alpha, &D->d_layer, &D->d_slot_row, &D->d_estart, &D->d_idx16, &D->d_idx32, &D->d_queue, &D->d_vglobal}) b->release();
+    delete D;
+}
+
+QLDPC_EXPORT int qldpc_layered_decoder_info(const qldpc_layered_decoder *D, int *layers, int *max_layer_rows, int *max_layer_edges, int *lds_bytes,
+                                            int *form) {
+    QLDPC_REQUIRE(D != nullptr, "decoder is NULL");
+    if (layers) *layers = D->nlayers;
+    if (max_layer_rows) *max_layer_rows = D->max_rows;
+    if (max_layer_edges) *max_layer_edges = D->max_edges;
+    if (lds_bytes) *lds_bytes = D->lds;
+    if (form) *form = D->block | (D->vg ? QLDPC_LAYERED_FORM_VGLOBAL : 0) | (D->idxl ? QLDPC_LAYERED_FORM_LDS_INDICES : 0);
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_layered_decoder_layers(const qldpc_layered_decoder *D, int32_t *row_layer) {
+    QLDPC_REQUIRE(D != nullptr && row_layer != nullptr, "NULL argument");
+    std::copy(D->row_layer.begin(), D->row_layer.end(), row_layer);
+    return QLDPC_OK;
+}
+
+static int layered_check_call(const qldpc_layered_decoder *D, int64_t B, const void *synd, const void *err, const void *llr, const void *conv,
+                              const void *iter) {
+    QLDPC_REQUIRE(D != nullptr, "decoder is NULL");
+    QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
+    if (B > 0) QLDPC_REQUIRE(synd && err && llr && conv && iter, "NULL buffer");
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *D, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
+                                                uint8_t *d_conv, int32_t *d_iter, void *stream) {
+    int rc = layered_check_call(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(D->device);
+    if (B == 0) return QLDPC_OK;
+    return layered_lock_and_launch(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter, reinterpret_cast<hipStream_t>(stream));
+}
+
+QLDPC_EXPORT int qldpc_layered_decode_batch(qldpc_layered_decoder *D, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
+                                            int32_t *iter) {
+    int rc = layered_check_call(D, B, syndromes, err, llr, conv, iter);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(D->device);
+    if (B == 0) return QLDPC_OK;
+    const size_t Bz = (size_t)B, m = D->m, n = D->n;
+    DevTmp ds, de, dl, dc, di;
+    if ((rc = ds.alloc(Bz * m)) || (rc = de.alloc(Bz * n)) || (rc = dl.alloc(Bz * n * 8)) || (rc = dc.alloc(Bz)) || (rc = di.alloc(Bz * 4))) return rc;
+    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * m, hipMemcpyHostToDevice));
+    {
+        std::lock_guard<std::mutex> lk(D->mu);
+        rc = layered_launch(D, B, ds.as<int8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(), di.as<int32_t>(), nullptr);
+        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("layered decode failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+    }
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * n, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(llr, dl.p, Bz * n * 8, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(iter, di.p, Bz * 4, hipMemcpyDeviceToHost));
+    return QLDPC_OK;
+}

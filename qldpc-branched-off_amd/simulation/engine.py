@@ -36,6 +36,12 @@ ValueError.  OSD-CS returns OSD-0's answer wherever the syndrome is not reproduc
 ``window=(W, C)`` (an extension; ``decoder="bp_osd"`` with ``osd_order=0`` only, anything else raises ValueError) decodes both sectors with the
 sliding-window decoder (``decoding/window.py``): W syndrome cycles at a time, the first C of them committed, min-sum + OSD-0 per window.  The
 window graphs do not grow with ``num_cycles``.  The result also holds ``window``.
+
+``schedule="layered"`` (an extension; ``"flooding"`` is the default and today's behaviour) runs the BP stage of both sectors with the layered
+schedule (``decoding/layered.py``); only that stage changes, OSD-0 (``decoder="bp_osd"``) or OSD-CS (``decoder="bp_osd_cs"``) follows as before.
+``layers=(row_layer_z, row_layer_x)`` names the layers (either may be None = the greedy colouring).  The alpha / SCOPT estimators measure flooding
+messages, so anything that would run one raises ValueError (``alpha_mode="alvarado"`` without ``alvarado_alpha``, ``"alvarado-autoregressive"``,
+``scopt=True``), as do ``decoder="relay_bp"``, ``window=...`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``schedule`` and ``layers_z`` / ``layers_x`` (layer counts).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -45,6 +51,7 @@ import numpy as np
 from .. import _lib, parallel
 from ..decoding.alpha import estimate_alpha_alvarado, estimate_alpha_alvarado_autoregressive
 from ..decoding.scopt import estimate_scopt_beta
+from ..decoding.layered import check_layers, layer_count, validate_layers
 from ..codes.bb_code import BBCodeCircuit
 from ..noise.compiled import CompiledCircuit
 from ..noise.builder import build_decoding_matrices
@@ -65,9 +72,32 @@ def _estimation_trials(requested, n_cols, error_rate):
 def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
-                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, **bb_params):
+                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
+                   layers=None, **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
+    if schedule not in ("flooding", "layered"):
+        raise ValueError(f"Unsupported schedule: {schedule!r} (expected 'flooding' or 'layered')")
+    layered = schedule == "layered"
+    if layers is not None and not layered:
+        raise ValueError("layers is for schedule='layered'")
+    if layered:                          # (before any device call: these are argument rules)
+        if decoder == "relay_bp":
+            raise ValueError("schedule='layered' goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
+        if window is not None:
+            raise ValueError(f"schedule='layered' does not go with window={window!r}")
+        mode = alpha_mode if alpha_mode is not None else ("dynamical" if use_dynamic_alpha else "alvarado")
+        if mode == "alvarado-autoregressive" or (mode == "alvarado" and alvarado_alpha is None):
+            raise ValueError(f"schedule='layered' has no alpha estimator (alpha_mode={mode!r} would run the flooding one): pass alvarado_alpha or use 'dynamical'")
+        if scopt:
+            raise ValueError("schedule='layered' has no SCOPT estimator (scopt=True would run the flooding one)")
+        if decoder == "bp_osd" and osd_order > 0:
+            raise ValueError(f"schedule='layered' goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes with the flooding schedule)")
+        _lib.check_layered_args(maxIter, 20.0)
+        if layers is None:
+            layers = (None, None)
+        if not isinstance(layers, (tuple, list)) or len(layers) != 2:
+            raise ValueError("layers must be a pair (row_layer_z, row_layer_x); either may be None")
     if window is not None:
         if decoder != "bp_osd" or osd_order != 0:
             raise ValueError("window=(W, C) goes with decoder='bp_osd' and osd_order=0 only")
@@ -181,6 +211,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
 
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
+    if layered:                          # host code: the layers every worker's plan gets
+        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, layers)]
     osdw_pass = osd_order > 0 and not osd_cs          # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
     class Worker:
@@ -198,6 +230,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                 self.plan.use_osd_cs(int(osd_order))
             if window is not None:
                 self.plan.use_window(*window)
+            if layered:
+                self.plan.use_layered(*layers)
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -336,5 +370,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         result.update(decoder=decoder, osd_order=int(osd_order))
     if window is not None:
         result.update(window=tuple(window))
+    if layered:
+        result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]))
     result["tally"] = total
     return result
