@@ -7,6 +7,17 @@
 // columns), but with compile-time degrees the check update is straight-line code:
 //   * Q = clip(V[col] - R) as v_min_f64/v_max_f64 (the NaN test of kernels.py:328 is kept unless the launcher proved
 //     that no NaN can arise: finite prior/clip/alpha and every check degree >= 2);
+//   * clean undamped inputs (NANFREE && !DAMP; "clean" includes a finite clip > 0, inputs_clean() in decode_api.hip) do not clip
+//     the CDEG edges at all: they clip the two minima.  After the clip, Q is used only through its sign, its magnitude inside
+//     the min1 / min2 network, and the test |Q| == min1, and each of them follows from the UNCLIPPED t = V[col] - R:
+//       sign       clip(t) < 0 <=> t < 0 for clip > 0 (-0.0 stays -0.0 and counts as >= 0 either way);
+//       magnitude  |clip(t)| = min(|t|, clip), and min is monotone and rounds nothing, so the two smallest clipped magnitudes
+//                  (with multiplicity) are min(min1, clip) and min(min2, clip) of the unclipped ones, bit for bit;
+//       selector   min1 < clip: |clip(t_k)| == min(min1, clip) <=> |t_k| == min1, the same positions; min1 >= clip: every
+//                  clipped magnitude is clip, alpha*min1 == alpha*min2, and the selector cannot change a message.
+//     Two v_min_f64 per check instead of 2 * CDEG per check; messages, posteriors, iteration counts and tallies are unchanged.
+//     clip == 0 is NOT covered (clip(t) = +-0.0 loses the sign the reference then reads as >= 0): such a call is not clean and
+//     takes the NaN-tolerant per-edge form, like the damped form, whose Q_old needs the clipped value of every edge;
 //   * min1 / min2 = the two smallest magnitudes WITH multiplicity, from a 14-op v_min/v_max network (kernels.py:301-306);
 //     the position that receives min2 is selected by |q| == min1: if the minimum is attained twice, min2 == min1, so
 //     this equals the reference's "first strict minimum" rule at every position;
@@ -71,6 +82,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     int *sres = I + 2 * S + 2 + 4 * sl; // conv, final_iter, nonzero syndrome, failure index
     const double *Al = reinterpret_cast<const double *>(lds + A.offA);                  // alpha_k staged in LDS
     unsigned long long *Tl = reinterpret_cast<unsigned long long *>(lds + A.offT);      // block tally (MC)
+    constexpr bool CLIPMIN = NANFREE && !DAMP;      // clip the two minima of a check instead of its CDEG edges (header comment); needs clip > 0, which NANFREE includes
     const double clip = A.clip, nclip = -A.clip, damping = A.damping, one_minus_d = 1.0 - A.damping;
     for (int k = threadIdx.x; k < max_iter; k += blockDim.x) reinterpret_cast<double *>(lds + A.offA)[k] = A.alpha[k];
     if (MC && threadIdx.x < 6) Tl[threadIdx.x] = 0ull;
@@ -198,7 +210,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                         for (int k = 0; k < CDEG; k++) {
                             double t = x[k] - Rprev[k];                                        // kernels.py:325
                             if (!NANFREE) t = (t != t) ? 0.0 : t;                              // kernels.py:328-329
-                            t = vmax(vmin(t, clip), nclip);                                    // kernels.py:330-333
+                            if (!CLIPMIN) t = vmax(vmin(t, clip), nclip);                      // kernels.py:330-333 (CLIPMIN: the two minima are clipped below instead)
                             if (DAMP) {                                                        // kernels.py:336-342
                                 const double qd = damping * t + one_minus_d * Qold[k];
                                 t = NANFREE ? vmax(vmin(qd, clip), nclip) : clip_only(qd, clip);       // a NaN (from a NaN Q_old) must survive the clip
@@ -232,7 +244,10 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
                     // the first minimum gets min2, everybody else min1 (kernels.py:313).  If the minimum is attained twice,
                     // min2 == min1, so selecting on |q| == min1 gives the same value at every position.
-                    const double p1 = alpha * min1, p2 = alpha * min2;                         // (+-alpha)*mag == +-(alpha*mag)
+                    // CLIPMIN: x holds UNCLIPPED values; |clip(t)| = min(|t|, clip) and min is monotone, so clipping min1 and min2 gives the minima of the
+                    // clipped magnitudes (header comment).  Iteration 0 takes no clip (kernels.py:263-265): its inputs are priors.
+                    const double cmin = (it > 0) ? clip : INFINITY;
+                    const double p1 = alpha * (CLIPMIN ? vmin(min1, cmin) : min1), p2 = alpha * (CLIPMIN ? vmin(min2, cmin) : min2);   // (+-alpha)*mag == +-(alpha*mag)
                     const int p1lo = __double2loint(p1), p1hi = __double2hiint(p1), p2lo = __double2loint(p2), p2hi = __double2hiint(p2);
 #pragma unroll
                     for (int k = 0; k < CDEG; k++) {
@@ -430,7 +445,7 @@ static int launch_reg2(const RegArgs &A, bool damp, bool nanfree, unsigned grid,
     if (damp) {
         if (MC) return QLDPC_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, true, false, false, FIXED>), dim3(grid), dim3(block), lds, stream, A);
-    } else if (nanfree) {
+    } else if (nanfree && A.clip > 0.0) {             // the clean form clips minima, not edges: exact for clip > 0 only (inputs_clean() has checked it; kept next to the launch)
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, true, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
     } else {
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, false, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
