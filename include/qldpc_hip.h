@@ -34,6 +34,8 @@
  *        qldpc_circuit_plan_use_window
  *        additive, same version: layered-schedule min-sum, qldpc_layered_decoder_*, qldpc_layered_decode_batch[_dev], qldpc_check_layers,
  *        qldpc_circuit_plan_use_layered, QLDPC_FLAG_LAYERED_* and QLDPC_LAYERED_FORM_*
+ *        additive, same version: BP with guided decimation, qldpc_decim_decode_batch[_dev], qldpc_circuit_plan_use_decimation; the tally slots
+ *        QLDPC_TALLY_LEGS_Z / _X also carry its rounds
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -106,7 +108,7 @@ extern "C" {
 #define QLDPC_TALLY_ZERO_SYND_X 11
 #define QLDPC_TALLY_UNSAT_Z 12    /* decoder output (after OSD if enabled) does not reproduce the syndrome */
 #define QLDPC_TALLY_UNSAT_X 13
-#define QLDPC_TALLY_LEGS_Z 14     /* Relay-BP circuit plans: sum over trials of the legs run (0 on every other path) */
+#define QLDPC_TALLY_LEGS_Z 14     /* Relay-BP: legs; decimation: rounds -- summed over the trials of a circuit plan (0 on every other path) */
 #define QLDPC_TALLY_LEGS_X 15
 
 typedef struct qldpc_graph qldpc_graph; /* Tanner graph: host CSR + CSC (ascending check order) + device copies */
@@ -215,6 +217,38 @@ int qldpc_relay_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *
                                  double clip_llr, double gamma0, double gamma_min, double gamma_max, int t0, int tr, int max_legs,
                                  int stop_after, uint64_t seed, int64_t shot_begin, int tag, int8_t *d_err, uint8_t *d_conv, int32_t *d_legs,
                                  int32_t *d_iters, int32_t *d_solutions, void *stream);
+
+/* BP with guided decimation (BPGD; Yao, Laird, Gokduman, Pfister et al. 2024).  New here: the reference has no counterpart.  Constant-alpha
+ * normalised min-sum in rounds of t_round iterations; after a round that did not converge the most reliable undecided columns are frozen to
+ * their hard decision by replacing their prior with +-fix_llr.  No elimination, no random numbers.
+ * Arguments: prior[n] finite (checked in the host entry; a precondition of the _dev entry); alpha, clip_llr, fix_llr finite and > 0;
+ * t_round >= 1; 0 <= max_rounds < 2^20; 1 <= per_round <= 64; B = 0 is a no-op.  Per shot:
+ *   1. bias_j = prior_j and V_j = prior_j; no column is fixed.
+ *   2. Round r = 0 .. max_rounds runs exactly one leg of Relay-BP (qldpc_relay_decode_batch) with T = t_round, gamma_j = 0 and bias_j in
+ *      place of prior_j: the check state is rebuilt at the round's first pass (it = 0) from Q = V; from it = 1 on Q = V - R with a NaN
+ *      becoming 0.0 and the result clipped to +-clip_llr; the minima, signs and alpha * min of the flooding decoder; s_j = 0.0 + the sum of
+ *      R in ascending check order; V_j = s_j + bias_j (each one correctly rounded f64 operation, nothing contracted).  Convergence
+ *      (H (V < 0) = s over every row) is tested at it >= 1 on V; the round's iteration count is it if it converged at it, else T.
+ *   3. If the round converged, stop: conv = 1.
+ *   4. Otherwise, if r == max_rounds or no column is unfixed, stop: conv = 0.
+ *   5. Otherwise decimate: the unfixed columns are keyed by a_j = |V_j| (a NaN counts as 0, +inf is the largest) and ordered by a_j
+ *      descending, then by ORIGINAL column index ascending; the first min(per_round, #unfixed) of them become fixed, each with
+ *      bias_j = (V_j < 0) ? -fix_llr : +fix_llr and V_j = bias_j.  Everything else in V stays, and the next round starts from there.
+ *   6. Outputs: err[j] = V_j < 0; llr = V (f64[n], the posteriors qldpc_osd0_batch / qldpc_osdcs_batch read; may be NULL in the host entry);
+ *      conv uint8; iters = the sum of the rounds' iteration counts; rounds = rounds run, 1 .. 1 + max_rounds; fixed = columns fixed.
+ *      rounds and fixed may be NULL.
+ *   7. max_rounds = 0 is qldpc_relay_decode_batch(max_legs = 0, gamma0 = 0, t0 = t_round) bit for bit: constant-alpha min-sum.
+ * A frozen column is not immune: its marginal is s_j +- fix_llr, and |s_j| <= (column degree) * alpha * clip_llr on a graph without
+ * degree-1 checks, so fix_llr above that bound keeps its hard decision for good.
+ * QLDPC_ERR_UNSUPPORTED under Relay-BP's conditions (a row degree above 56, a check state that does not fit in LDS); QLDPC_ERR_INVALID
+ * for the arguments above.  Results depend only on the inputs: not on batch splits, the grid or the order of the shots. */
+int qldpc_decim_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior, double alpha, double clip_llr,
+                             int t_round, int max_rounds, int per_round, double fix_llr, int8_t *err, double *llr, uint8_t *conv,
+                             int32_t *iters, int32_t *rounds, int32_t *fixed);
+/* same on device pointers (d_rounds / d_fixed may be NULL, d_llr not); only enqueues on `stream`.  Precondition: every d_prior entry is finite. */
+int qldpc_decim_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_prior, double alpha,
+                                 double clip_llr, int t_round, int max_rounds, int per_round, double fix_llr, int8_t *d_err, double *d_llr,
+                                 uint8_t *d_conv, int32_t *d_iters, int32_t *d_rounds, int32_t *d_fixed, void *stream);
 
 /* a6: GF(2) syndrome SpMV  s = H e (kernels.py:222-231, 352-359; H_csr.dot(e)%2 in alpha.py:128): vectors[B][n] -> out[B][m] */
 int qldpc_gf2_spmv_batch(const qldpc_graph *g, int64_t B, const int8_t *vectors, int8_t *out);
@@ -509,6 +543,15 @@ int qldpc_circuit_plan_use_window(qldpc_circuit_plan *plan, int window, int comm
  * or switched to Relay-BP or to windows (and qldpc_circuit_plan_use_relay / _use_window after this call return QLDPC_ERR_INVALID); otherwise
  * what qldpc_layered_decoder_create returns. */
 int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *plan, const int32_t *row_layer_z, const int32_t *row_layer_x);
+/* Switches the BP launch of both sectors to BP with guided decimation (qldpc_decim_decode_batch's kernel) with the plan's priors and clip_llr and
+ * the arguments given here.  Only the launch inside the BP bracket changes: it writes the plan's hard decisions, posteriors, converged flags and
+ * iteration counts, so sampler, unconverged list, the OSD-0 / OSD-CS stage and judge are untouched, and qldpc_circuit_plan_use_osd_cs may come
+ * before or after.  The plan's own max_iter and alpha table are NOT used by the switched bracket.  The tally keeps its meaning: bp_conv =
+ * decimation converged, iters = the sum of its iterations, and QLDPC_TALLY_LEGS_Z / _X sum the rounds.  A second call replaces the
+ * arguments.  QLDPC_ERR_INVALID for arguments qldpc_decim_decode_batch refuses, priors that are not finite, damping != 1, a plan switched to
+ * Relay-BP or to windows or whose BP stage runs the layered schedule (and qldpc_circuit_plan_use_relay / _use_window / _use_layered after this
+ * call return QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_decim_decode_batch refuses. */
+int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *plan, double alpha, int t_round, int max_rounds, int per_round, double fix_llr);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

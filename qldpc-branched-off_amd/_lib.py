@@ -459,6 +459,55 @@ def relay_decode_batch(graph, syndromes, prior, seed, shot_begin=0, tag=0, **par
     return err, conv, legs, iters, sols
 
 
+# Guided decimation: the starting point of the sweep in tools/kbench_decimation.py (see DESIGN 4.8 for what has been measured); the tests pass every
+# parameter explicitly
+DECIM_DEFAULTS = {"alpha": 1.0, "clip_llr": 20.0, "t_round": 12, "max_rounds": 32, "per_round": 8, "fix_llr": 50.0}
+
+
+def decim_params(params, with_clip=True):
+    """DECIM_DEFAULTS updated by `params` and validated: ValueError for an unknown name or a value qldpc_decim_decode_batch rejects."""
+    unknown = set(params) - set(DECIM_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown decimation parameter(s): {sorted(unknown)}")
+    p = dict(DECIM_DEFAULTS, **params)
+    for k in ("alpha", "clip_llr", "fix_llr"):
+        p[k] = float(p[k])
+        if not np.isfinite(p[k]) or p[k] <= 0:
+            raise ValueError(f"{k} must be finite and > 0")
+    for k in ("t_round", "max_rounds", "per_round"):
+        if int(p[k]) != p[k]:
+            raise ValueError(f"{k} must be an integer")
+        p[k] = int(p[k])
+    if p["t_round"] < 1:
+        raise ValueError("t_round must be >= 1")
+    if not 0 <= p["max_rounds"] < 2 ** 20:
+        raise ValueError("max_rounds must be in [0, 2**20)")
+    if not 1 <= p["per_round"] <= 64:
+        raise ValueError("per_round must be in 1..64")
+    if not with_clip:
+        p.pop("clip_llr")
+    return p
+
+
+def decim_decode_batch(graph, syndromes, prior, **params):
+    """qldpc_decim_decode_batch on host arrays -> (err int8[B, n], llr f64[B, n], conv uint8[B], iters int32[B], rounds int32[B], fixed int32[B])."""
+    p = decim_params(params)
+    prior = f64(prior).reshape(-1)
+    if prior.size != graph.n:
+        raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+    if not np.all(np.isfinite(prior)):
+        raise ValueError("guided decimation needs a finite prior")
+    syndromes = i8(syndromes).reshape(-1, graph.m)
+    B = syndromes.shape[0]
+    err, llr = np.zeros((B, graph.n), np.int8), np.zeros((B, graph.n), np.float64)
+    conv = np.zeros(B, np.uint8)
+    iters, rounds, fixed = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    check(lib().qldpc_decim_decode_batch(graph.handle, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(prior, C.c_double), p["alpha"], p["clip_llr"],
+                                         p["t_round"], p["max_rounds"], p["per_round"], p["fix_llr"], ptr(err, C.c_int8), ptr(llr, C.c_double),
+                                         ptr(conv, C.c_uint8), ptr(iters, C.c_int32), ptr(rounds, C.c_int32), ptr(fixed, C.c_int32)))
+    return err, llr, conv, iters, rounds, fixed
+
+
 def check_window_args(layer_rows, window, commit, m=None):
     """ValueError unless window >= 1, 1 <= commit <= window and layer_rows >= 1 (dividing m when m is given) -> the three as ints."""
     for name, v in (("layer_rows", layer_rows), ("window", window), ("commit", commit)):
@@ -874,6 +923,16 @@ class CircuitPlan:
         lz, lx = check_row_layer(layers_z, self.graph_z.m), check_row_layer(layers_x, self.graph_x.m)
         check(lib().qldpc_circuit_plan_use_layered(self._h, ptr(lz, C.c_int32) if lz is not None else None, ptr(lx, C.c_int32) if lx is not None else None))
         self.layered = True
+
+    def use_decimation(self, **params):
+        """Run the BP stage of both sectors as BP with guided decimation from now on (qldpc_circuit_plan_use_decimation): alpha, t_round, max_rounds,
+        per_round, fix_llr; the plan's clip_llr applies and its max_iter / alpha table are not used by that stage.  Goes with OSD-0 and OSD-CS; not
+        with Relay-BP, windows or the layered schedule."""
+        if "clip_llr" in params:
+            raise ValueError("a circuit plan's clip_llr is set when the plan is created")
+        p = decim_params(params, with_clip=False)
+        check(lib().qldpc_circuit_plan_use_decimation(self._h, p["alpha"], p["t_round"], p["max_rounds"], p["per_round"], p["fix_llr"]))
+        self.decimation = p
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))

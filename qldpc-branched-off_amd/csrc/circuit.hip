@@ -261,7 +261,7 @@ struct qldpc_circuit_plan {
         PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
         PlanBuf d_alpha, d_prior, d_lm;
         PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
-        PlanBuf d_legs;                            // Decoder::RELAY: legs per trial
+        PlanBuf d_legs;                            // Decoder::RELAY: legs per trial; guided decimation: rounds per trial
         PlanBuf d_flips;                           // Decoder::BP_OSD_CS: workspace of the sweep
     } sec[2];
     int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
@@ -273,6 +273,8 @@ struct qldpc_circuit_plan {
     Decoder decoder = Decoder::BP_OSD0;
     RelayParams rp{};                              // Decoder::RELAY (relay_bp.hip)
     int cs_order = 0;                              // Decoder::BP_OSD_CS (osd_cs.hip)
+    bool decim = false;                            // guided decimation in the BP bracket of both sectors (decimation.hip); the mode stays BP_OSD0 / BP_OSD_CS
+    DecimParams dp{};
     // hipEvent brackets of the phases of every batch not yet read by qldpc_circuit_plan_phase_times
     struct Bracket { int phase; hipEvent_t a, b; };
     std::vector<Bracket> pending;
@@ -544,6 +546,10 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
                                  S.d_conv.as<uint8_t>(), S.d_legs.as<int32_t>(), S.d_iter.as<int32_t>(), nullptr, s);
     } else if (S.lay) {                   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
         rc = layered_lock_and_launch(S.lay, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
+    } else if (P->decim) {                // guided decimation: same outputs too; iter_bias -1 as for Relay-BP, the rounds go where its legs go
+        std::lock_guard<std::mutex> lk(g->mu);
+        rc = decim_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->dp, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(),
+                                 S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), S.d_legs.as<int32_t>(), nullptr, s);
     } else {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk : nullptr;                  // sector Z carries the probe (one writer per buffer)
@@ -598,7 +604,7 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
                            outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
-        if (P->decoder == Decoder::RELAY &&
+        if ((P->decoder == Decoder::RELAY || P->decim) &&
             (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), P->sec[1].d_legs.as<int32_t>(), P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
             return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
@@ -697,11 +703,14 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 //
 // The layered schedule (qldpc_circuit_plan_use_layered) replaces the launch inside the BP bracket and leaves the mode alone: it goes with BP_OSD0 and
 // BP_OSD_CS in either order, and a plan that has it moves to neither RELAY nor WINDOW (nor gets it once there).
-// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS), damping = 1 (WINDOW, layered).
+// Guided decimation (qldpc_circuit_plan_use_decimation) is a second replacement of that launch under the same rules; a plan has at most one of the two.
+// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS, decimation), damping = 1
+// (WINDOW, layered, decimation).
 static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
     static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(!P->sec[0].lay || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to the layered schedule: %s cannot follow", name[(int)to]);
+    QLDPC_REQUIRE(!P->decim || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to guided decimation: %s cannot follow", name[(int)to]);
     QLDPC_REQUIRE(to == Decoder::RELAY || P->use_osd, "the plan was created with use_osd = 0: %s needs its OSD stage", name[(int)to]);
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || (P->decoder == to && to != Decoder::WINDOW), "the plan was switched to %s: %s cannot follow",
                   name[(int)P->decoder], name[(int)to]);
@@ -766,6 +775,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: the layered schedule cannot follow",
                   name[(int)P->decoder]);
+    QLDPC_REQUIRE(!P->decim, "the plan's BP stage was switched to guided decimation: the layered schedule cannot follow");
     QLDPC_REQUIRE(P->damping == 1.0, "the layered schedule needs damping = 1 (the plan has %g)", P->damping);
     QLDPC_USE_DEVICE(P->device);
     const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
@@ -776,6 +786,26 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int
         if (rc != QLDPC_OK) { qldpc_layered_decoder_destroy(d[0]); return rc; }
     }
     for (int i = 0; i < 2; i++) { qldpc_layered_decoder_destroy(P->sec[i].lay); P->sec[i].lay = d[i]; }
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double alpha, int t_round, int max_rounds, int per_round, double fix_llr) {
+    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: guided decimation cannot follow",
+                  name[(int)P->decoder]);
+    QLDPC_REQUIRE(!P->sec[0].lay, "the plan's BP stage was switched to the layered schedule: guided decimation cannot follow");
+    QLDPC_REQUIRE(P->damping == 1.0, "guided decimation needs damping = 1 (the plan has %g)", P->damping);
+    const DecimParams dp{alpha, P->clip, fix_llr, t_round, max_rounds, per_round};
+    int rc;
+    if ((rc = decim_check_params(dp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
+    for (const Sector &S : P->sec)
+        if (!decim_supported(S.g)) return decim_unsupported(S.g);
+    QLDPC_USE_DEVICE(P->device);
+    for (Sector &S : P->sec)
+        if ((rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    P->dp = dp;
+    P->decim = true;
     return QLDPC_OK;
 }
 

@@ -125,6 +125,15 @@ int relay_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, c
                         int64_t shot_begin, int tag, int iter_bias, int8_t *d_err, uint8_t *d_conv, int32_t *d_legs, int32_t *d_iters,
                         int32_t *d_sol, hipStream_t stream);
 int relay_legs_tally_launch(int64_t B, const int32_t *d_legs_z, const int32_t *d_legs_x, unsigned long long *d_tally, hipStream_t stream);
+// BP with guided decimation (decimation.hip): rounds of constant-alpha min-sum with the most reliable columns frozen in between.  Parameters as in
+// qldpc_decim_decode_batch; callers validate them with decim_check_params.
+struct DecimParams { double alpha, clip, fix; int t_round, max_rounds, per_round; };
+int decim_check_params(const DecimParams &P);
+bool decim_supported(const qldpc_graph *g);
+int decim_unsupported(const qldpc_graph *g);     // sets the error text, returns QLDPC_ERR_UNSUPPORTED
+// callers hold g->mu.  iter_bias is added to every iteration count written to d_iters; d_llr / d_rounds / d_fixed may be NULL
+int decim_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, const DecimParams &P, int iter_bias, int8_t *d_err,
+                        double *d_llr, uint8_t *d_conv, int32_t *d_iters, int32_t *d_rounds, int32_t *d_fixed, hipStream_t stream);
 // h_prior: the same prior on the host when the caller has it (a circuit plan, the host-pointer entry point), else NULL
 int minsum_decode_dispatch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter,
                            const double *d_alpha, double damping, double clip, int flags, bool nanfree, int8_t *d_err, double *d_llr,

@@ -42,6 +42,14 @@ schedule (``decoding/layered.py``); only that stage changes, OSD-0 (``decoder="b
 ``layers=(row_layer_z, row_layer_x)`` names the layers (either may be None = the greedy colouring).  The alpha / SCOPT estimators measure flooding
 messages, so anything that would run one raises ValueError (``alpha_mode="alvarado"`` without ``alvarado_alpha``, ``"alvarado-autoregressive"``,
 ``scopt=True``), as do ``decoder="relay_bp"``, ``window=...`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``schedule`` and ``layers_z`` / ``layers_x`` (layer counts).
+
+``decimation={...}`` (an extension; None is today's behaviour) runs the BP stage of both sectors as BP with guided decimation
+(``decoding/decimation.py``); the dict holds any of ``alpha, t_round, max_rounds, per_round, fix_llr`` (``_lib.DECIM_DEFAULTS`` for the rest).  Only
+that stage changes: OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_osd_cs"``) follows on the unconverged trials as before.  Its
+alpha is the constant of the dict and ``maxIter`` is not used by it, so every argument that selects or estimates another alpha raises ValueError
+(``alpha_mode``, ``alvarado_alpha``, ``use_dynamic_alpha=False``, ``scopt=True``), as do ``decoder="relay_bp"``, ``window=...``,
+``schedule="layered"`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``decimation`` (the parameters used) and
+``mean_rounds_z`` / ``mean_rounds_x``.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -73,9 +81,27 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, **bb_params):
+                   layers=None, decimation=None, **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
+    if decimation is not None:           # (before any device call: these are argument rules)
+        if not isinstance(decimation, dict):
+            raise ValueError("decimation must be a dict of guided-decimation parameters (or None)")
+        if decoder == "relay_bp":
+            raise ValueError("decimation=... goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
+        if window is not None:
+            raise ValueError(f"decimation=... does not go with window={window!r}")
+        if schedule == "layered":
+            raise ValueError("decimation=... does not go with schedule='layered' (both replace the BP stage)")
+        if decoder == "bp_osd" and osd_order > 0:
+            raise ValueError(f"decimation=... goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes with flooding min-sum)")
+        bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None),
+                                        ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
+        if bad:
+            raise ValueError(f"decimation=... does not use {', '.join(bad)}: its alpha is the constant decimation['alpha']")
+        if "clip_llr" in decimation:
+            raise ValueError("decimation: the circuit plan's clip_llr is fixed (20)")
+        decimation = _lib.decim_params(decimation, with_clip=False)
     if schedule not in ("flooding", "layered"):
         raise ValueError(f"Unsupported schedule: {schedule!r} (expected 'flooding' or 'layered')")
     layered = schedule == "layered"
@@ -232,6 +258,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                 self.plan.use_window(*window)
             if layered:
                 self.plan.use_layered(*layers)
+            if decimation is not None:
+                self.plan.use_decimation(**decimation)
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -372,5 +400,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         result.update(window=tuple(window))
     if layered:
         result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]))
+    if decimation is not None:
+        trials = max(int(total[T["trials"]]), 1)
+        result.update(decimation=dict(decimation), mean_rounds_z=float(total[T["legs_z"]]) / trials, mean_rounds_x=float(total[T["legs_x"]]) / trials)
     result["tally"] = total
     return result
