@@ -18,6 +18,9 @@ struct RegCold {
 __device__ __forceinline__ double vmin(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double vmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double vmin_abs(double a, double b) { double r; asm("v_min_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// min(|a|, b) with b >= 0 read from scalar registers: no vector copy of b.  b MUST be wave-uniform (a kernel argument, or a value selected
+// by a wave-uniform condition): the "s" constraint makes the compiler read a divergent b from its first active lane without a diagnostic.
+__device__ __forceinline__ double vmin_abs_u(double a, double b) { double r; asm("v_min_f64 %0, |%1|, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
 __device__ __forceinline__ double vmax_abs(double a, double b) { double r; asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
 // The two smallest magnitudes (with multiplicity) of x[0..D): pairs -> (min,max), then merge (lo,hi) sets:

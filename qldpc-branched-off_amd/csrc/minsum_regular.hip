@@ -7,22 +7,42 @@
 // columns), but with compile-time degrees the check update is straight-line code:
 //   * Q = clip(V[col] - R) as v_min_f64/v_max_f64 (the NaN test of kernels.py:328 is kept unless the launcher proved
 //     that no NaN can arise: finite prior/clip/alpha and every check degree >= 2);
-//   * clean undamped inputs (NANFREE && !DAMP; "clean" includes a finite clip > 0, inputs_clean() in decode_api.hip) do not clip
-//     the CDEG edges at all: they clip the two minima.  After the clip, Q is used only through its sign, its magnitude inside
-//     the min1 / min2 network, and the test |Q| == min1, and each of them follows from the UNCLIPPED t = V[col] - R:
-//       sign       clip(t) < 0 <=> t < 0 for clip > 0 (-0.0 stays -0.0 and counts as >= 0 either way);
-//       magnitude  |clip(t)| = min(|t|, clip), and min is monotone and rounds nothing, so the two smallest clipped magnitudes
-//                  (with multiplicity) are min(min1, clip) and min(min2, clip) of the unclipped ones, bit for bit;
-//       selector   min1 < clip: |clip(t_k)| == min(min1, clip) <=> |t_k| == min1, the same positions; min1 >= clip: every
-//                  clipped magnitude is clip, alpha*min1 == alpha*min2, and the selector cannot change a message.
-//     Two v_min_f64 per check instead of 2 * CDEG per check; messages, posteriors, iteration counts and tallies are unchanged.
-//     clip == 0 is NOT covered (clip(t) = +-0.0 loses the sign the reference then reads as >= 0): such a call is not clean and
-//     takes the NaN-tolerant per-edge form, like the damped form, whose Q_old needs the clipped value of every edge;
-//   * min1 / min2 = the two smallest magnitudes WITH multiplicity, from a 14-op v_min/v_max network (kernels.py:301-306);
+//   * the damped and the NaN-tolerant forms: min1 / min2 = the two smallest magnitudes WITH multiplicity (kernels.py:301-306);
 //     the position that receives min2 is selected by |q| == min1: if the minimum is attained twice, min2 == min1, so
-//     this equals the reference's "first strict minimum" rule at every position;
-//   * signs are boolean masks (x < 0; note -0.0 counts as >= 0 exactly like `val >= 0`, kernels.py:296), the message is
-//     (+-alpha) * mag, one rounding, equal to the reference's (alpha * sign) * mag.
+//     this equals the reference's "first strict minimum" rule at every position; signs are boolean masks (x < 0; note -0.0
+//     counts as >= 0 exactly like `val >= 0`, kernels.py:296), the message is (+-alpha) * mag, one rounding, equal to the
+//     reference's (alpha * sign) * mag;
+//   * clean undamped inputs (CLIPMIN = NANFREE && !DAMP; "clean", inputs_clean() in decode_api.hip: every prior finite and not
+//     -0.0, clip finite > 0, every alpha finite > 0) build the CDEG message words of a check with neither a compare nor a select,
+//     from the UNCLIPPED t_k = V[col_k] - Rprev_k.  Why each word equals the reference's, bit for bit:
+//       signs      A posterior is never -0.0: it is 0.0 + R + ... + R + prior (kernels.py:279,316,320), a sum that starts at +0.0
+//                  stays +0.0 or nonzero under round-to-nearest (x + y is -0.0 only for x = y = -0.0), and the prior is not -0.0.
+//                  a - b is -0.0 only for a = -0.0, b = +0.0, so no t_k is -0.0 either, and none is NaN (all operands finite:
+//                  |R| <= max(|prior|, clip)).  Hence x < 0 <=> the sign bit of x's high word, for posteriors and for t_k:
+//                  the parity of the hard decisions is the sign bit of the XOR of the posteriors' high words, and the sign of
+//                  the whole row is that of spw = syndrome bit ^ hi(t_0) ^ ... ^ hi(t_{CDEG-1}).  Edge k's message takes the
+//                  sign bit of spw ^ hi(t_k): the row without the edge itself (kernels.py:311-314).  The reference reads
+//                  signs AFTER the clip; clip(t) < 0 <=> t < 0 for clip > 0.  (A MESSAGE may be -0.0, namely when its
+//                  magnitude is 0; the reference's (alpha * sign) * 0.0 is the same word, and a - (-0.0) = a.)
+//       ties       The reference gives min2 to the first strict minimum and min1 to every other edge (kernels.py:301-313).
+//                  Here mag_k = min over j != k of |t_j|, from prefix minima p_k = min(|t_0|..|t_k|) and suffix minima
+//                  s_k = min(|t_k|..|t_{CDEG-1}|): mag_0 = s_1, mag_{CDEG-1} = p_{CDEG-2}, mag_k = min(p_{k-1}, s_{k+1}).
+//                  If the minimum is attained once, at k: mag_k = min2 and every other mag_j = min1 -- the reference's rule.
+//                  If it is attained twice or more, min2 == min1 and every mag_j = min1 -- again what the reference stores at
+//                  every position.  No selector exists, so a tie cannot pick a different position.
+//       clip       |clip(t)| = min(|t|, clip) and min is associative, commutative, monotone and rounds nothing.  The two
+//                  chain seeds are p_0 = min(|t_0|, cmin) and s_{CDEG-1} = min(|t_{CDEG-1}|, cmin); every mag_k contains at
+//                  least one seed (CDEG >= 2), so mag_k = min(min over j != k of |t_j|, cmin) = the minimum over j != k of the
+//                  CLIPPED magnitudes.  cmin = clip for it > 0 and +inf at it == 0, whose inputs are priors and take no clip
+//                  (kernels.py:263-265).  clip == 0 is NOT covered (clip(t) = +-0.0 loses the sign the reference then reads as
+//                  >= 0): such a call is not clean and takes the NaN-tolerant per-edge form, like the damped form, whose
+//                  Q_old needs the clipped value of every edge.
+//       rounding   The word is sign | (alpha * mag_k): one v_mul_f64 of the same two operands the reference multiplies
+//                  (mag_k is its min1 or min2 after the clip), and (alpha * sign) * mag == sign * (alpha * mag) exactly for
+//                  sign = +-1.  The sign bit goes in with v_bfi_b32; alpha * mag_k >= 0 has a clear sign bit to replace.
+//     Per check and iteration: CDEG v_sub, 3 * CDEG - 4 v_min_f64 (two of them the seeds), CDEG v_mul_f64, 2 * CDEG + 1 v_xor,
+//     CDEG v_bfi.  The suffix chain is built first, the prefix chain runs forward and each message leaves as soon as its two
+//     inputs exist, so t_k dies edge by edge.
 // MC = true fuses the sampler (Philox4x32-10 stream of mc_common.h), the GF(2) syndrome (a6), the decode, the logical
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
@@ -53,10 +73,6 @@ struct RegArgs {
     int offV, offE, offL, offI, offA, offT;
 };
 
-#ifndef QLDPC_REG_SIGNBITS
-#define QLDPC_REG_SIGNBITS 0      // 1: clean inputs take signs, parities and the message sign from the high words (integer XORs) instead of f64 compares --
-                                  // 12 fewer 4-cycle compares per check, measured 1.1 % SLOWER (12.74 / 12.78 vs 12.60 / 12.63 ms, same box, profiles/r03_experiments.txt)
-#endif
 #ifndef QLDPC_LB_T
 #define QLDPC_LB_T 512
 #define QLDPC_LB_W 8
@@ -82,7 +98,8 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     int *sres = I + 2 * S + 2 + 4 * sl; // conv, final_iter, nonzero syndrome, failure index
     const double *Al = reinterpret_cast<const double *>(lds + A.offA);                  // alpha_k staged in LDS
     unsigned long long *Tl = reinterpret_cast<unsigned long long *>(lds + A.offT);      // block tally (MC)
-    constexpr bool CLIPMIN = NANFREE && !DAMP;      // clip the two minima of a check instead of its CDEG edges (header comment); needs clip > 0, which NANFREE includes
+    constexpr bool CLIPMIN = NANFREE && !DAMP;      // compare-free message words with the clip in the two chain seeds (header comment); needs clip > 0, which NANFREE includes
+    static_assert(CDEG >= 3, "the prefix / suffix chains need a middle edge");
     const double clip = A.clip, nclip = -A.clip, damping = A.damping, one_minus_d = 1.0 - A.damping;
     for (int k = threadIdx.x; k < max_iter; k += blockDim.x) reinterpret_cast<double *>(lds + A.offA)[k] = A.alpha[k];
     if (MC && threadIdx.x < 6) Tl[threadIdx.x] = 0ull;
@@ -152,6 +169,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
         } else {
             csyn = (valid && has_check) ? (A.synd[b * m + member] & 1) : false;
         }
+        const unsigned synw = csyn ? 0x80000000u : 0u;       // the syndrome bit as the sign bit of a word: sign of 1 - 2 s (kernels.py:252,289)
         double Rprev[CDEG], Qold[CDEG];
 #pragma unroll
         for (int k = 0; k < CDEG; k++) { Rprev[k] = 0.0; Qold[k] = 0.0; }
@@ -168,11 +186,11 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             double x[CDEG];
             if (in_check) {
                 bool par = csyn;
-                if (NANFREE && QLDPC_REG_SIGNBITS) {                  // clean inputs: a posterior is never -0.0 (minsum_common.h), so x < 0 <=> its sign bit: one XOR per edge
-                    unsigned ph = 0u;
+                if (CLIPMIN) {                                        // clean inputs: a posterior is never -0.0 (header comment), so x < 0 <=> its sign bit: one XOR per edge
+                    unsigned ph = synw;
 #pragma unroll
                     for (int k = 0; k < CDEG; k++) { x[k] = Vl[coff[k]]; ph ^= (unsigned)__double2hiint(x[k]); }
-                    par ^= (ph >> 31) != 0u;
+                    par = (int)ph < 0;                                                            // kernels.py:349,356
                 } else {
 #pragma unroll
                     for (int k = 0; k < CDEG; k++) { x[k] = Vl[coff[k]]; par ^= (x[k] < 0.0); }   // kernels.py:349,356
@@ -203,14 +221,40 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     for (int k = 0; k < CDEG; k++) { Rprev[k] = msg; Rl[roff + k] = msg; }
                 }
             } else if (in_check && !skip_msg) {
-                if (it < max_iter) {
+                if (CLIPMIN && it < max_iter) {
+                    // compare-free form (header comment): x becomes the unclipped t_k, the clip sits in the two chain seeds
+                    const double alpha = Al[it];
+                    const double cmin = (it > 0) ? clip : INFINITY;                            // iteration 0 reads priors: no clip (kernels.py:263-265)
+                    unsigned spw = synw;                                                       // sign of the whole row in bit 31
+#pragma unroll
+                    for (int k = 0; k < CDEG; k++) {
+                        if (it > 0) x[k] = x[k] - Rprev[k];                                    // kernels.py:325
+                        spw ^= (unsigned)__double2hiint(x[k]);
+                    }
+                    double suf[CDEG];                                                          // suf[k] = min(|t_k|, .., |t_{CDEG-1}|, cmin), k = CDEG-1 .. 1
+                    suf[CDEG - 1] = vmin_abs_u(x[CDEG - 1], cmin);
+#pragma unroll
+                    for (int k = CDEG - 2; k >= 1; k--) suf[k] = vmin_abs(x[k], suf[k + 1]);
+                    double pre = 0.0;                                                          // pre = min(|t_0|, .., |t_{k-1}|, cmin) from k = 1 on
+#pragma unroll
+                    for (int k = 0; k < CDEG; k++) {
+                        const double mag = (k == 0) ? suf[1] : (k == CDEG - 1) ? pre : vmin(pre, suf[k + 1]);   // the minimum over the other edges (kernels.py:301-313)
+                        const unsigned sgn = spw ^ (unsigned)__double2hiint(x[k]);             // the row's sign without the edge itself (kernels.py:311-314)
+                        if (k < CDEG - 1) pre = (k == 0) ? vmin_abs_u(x[0], cmin) : vmin_abs(x[k], pre);
+                        const double prod = alpha * mag;                                       // >= 0: (alpha * sign) * mag == sign * (alpha * mag)
+                        const unsigned hi = ((unsigned)__double2hiint(prod) & 0x7fffffffu) | (sgn & 0x80000000u);
+                        const double msg = __hiloint2double((int)hi, __double2loint(prod));
+                        Rprev[k] = msg;
+                        Rl[roff + k] = msg;
+                    }
+                } else if (it < max_iter) {
                     const double alpha = Al[it];
                     if (it > 0) {
 #pragma unroll
                         for (int k = 0; k < CDEG; k++) {
                             double t = x[k] - Rprev[k];                                        // kernels.py:325
                             if (!NANFREE) t = (t != t) ? 0.0 : t;                              // kernels.py:328-329
-                            if (!CLIPMIN) t = vmax(vmin(t, clip), nclip);                      // kernels.py:330-333 (CLIPMIN: the two minima are clipped below instead)
+                            t = vmax(vmin(t, clip), nclip);                                    // kernels.py:330-333
                             if (DAMP) {                                                        // kernels.py:336-342
                                 const double qd = damping * t + one_minus_d * Qold[k];
                                 t = NANFREE ? vmax(vmin(qd, clip), nclip) : clip_only(qd, clip);       // a NaN (from a NaN Q_old) must survive the clip
@@ -221,15 +265,11 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
                     bool neg[CDEG];
                     bool sp = csyn;                                                            // sign of 1 - 2 s (kernels.py:252,289)
-                    unsigned spw = csyn ? 0x80000000u : 0u;                                    // the same in the sign bit of a word (NANFREE: Q is never -0.0)
 #pragma unroll
                     for (int k = 0; k < CDEG; k++) {
                         if (DAMP) Qold[k] = x[k];
-                        if (NANFREE && !DAMP && QLDPC_REG_SIGNBITS) { spw ^= (unsigned)__double2hiint(x[k]); neg[k] = false; }
-                        else {
-                            neg[k] = NANFREE ? (x[k] < 0.0) : !(x[k] >= 0.0);                  // kernels.py:296-299 (-0.0 counts as >= 0)
-                            sp ^= neg[k];
-                        }
+                        neg[k] = NANFREE ? (x[k] < 0.0) : !(x[k] >= 0.0);                      // kernels.py:296-299 (-0.0 counts as >= 0)
+                        sp ^= neg[k];
                     }
                     double min1, min2;
                     if (NANFREE) {
@@ -244,17 +284,13 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
                     // the first minimum gets min2, everybody else min1 (kernels.py:313).  If the minimum is attained twice,
                     // min2 == min1, so selecting on |q| == min1 gives the same value at every position.
-                    // CLIPMIN: x holds UNCLIPPED values; |clip(t)| = min(|t|, clip) and min is monotone, so clipping min1 and min2 gives the minima of the
-                    // clipped magnitudes (header comment).  Iteration 0 takes no clip (kernels.py:263-265): its inputs are priors.
-                    const double cmin = (it > 0) ? clip : INFINITY;
-                    const double p1 = alpha * (CLIPMIN ? vmin(min1, cmin) : min1), p2 = alpha * (CLIPMIN ? vmin(min2, cmin) : min2);   // (+-alpha)*mag == +-(alpha*mag)
+                    const double p1 = alpha * min1, p2 = alpha * min2;                         // (+-alpha)*mag == +-(alpha*mag)
                     const int p1lo = __double2loint(p1), p1hi = __double2hiint(p1), p2lo = __double2loint(p2), p2hi = __double2hiint(p2);
 #pragma unroll
                     for (int k = 0; k < CDEG; k++) {
                         const bool eq = (fabs(x[k]) == min1);
                         const int lo = eq ? p2lo : p1lo;
-                        const int hi = (NANFREE && !DAMP && QLDPC_REG_SIGNBITS) ? (int)(((unsigned)(eq ? p2hi : p1hi)) ^ ((spw ^ (unsigned)__double2hiint(x[k])) & 0x80000000u))
-                                                          : ((eq ? p2hi : p1hi) ^ ((sp != neg[k]) ? (int)0x80000000 : 0));   // kernels.py:311-314
+                        const int hi = (eq ? p2hi : p1hi) ^ ((sp != neg[k]) ? (int)0x80000000 : 0);   // kernels.py:311-314
                         const double msg = __hiloint2double(hi, lo);
                         Rprev[k] = msg;
                         Rl[roff + k] = msg;
@@ -445,7 +481,7 @@ static int launch_reg2(const RegArgs &A, bool damp, bool nanfree, unsigned grid,
     if (damp) {
         if (MC) return QLDPC_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, true, false, false, FIXED>), dim3(grid), dim3(block), lds, stream, A);
-    } else if (nanfree && A.clip > 0.0) {             // the clean form clips minima, not edges: exact for clip > 0 only (inputs_clean() has checked it; kept next to the launch)
+    } else if (nanfree && A.clip > 0.0) {             // the clean form folds the clip into its two chain seeds: exact for clip > 0 only (inputs_clean() has checked it; kept next to the launch)
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, true, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
     } else {
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, false, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
