@@ -8,7 +8,10 @@ decode against the CPU checker.  Plain module (no pytest hooks); deterministic f
 
 rule_path() and the constants below are a SECOND COPY of the host selection logic (plan_resident, regular_supported, wg_mode, wg2_build), kept on purpose
 as an independent statement of the rules: the GPU module asserts the library's own answer (qldpc_minsum_decode_path) on both sides of every limit
-(rowdeg40 / 41, coldeg8 / 9, m1024 / 1025, rowdeg56 / 57, the two LDS pairs), so a limit that moves in csrc/ fails there and has to be moved here too.
+(rowdeg40 / 41, coldeg8 / 9, m1024 / 1025, rowdeg56 / 57, the two LDS pairs, and reg63_m512 / 513: the 512-thread team of plan_regular in
+csrc/minsum_regular.hip), so a limit that moves in csrc/ fails there and has to be moved here too.  The regular kernel's other two conditions,
+max_iter <= 1024 (its alpha table in LDS, kMaxIterLds) and clip >= 0, are arguments of rule_path(); tests/test_regular_domain_gpu.py asserts them
+against the library.
 """
 import zlib
 from types import SimpleNamespace
@@ -19,6 +22,7 @@ LDS_BYTES = 160 * 1024
 WG2_FIXED = 16 * 1025 + 8 * 1025 + 8          # check states of minsum_wg2.hip at fixed offsets (kWg2OffV)
 WG2_ROW_DEG, WG2_COL_DEG, WG2_ROWS = 40, 8, 1024
 WG_ROW_DEG, REG_INDEX_ROW_DEG = 56, 40
+REGULAR_TEAM, REGULAR_MAX_ITER = 512, 1024        # plan_regular of minsum_regular.hip: QLDPC_LB_T threads per team, kMaxIterLds alpha values in LDS
 
 
 def _up(x, a):
@@ -88,19 +92,20 @@ def regular_takes(rd, cd):
     return pair in ((6, 3), (4, 2), (8, 4)) and (rd == pair[0]).all() and (cd == pair[1]).all()
 
 
-def rule_path(indptr, indices, n, prior, host_prior=True, damping=1.0, table_flags=False):
-    """The decoder form the selection rules give (dispatch of csrc/decode_api.hip) for a clean clip / alpha schedule and no kernel-forcing flag;
-    table_flags: one of the flags that ask for a form of the table kernel is set."""
+def rule_path(indptr, indices, n, prior, host_prior=True, damping=1.0, table_flags=False, max_iter=50, clip=20.0):
+    """The decoder form the selection rules give (dispatch of csrc/decode_api.hip) for a clean alpha schedule and no kernel-forcing flag;
+    table_flags: one of the flags that ask for a form of the table kernel is set.  max_iter and clip matter to the regular kernel alone
+    (regular_supported: clip >= 0, plan_regular: max_iter <= 1024); a negative clip is not clean, which the workgroup forms below then see too."""
     m, nnz = len(indptr) - 1, len(indices)
     rd, cd = degrees(indptr, indices, n)
-    if m and n and regular_takes(rd, cd) and max(m, (n + 1) // 2) <= 1024:
+    if m and n and regular_takes(rd, cd) and max(m, (n + 1) // 2) <= REGULAR_TEAM and max_iter <= REGULAR_MAX_ITER and clip >= 0:
         return "REGULAR"
     if resident_takes(m, n, nnz, rd, cd):
         return "RESIDENT"
     tables = n < 65535 and rd.max() < 256                                     # graph.hip: the ELL tables exist
     if not (tables and m > 0 and n > 0 and rd.max() <= WG_ROW_DEG and wg_lds_bytes(m, n, True) <= LDS_BYTES):
         return "STREAM"
-    if host_prior and damping == 1.0 and not table_flags and prior_is_clean(prior):
+    if host_prior and damping == 1.0 and not table_flags and prior_is_clean(prior) and clip > 0 and np.isfinite(clip):
         if (m <= WG2_ROWS and n < 65536 and rd.max() <= WG2_ROW_DEG and cd.max() <= WG2_COL_DEG and nnz >= 1 and
                 wg2_lds_bytes(n, nnz) <= LDS_BYTES):
             _, pure, _ = wg2_chunks(cd, prior)
@@ -378,6 +383,11 @@ def families(seed=20261016):
     rdc, cdc = degrees(ip, ix, 72)
     assert regular_takes(rdc, cdc)
     out.append(_case("regular63", zlib.crc32(b"regular63"), ip, ix, 72, {"uniform": np.full(72, 3.0)}, "REGULAR", claims=dict(regular=(6, 3)), err_weight=2))
+    # the largest team of the regular kernel (plan_regular: max(m, (n + 1) / 2) <= 512 threads) and the first graph beyond it, which the resident
+    # kernel takes with two checks per thread
+    for m, path in ((512, "REGULAR"), (513, "RESIDENT")):
+        add(f"reg63_m{m}", m, np.full(2 * m, 3), {"uniform": uniform(3.0)}, path, row_cap=6, claims=dict(regular=(6, 3), m=m, regular_team=(path == "REGULAR")),
+            err_weight=40, axes=("iter9",))
     add("small_irregular", 12, blocks(rng_of("si"), (3, 10), (2, 14), (1, 6)), {"uniform": uniform(3.0)}, "RESIDENT", claims=dict(max_row_le=8, max_col_le=4),
         row_cap=8, err_weight=1)
     names = [c.name for c in out]

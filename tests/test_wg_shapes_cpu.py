@@ -43,6 +43,7 @@ def test_family_has_the_structure_and_the_path_it_claims(name):
               "empty_rows": lambda v: (rd == 0).sum() == v and rd[-1] == 0 and (rd[17:119:17] == 0).all(),
               "twin_rows": lambda v: np.array_equal(c.indices[c.indptr[v[0]]:c.indptr[v[0] + 1]], c.indices[c.indptr[v[1]]:c.indptr[v[1] + 1]]) and rd[v[0]] > 1,
               "other_rows": lambda v: (np.sort(rd)[:-1] == v).all(), "regular": lambda v: (rd == v[0]).all() and (cd == v[1]).all(),
+              "regular_team": lambda v: (max(c.m, (c.n + 1) // 2) <= GS.REGULAR_TEAM) == v and max(c.m, (c.n + 1) // 2) == GS.REGULAR_TEAM + (0 if v else 1),
               "wg2_lds_fits": lambda v: (GS.wg2_lds_bytes(c.n, c.nnz) <= GS.LDS_BYTES) == v and (GS.wg2_lds_bytes(c.n + (1 if v else -1), c.nnz) <= GS.LDS_BYTES) != v,
               "wg_all_lds": lambda v: (GS.wg_lds_bytes(c.m, c.n, False) <= GS.LDS_BYTES) == v and (GS.wg_lds_bytes(c.m, c.n + (1 if v else -1), False) <= GS.LDS_BYTES) != v}
     for key, want in k.items():
@@ -71,6 +72,23 @@ def test_family_has_the_structure_and_the_path_it_claims(name):
             assert GS.rule_path(c.indptr, c.indices, c.n, pr, host_prior=False) == "WG" and GS.rule_path(c.indptr, c.indices, c.n, pr, table_flags=True) == "WG"
     if c.expected_path in ("WG2", "WG") and c.m <= 64:
         assert rd.max() > 8 or cd.max() > 4, name
+
+
+def test_regular_kernel_limits_follow_from_the_rules():
+    """plan_regular / regular_supported of csrc/minsum_regular.hip: a team of at most 512 threads, at most 1024 iterations, clip >= 0.  The pair
+    reg63_m512 / reg63_m513 differs by one check and is regular on both sides; beyond either limit the resident kernel takes the graph."""
+    a, b, small = BY_NAME["reg63_m512"], BY_NAME["reg63_m513"], BY_NAME["regular63"]
+    assert (a.m, a.n, b.m, b.n) == (512, 1024, 513, 1026)
+    for c in (a, b, small):
+        rd, cd = GS.degrees(c.indptr, c.indices, c.n)
+        assert GS.regular_takes(rd, cd) and (rd.max(), cd.max()) == (6, 3), c.name
+    assert a.expected_path == "REGULAR" and b.expected_path == "RESIDENT"
+    for c in (a, small):
+        pr = c.priors["uniform"]
+        assert GS.rule_path(c.indptr, c.indices, c.n, pr, max_iter=1024) == "REGULAR" and GS.rule_path(c.indptr, c.indices, c.n, pr, max_iter=1025) == "RESIDENT"
+        assert GS.rule_path(c.indptr, c.indices, c.n, pr, clip=0.0) == "REGULAR" and GS.rule_path(c.indptr, c.indices, c.n, pr, clip=-1.0) == "RESIDENT"
+        assert GS.rule_path(c.indptr, c.indices, c.n, pr, damping=0.8) == "REGULAR" and GS.rule_path(c.indptr, c.indices, c.n, pr, host_prior=False) == "REGULAR"
+    assert GS.rule_path(b.indptr, b.indices, b.n, b.priors["uniform"], max_iter=1) == "RESIDENT"
 
 
 def test_pairs_differ_only_where_they_say():
