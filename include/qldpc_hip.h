@@ -36,6 +36,8 @@
  *        qldpc_circuit_plan_use_layered, QLDPC_FLAG_LAYERED_* and QLDPC_LAYERED_FORM_*
  *        additive, same version: BP with guided decimation, qldpc_decim_decode_batch[_dev], qldpc_circuit_plan_use_decimation; the tally slots
  *        QLDPC_TALLY_LEGS_Z / _X also carry its rounds
+ *        additive, same version: single-precision (f32) min-sum, qldpc_minsum32_decoder_*, qldpc_minsum32_decode_batch[_dev],
+ *        qldpc_circuit_plan_use_f32, QLDPC_FLAG_F32_* and QLDPC_F32_FORM_*
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -85,6 +87,11 @@ extern "C" {
 #define QLDPC_FLAG_LAYERED_BLOCK_1024 0x1000000
 #define QLDPC_FLAG_LAYERED_GLOBAL_IDX 0x2000000  /* column indices in HBM/L2 even when they fit LDS */
 #define QLDPC_FLAG_LAYERED_VGLOBAL 0x4000000     /* posteriors in HBM/L2 even when they fit LDS */
+/* f32 decoder (qldpc_minsum32_decoder_create): form selectors for tools/ and the parity tests; results never depend on them */
+#define QLDPC_FLAG_F32_GENERIC 0x1000            /* the any-input kernel even for host-verified clean inputs */
+#define QLDPC_FLAG_F32_BLOCK_256 0x2000          /* threads per workgroup (default: by size and the occupancy query); at most one of the three */
+#define QLDPC_FLAG_F32_BLOCK_512 0x10000
+#define QLDPC_FLAG_F32_BLOCK_1024 0x8000000
 /* measured-and-rejected kernels: libqldpc_hip_experiments.so only (make -C csrc experiments; same ABI, loaded by the parity tests).  The product
  * library answers these with QLDPC_ERR_UNSUPPORTED.  Numbers: profiles/r02_osd_experiments.txt, r02_bp_lane_mapping.txt, r03_wave_kernel.txt */
 #define QLDPC_FLAG_WG_EDGE_LANES 0x2     /* workgroup-per-shot decoder: check pass with 16 lanes per check and shuffle reductions (SURVEY 7-6 option B) */
@@ -390,6 +397,48 @@ int qldpc_layered_decode_batch(qldpc_layered_decoder *ld, int64_t B, const int8_
 int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *ld, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
                                    uint8_t *d_conv, int32_t *d_iter, void *stream);
 
+/* Normalised min-sum (flooding schedule) in SINGLE PRECISION.  New here: an opt-in fast mode; f64 stays the default everywhere.  The algorithm is
+ * that of qldpc_minsum_decode_batch (src/decoding/kernels.py:234-366 of the reference) with damping 1 and no damping arithmetic, and every
+ * floating-point operation is one correctly rounded f32 operation (nothing is contracted into an FMA; f32 subnormals are kept, not flushed).
+ * Rounding is amplified by the iteration, so on ordinary inputs the results differ from the f64 decoder's in some shots -- mostly the hard
+ * decisions of shots that do not converge; tests/minsum32_model.py is the numpy model the library equals bit for bit, and the f64 decoder is
+ * equalled only on inputs where no f32 operation rounds.  Compare logical error rates, not shots (tools/kbench_f32.py).
+ *   Inputs.  prior32_j = (float)prior_j (round to nearest even; +-inf and NaN pass through).  clip32 = (float)clip_llr must be finite and > 0
+ *     AFTER rounding (QLDPC_ERR_INVALID otherwise).  alpha_k is computed in f64 exactly as qldpc_minsum_decode_batch computes it (QLDPC_ALPHA_*),
+ *     then rounded to f32.  max_iter >= 1.  There is no damping argument.
+ *   Iteration 0.  Q_ij = prior32_j, unclipped, as in the reference.
+ *   Check pass, for every check i with at least one entry, over its columns j in ascending order:
+ *       the sign of Q is + for Q >= 0 (so a NaN counts as -);  sign_prod = the syndrome sign times the product of the signs;
+ *       min1, min2 over |Q| by the reference's strict-< scan (min2 is the second smallest of the multiset; a NaN never enters), min1_pos = the
+ *       FIRST position of the minimum;  a degree-1 check has min2 = +inf;
+ *       R_ij = +-(alpha_k * mag), mag = min2 if j is at min1_pos else min1: ONE f32 multiply, then the sign sign_prod * sign_ij.
+ *   Variable pass.  s_j = 0.0f + R_ij over the checks of j in ASCENDING check order, one f32 add each;  V_j = s_j + prior32_j;
+ *       Q_ij = V_j - R_ij;  a NaN becomes 0.0f;  then clip to +-clip32.
+ *     (With a non-finite prior the f64 decoder also reproduces the NaN of the reference's 0.0 * Q_old damping term; this decoder has no such term:
+ *     a prior of +-inf gives Q = +-clip32 and a NaN prior Q = 0 from iteration 1 on.)
+ *   Stop.  e_j = (V_j < 0); if H e = s over every row (those without entries included) the shot stops: converged, final_iter = k.
+ *   Outputs per shot, exactly those of qldpc_minsum_decode_batch: err int8[n], llr f64[n] = the f32 V widened (exact), conv, final_iter
+ *     (max_iter - 1 when not converged), so qldpc_osd0_batch, qldpc_osdcs_batch and a circuit plan's OSD stage take them unchanged.
+ *   Results do not depend on batch splits, the grid or any flag.
+ * Limits (QLDPC_ERR_UNSUPPORTED, the limit in qldpc_last_error): 1 <= m < 2^24, 1 <= n < 65535, row degree <= 56, and 4 bytes per column + 17 per
+ * row + 48 must fit the 163 840 bytes of LDS of a CU ([[288,12,18]] x 18 cycles, 2880 x 26 209: 153 824).
+ * flags: QLDPC_FLAG_F32_* (other bits are ignored).  The decoder owns its tables; it keeps a pointer to g, which must outlive it.  Calls on one
+ * decoder serialise (a mutex while enqueuing, an event between streams).
+ * qldpc_minsum32_decoder_info: LDS bytes of a workgroup, threads per workgroup, workgroups resident per CU (the runtime's occupancy query for
+ * this kernel, size and LDS) and QLDPC_F32_FORM_* bits; any output may be NULL. */
+#define QLDPC_F32_FORM_CLEAN 0x1                 /* the clean-input kernel: no degree-1 check, |prior32| and clip32 <= 2^100, 0 < alpha32 <= 1024 */
+typedef struct qldpc_minsum32_decoder qldpc_minsum32_decoder;
+int qldpc_minsum32_decoder_create(const qldpc_graph *g, const double *prior, int max_iter, int alpha_mode, double alpha_val,
+                                  const double *alpha_seq, int alpha_len, double clip_llr, int flags, qldpc_minsum32_decoder **out);
+void qldpc_minsum32_decoder_destroy(qldpc_minsum32_decoder *dec);
+int qldpc_minsum32_decoder_info(const qldpc_minsum32_decoder *dec, int *lds_bytes, int *threads, int *wg_per_cu, int *form);
+/* host pointers: syndromes int8[B][m] -> err int8[B][n], llr f64[B][n], conv uint8[B], iter int32[B]; returns when they are complete.  B = 0: a no-op */
+int qldpc_minsum32_decode_batch(qldpc_minsum32_decoder *dec, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
+                                int32_t *iter);
+/* same on device pointers; only enqueues on `stream` */
+int qldpc_minsum32_decode_batch_dev(qldpc_minsum32_decoder *dec, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
+                                    uint8_t *d_conv, int32_t *d_iter, void *stream);
+
 /* a10: generate_noisy_circuit_jit (src/noise/kernels.py:175-353), batched over B draws of explicit random
  * arrays rv/rp/rt [B][n_locs]; out_* [B][cap]; out_len int64[B]. */
 int qldpc_noisy_circuit_batch(int64_t B, int64_t len, const int32_t *ops, const int32_t *q1, const int32_t *q2, double p,
@@ -552,6 +601,13 @@ int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *plan, const int32_t *row_
  * Relay-BP or to windows or whose BP stage runs the layered schedule (and qldpc_circuit_plan_use_relay / _use_window / _use_layered after this
  * call return QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_decim_decode_batch refuses. */
 int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *plan, double alpha, int t_round, int max_rounds, int per_round, double fix_llr);
+/* Switches the BP launch of both sectors to the single-precision decoder (one-way): a qldpc_minsum32_decoder per sector with the plan's prior, alpha
+ * table, max_iter (>= 1) and clip_llr.  Only the launch inside the BP bracket changes: it writes the plan's hard decisions, posteriors (f64, the f32
+ * values widened), converged flags and iteration counts, so sampler, unconverged list, the OSD-0 / OSD-CS stage, judge and tally slots are untouched,
+ * and qldpc_circuit_plan_use_osd_cs may come before or after.  QLDPC_ERR_INVALID on a plan with damping != 1, switched to Relay-BP or to windows, or
+ * whose BP stage runs the layered schedule or guided decimation (and qldpc_circuit_plan_use_relay / _use_window / _use_layered / _use_decimation
+ * after this call return QLDPC_ERR_INVALID); otherwise what qldpc_minsum32_decoder_create returns. */
+int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *plan);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

@@ -38,6 +38,9 @@ DETAIL_LEAN, DETAIL_REG_INDICES, DETAIL_VGLOBAL, DETAIL_DAMPING, DETAIL_BLOCK_10
 # layered decoder: form selectors (results never depend on them) and the bits qldpc_layered_decoder_info reports beside the threads per workgroup
 FLAG_LAYERED_BLOCK_256, FLAG_LAYERED_BLOCK_512, FLAG_LAYERED_BLOCK_1024, FLAG_LAYERED_GLOBAL_IDX, FLAG_LAYERED_VGLOBAL = 0x400000, 0x800000, 0x1000000, 0x2000000, 0x4000000
 LAYERED_FORM_BLOCK_MASK, LAYERED_FORM_VGLOBAL, LAYERED_FORM_LDS_INDICES = 0xFFFF, 0x10000, 0x20000
+# f32 decoder: form selectors (results never depend on them) and the form bit qldpc_minsum32_decoder_info reports
+FLAG_F32_GENERIC, FLAG_F32_BLOCK_256, FLAG_F32_BLOCK_512, FLAG_F32_BLOCK_1024 = 0x1000, 0x2000, 0x10000, 0x8000000
+F32_FORM_CLEAN = 0x1
 CIRCUIT_PHASES = ("sample", "bp_z", "osd_z", "bp_x", "osd_x", "judge")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "qldpc_hip.h")
 
@@ -659,6 +662,64 @@ class LayeredDecoder:
             pass
 
 
+def check_minsum32_args(max_iter, clip_llr):
+    """ValueError unless max_iter is an integer >= 1 and clip_llr is finite and > 0 once rounded to f32 -> (int, float)."""
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"the f32 decoder needs an integer max_iter >= 1, got {max_iter}")
+    clip_llr = float(clip_llr)
+    with np.errstate(over="ignore"):
+        c32 = float(np.float32(clip_llr))
+    if not (c32 > 0 and np.isfinite(c32)):
+        raise ValueError(f"clip_llr must be finite and > 0 as an f32, got {clip_llr}")
+    return int(max_iter), clip_llr
+
+
+class Minsum32Decoder:
+    """Owning wrapper of a qldpc_minsum32_decoder (single-precision flooding min-sum on `graph`; semantics in include/qldpc_hip.h)."""
+
+    def __init__(self, graph, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, flags=0):
+        max_iter, clip_llr = check_minsum32_args(max_iter, clip_llr)
+        mode, aval, seq = alpha_args(alpha_mode, alpha)
+        prior = f64(prior).reshape(-1)
+        if prior.size != graph.n:
+            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        self.graph = graph                     # the decoder keeps a pointer to the graph handle
+        self._h = C.c_void_p()
+        check(lib().qldpc_minsum32_decoder_create(graph.handle, ptr(prior, C.c_double), max_iter, mode, aval, ptr(seq, C.c_double), seq.size, clip_llr,
+                                                  int(flags), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        """{lds_bytes, block (threads per workgroup), wg_per_cu (resident workgroups per CU, the runtime's occupancy query), clean}"""
+        v = [C.c_int(0) for _ in range(4)]
+        check(lib().qldpc_minsum32_decoder_info(self._h, *[C.byref(x) for x in v]))
+        return dict(lds_bytes=v[0].value, block=v[1].value, wg_per_cu=v[2].value, clean=bool(v[3].value & F32_FORM_CLEAN))
+
+    def decode(self, syndromes):
+        """int8[B, m] -> (err int8[B, n], conv uint8[B], llr f64[B, n] (f32 values widened), iters int32[B]): the outputs of minsum_decode_batch"""
+        syndromes = i8(syndromes).reshape(-1, self.graph.m)
+        B = syndromes.shape[0]
+        err, llr = np.zeros((B, self.graph.n), np.int8), np.zeros((B, self.graph.n), np.float64)
+        conv, iters = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        check(lib().qldpc_minsum32_decode_batch(self._h, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(err, C.c_int8), ptr(llr, C.c_double),
+                                                ptr(conv, C.c_uint8), ptr(iters, C.c_int32)))
+        return err, conv, llr, iters
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib().qldpc_minsum32_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def osd_timers(reset=True):
     """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/osd_common.h) -> uint64[32]."""
     out = np.zeros(32, np.uint64)
@@ -923,6 +984,12 @@ class CircuitPlan:
         lz, lx = check_row_layer(layers_z, self.graph_z.m), check_row_layer(layers_x, self.graph_x.m)
         check(lib().qldpc_circuit_plan_use_layered(self._h, ptr(lz, C.c_int32) if lz is not None else None, ptr(lx, C.c_int32) if lx is not None else None))
         self.layered = True
+
+    def use_f32(self):
+        """Run the BP stage of both sectors in single precision from now on (one-way; qldpc_circuit_plan_use_f32) with the plan's priors, alpha table,
+        max_iter and clip_llr.  Goes with OSD-0 and OSD-CS; not with Relay-BP, windows, the layered schedule or guided decimation."""
+        check(lib().qldpc_circuit_plan_use_f32(self._h))
+        self.precision = "f32"
 
     def use_decimation(self, **params):
         """Run the BP stage of both sectors as BP with guided decimation from now on (qldpc_circuit_plan_use_decimation): alpha, t_round, max_rounds,

@@ -258,6 +258,7 @@ struct qldpc_circuit_plan {
         std::vector<double> h_prior, h_alpha;
         qldpc_window_decoder *win = nullptr;       // Decoder::WINDOW (window.hip)
         qldpc_layered_decoder *lay = nullptr;      // the layered schedule in the BP bracket (minsum_layered.hip); both sectors or neither
+        qldpc_minsum32_decoder *f32 = nullptr;     // single-precision min-sum in the BP bracket (minsum_f32.hip); both sectors or neither
         PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
         PlanBuf d_alpha, d_prior, d_lm;
         PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
@@ -546,6 +547,8 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
                                  S.d_conv.as<uint8_t>(), S.d_legs.as<int32_t>(), S.d_iter.as<int32_t>(), nullptr, s);
     } else if (S.lay) {                   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
         rc = layered_lock_and_launch(S.lay, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
+    } else if (S.f32) {                   // single precision: same outputs (the posteriors widened to f64)
+        rc = minsum32_lock_and_launch(S.f32, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
     } else if (P->decim) {                // guided decimation: same outputs too; iter_bias -1 as for Relay-BP, the rounds go where its legs go
         std::lock_guard<std::mutex> lk(g->mu);
         rc = decim_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->dp, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(),
@@ -704,13 +707,15 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 // The layered schedule (qldpc_circuit_plan_use_layered) replaces the launch inside the BP bracket and leaves the mode alone: it goes with BP_OSD0 and
 // BP_OSD_CS in either order, and a plan that has it moves to neither RELAY nor WINDOW (nor gets it once there).
 // Guided decimation (qldpc_circuit_plan_use_decimation) is a second replacement of that launch under the same rules; a plan has at most one of the two.
+// Single precision (qldpc_circuit_plan_use_f32) is a third replacement of that launch under the same rules; a plan has at most one of the three.
 // Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS, decimation), damping = 1
-// (WINDOW, layered, decimation).
+// (WINDOW, layered, decimation, f32).
 static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
     static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(!P->sec[0].lay || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to the layered schedule: %s cannot follow", name[(int)to]);
     QLDPC_REQUIRE(!P->decim || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to guided decimation: %s cannot follow", name[(int)to]);
+    QLDPC_REQUIRE(!P->sec[0].f32 || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to single precision (f32): %s cannot follow", name[(int)to]);
     QLDPC_REQUIRE(to == Decoder::RELAY || P->use_osd, "the plan was created with use_osd = 0: %s needs its OSD stage", name[(int)to]);
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || (P->decoder == to && to != Decoder::WINDOW), "the plan was switched to %s: %s cannot follow",
                   name[(int)P->decoder], name[(int)to]);
@@ -776,6 +781,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: the layered schedule cannot follow",
                   name[(int)P->decoder]);
     QLDPC_REQUIRE(!P->decim, "the plan's BP stage was switched to guided decimation: the layered schedule cannot follow");
+    QLDPC_REQUIRE(!P->sec[0].f32, "the plan's BP stage was switched to single precision (f32): the layered schedule cannot follow");
     QLDPC_REQUIRE(P->damping == 1.0, "the layered schedule needs damping = 1 (the plan has %g)", P->damping);
     QLDPC_USE_DEVICE(P->device);
     const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
@@ -795,6 +801,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double
     QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: guided decimation cannot follow",
                   name[(int)P->decoder]);
     QLDPC_REQUIRE(!P->sec[0].lay, "the plan's BP stage was switched to the layered schedule: guided decimation cannot follow");
+    QLDPC_REQUIRE(!P->sec[0].f32, "the plan's BP stage was switched to single precision (f32): guided decimation cannot follow");
     QLDPC_REQUIRE(P->damping == 1.0, "guided decimation needs damping = 1 (the plan has %g)", P->damping);
     const DecimParams dp{alpha, P->clip, fix_llr, t_round, max_rounds, per_round};
     int rc;
@@ -809,10 +816,30 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double
     return QLDPC_OK;
 }
 
+QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
+    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: single precision (f32) cannot follow",
+                  name[(int)P->decoder]);
+    QLDPC_REQUIRE(!P->sec[0].lay, "the plan's BP stage was switched to the layered schedule: single precision (f32) cannot follow");
+    QLDPC_REQUIRE(!P->decim, "the plan's BP stage was switched to guided decimation: single precision (f32) cannot follow");
+    QLDPC_REQUIRE(P->damping == 1.0, "single precision (f32) needs damping = 1 (the plan has %g)", P->damping);
+    if (P->sec[0].f32) return QLDPC_OK;                     // one-way, and nothing to replace
+    QLDPC_USE_DEVICE(P->device);
+    qldpc_minsum32_decoder *d[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; i++) {
+        const Sector &S = P->sec[i];
+        const int rc = minsum32_decoder_create_tab(S.g, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
+        if (rc != QLDPC_OK) { qldpc_minsum32_decoder_destroy(d[0]); return rc; }
+    }
+    for (int i = 0; i < 2; i++) P->sec[i].f32 = d[i];
+    return QLDPC_OK;
+}
+
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {
     if (!P) return;
     (void)hipSetDevice(P->device);
-    for (Sector &S : P->sec) { qldpc_window_decoder_destroy(S.win); qldpc_layered_decoder_destroy(S.lay); }
+    for (Sector &S : P->sec) { qldpc_window_decoder_destroy(S.win); qldpc_layered_decoder_destroy(S.lay); qldpc_minsum32_decoder_destroy(S.f32); }
     for (auto &br : P->pending) { (void)hipEventDestroy(br.a); if (br.b) (void)hipEventDestroy(br.b); }
     for (auto e : P->pool) (void)hipEventDestroy(e);
     delete P;                                      // every PlanBuf releases itself

@@ -90,6 +90,12 @@ int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, c
                                double clip_llr, int flags, qldpc_layered_decoder **out);
 int layered_lock_and_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                             hipStream_t s);
+// Single-precision min-sum (minsum_f32.hip) inside a circuit plan.  create_tab: qldpc_minsum32_decoder_create on a ready f64 alpha table.
+// lock_and_launch enqueues the decode of B shots with the outputs of minsum_decode_dispatch.
+int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int max_iter, const std::vector<double> &tab, double clip_llr, int flags,
+                                qldpc_minsum32_decoder **out);
+int minsum32_lock_and_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
+                             hipStream_t s);
 int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
 
 }  // namespace qldpc

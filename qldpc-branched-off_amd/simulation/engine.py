@@ -50,6 +50,13 @@ alpha is the constant of the dict and ``maxIter`` is not used by it, so every ar
 (``alpha_mode``, ``alvarado_alpha``, ``use_dynamic_alpha=False``, ``scopt=True``), as do ``decoder="relay_bp"``, ``window=...``,
 ``schedule="layered"`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``decimation`` (the parameters used) and
 ``mean_rounds_z`` / ``mean_rounds_x``.
+
+``precision="f32"`` (an extension; ``"f64"`` is the default and today's behaviour) runs the BP stage of both sectors in single precision
+(``decoding/single.py``): the plan's priors, alpha table, ``maxIter`` and clip rounded to f32, every operation one f32 operation.  Only that stage
+changes; OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_osd_cs"``) follows as before.  The alpha / SCOPT estimators stay
+f64: the alpha they return is rounded to f32 like any other.  Results differ from ``"f64"`` in some trials (rounding, amplified by the iteration);
+compare logical error rates, not trials.  ``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``osd_order > 0``
+with ``decoder="bp_osd"`` raise ValueError.  The result holds ``precision``.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -81,9 +88,24 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, **bb_params):
+                   layers=None, decimation=None, precision="f64", **bb_params):
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
+    if precision not in ("f64", "f32"):
+        raise ValueError(f"Unsupported precision: {precision!r} (expected 'f64' or 'f32')")
+    single = precision == "f32"
+    if single:                           # (before any device call: these are argument rules)
+        if decoder == "relay_bp":
+            raise ValueError("precision='f32' goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
+        if window is not None:
+            raise ValueError(f"precision='f32' does not go with window={window!r}")
+        if schedule == "layered":
+            raise ValueError("precision='f32' does not go with schedule='layered' (both replace the BP stage)")
+        if decimation is not None:
+            raise ValueError("precision='f32' does not go with decimation=... (both replace the BP stage)")
+        if decoder == "bp_osd" and osd_order > 0:
+            raise ValueError(f"precision='f32' goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes in f64)")
+        _lib.check_minsum32_args(maxIter, 20.0)
     if decimation is not None:           # (before any device call: these are argument rules)
         if not isinstance(decimation, dict):
             raise ValueError("decimation must be a dict of guided-decimation parameters (or None)")
@@ -260,6 +282,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                 self.plan.use_layered(*layers)
             if decimation is not None:
                 self.plan.use_decimation(**decimation)
+            if single:
+                self.plan.use_f32()
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -403,5 +427,6 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if decimation is not None:
         trials = max(int(total[T["trials"]]), 1)
         result.update(decimation=dict(decimation), mean_rounds_z=float(total[T["legs_z"]]) / trials, mean_rounds_x=float(total[T["legs_x"]]) / trials)
+    result["precision"] = precision
     result["tally"] = total
     return result
