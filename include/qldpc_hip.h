@@ -38,6 +38,7 @@
  *        QLDPC_TALLY_LEGS_Z / _X also carry its rounds
  *        additive, same version: single-precision (f32) min-sum, qldpc_minsum32_decoder_*, qldpc_minsum32_decode_batch[_dev],
  *        qldpc_circuit_plan_use_f32, QLDPC_FLAG_F32_* and QLDPC_F32_FORM_*
+ *        additive, same version: qldpc_osd0_last_path (which OSD-0 kernel the last call on a handle took), QLDPC_OSD_PATH_* and QLDPC_OSD_DETAIL_*
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -281,6 +282,28 @@ int qldpc_osd0_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, c
 int qldpc_osd0_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
                          const int32_t *d_ordering, const int32_t *d_select, const int32_t *d_select_count, int flags, int8_t *d_solution,
                          void *stream);
+/* Which OSD-0 kernel the last OSD-0 launch on this handle took: qldpc_osd0_batch[_dev], or the OSD-0 stage of a plan or window decoder that owns the
+ * handle.  Launches nothing; the values are written by the launch code itself at the point where it starts each kernel, so the query cannot drift
+ * from what ran.  Results never depend on the form.  With several threads on one handle it reports whichever call enqueued last.  New here (the
+ * reference has no counterpart); for tests and tools.
+ *   path    QLDPC_OSD_PATH_*: the kernel that was given every listed shot.  NONE: nothing was launched (no call yet, m == 0 or n == 0, or the call
+ *           was refused); SMALL csrc/osd_small.hip (one wave per shot, m <= 128 and n <= 1024); GJ csrc/osd_gj.hip (free pivot rows, row transform in
+ *           LDS, m <= 1024); GJG csrc/osd_gjg.hip (the same with the transform in HBM / L2, m <= 4096); REFORDER_LDS / REFORDER_UG osd0_lds_kernel of
+ *           csrc/gf2.hip (the reference's row choice at every pivot; transform in LDS / in HBM / L2) on every shot, as QLDPC_FLAG_OSD_REFORDER asks for
+ *           or when a heavy column leaves the free-pivot kernels no room in LDS; GLOBAL osd0_kernel of csrc/gf2.hip (literal elimination in HBM)
+ *   detail  bits 0-1 (QLDPC_OSD_DETAIL_MODE_MASK): the reference-order form the launch planned, 0 none, 1 transform in LDS, 2 in HBM / L2;
+ *           QLDPC_OSD_DETAIL_REDO: a second kernel was queued behind GJ / GJG for the shots they list (right-hand side outside the column space):
+ *           the reference-order form of bits 0-1, or with mode 0 the GLOBAL kernel on every shot */
+#define QLDPC_OSD_PATH_NONE (-1)
+#define QLDPC_OSD_PATH_SMALL 0
+#define QLDPC_OSD_PATH_GJ 1
+#define QLDPC_OSD_PATH_GJG 2
+#define QLDPC_OSD_PATH_REFORDER_LDS 3
+#define QLDPC_OSD_PATH_REFORDER_UG 4
+#define QLDPC_OSD_PATH_GLOBAL 5
+#define QLDPC_OSD_DETAIL_MODE_MASK 0x3
+#define QLDPC_OSD_DETAIL_REDO 0x4
+int qldpc_osd0_last_path(const qldpc_graph *g, int *path, int *detail);
 /* Phase counters of the OSD-0 kernels and of the workgroup BP kernel on the current device (uint64[32]; layout in csrc/osd_common.h).  Only the diagnostic build
  * (make -C csrc timers) counts; the product build carries no clock reads and returns QLDPC_ERR_UNSUPPORTED. */
 int qldpc_osd_timers_read(uint64_t *out32, int reset);

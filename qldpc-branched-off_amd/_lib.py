@@ -35,6 +35,9 @@ FLAG_WG_VGLOBAL, FLAG_WG_GENERIC, FLAG_OSD_UG, FLAG_OSD_GLOBAL, FLAG_CLOCK_PROBE
 # qldpc_minsum_decode_path: the decoder form a call takes (QLDPC_PATH_*) and the QLDPC_DETAIL_* bits of the workgroup forms
 PATH_REGULAR, PATH_RESIDENT, PATH_WG2, PATH_WG, PATH_STREAM, PATH_WAVE = 0, 1, 2, 3, 4, 5
 DETAIL_LEAN, DETAIL_REG_INDICES, DETAIL_VGLOBAL, DETAIL_DAMPING, DETAIL_BLOCK_1024, DETAIL_DEG1, DETAIL_NAN_DEG1_ONLY = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+# qldpc_osd0_last_path: the OSD-0 kernel the last call on a graph handle took (QLDPC_OSD_PATH_*) and its QLDPC_OSD_DETAIL_* bits
+OSD_PATH_NONE, OSD_PATH_SMALL, OSD_PATH_GJ, OSD_PATH_GJG, OSD_PATH_REFORDER_LDS, OSD_PATH_REFORDER_UG, OSD_PATH_GLOBAL = -1, 0, 1, 2, 3, 4, 5
+OSD_DETAIL_MODE_MASK, OSD_DETAIL_REDO = 0x3, 0x4
 # layered decoder: form selectors (results never depend on them) and the bits qldpc_layered_decoder_info reports beside the threads per workgroup
 FLAG_LAYERED_BLOCK_256, FLAG_LAYERED_BLOCK_512, FLAG_LAYERED_BLOCK_1024, FLAG_LAYERED_GLOBAL_IDX, FLAG_LAYERED_VGLOBAL = 0x400000, 0x800000, 0x1000000, 0x2000000, 0x4000000
 LAYERED_FORM_BLOCK_MASK, LAYERED_FORM_VGLOBAL, LAYERED_FORM_LDS_INDICES = 0xFFFF, 0x10000, 0x20000
@@ -352,6 +355,13 @@ def osd0_batch(graph, syndromes, llr, hard, ordering=None, flags=0):
         op = ptr(ordering, C.c_int32)
     check(lib().qldpc_osd0_batch(graph.handle, B, ptr(syndromes, C.c_int8), ptr(llr, C.c_double), ptr(hard, C.c_int8), op, int(flags), ptr(sol, C.c_int8)))
     return sol
+
+
+def osd0_last_path(graph):
+    """qldpc_osd0_last_path -> (path, detail): the OSD-0 kernel the last OSD-0 call on this graph handle took (OSD_PATH_*, OSD_DETAIL_* bits)."""
+    path, detail = C.c_int(-2), C.c_int(0)
+    check(lib().qldpc_osd0_last_path(graph.handle, C.byref(path), C.byref(detail)))
+    return path.value, detail.value
 
 
 def osdw_batch(graph, syndromes, llr, hard, order, max_combinations=None, ordering=None):

@@ -151,6 +151,7 @@ struct qldpc_graph {
     mutable void *pin = nullptr;     // pinned host staging for small results
     mutable size_t pin_cap = 0;
     mutable int gf2_rank = -1;       // rank of H over GF(2), computed on first OSD use
+    mutable int osd_path = -1, osd_detail = 0;   // what the last OSD-0 launch on this handle took (QLDPC_OSD_PATH_*, QLDPC_OSD_DETAIL_*; guarded by mu)
     mutable uint16_t *d_col_rows = nullptr;   // [n][max_col_deg] rows of every column (ascending, padded with m), built on first OSD use
     mutable void *wg2_cache = nullptr;   // tables of the LDS-resident workgroup decoder per prior (minsum_wg2.hip), built on first use (guarded by mu)
     mutable unsigned long long *clk_probe = nullptr;   // set (under mu) by a plan created with QLDPC_FLAG_CLOCK_PROBE around one launch

@@ -203,12 +203,19 @@ static int osd0_global_launch(const qldpc_graph *g, const int32_t *d_list, const
 // callers hold g->mu; the graph's device workspaces are handed over in stream order (common.h)
 int osd0_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
                        const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, OsdJudge *judge) {
+    g->osd_path = QLDPC_OSD_PATH_NONE; g->osd_detail = 0;      // what qldpc_osd0_last_path reports: written below, where each launch is made
     if (g->m == 0 || g->n == 0) return QLDPC_OK;
     int rc = g->ws_acquire(stream);                 // (a no-op for a caller that already holds the workspaces on this stream)
     if (rc != QLDPC_OK) return rc;
     bool handled = false;           // LDS-resident kernels for m <= 4096; the global-memory kernel is the general fallback
     rc = osd0_lds_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, handled, judge);
-    if (rc == QLDPC_OK && !handled) rc = osd0_global_launch(g, d_list, d_count, d_synd, d_llr, d_hard, d_ordering, d_solution, stream);
+    if (rc == QLDPC_OK && !handled) {
+        rc = osd0_global_launch(g, d_list, d_count, d_synd, d_llr, d_hard, d_ordering, d_solution, stream);
+        if (rc == QLDPC_OK) {
+            // (a free-pivot kernel that found no reference-order form for its redo list is followed by this kernel on EVERY shot)
+            if (g->osd_path == QLDPC_OSD_PATH_NONE) g->osd_path = QLDPC_OSD_PATH_GLOBAL; else g->osd_detail |= QLDPC_OSD_DETAIL_REDO;
+        }
+    }
     const int rel = g->ws_release(stream);          // always: a failing call may have enqueued launches the next stream has to wait for
     return rc != QLDPC_OK ? rc : rel;
 }
@@ -1157,6 +1164,7 @@ int osd0_lds_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *
     handled = false;
     if (!(flags & (QLDPC_FLAG_OSD_LDS | QLDPC_FLAG_OSD_UG | QLDPC_FLAG_OSD_GLOBAL))) {      // small matrices: the literal elimination, one wave per shot
         const int rcs = osd0_small_launch(g, d_list, d_count, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, handled, judge);
+        if (rcs == QLDPC_OK && handled) g->osd_path = QLDPC_OSD_PATH_SMALL;
         if (rcs != QLDPC_OK || handled) return rcs;
     }
 #ifndef QLDPC_EXPERIMENTS
@@ -1173,14 +1181,17 @@ int osd0_lds_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *
         if (!(flags & QLDPC_FLAG_OSD_UG)) {
             const int rcg = osd0_gj_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, took);
             if (rcg != QLDPC_OK) return rcg;
+            if (took) g->osd_path = QLDPC_OSD_PATH_GJ;
         }
         if (!took) {
             const int rcg = osd0_gjg_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, stream, 0, took);
             if (rcg != QLDPC_OK) return rcg;
+            if (took) g->osd_path = QLDPC_OSD_PATH_GJG;
         }
         if (took) { d_count = g->ws_redo.as<int32_t>(); d_list = d_count + 4; }
     }
     const int mode = (flags & QLDPC_FLAG_OSD_GLOBAL) ? 0 : plan_osd_lds(g, P, lds, flags);
+    g->osd_detail = mode & QLDPC_OSD_DETAIL_MODE_MASK;
     if (mode == 0) return QLDPC_OK;
     if (g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);      // callers hold g->mu
     P.rankH = g->gf2_rank;
@@ -1207,11 +1218,22 @@ int osd0_lds_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *
     if (mode == 2) hipLaunchKernelGGL(osd0_lds_kernel<true>, dim3(grid), dim3(1024), lds, stream, P);
     else hipLaunchKernelGGL(osd0_lds_kernel<false>, dim3(grid), dim3(block), lds, stream, P);
     QLDPC_HIP_TRY(hipGetLastError());
+    if (g->osd_path == QLDPC_OSD_PATH_NONE) g->osd_path = (mode == 2) ? QLDPC_OSD_PATH_REFORDER_UG : QLDPC_OSD_PATH_REFORDER_LDS;
+    else g->osd_detail |= QLDPC_OSD_DETAIL_REDO;       // behind a free-pivot kernel, on the shots it listed in ws_redo
     handled = true;
     return QLDPC_OK;
 }
 
 }  // namespace qldpc
+
+// the OSD-0 form the last qldpc_osd0_batch[_dev] (or a plan's / a window decoder's OSD-0 stage) on this handle took
+QLDPC_EXPORT int qldpc_osd0_last_path(const qldpc_graph *g, int *path, int *detail) {
+    QLDPC_REQUIRE(g != nullptr, "graph is NULL");
+    QLDPC_REQUIRE(path != nullptr && detail != nullptr, "NULL output");
+    std::lock_guard<std::mutex> lk(g->mu);
+    *path = g->osd_path; *detail = g->osd_detail;
+    return QLDPC_OK;
+}
 
 // ---- diagnostic phase counters (see osd_common.h) ----
 namespace qldpc {

@@ -350,6 +350,20 @@ __global__ __launch_bounds__(1024) void osd0_gj_kernel(OsdGjArgs P) {
                             }
                             if (wave != 1) break;
                         }
+                        if (m + 2 > 1024 && wave == 2) {
+                            // m = 1023, 1024: the rows q >= 1024 have no lane above (q = 16 * lane + .. <= 1023).  The only row of the transform among them
+                            // is the right-hand side, row m + 1: tested here on the old state and put on the list (uniform over the wave, lane 0 appends)
+                            const uint32_t *row32 = reinterpret_cast<const uint32_t *>(U + brow * 16);
+                            const int sz = (brow >> 3) & 14;
+                            uint32_t sel = 0u;
+#pragma unroll
+                            for (int k = 0; k < 16; k++) {
+                                const int d = pk[k] >> 5;
+                                sel |= ((row32[2 * ((d >> 1) ^ sz) + (d & 1)] >> (pk[k] & 31)) & 1u) << k;
+                            }
+                            sel &= pend;
+                            if (lane == 0 && sel != 0u) tlist[atomicAdd(tcnt, 1)] = (uint32_t)brow | (sel << 16);
+                        }
                         // every row has been tested on the OLD state: now the updates may land (a barrier of the waves 1 .. 15)
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                         if (lane == 0) atomicAdd(sbar, 1);

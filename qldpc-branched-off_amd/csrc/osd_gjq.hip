@@ -269,6 +269,8 @@ __global__ __launch_bounds__(1024) void osd0_gjq_kernel(OsdGjqArgs PP) {
                         gj_rows_apply<true>(U, Cp, act ? q : m, 16, pend, ppvPrev, lane, c_gat);
                         if (wave != 1) break;
                     }
+                    // m = 1023, 1024: the right-hand side, row m + 1 >= 1024, has no lane above (q <= 1023): lane 0 of wave 2 takes it
+                    if (m + 2 > 1024 && wave == 2) gj_rows_apply<true>(U, Cp, lane == 0 ? m + 1 : m, 16, pend, ppvPrev, lane, c_gat);
 #ifdef QLDPC_OSD_TIMERS
                     c_p3own += OSD_CLOCK() - tp;
 #endif
@@ -295,6 +297,7 @@ __global__ __launch_bounds__(1024) void osd0_gjq_kernel(OsdGjqArgs PP) {
             const int q = (lane << 4) + (((tid >> 6) + tid) & 15);
             const bool act = (q < m + 2) && (q != m);
             gj_rows_apply<true>(U, Cb + 16 * cprev * 16, act ? q : m, 16, pend, ppv, lane, c_gat);
+            if (m + 2 > 1024 && wave == 2) gj_rows_apply<true>(U, Cb + 16 * cprev * 16, lane == 0 ? m + 1 : m, 16, pend, ppv, lane, c_gat);      // (row m + 1 >= 1024, as above)
             pend = 0u;
             __syncthreads();
             c_last += OSD_CLOCK() - tp;
