@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -87,6 +89,45 @@ struct DevTmp {
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 
+// Replaces the contents of a device buffer with a host vector (synchronous copy; an empty vector still leaves an allocation).
+template <class T>
+int upload(DevBuf &b, const std::vector<T> &v) {
+    int rc = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (rc != QLDPC_OK) return rc;
+    if (!v.empty()) QLDPC_HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return QLDPC_OK;
+}
+
+// Regions of one device slab (the host-pointer entry points' ws_io): add() hands out 16-aligned offsets in order, ensure() sizes the
+// buffer for all of them, at() is a region's address afterwards.
+struct IoSlab {
+    size_t total = 0;
+    unsigned char *base = nullptr;
+    size_t add(size_t bytes) { const size_t o = total; total += (size_t)round_up((int64_t)bytes, 16); return o; }
+    int ensure(DevBuf &b) { const int rc = b.ensure(total); base = b.as<unsigned char>(); return rc; }
+    template <class T = unsigned char> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+};
+
+// Compute units of a device (256 when the runtime does not say): what the persistent grids are sized by.
+int cu_count(int device);
+
+// Device state that one stream uses at a time, handed from stream to stream through an event: a user calls acquire(stream) before its
+// launches (a launch on another stream first waits for the previous user to finish) and release(stream) after them -- on every path once
+// anything may have been enqueued, failures included, since the next stream has to wait for those launches too.  The owner serialises the calls.
+struct StreamHandover {
+    hipEvent_t event = nullptr;
+    hipStream_t stream = nullptr;
+    bool used = false;
+    int acquire(hipStream_t s);
+    int release(hipStream_t s);
+    void destroy();
+};
+
+// The host-pointer entry of the decoders whose outputs are (err, llr, conv, iter): temporary device buffers, syndromes in, launch(d_synd,
+// d_err, d_llr, d_conv, d_iter) on the null stream under `mu`, wait, results out.  `what` names the decoder in the error text.
+int decode_batch_via_device(std::mutex &mu, const char *what, int64_t B, int m, int n, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
+                            int32_t *iter, const std::function<int(const int8_t *, int8_t *, double *, uint8_t *, int32_t *)> &launch);
+
 // Shader-clock probe (QLDPC_FLAG_CLOCK_PROBE): thread 0 of a workgroup stamps the shader-clock counter (s_memtime) and the constant
 // 100 MHz counter (s_memrealtime) when it starts and when it ends; clock held under this kernel's load = delta ratio x 100 MHz
 // (MI355X_MICROARCH.md, DVFS give-back item 6).  Buffer: kClkSlots pairs (delta memtime, delta memrealtime) indexed by blockIdx.x.
@@ -129,16 +170,14 @@ struct qldpc_graph {
     uint32_t *d_ell_var_s = nullptr; // [max_col_deg][n] indexed by column slot: (row slot << 8) | position-in-row, ascending ROW order
     int32_t *d_identity = nullptr;   // [max(m, n)] 0, 1, 2, ... (the natural-order "permutation")
     // Device workspaces of the decode / OSD kernels.  `mu` guards the bookkeeping while launches are enqueued; the buffers themselves
-    // are protected in STREAM order: every user calls ws_acquire(stream) before its launches and ws_release(stream) after them, so a
-    // launch on another stream first waits (hipStreamWaitEvent) for the previous user of the workspaces to finish.
+    // are protected in STREAM order: every user calls ws_acquire(stream) before its launches and ws_release(stream) after them
+    // (StreamHandover above).
     mutable std::mutex mu;
     mutable qldpc::DevBuf ws_msg, ws_qold, ws_vals, ws_misc, ws_queue, ws_list, ws_prior, ws_redo;
     mutable qldpc::DevBuf ws_cs;      // OSD-CS (osd_cs.hip): [0] count, [4..] shots whose right-hand side is outside the column space
     mutable qldpc::DevBuf ws_squeue;  // work queue of the one-wave OSD-0 kernels (osd_small.hip): zeroed once, the kernels reset it themselves
     mutable bool ws_private = false;  // the handle is used from ONE stream only (a private copy owned by a plan lane): no hand-over events
-    mutable hipEvent_t ws_event = nullptr;
-    mutable hipStream_t ws_stream = nullptr;
-    mutable bool ws_used = false;
+    mutable qldpc::StreamHandover ws_hand;
     int ws_acquire(hipStream_t stream) const;     // callers hold mu
     int ws_release(hipStream_t stream) const;
     mutable std::mutex mu_io;        // host-pointer entry points: serialises use of ws_io (taken before mu)

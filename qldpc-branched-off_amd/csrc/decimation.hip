@@ -5,8 +5,8 @@
 // include/qldpc_hip.h; tests/decimation_model.py is the numpy model the kernel equals bit for bit.
 //
 // One workgroup per shot, persistent grid, shots handed out through an atomic queue.  A round is one leg of relay_bp_kernel (relay_bp.hip)
-// with gamma_j = 0 and bias_j in place of prior_j: the same slot tables, the same 24-byte compressed check state, the same order of every
-// floating-point operation (the loop is restated here, not shared, so that relay_bp.hip compiles to what it compiled to before).
+// with gamma_j = 0 and bias_j in place of prior_j: both kernels call the one leg of bp_leg.h (slot tables, 24-byte compressed check state,
+// order of every floating-point operation) and differ in the bias they hand it.
 // LDS: V[n] f64 (or a per-workgroup slab in HBM/L2 when it does not fit: VG), the check states, two bits per ORIGINAL column (fixed, sign of
 // the fixed value) as two bit planes of 32-bit words, the unsat flags and the per-wave candidates of the selection.
 // Selection: every thread keeps the best (|V| bits, column) of its own columns j = tid, tid + NT, ...; a pick is a lexicographic max over
@@ -14,9 +14,7 @@
 // the waves in every thread.  The thread that owns the winner freezes it and rescans its own columns.  The comparison is exact (integer
 // compare of the magnitude bits, then the column), so lane and wave order cannot matter.  Every loop is bounded by per_round, n, t_round and
 // max_rounds; workgroup barriers are the only synchronisation.
-#include "common.h"
-#include "mc_common.h"
-#include "minsum_common.h"
+#include "bp_leg.h"
 
 #include <algorithm>
 #include <climits>
@@ -25,11 +23,7 @@
 namespace qldpc {
 
 struct DecimArgs {
-    int m, n, cdeg;
-    const int32_t *row_of_slot, *col_of_slot;
-    const uint8_t *degr;           // [m] degree of the row in slot s
-    const uint16_t *ell_col;       // [round_up(rdeg, 8)][m] by row slot
-    const uint32_t *ell_var;       // [cdeg][n] by column slot: (row slot << 8) | position in the row, ascending rows
+    SlotGraph G;
     int64_t B;
     const int8_t *synd;
     const double *prior;           // [n] finite (host-verified, or the documented precondition of the _dev entry)
@@ -53,7 +47,7 @@ template <bool VG>
 __global__ __launch_bounds__(1024) void decim_bp_kernel(DecimArgs A) {
     extern __shared__ unsigned char lds[];
     double *V;
-    if (VG) V = A.vglobal + (size_t)blockIdx.x * A.n; else V = reinterpret_cast<double *>(lds);
+    if (VG) V = A.vglobal + (size_t)blockIdx.x * A.G.n; else V = reinterpret_cast<double *>(lds);
     double2 *SP = reinterpret_cast<double2 *>(lds + A.offP);                       // (alpha*min1, alpha*min2) per check
     unsigned long long *SI = reinterpret_cast<unsigned long long *>(lds + A.offI); // bits 0-55 input signs, 56-62 argmin (127 = none), 63 total sign
     uint32_t *FX = reinterpret_cast<uint32_t *>(lds + A.offB);                     // bit j: ORIGINAL column j is fixed
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(1024) void decim_bp_kernel(DecimArgs A) {
     int *F = reinterpret_cast<int *>(lds + A.offF);                                // [0], [1] unsat flags, [2] shot
     unsigned long long *WK = reinterpret_cast<unsigned long long *>(lds + A.offK); // [2][16] per-wave candidate keys
     int *WC = reinterpret_cast<int *>(lds + A.offC);                               // [2][16] and their columns
-    const int m = A.m, n = A.n, tid = threadIdx.x, NT = blockDim.x, T = A.t_round;
+    const int n = A.G.n, tid = threadIdx.x, NT = blockDim.x, T = A.t_round;
     const int nw = NT >> 6, nwords = (n + 31) >> 5;
     const double clip = A.clip, alpha = A.alpha, fix = A.fix;
 
@@ -77,69 +71,12 @@ __global__ __launch_bounds__(1024) void decim_bp_kernel(DecimArgs A) {
         for (int r = 0; r <= A.max_rounds; r++) {                                    // (uniform: every thread holds the same r, nfix, conv)
             if (tid < 2) F[tid] = 0;
             __syncthreads();
-            int itc = T;
-            for (int it = 0; it <= T; it++) {
-                // ---------------- check pass (relay_bp_kernel's) ----------------
-                for (int i = tid; i < m; i += NT) {                                  // i = row slot
-                    const int deg = A.degr[i];
-                    const bool csyn = A.synd[b * m + A.row_of_slot[i]] & 1;
-                    double p1p = 0.0, p2p = 0.0;
-                    unsigned long long ip = 0ull;
-                    if (it > 0 && deg > 0) { const double2 t = SP[i]; p1p = t.x; p2p = t.y; ip = SI[i]; }
-                    const int argp = (int)((ip >> 56) & 127);
-                    const bool spp = (ip >> 63) & 1;
-                    bool par = csyn, sp = csyn;
-                    double min1 = INFINITY, min2 = INFINITY;
-                    int arg = 127;
-                    unsigned long long negbits = 0ull;
-                    for (int k = 0; k < deg; k++) {
-                        const int col = A.ell_col[(size_t)k * m + i];
-                        const double v = V[col];
-                        par ^= (v < 0.0);
-                        double x = v;                                                // the round's first pass: Q = V[col], nothing subtracted
-                        if (it > 0) {
-                            const double mag = (k == argp) ? p2p : p1p;
-                            const double rr = (spp != (bool)((ip >> k) & 1)) ? -mag : mag;
-                            x = clip_nan(v - rr, clip);
-                        }
-                        const bool neg = !(x >= 0.0);
-                        sp ^= neg;
-                        negbits |= (unsigned long long)neg << k;
-                        const double a = fabs(x);
-                        if (a < min1) { min2 = min1; min1 = a; arg = k; }
-                        else if (a < min2) { min2 = a; }
-                    }
-                    if (it >= 1 && par) F[it & 1] = 1;
-                    if (it < T && deg > 0) {
-                        SP[i] = make_double2(alpha * min1, alpha * min2);
-                        SI[i] = negbits | ((unsigned long long)arg << 56) | ((unsigned long long)sp << 63);
-                    }
-                }
-                __syncthreads();
-                if (it >= 1 && F[it & 1] == 0) { conv = true; itc = it; break; }     // V holds values_{it-1}: it reproduces the syndrome
-                if (it == T) break;
-                if (tid == 0) F[(it + 1) & 1] = 0;
-                // ---------------- variable pass: V_j = s_j + bias_j ----------------
-                for (int c = tid; c < n; c += NT) {                                  // c = column slot
-                    const int j = A.col_of_slot[c];
-                    double s = 0.0;
-                    for (int d = 0; d < A.cdeg; d++) {
-                        const uint32_t e = A.ell_var[(size_t)d * n + c];
-                        if (e == 0xFFFFFFFFu) break;
-                        const int i = (int)(e >> 8), k = (int)(e & 255u);
-                        const double2 pp = SP[i];
-                        const unsigned long long inf = SI[i];
-                        const double mag = (k == (int)((inf >> 56) & 127)) ? pp.y : pp.x;
-                        s += ((bool)((inf >> 63) & 1) != (bool)((inf >> k) & 1)) ? -mag : mag;   // ascending check order
-                    }
-                    const uint32_t bit = 1u << (j & 31);
-                    const double bias = (FX[j >> 5] & bit) ? ((SG[j >> 5] & bit) ? -fix : fix) : A.prior[j];
-                    V[j] = s + bias;
-                }
-                __syncthreads();
-            }
-            __syncthreads();                                                         // every thread has read the flags before the next round resets them
-            iters += itc;
+            const LegResult L = bp_leg(A.G, A.synd, b, T, alpha, clip, V, SP, SI, F, [&](int j, double) {       // V_j = s_j + bias_j
+                const uint32_t bit = 1u << (j & 31);
+                return (FX[j >> 5] & bit) ? ((SG[j >> 5] & bit) ? -fix : fix) : A.prior[j];
+            });
+            if (L.conv) conv = true;                                                 // (a converged round ends the loop below)
+            iters += L.itc;
             rounds = r + 1;
             if (conv || r == A.max_rounds || nfix == n) break;
             // ---------------- decimation: freeze the min(per_round, unfixed) most reliable unfixed columns ----------------
@@ -204,9 +141,7 @@ __global__ __launch_bounds__(1024) void decim_bp_kernel(DecimArgs A) {
 
 // Relay-BP's layout with its round_up(n, 4) * 2 bytes of draws replaced by two bit planes of ceil(n / 32) words, plus 384 bytes of candidates
 static size_t decim_lds_bytes(const qldpc_graph *g, bool vg, DecimArgs &A) {
-    A.offP = vg ? 0 : (int)round_up((int64_t)g->n * 8, 16);
-    A.offI = A.offP + g->m * 16;
-    A.offB = (int)round_up(A.offI + (int64_t)g->m * 8, 16);
+    A.offB = leg_lds_prefix(g, vg, A.offP, A.offI);
     const int plane = (int)round_up((int64_t)((g->n + 31) / 32) * 4, 16);
     A.offS = A.offB + plane;
     A.offF = A.offS + plane;
@@ -248,9 +183,7 @@ int decim_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, c
     if (mode == 0) return decim_unsupported(g);
     if (B == 0) return QLDPC_OK;
     DecimArgs A;
-    A.m = g->m; A.n = g->n; A.cdeg = g->max_col_deg;
-    A.row_of_slot = g->d_row_of_slot; A.col_of_slot = g->d_col_of_slot; A.degr = g->d_deg_of_rslot;
-    A.ell_col = g->d_ell_col_s; A.ell_var = g->d_ell_var_s;
+    A.G = slot_graph(g);
     A.B = B; A.synd = d_synd; A.prior = d_prior;
     A.alpha = P.alpha; A.clip = P.clip; A.fix = P.fix;
     A.t_round = P.t_round; A.max_rounds = P.max_rounds; A.per_round = P.per_round;
@@ -258,32 +191,7 @@ int decim_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, c
     A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iters = d_iters; A.out_rounds = d_rounds; A.out_fixed = d_fixed;
     const bool vg = mode == 2;
     const size_t lds = decim_lds_bytes(g, vg, A);
-    const int block = (g->m > 512 || g->n > 4096) ? 1024 : 512;
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>((160 * 1024) / (int64_t)lds, 2048 / block));
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)cus * per_cu);
-    int rc = g->ws_acquire(stream);
-    if (rc != QLDPC_OK) return rc;
-    auto launch = [&]() -> int {
-        int rcl = g->ws_queue.ensure(16);
-        if (rcl != QLDPC_OK) return rcl;
-        QLDPC_HIP_TRY(hipMemsetAsync(g->ws_queue.p, 0, 16, stream));
-        A.queue = g->ws_queue.as<int>();
-        A.vglobal = nullptr;
-        if (vg) {
-            if ((rcl = g->ws_vals.ensure((size_t)grid * g->n * 8)) != QLDPC_OK) return rcl;
-            A.vglobal = g->ws_vals.as<double>();
-        }
-        void (*kern)(DecimArgs) = vg ? decim_bp_kernel<true> : decim_bp_kernel<false>;
-        if ((rcl = ensure_max_lds(g->device, reinterpret_cast<const void *>(kern), 160 * 1024)) != QLDPC_OK) return rcl;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, A);
-        QLDPC_HIP_TRY(hipGetLastError());
-        return QLDPC_OK;
-    };
-    rc = launch();
-    const int rel = g->ws_release(stream);          // always: a failing call may have enqueued launches the next stream has to wait for
-    return rc != QLDPC_OK ? rc : rel;
+    return shot_queue_launch(g, B, vg ? decim_bp_kernel<true> : decim_bp_kernel<false>, A, lds, vg, stream);
 }
 
 }  // namespace qldpc
@@ -321,28 +229,25 @@ QLDPC_EXPORT int qldpc_decim_decode_batch(const qldpc_graph *g, int64_t B, const
     for (size_t j = 0; j < n; j++) QLDPC_REQUIRE(std::isfinite(prior[j]), "prior[%zu] is not finite", j);
     QLDPC_USE_DEVICE(g->device);
     if (!decim_supported(g)) return decim_unsupported(g);
-    // one grow-only slab per graph handle:  prior | llr | syndromes | err | conv | iters | rounds | fixed
-    const size_t o_prior = 0, o_llr = round_up((int64_t)n * 8, 16), o_synd = o_llr + (llr ? round_up((int64_t)B * n * 8, 16) : 0),
-                 o_err = o_synd + round_up((int64_t)B * m, 16), o_conv = o_err + round_up((int64_t)B * n, 16), o_iters = o_conv + round_up(B, 16),
-                 o_rounds = o_iters + round_up(B * 4, 16), o_fixed = o_rounds + round_up(B * 4, 16), total = o_fixed + round_up(B * 4, 16);
+    // one grow-only slab per graph handle:  prior | llr (when asked for) | syndromes | err | conv | iters | rounds | fixed
+    IoSlab S;
+    const size_t o_prior = S.add(n * 8), o_llr = S.add(llr ? B * n * 8 : 0), o_synd = S.add(B * m), o_err = S.add(B * n), o_conv = S.add(B),
+                 o_iters = S.add(B * 4), o_rounds = S.add(B * 4), o_fixed = S.add(B * 4);
     std::unique_lock<std::mutex> io(g->mu_io);
-    if ((rc = g->ws_io.ensure(total)) != QLDPC_OK) return rc;
-    unsigned char *base = g->ws_io.as<unsigned char>();
-    QLDPC_HIP_TRY(hipMemcpyAsync(base + o_synd, syndromes, B * m, hipMemcpyHostToDevice, nullptr));
-    QLDPC_HIP_TRY(hipMemcpyAsync(base + o_prior, prior, n * 8, hipMemcpyHostToDevice, nullptr));
+    if ((rc = S.ensure(g->ws_io)) != QLDPC_OK) return rc;
+    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_synd), syndromes, B * m, hipMemcpyHostToDevice, nullptr));
+    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_prior), prior, n * 8, hipMemcpyHostToDevice, nullptr));
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = decim_decode_launch(g, B, reinterpret_cast<int8_t *>(base + o_synd), reinterpret_cast<double *>(base + o_prior), P, 0,
-                                 reinterpret_cast<int8_t *>(base + o_err), llr ? reinterpret_cast<double *>(base + o_llr) : nullptr,
-                                 reinterpret_cast<uint8_t *>(base + o_conv), reinterpret_cast<int32_t *>(base + o_iters),
-                                 reinterpret_cast<int32_t *>(base + o_rounds), reinterpret_cast<int32_t *>(base + o_fixed), nullptr);
+        rc = decim_decode_launch(g, B, S.at<int8_t>(o_synd), S.at<double>(o_prior), P, 0, S.at<int8_t>(o_err), llr ? S.at<double>(o_llr) : nullptr,
+                                 S.at<uint8_t>(o_conv), S.at<int32_t>(o_iters), S.at<int32_t>(o_rounds), S.at<int32_t>(o_fixed), nullptr);
     }
     if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, base + o_err, B * n, hipMemcpyDeviceToHost));
-    if (llr) QLDPC_HIP_TRY(hipMemcpy(llr, base + o_llr, B * n * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, base + o_conv, B, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iters, base + o_iters, B * 4, hipMemcpyDeviceToHost));
-    if (rounds) QLDPC_HIP_TRY(hipMemcpy(rounds, base + o_rounds, B * 4, hipMemcpyDeviceToHost));
-    if (fixed) QLDPC_HIP_TRY(hipMemcpy(fixed, base + o_fixed, B * 4, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(err, S.at(o_err), B * n, hipMemcpyDeviceToHost));
+    if (llr) QLDPC_HIP_TRY(hipMemcpy(llr, S.at(o_llr), B * n * 8, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(conv, S.at(o_conv), B, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(iters, S.at(o_iters), B * 4, hipMemcpyDeviceToHost));
+    if (rounds) QLDPC_HIP_TRY(hipMemcpy(rounds, S.at(o_rounds), B * 4, hipMemcpyDeviceToHost));
+    if (fixed) QLDPC_HIP_TRY(hipMemcpy(fixed, S.at(o_fixed), B * 4, hipMemcpyDeviceToHost));
     return QLDPC_OK;
 }

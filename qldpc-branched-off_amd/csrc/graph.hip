@@ -89,22 +89,53 @@ void DevBuf::release() {
     cap = 0;
 }
 
+int cu_count(int device) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    return cus;
+}
+
+int StreamHandover::acquire(hipStream_t s) {
+    if (used && s != stream && event) QLDPC_HIP_TRY(hipStreamWaitEvent(s, event, 0));
+    return QLDPC_OK;
+}
+int StreamHandover::release(hipStream_t s) {
+    if (!event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&event, hipEventDisableTiming));
+    QLDPC_HIP_TRY(hipEventRecord(event, s));
+    stream = s; used = true;
+    return QLDPC_OK;
+}
+void StreamHandover::destroy() {
+    if (event) (void)hipEventDestroy(event);
+    event = nullptr;
+}
+
+int decode_batch_via_device(std::mutex &mu, const char *what, int64_t B, int m, int n, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
+                            int32_t *iter, const std::function<int(const int8_t *, int8_t *, double *, uint8_t *, int32_t *)> &launch) {
+    const size_t Bz = (size_t)B, mz = (size_t)m, nz = (size_t)n;
+    DevTmp ds, de, dl, dc, di;
+    int rc;
+    if ((rc = ds.alloc(Bz * mz)) || (rc = de.alloc(Bz * nz)) || (rc = dl.alloc(Bz * nz * 8)) || (rc = dc.alloc(Bz)) || (rc = di.alloc(Bz * 4))) return rc;
+    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * mz, hipMemcpyHostToDevice));
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        rc = launch(ds.as<int8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(), di.as<int32_t>());
+        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("%s decode failed: %s", what, hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+    }
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * nz, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(llr, dl.p, Bz * nz * 8, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(iter, di.p, Bz * 4, hipMemcpyDeviceToHost));
+    return QLDPC_OK;
+}
+
 }  // namespace qldpc
 
 using namespace qldpc;
 
-int qldpc_graph::ws_acquire(hipStream_t stream) const {
-    if (ws_private) return QLDPC_OK;
-    if (ws_used && stream != ws_stream && ws_event) QLDPC_HIP_TRY(hipStreamWaitEvent(stream, ws_event, 0));
-    return QLDPC_OK;
-}
-int qldpc_graph::ws_release(hipStream_t stream) const {
-    if (ws_private) return QLDPC_OK;
-    if (!ws_event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&ws_event, hipEventDisableTiming));
-    QLDPC_HIP_TRY(hipEventRecord(ws_event, stream));
-    ws_stream = stream; ws_used = true;
-    return QLDPC_OK;
-}
+int qldpc_graph::ws_acquire(hipStream_t stream) const { return ws_private ? QLDPC_OK : ws_hand.acquire(stream); }
+int qldpc_graph::ws_release(hipStream_t stream) const { return ws_private ? QLDPC_OK : ws_hand.release(stream); }
 
 int qldpc_graph::alpha_table(const std::vector<double> &tab, hipStream_t stream, const double **d_out) const {
     for (const AlphaEntry &e : alpha_cache)
@@ -262,7 +293,7 @@ QLDPC_EXPORT void qldpc_graph_destroy(qldpc_graph *g) {
     g->ws_msg.release(); g->ws_qold.release(); g->ws_vals.release(); g->ws_misc.release(); g->ws_io.release(); g->ws_queue.release(); g->ws_squeue.release(); g->ws_list.release(); g->ws_redo.release(); g->ws_cs.release();
     for (auto &e : g->alpha_cache) { if (e.dev) (void)hipFree(e.dev); if (e.pinned) (void)hipHostFree(e.pinned); if (e.ready) (void)hipEventDestroy(e.ready); }
     if (g->wg2_cache) qldpc::wg2_cache_free(g->wg2_cache);
-    if (g->ws_event) (void)hipEventDestroy(g->ws_event);
+    g->ws_hand.destroy();
     if (g->pin) (void)hipHostFree(g->pin);
     delete g;
 }

@@ -167,22 +167,12 @@ struct qldpc_minsum32_decoder {
     bool clean = false;
     int offR = 0, offD = 0, offF = 0;
     DevBuf d_prior, d_alpha, d_queue;
-    // the queue word is handed from stream to stream through an event like a graph handle's workspaces (common.h)
+    // the queue word is handed from stream to stream like a graph handle's workspaces (common.h)
     std::mutex mu;
-    hipEvent_t ws_event = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
+    StreamHandover hand;
 };
 
 namespace qldpc {
-
-template <class T>
-static int upload32(DevBuf &b, const std::vector<T> &v) {
-    int rc = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (rc != QLDPC_OK) return rc;
-    if (!v.empty()) QLDPC_HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return QLDPC_OK;
-}
 
 // Creation on a ready f64 alpha table (the circuit plan holds one per sector); the exported form builds the table from the alpha mode.
 int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int max_iter, const std::vector<double> &tab, double clip_llr, int flags,
@@ -235,8 +225,6 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
     auto fail = [&](int code) { qldpc_minsum32_decoder_destroy(D.release()); return code; };
     // ---- workgroup size.  One workgroup of a CU: all 1024 threads; else the size whose passes have work for every thread (a row and eight columns),
     // and the host asks the runtime whether as many workgroups as LDS allows (two are enough) are resident with it; if not, the next smaller size.
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
     const int by_lds = kF32Lds / D->lds, work = std::max(m, n / 8);
     int block = fb == QLDPC_FLAG_F32_BLOCK_256 ? 256 : fb == QLDPC_FLAG_F32_BLOCK_512 ? 512 : fb == QLDPC_FLAG_F32_BLOCK_1024 ? 1024
                 : by_lds < 2 ? 1024 : work > 256 ? 512 : 256;
@@ -250,8 +238,8 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
         if (fb || block == 256 || nb >= std::min(by_lds, 2)) break;
     }
     if (D->wg_per_cu < 1) { set_error("the f32 decoder's kernel is not launchable with %d threads and %d bytes of LDS", D->block, D->lds); return fail(QLDPC_ERR_HIP); }
-    D->grid_cap = cus * D->wg_per_cu;
-    if ((rc = upload32(D->d_prior, prior_s)) || (rc = upload32(D->d_alpha, alpha32)) || (rc = D->d_queue.ensure(16))) return fail(rc);
+    D->grid_cap = cu_count(g->device) * D->wg_per_cu;
+    if ((rc = upload(D->d_prior, prior_s)) || (rc = upload(D->d_alpha, alpha32)) || (rc = D->d_queue.ensure(16))) return fail(rc);
     *out = D.release();
     return QLDPC_OK;
 }
@@ -259,7 +247,8 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
 // Enqueues the decode of B shots on `s`.  Callers hold D->mu.
 static int minsum32_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                            hipStream_t s) {
-    if (D->ws_used && s != D->ws_stream && D->ws_event) QLDPC_HIP_TRY(hipStreamWaitEvent(s, D->ws_event, 0));
+    int rc = D->hand.acquire(s);
+    if (rc != QLDPC_OK) return rc;
     const qldpc_graph *g = D->g;
     F32Args A;
     A.m = D->m; A.n = D->n; A.cdeg = g->max_col_deg;
@@ -269,17 +258,19 @@ static int minsum32_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d
     A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
     A.offR = D->offR; A.offD = D->offD; A.offF = D->offF;
     A.queue = D->d_queue.as<int>();
-    QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
-    const F32Kernel kern = f32_kernel(D->block, D->clean);
-    const int rc = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kF32Lds);
-    if (rc != QLDPC_OK) return rc;
-    const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
-    QLDPC_HIP_TRY(hipGetLastError());
-    if (!D->ws_event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&D->ws_event, hipEventDisableTiming));
-    QLDPC_HIP_TRY(hipEventRecord(D->ws_event, s));
-    D->ws_stream = s; D->ws_used = true;
-    return QLDPC_OK;
+    auto launch = [&]() -> int {
+        QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
+        const F32Kernel kern = f32_kernel(D->block, D->clean);
+        const int rcl = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kF32Lds);
+        if (rcl != QLDPC_OK) return rcl;
+        const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
+        QLDPC_HIP_TRY(hipGetLastError());
+        return QLDPC_OK;
+    };
+    rc = launch();
+    const int rel = D->hand.release(s);             // always: a failing call may have enqueued work the next stream has to wait for
+    return rc != QLDPC_OK ? rc : rel;
 }
 
 int minsum32_lock_and_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
@@ -304,8 +295,8 @@ QLDPC_EXPORT int qldpc_minsum32_decoder_create(const qldpc_graph *g, const doubl
 QLDPC_EXPORT void qldpc_minsum32_decoder_destroy(qldpc_minsum32_decoder *D) {
     if (!D) return;
     (void)hipSetDevice(D->device);
-    if (D->ws_used) (void)hipDeviceSynchronize();
-    if (D->ws_event) (void)hipEventDestroy(D->ws_event);
+    if (D->hand.used) (void)hipDeviceSynchronize();
+    D->hand.destroy();
     for (DevBuf *b : {&D->d_prior, &D->d_alpha, &D->d_queue}) b->release();
     delete D;
 }
@@ -342,19 +333,6 @@ QLDPC_EXPORT int qldpc_minsum32_decode_batch(qldpc_minsum32_decoder *D, int64_t 
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(D->device);
     if (B == 0) return QLDPC_OK;
-    const size_t Bz = (size_t)B, m = D->m, n = D->n;
-    DevTmp ds, de, dl, dc, di;
-    if ((rc = ds.alloc(Bz * m)) || (rc = de.alloc(Bz * n)) || (rc = dl.alloc(Bz * n * 8)) || (rc = dc.alloc(Bz)) || (rc = di.alloc(Bz * 4))) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * m, hipMemcpyHostToDevice));
-    {
-        std::lock_guard<std::mutex> lk(D->mu);
-        rc = minsum32_launch(D, B, ds.as<int8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(), di.as<int32_t>(), nullptr);
-        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("f32 decode failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
-    }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(llr, dl.p, Bz * n * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iter, di.p, Bz * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return decode_batch_via_device(D->mu, "f32", B, D->m, D->n, syndromes, err, llr, conv, iter,
+                                   [&](const int8_t *ds, int8_t *de, double *dl, uint8_t *dc, int32_t *di) { return minsum32_launch(D, B, ds, de, dl, dc, di, nullptr); });
 }

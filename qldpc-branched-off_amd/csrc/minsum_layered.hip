@@ -196,24 +196,14 @@ struct qldpc_layered_decoder {
     int offP = 0, offI = 0, offE = 0, offL = 0, offS = 0, offX = 0, offF = 0;
     std::vector<int32_t> row_layer;
     DevBuf d_prior, d_alpha, d_layer, d_slot_row, d_estart, d_idx16, d_idx32, d_queue, d_vglobal;
-    // the queue word and the VG slab are handed from stream to stream through an event like a graph handle's workspaces (common.h)
+    // the queue word and the VG slab are handed from stream to stream like a graph handle's workspaces (common.h)
     std::mutex mu;
-    hipEvent_t ws_event = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
+    StreamHandover hand;
 };
 
 namespace qldpc {
 
 static int ceil_log2(int x) { int l = 0; while ((1 << l) < x) l++; return l; }
-
-template <class T>
-static int upload(DevBuf &b, const std::vector<T> &v) {
-    int rc = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (rc != QLDPC_OK) return rc;
-    if (!v.empty()) QLDPC_HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return QLDPC_OK;
-}
 
 // Creation on a ready alpha table (the circuit plan holds one per sector); the exported form builds the table from the alpha mode.
 int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, const double *prior, int max_iter, const std::vector<double> &tab,
@@ -316,9 +306,7 @@ int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, c
     D->lds = (int)bytes;
     QLDPC_USE_DEVICE(g->device);
     auto fail = [&](int code) { qldpc_layered_decoder_destroy(D.release()); return code; };
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-    D->grid_cap = cus * (int)std::max<int64_t>(1, std::min<int64_t>(kLayeredLds / D->lds, 2048 / D->block));
+    D->grid_cap = cu_count(g->device) * (int)std::max<int64_t>(1, std::min<int64_t>(kLayeredLds / D->lds, 2048 / D->block));
     int rc;
     if (D->idxl) { idx16.assign(idx32.begin(), idx32.end()); if ((rc = upload(D->d_idx16, idx16)) != QLDPC_OK) return fail(rc); }
     const std::vector<double> pv(prior, prior + n), av(tab.begin(), tab.begin() + max_iter);
@@ -333,7 +321,8 @@ int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, c
 // Enqueues the decode of B shots on `s`.  Callers hold D->mu.
 static int layered_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                           hipStream_t s) {
-    if (D->ws_used && s != D->ws_stream && D->ws_event) QLDPC_HIP_TRY(hipStreamWaitEvent(s, D->ws_event, 0));
+    int rc = D->hand.acquire(s);
+    if (rc != QLDPC_OK) return rc;
     LayeredArgs A;
     A.m = D->m; A.n = D->n; A.nslots = D->nslots; A.nlayers = D->nlayers; A.nnz = D->nnz;
     A.layer = D->d_layer.as<uint32_t>(); A.slot_row = D->d_slot_row.as<int32_t>(); A.estart = D->d_estart.as<uint32_t>();
@@ -342,18 +331,20 @@ static int layered_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_s
     A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
     A.offP = D->offP; A.offI = D->offI; A.offE = D->offE; A.offL = D->offL; A.offS = D->offS; A.offX = D->offX; A.offF = D->offF;
     A.vglobal = D->d_vglobal.as<double>(); A.queue = D->d_queue.as<int>();
-    QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
-    void (*kern)(LayeredArgs) = D->vg ? (D->idxl ? minsum_layered_kernel<true, true> : minsum_layered_kernel<true, false>)
-                                      : (D->idxl ? minsum_layered_kernel<false, true> : minsum_layered_kernel<false, false>);
-    const int rc = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kLayeredLds);
-    if (rc != QLDPC_OK) return rc;
-    const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
-    QLDPC_HIP_TRY(hipGetLastError());
-    if (!D->ws_event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&D->ws_event, hipEventDisableTiming));
-    QLDPC_HIP_TRY(hipEventRecord(D->ws_event, s));
-    D->ws_stream = s; D->ws_used = true;
-    return QLDPC_OK;
+    auto launch = [&]() -> int {
+        QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
+        void (*kern)(LayeredArgs) = D->vg ? (D->idxl ? minsum_layered_kernel<true, true> : minsum_layered_kernel<true, false>)
+                                          : (D->idxl ? minsum_layered_kernel<false, true> : minsum_layered_kernel<false, false>);
+        const int rcl = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kLayeredLds);
+        if (rcl != QLDPC_OK) return rcl;
+        const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
+        QLDPC_HIP_TRY(hipGetLastError());
+        return QLDPC_OK;
+    };
+    rc = launch();
+    const int rel = D->hand.release(s);             // always: a failing call may have enqueued work the next stream has to wait for
+    return rc != QLDPC_OK ? rc : rel;
 }
 
 int layered_lock_and_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
@@ -388,8 +379,8 @@ QLDPC_EXPORT int qldpc_layered_decoder_create(const qldpc_graph *g, const int32_
 QLDPC_EXPORT void qldpc_layered_decoder_destroy(qldpc_layered_decoder *D) {
     if (!D) return;
     (void)hipSetDevice(D->device);
-    if (D->ws_used) (void)hipDeviceSynchronize();
-    if (D->ws_event) (void)hipEventDestroy(D->ws_event);
+    if (D->hand.used) (void)hipDeviceSynchronize();
+    D->hand.destroy();
     for (DevBuf *b : {&D->d_prior, &D->d_alpha, &D->d_layer, &D->d_slot_row, &D->d_estart, &D->d_idx16, &D->d_idx32, &D->d_queue, &D->d_vglobal}) b->release();
     delete D;
 }
@@ -434,19 +425,6 @@ QLDPC_EXPORT int qldpc_layered_decode_batch(qldpc_layered_decoder *D, int64_t B,
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(D->device);
     if (B == 0) return QLDPC_OK;
-    const size_t Bz = (size_t)B, m = D->m, n = D->n;
-    DevTmp ds, de, dl, dc, di;
-    if ((rc = ds.alloc(Bz * m)) || (rc = de.alloc(Bz * n)) || (rc = dl.alloc(Bz * n * 8)) || (rc = dc.alloc(Bz)) || (rc = di.alloc(Bz * 4))) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * m, hipMemcpyHostToDevice));
-    {
-        std::lock_guard<std::mutex> lk(D->mu);
-        rc = layered_launch(D, B, ds.as<int8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(), di.as<int32_t>(), nullptr);
-        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("layered decode failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
-    }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(llr, dl.p, Bz * n * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iter, di.p, Bz * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return decode_batch_via_device(D->mu, "layered", B, D->m, D->n, syndromes, err, llr, conv, iter,
+                                   [&](const int8_t *ds, int8_t *de, double *dl, uint8_t *dc, int32_t *di) { return layered_launch(D, B, ds, de, dl, dc, di, nullptr); });
 }

@@ -5,8 +5,8 @@
 // or after leg `max_legs`.  No OSD stage.
 //
 // One workgroup per shot, persistent grid, shots handed out through an atomic queue -- the structure of minsum_wg_kernel (minsum_wg.hip)
-// with its slot tables and its 24-byte compressed check state (alpha*min1, alpha*min2, argmin, sign bits).  One leg is that kernel's
-// loop with two changes: V (the marginals) is not reset to the prior at the start of a leg r >= 1, and the variable pass writes
+// with its slot tables and its 24-byte compressed check state (alpha*min1, alpha*min2, argmin, sign bits).  One leg (bp_leg.h, shared
+// with decimation.hip) is that kernel's loop with two changes: V (the marginals) is not reset to the prior at the start of a leg r >= 1, and the variable pass writes
 //     V_j = s_j + ((1 - gamma_j) * prior_j + gamma_j * V_j)           s_j = 0.0 + sum of R in ascending check order
 // (with gamma_j = 0 the existing update).  A marginal that is not finite -- the +-inf messages of degree-1 checks, which the circuit-level
 // X-sector matrices have, make it +-inf -- enters the memory term as 0.0: gamma_j * inf would turn the marginal into NaN for gamma_j <= 0,
@@ -14,9 +14,8 @@
 // first check pass is the it == 0 pass).
 // LDS: V[n] f64 (or a per-workgroup slab in HBM/L2 when it does not fit: VG), the check states, the memory draws as u16 per column and
 // a few words of flags and the weight accumulator.  Every loop is bounded by the iteration and leg counts.
-#include "common.h"
+#include "bp_leg.h"
 #include "mc_common.h"
-#include "minsum_common.h"
 
 #include <algorithm>
 #include <climits>
@@ -25,11 +24,7 @@
 namespace qldpc {
 
 struct RelayArgs {
-    int m, n, cdeg;
-    const int32_t *row_of_slot, *col_of_slot;
-    const uint8_t *degr;           // [m] degree of the row in slot s
-    const uint16_t *ell_col;       // [round_up(rdeg, 8)][m] by row slot
-    const uint32_t *ell_var;       // [cdeg][n] by column slot: (row slot << 8) | position in the row, ascending rows
+    SlotGraph G;
     int64_t B, shot_begin;
     const int8_t *synd;
     const double *prior;           // [n] finite (host-verified, or the documented precondition of the _dev entry)
@@ -47,13 +42,13 @@ template <bool VG>
 __global__ __launch_bounds__(1024) void relay_bp_kernel(RelayArgs A) {
     extern __shared__ unsigned char lds[];
     double *V;
-    if (VG) V = A.vglobal + (size_t)blockIdx.x * A.n; else V = reinterpret_cast<double *>(lds);
+    if (VG) V = A.vglobal + (size_t)blockIdx.x * A.G.n; else V = reinterpret_cast<double *>(lds);
     double2 *SP = reinterpret_cast<double2 *>(lds + A.offP);                       // (alpha*min1, alpha*min2) per check
     unsigned long long *SI = reinterpret_cast<unsigned long long *>(lds + A.offI); // bits 0-55 input signs, 56-62 argmin (127 = none), 63 total sign
     uint16_t *G = reinterpret_cast<uint16_t *>(lds + A.offG);                      // memory draws of the leg by ORIGINAL column
     int *F = reinterpret_cast<int *>(lds + A.offF);                                // [0], [1] unsat flags, [2] shot
     unsigned long long *Wacc = reinterpret_cast<unsigned long long *>(lds + A.offF + 16);   // weight of the leg's hard decision (two's complement)
-    const int m = A.m, n = A.n, tid = threadIdx.x, NT = blockDim.x;
+    const int n = A.G.n, tid = threadIdx.x, NT = blockDim.x;
     const double clip = A.clip, alpha = A.alpha;
     const int nblk = (n + 3) >> 2;
 
@@ -80,74 +75,15 @@ __global__ __launch_bounds__(1024) void relay_bp_kernel(RelayArgs A) {
             if (tid < 2) F[tid] = 0;
             if (tid == 0) *Wacc = 0ull;
             __syncthreads();
-            bool conv = false;
-            int itc = T;
-            for (int it = 0; it <= T; it++) {
-                // ---------------- check pass (minsum_wg_kernel's, constant alpha) ----------------
-                for (int i = tid; i < m; i += NT) {                                  // i = row slot
-                    const int deg = A.degr[i];
-                    const bool csyn = A.synd[b * m + A.row_of_slot[i]] & 1;
-                    double p1p = 0.0, p2p = 0.0;
-                    unsigned long long ip = 0ull;
-                    if (it > 0 && deg > 0) { const double2 t = SP[i]; p1p = t.x; p2p = t.y; ip = SI[i]; }
-                    const int argp = (int)((ip >> 56) & 127);
-                    const bool spp = (ip >> 63) & 1;
-                    bool par = csyn, sp = csyn;
-                    double min1 = INFINITY, min2 = INFINITY;
-                    int arg = 127;
-                    unsigned long long negbits = 0ull;
-                    for (int k = 0; k < deg; k++) {
-                        const int col = A.ell_col[(size_t)k * m + i];
-                        const double v = V[col];
-                        par ^= (v < 0.0);
-                        double x = v;                                                // the leg's first pass: Q = V[col], nothing subtracted
-                        if (it > 0) {
-                            const double mag = (k == argp) ? p2p : p1p;
-                            const double rr = (spp != (bool)((ip >> k) & 1)) ? -mag : mag;
-                            x = clip_nan(v - rr, clip);
-                        }
-                        const bool neg = !(x >= 0.0);
-                        sp ^= neg;
-                        negbits |= (unsigned long long)neg << k;
-                        const double a = fabs(x);
-                        if (a < min1) { min2 = min1; min1 = a; arg = k; }
-                        else if (a < min2) { min2 = a; }
-                    }
-                    if (it >= 1 && par) F[it & 1] = 1;
-                    if (it < T && deg > 0) {
-                        SP[i] = make_double2(alpha * min1, alpha * min2);
-                        SI[i] = negbits | ((unsigned long long)arg << 56) | ((unsigned long long)sp << 63);
-                    }
-                }
-                __syncthreads();
-                if (it >= 1 && F[it & 1] == 0) { conv = true; itc = it; break; }     // V holds values_{it-1}: it reproduces the syndrome
-                if (it == T) break;
-                if (tid == 0) F[(it + 1) & 1] = 0;
-                // ---------------- variable pass with memory ----------------
-                for (int c = tid; c < n; c += NT) {                                  // c = column slot
-                    const int j = A.col_of_slot[c];
-                    double s = 0.0;
-                    for (int d = 0; d < A.cdeg; d++) {
-                        const uint32_t e = A.ell_var[(size_t)d * n + c];
-                        if (e == 0xFFFFFFFFu) break;
-                        const int i = (int)(e >> 8), k = (int)(e & 255u);
-                        const double2 pp = SP[i];
-                        const unsigned long long inf = SI[i];
-                        const double mag = (k == (int)((inf >> 56) & 127)) ? pp.y : pp.x;
-                        s += ((bool)((inf >> 63) & 1) != (bool)((inf >> k) & 1)) ? -mag : mag;   // ascending check order
-                    }
-                    const double gam = (r == 0) ? A.gamma0 : A.gamma_min + A.gamma_range * ((double)G[j] * (1.0 / 65536.0));
-                    const double pj = A.prior[j], vj = V[j];
-                    const double mem = (fabs(vj) < INFINITY) ? vj : 0.0;             // a non-finite marginal carries no memory (see the header)
-                    const double bias = (1.0 - gam) * pj + gam * mem;
-                    V[j] = s + bias;
-                }
-                __syncthreads();
-            }
-            __syncthreads();                                                         // every thread has read the flags before the next leg resets them
-            iters += itc;
+            const LegResult L = bp_leg(A.G, A.synd, b, T, alpha, clip, V, SP, SI, F, [&](int j, double vj) {   // the variable pass with memory
+                const double gam = (r == 0) ? A.gamma0 : A.gamma_min + A.gamma_range * ((double)G[j] * (1.0 / 65536.0));
+                const double pj = A.prior[j];
+                const double mem = (fabs(vj) < INFINITY) ? vj : 0.0;                 // a non-finite marginal carries no memory (see the header)
+                return (1.0 - gam) * pj + gam * mem;
+            });
+            iters += L.itc;
             legs = r + 1;
-            if (conv) {
+            if (L.conv) {
                 long long part = 0;
                 for (int j = tid; j < n; j += NT)
                     if (V[j] < 0.0) part += relay_weight(A.prior[j]);
@@ -178,9 +114,7 @@ __global__ __launch_bounds__(1024) void relay_bp_kernel(RelayArgs A) {
 }
 
 static size_t relay_lds_bytes(const qldpc_graph *g, bool vg, int &offP, int &offI, int &offG, int &offF) {
-    offP = vg ? 0 : (int)round_up((int64_t)g->n * 8, 16);
-    offI = offP + g->m * 16;
-    offG = (int)round_up(offI + (int64_t)g->m * 8, 16);
+    offG = leg_lds_prefix(g, vg, offP, offI);
     offF = (int)round_up(offG + round_up(g->n, 4) * 2, 16);
     return (size_t)offF + 32;
 }
@@ -200,12 +134,6 @@ int relay_unsupported(const qldpc_graph *g) {
     return QLDPC_ERR_UNSUPPORTED;
 }
 
-static int cu_count(int device) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-    return cus;
-}
-
 // callers hold g->mu and have validated the parameters (relay_check_params); the workspaces are handed over in stream order (common.h)
 int relay_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, const RelayParams &P, uint64_t seed,
                         int64_t shot_begin, int tag, int iter_bias, int8_t *d_err, uint8_t *d_conv, int32_t *d_legs, int32_t *d_iters,
@@ -214,9 +142,7 @@ int relay_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, c
     if (mode == 0) return relay_unsupported(g);
     if (B == 0) return QLDPC_OK;
     RelayArgs A;
-    A.m = g->m; A.n = g->n; A.cdeg = g->max_col_deg;
-    A.row_of_slot = g->d_row_of_slot; A.col_of_slot = g->d_col_of_slot; A.degr = g->d_deg_of_rslot;
-    A.ell_col = g->d_ell_col_s; A.ell_var = g->d_ell_var_s;
+    A.G = slot_graph(g);
     A.B = B; A.shot_begin = shot_begin; A.synd = d_synd; A.prior = d_prior;
     A.alpha = P.alpha; A.clip = P.clip; A.gamma0 = P.gamma0; A.gamma_min = P.gamma_min; A.gamma_range = P.gamma_max - P.gamma_min;
     A.t0 = P.t0; A.tr = P.tr; A.max_legs = P.max_legs; A.stop_after = P.stop_after;
@@ -225,30 +151,7 @@ int relay_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, c
     A.out_err = d_err; A.out_conv = d_conv; A.out_legs = d_legs; A.out_iters = d_iters; A.out_sol = d_sol;
     const bool vg = mode == 2;
     const size_t lds = relay_lds_bytes(g, vg, A.offP, A.offI, A.offG, A.offF);
-    const int block = (g->m > 512 || g->n > 4096) ? 1024 : 512;
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>((160 * 1024) / (int64_t)lds, 2048 / block));
-    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)cu_count(g->device) * per_cu);
-    int rc = g->ws_acquire(stream);
-    if (rc != QLDPC_OK) return rc;
-    auto launch = [&]() -> int {
-        int rcl = g->ws_queue.ensure(16);
-        if (rcl != QLDPC_OK) return rcl;
-        QLDPC_HIP_TRY(hipMemsetAsync(g->ws_queue.p, 0, 16, stream));
-        A.queue = g->ws_queue.as<int>();
-        A.vglobal = nullptr;
-        if (vg) {
-            if ((rcl = g->ws_vals.ensure((size_t)grid * g->n * 8)) != QLDPC_OK) return rcl;
-            A.vglobal = g->ws_vals.as<double>();
-        }
-        void (*kern)(RelayArgs) = vg ? relay_bp_kernel<true> : relay_bp_kernel<false>;
-        if ((rcl = ensure_max_lds(g->device, reinterpret_cast<const void *>(kern), 160 * 1024)) != QLDPC_OK) return rcl;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, A);
-        QLDPC_HIP_TRY(hipGetLastError());
-        return QLDPC_OK;
-    };
-    rc = launch();
-    const int rel = g->ws_release(stream);          // always: a failing call may have enqueued launches the next stream has to wait for
-    return rc != QLDPC_OK ? rc : rel;
+    return shot_queue_launch(g, B, vg ? relay_bp_kernel<true> : relay_bp_kernel<false>, A, lds, vg, stream);
 }
 
 int relay_check_params(const RelayParams &P) {
@@ -324,25 +227,23 @@ QLDPC_EXPORT int qldpc_relay_decode_batch(const qldpc_graph *g, int64_t B, const
     QLDPC_USE_DEVICE(g->device);
     if (relay_mode(g) == 0) return relay_unsupported(g);
     // one grow-only slab per graph handle:  prior | syndromes | err | conv | legs | iters | solutions
-    const size_t o_prior = 0, o_synd = round_up((int64_t)n * 8, 16), o_err = o_synd + round_up((int64_t)B * m, 16),
-                 o_conv = o_err + round_up((int64_t)B * n, 16), o_legs = o_conv + round_up(B, 16), o_iters = o_legs + round_up(B * 4, 16),
-                 o_sol = o_iters + round_up(B * 4, 16), total = o_sol + round_up(B * 4, 16);
+    IoSlab S;
+    const size_t o_prior = S.add(n * 8), o_synd = S.add(B * m), o_err = S.add(B * n), o_conv = S.add(B), o_legs = S.add(B * 4), o_iters = S.add(B * 4),
+                 o_sol = S.add(B * 4);
     std::unique_lock<std::mutex> io(g->mu_io);
-    if ((rc = g->ws_io.ensure(total)) != QLDPC_OK) return rc;
-    unsigned char *base = g->ws_io.as<unsigned char>();
-    QLDPC_HIP_TRY(hipMemcpyAsync(base + o_synd, syndromes, B * m, hipMemcpyHostToDevice, nullptr));
-    QLDPC_HIP_TRY(hipMemcpyAsync(base + o_prior, prior, n * 8, hipMemcpyHostToDevice, nullptr));
+    if ((rc = S.ensure(g->ws_io)) != QLDPC_OK) return rc;
+    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_synd), syndromes, B * m, hipMemcpyHostToDevice, nullptr));
+    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_prior), prior, n * 8, hipMemcpyHostToDevice, nullptr));
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = relay_decode_launch(g, B, reinterpret_cast<int8_t *>(base + o_synd), reinterpret_cast<double *>(base + o_prior), P, seed, shot_begin, tag, 0,
-                                 reinterpret_cast<int8_t *>(base + o_err), reinterpret_cast<uint8_t *>(base + o_conv), reinterpret_cast<int32_t *>(base + o_legs),
-                                 reinterpret_cast<int32_t *>(base + o_iters), reinterpret_cast<int32_t *>(base + o_sol), nullptr);
+        rc = relay_decode_launch(g, B, S.at<int8_t>(o_synd), S.at<double>(o_prior), P, seed, shot_begin, tag, 0, S.at<int8_t>(o_err), S.at<uint8_t>(o_conv),
+                                 S.at<int32_t>(o_legs), S.at<int32_t>(o_iters), S.at<int32_t>(o_sol), nullptr);
     }
     if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, base + o_err, B * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, base + o_conv, B, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(legs, base + o_legs, B * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iters, base + o_iters, B * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(solutions, base + o_sol, B * 4, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(err, S.at(o_err), B * n, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(conv, S.at(o_conv), B, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(legs, S.at(o_legs), B * 4, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(iters, S.at(o_iters), B * 4, hipMemcpyDeviceToHost));
+    QLDPC_HIP_TRY(hipMemcpy(solutions, S.at(o_sol), B * 4, hipMemcpyDeviceToHost));
     return QLDPC_OK;
 }

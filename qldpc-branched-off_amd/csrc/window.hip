@@ -132,12 +132,10 @@ struct qldpc_window_decoder {
     std::vector<std::unique_ptr<Shared>> shared;
     std::vector<std::unique_ptr<Stage>> stages;
     int max_wm = 0, max_wn = 0;
-    // device workspaces for the shots of one call, handed from stream to stream through an event like a graph handle's (common.h)
+    // device workspaces for the shots of one call, handed from stream to stream like a graph handle's (common.h)
     std::mutex mu, mu_io;
     DevBuf run, wsyn, werr, wllr, wconv, witer, list, count, acc;
-    hipEvent_t ws_event = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
+    StreamHandover hand;
 };
 
 namespace qldpc {
@@ -241,13 +239,11 @@ int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, 
     return QLDPC_OK;
 }
 
-// Enqueues the window loop for B shots on `stream`.  Callers hold D->mu.  plan: the circuit plan's per-trial slots (see WindowCommitArgs); mark: brackets
-// the BP part (phase 0) and the OSD + commit part (phase 1) of every window for the plan's phase times.
-int window_decode_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, int32_t *d_conv, int32_t *d_iters, int32_t *d_osd,
-                         uint8_t *d_unsat, const WindowPlanSlots *plan, const std::function<int(int, bool)> *mark, hipStream_t s) {
+// The window loop of window_decode_launch, which owns the hand-over: an error return may leave earlier stages enqueued.
+static int window_stages_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, int32_t *d_conv, int32_t *d_iters, int32_t *d_osd,
+                                uint8_t *d_unsat, const WindowPlanSlots *plan, const std::function<int(int, bool)> *mark, hipStream_t s) {
     int rc;
     const size_t Bz = (size_t)B;
-    if (D->ws_used && s != D->ws_stream && D->ws_event) QLDPC_HIP_TRY(hipStreamWaitEvent(s, D->ws_event, 0));
     if ((rc = D->run.ensure(Bz * D->m)) || (rc = D->wsyn.ensure(Bz * D->max_wm)) || (rc = D->werr.ensure(Bz * D->max_wn)) ||
         (rc = D->wllr.ensure(Bz * D->max_wn * 8)) || (rc = D->wconv.ensure(Bz)) || (rc = D->witer.ensure(Bz * 4)) || (rc = D->list.ensure(Bz * 4)) ||
         (rc = D->acc.ensure(Bz * 16)))
@@ -294,10 +290,18 @@ int window_decode_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_syn
         QLDPC_HIP_TRY(hipGetLastError());
         if (mark && (rc = (*mark)(1, false)) != QLDPC_OK) return rc;
     }
-    if (!D->ws_event) QLDPC_HIP_TRY(hipEventCreateWithFlags(&D->ws_event, hipEventDisableTiming));
-    QLDPC_HIP_TRY(hipEventRecord(D->ws_event, s));
-    D->ws_stream = s; D->ws_used = true;
     return QLDPC_OK;
+}
+
+// Enqueues the window loop for B shots on `stream`.  Callers hold D->mu.  plan: the circuit plan's per-trial slots (see WindowCommitArgs); mark: brackets
+// the BP part (phase 0) and the OSD + commit part (phase 1) of every window for the plan's phase times.
+int window_decode_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, int32_t *d_conv, int32_t *d_iters, int32_t *d_osd,
+                         uint8_t *d_unsat, const WindowPlanSlots *plan, const std::function<int(int, bool)> *mark, hipStream_t s) {
+    int rc = D->hand.acquire(s);
+    if (rc != QLDPC_OK) return rc;
+    rc = window_stages_launch(D, B, d_synd, d_err, d_conv, d_iters, d_osd, d_unsat, plan, mark, s);
+    const int rel = D->hand.release(s);             // always: a failing call may have enqueued stages the next stream has to wait for
+    return rc != QLDPC_OK ? rc : rel;
 }
 
 int window_decoder_lock_and_launch(qldpc_window_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, const WindowPlanSlots *plan,
@@ -323,8 +327,8 @@ QLDPC_EXPORT int qldpc_window_decoder_create(const qldpc_graph *g, int layer_row
 QLDPC_EXPORT void qldpc_window_decoder_destroy(qldpc_window_decoder *D) {
     if (!D) return;
     (void)hipSetDevice(D->device);
-    if (D->ws_used) (void)hipDeviceSynchronize();
-    if (D->ws_event) (void)hipEventDestroy(D->ws_event);
+    if (D->hand.used) (void)hipDeviceSynchronize();
+    D->hand.destroy();
     for (auto &S : D->stages) { S->d_colmap.release(); S->d_ccol.release(); S->d_cptr.release(); S->d_crow.release(); }
     for (auto &R : D->shared) { R->d_prior.release(); qldpc_graph_destroy(R->g); }
     for (DevBuf *b : {&D->run, &D->wsyn, &D->werr, &D->wllr, &D->wconv, &D->witer, &D->list, &D->count, &D->acc}) b->release();
