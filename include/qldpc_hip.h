@@ -39,6 +39,8 @@
  *        additive, same version: single-precision (f32) min-sum, qldpc_minsum32_decoder_*, qldpc_minsum32_decode_batch[_dev],
  *        qldpc_circuit_plan_use_f32, QLDPC_FLAG_F32_* and QLDPC_F32_FORM_*
  *        additive, same version: qldpc_osd0_last_path (which OSD-0 kernel the last call on a handle took), QLDPC_OSD_PATH_* and QLDPC_OSD_DETAIL_*
+ *        additive, same version (the suites pin 101): circuit plans that sample a detector error model, qldpc_dem_desc and
+ *        qldpc_circuit_plan_create_dem
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -631,6 +633,43 @@ int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *plan, double alpha, in
  * whose BP stage runs the layered schedule or guided decimation (and qldpc_circuit_plan_use_relay / _use_window / _use_layered / _use_decimation
  * after this call return QLDPC_ERR_INVALID); otherwise what qldpc_minsum32_decoder_create returns. */
 int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *plan);
+
+/* ---- a circuit plan that samples a detector error model (DEM).  New here: the reference has no counterpart. -------------------------------
+ * A DEM is a list of independent error mechanisms, each with a probability, the detectors it flips and the logical observables it flips.  It has one
+ * or two SECTORS: decoding problems with their own detectors, graph, prior and logicals, decoded independently (as Z and X of a circuit plan; sector 0
+ * takes every "Z" slot of the tally, the phases and the outcome bits, sector 1 every "X" slot).  One mechanism may touch both sectors -- that is how a
+ * Y-type fault correlates them -- so there is one mechanism table, projected per sector.  All pointers are host pointers, copied at plan creation.
+ *
+ * The law of the sampler, a pure function of (seed, global trial index): for trial g = trial_begin + t, mechanism l has Philox block q = l >> 2 and word
+ * w = l & 3 of o = Philox4x32-10(counter = (lo32(g), hi32(g), q, 3), key = (lo32(seed), hi32(seed))), and fires iff o[w] < thr_l = floor(p_l * 2^32)
+ * (uint32; p_l = 0 never fires).  Counter word 3 is the domain: 0 = the code-capacity samplers, 1 and 2 = the circuit sampler, 3 = this one,
+ * 0x52...... = Relay-BP.  A firing mechanism XORs its detectors into the sectors' syndromes and its logmask into the sectors' true logical flips. */
+typedef struct {
+    int64_t n_mech;
+    const double *prob;            /* [n_mech], 0 <= p < 1 */
+    int32_t n_sectors;             /* 1 or 2 */
+    int32_t k[2];                  /* logical observables per sector, 0..64 */
+    int32_t n_det[2];              /* detectors per sector = rows of that sector's graph, 1..65535 */
+    int32_t layer_rows[2];         /* rows per layer for sliding windows; 0 = the plan refuses qldpc_circuit_plan_use_window */
+    const int32_t *det_ptr[2];     /* [n_mech + 1] per sector */
+    const uint16_t *det_idx[2];    /* detector indices, strictly ascending inside a mechanism */
+    const uint64_t *logmask[2];    /* [n_mech] per sector, bit r = observable r */
+} qldpc_dem_desc;
+/* Creates an ordinary qldpc_circuit_plan whose sampler draws from `dem`: _run, _run_outcomes, _read, _sample, _phase_times, _clock, _destroy and every
+ * qldpc_circuit_plan_use_* work on it unchanged and under the same rules.  The graphs, priors and column logical masks (logmask0 / logmask1: uint64 per
+ * column of g0 / g1) are the DECODER's view and are given explicitly, as in qldpc_circuit_plan_create; the mechanisms are the truth that is sampled,
+ * and the two need not have the same columns.  g1, prior1, logmask1 are NULL iff n_sectors == 1 (the index-1 entries of the descriptor's arrays are
+ * then ignored).  qldpc_circuit_plan_use_window takes layer_rows[s] as the rows of a syndrome cycle and returns QLDPC_ERR_INVALID when it is 0 or does
+ * not divide the rows.  qldpc_circuit_plan_sample writes true_z as int8[count][k[0]] and true_x as int8[count][k[1]].
+ *   One sector: sector 1 has no buffers, no decode, no OSD and no phase brackets, and the judge runs sector 0 alone: every X tally slot stays 0,
+ *   outcome bit 1 is 0, total_err = z_err, and qldpc_circuit_plan_sample leaves sparse_x / true_x untouched (they may be NULL).
+ * QLDPC_ERR_INVALID, with qldpc_last_error naming the sector or the mechanism: NULL tables, a non-monotone det_ptr, a detector index out of range or
+ * not ascending, p outside [0, 1) or NaN, a logmask bit at or above k[s], g_s->m != n_det[s], n_sectors outside {1, 2}. */
+int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *dem, const qldpc_graph *g0, const qldpc_graph *g1, /* g1 NULL iff n_sectors == 1 */
+                                  const double *prior0, const double *prior1, const uint64_t *logmask0, const uint64_t *logmask1, int max_iter,
+                                  int alpha_mode, double alpha_val0, double alpha_val1, const double *alpha_seq0, int alpha_len0,
+                                  const double *alpha_seq1, int alpha_len1, double damping, double clip_llr, int use_osd, int flags, int64_t batch,
+                                  qldpc_circuit_plan **out);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

@@ -64,6 +64,13 @@ class CircuitDesc(C.Structure):
                 ("data_qubit_indices", C.POINTER(C.c_int32)), ("Lx", C.POINTER(C.c_uint8)), ("Lz", C.POINTER(C.c_uint8))]
 
 
+class DemDesc(C.Structure):
+    """qldpc_dem_desc (include/qldpc_hip.h)."""
+    _fields_ = [("n_mech", C.c_int64), ("prob", C.POINTER(C.c_double)), ("n_sectors", C.c_int32), ("k", C.c_int32 * 2), ("n_det", C.c_int32 * 2),
+                ("layer_rows", C.c_int32 * 2), ("det_ptr", C.POINTER(C.c_int32) * 2), ("det_idx", C.POINTER(C.c_uint16) * 2),
+                ("logmask", C.POINTER(C.c_uint64) * 2)]
+
+
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "double": C.c_double,
             "int8_t": C.c_int8, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16}
 
@@ -83,6 +90,8 @@ def _ctype_of(decl):
         return C.c_char_p              # NUL-terminated name
     if base == "qldpc_circuit_desc":
         t = CircuitDesc
+    elif base == "qldpc_dem_desc":
+        t = DemDesc
     elif base in ("void", "char") or base.startswith("qldpc_"):
         t = None                       # opaque: void*
     else:
@@ -991,7 +1000,8 @@ class CircuitPlan:
     def use_layered(self, layers_z=None, layers_x=None):
         """Run the BP stage of both sectors with the layered schedule from now on (qldpc_circuit_plan_use_layered); layers_*: a row_layer per
         sector, None = the greedy colouring.  Goes with OSD-0 and OSD-CS; not with Relay-BP or windows."""
-        lz, lx = check_row_layer(layers_z, self.graph_z.m), check_row_layer(layers_x, self.graph_x.m)
+        lz = check_row_layer(layers_z, self.graph_z.m)
+        lx = check_row_layer(layers_x, self.graph_x.m) if self.graph_x is not None else None      # (a one-sector DemPlan has no sector X)
         check(lib().qldpc_circuit_plan_use_layered(self._h, ptr(lz, C.c_int32) if lz is not None else None, ptr(lx, C.c_int32) if lx is not None else None))
         self.layered = True
 
@@ -1042,7 +1052,8 @@ class CircuitPlan:
     def sample(self, seed, trial_begin, count):
         """Batched run_trial_fast -> (sparse_z int8[count, nsx], true_z int8[count, k], sparse_x, true_x)."""
         spz, spx = np.zeros((count, self.nsx), np.int8), np.zeros((count, self.nsz), np.int8)
-        tz, tx = np.zeros((count, self.k), np.int8), np.zeros((count, self.k), np.int8)
+        kz, kx = getattr(self, "ks", (self.k, self.k))                         # (a DemPlan has a k per sector)
+        tz, tx = np.zeros((count, kz), np.int8), np.zeros((count, kx), np.int8)
         check(lib().qldpc_circuit_plan_sample(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), ptr(spz, C.c_int8),
                                               ptr(tz, C.c_int8), ptr(spx, C.c_int8), ptr(tx, C.c_int8)))
         return spz, tz, spx, tx
@@ -1057,3 +1068,45 @@ class CircuitPlan:
             self.close()
         except Exception:
             pass
+
+
+def make_dem_desc(prob, sectors):
+    """(prob, [(n_det, k, layer_rows, det_ptr, det_idx, logmask) per sector]) -> (DemDesc, keep-alive dict)."""
+    keep = {"prob": f64(prob)}
+    d = DemDesc()
+    d.n_mech, d.prob, d.n_sectors = keep["prob"].size, ptr(keep["prob"], C.c_double), len(sectors)
+    for s, (n_det, k, layer_rows, det_ptr, det_idx, logmask) in enumerate(sectors[:2]):
+        keep[s] = (i32(det_ptr), np.ascontiguousarray(det_idx, np.uint16), np.ascontiguousarray(logmask, np.uint64))
+        d.n_det[s], d.k[s], d.layer_rows[s] = int(n_det), int(k), int(layer_rows or 0)
+        d.det_ptr[s], d.det_idx[s], d.logmask[s] = ptr(keep[s][0], C.c_int32), ptr(keep[s][1], C.c_uint16), ptr(keep[s][2], C.c_uint64)
+    return d, keep
+
+
+class DemPlan(CircuitPlan):
+    """A circuit plan whose sampler draws from a detector error model (qldpc_circuit_plan_create_dem): independent mechanisms with a probability each,
+    one or two sectors.  `sectors`: per sector (n_det, k, layer_rows, det_ptr, det_idx, logmask) -- the mechanisms projected onto it; graphs, priors,
+    logmasks: the decoder's view per sector (same length).  Every use_*, run, run_outcomes, read, sample and close is CircuitPlan's; with one sector
+    sample() returns zeros for sector 1 (no detectors) and every X slot of the tally stays 0."""
+
+    def __init__(self, prob, sectors, graphs, priors, logmasks, max_iter=50, alphas=(1.0, 1.0), alpha_mode="dynamical", damping=1.0, clip_llr=20.0,
+                 use_osd=True, flags=0, batch=16384):
+        nsec = len(sectors)
+        if not (len(graphs) == len(priors) == len(logmasks) == nsec):
+            raise ValueError(f"the detector error model has {nsec} sector(s): give as many graphs, priors and logmasks")
+        d, keep = make_dem_desc(prob, sectors)
+        self._h = C.c_void_p()
+        g = list(graphs) + [None] * (2 - nsec)
+        al = [alpha_args(alpha_mode, alphas[s]) for s in range(2)]               # (mode, value, sequence) per sector
+        mode, al = al[0][0], [x[1:] for x in al]
+        pri = [f64(x) for x in priors] + [None] * (2 - nsec)
+        lms = [np.ascontiguousarray(x, np.uint64) for x in logmasks] + [None] * (2 - nsec)
+        nd, ks = [int(x[0]) for x in sectors] + [0, 0], [int(x[1]) for x in sectors] + [0, 0]
+        self.n_sectors, self.k, self.ks, self.nsx, self.nsz = nsec, max(ks), (ks[0], ks[1]), nd[0], nd[1]
+        self.graph_z, self.graph_x = g[0], g[1]
+        self.flags = flags
+        opt = lambda a, t: ptr(a, t) if a is not None else None
+        check(lib().qldpc_circuit_plan_create_dem(C.byref(d), g[0].handle if g[0] is not None else None, g[1].handle if g[1] is not None else None,
+                                                  opt(pri[0], C.c_double), opt(pri[1], C.c_double), opt(lms[0], C.c_uint64), opt(lms[1], C.c_uint64),
+                                                  C.c_int(max_iter), C.c_int(mode), C.c_double(al[0][0]), C.c_double(al[1][0]), ptr(al[0][1], C.c_double),
+                                                  C.c_int(al[0][1].size), ptr(al[1][1], C.c_double), C.c_int(al[1][1].size), C.c_double(damping),
+                                                  C.c_double(clip_llr), C.c_int(int(use_osd)), C.c_int(flags), C.c_int64(batch), C.byref(self._h)))

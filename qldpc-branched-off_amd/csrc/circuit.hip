@@ -185,7 +185,8 @@ __device__ __forceinline__ void judge_sector_sparse(const JudgeSector &S, int64_
     bad = bd != 0;
 }
 
-template <bool SPARSE>
+// TWO = false: a one-sector plan (a detector error model with n_sectors = 1): X is not read, its slots and outcome bit 1 stay 0
+template <bool SPARSE, bool TWO>
 __global__ __launch_bounds__(256) void circuit_judge_kernel(int64_t B, JudgeSector Z, JudgeSector X, unsigned long long *__restrict__ tally,
                                                             uint8_t *__restrict__ outcome, const int32_t *__restrict__ fail_counts) {
     __shared__ unsigned long long acc[QLDPC_TALLY_SLOTS];
@@ -194,20 +195,20 @@ __global__ __launch_bounds__(256) void circuit_judge_kernel(int64_t B, JudgeSect
     __syncthreads();
     if (fail_counts && blockIdx.x == 0 && threadIdx.x == 0) {                 // OSD-0 calls of this batch = its BP failures per sector
         acc[QLDPC_TALLY_OSD_Z] = (unsigned long long)fail_counts[0];
-        acc[QLDPC_TALLY_OSD_X] = (unsigned long long)fail_counts[4];
+        if (TWO) acc[QLDPC_TALLY_OSD_X] = (unsigned long long)fail_counts[4];
     }
     __syncthreads();
     const int lane = threadIdx.x & 31;
     const int64_t b = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
     if (b < B) {
-        bool ze, zn, zb, xe, xn, xb;
+        bool ze, zn, zb, xe = false, xn = false, xb = false;
         if (SPARSE) {
             uint32_t *par = parbits + (threadIdx.x >> 5) * 256;
             judge_sector_sparse(Z, b, lane, par, ze, zn, zb);
-            judge_sector_sparse(X, b, lane, par + 128, xe, xn, xb);
+            if (TWO) judge_sector_sparse(X, b, lane, par + 128, xe, xn, xb);
         } else {
             judge_sector(Z, b, lane, ze, zn, zb);
-            judge_sector(X, b, lane, xe, xn, xb);
+            if (TWO) judge_sector(X, b, lane, xe, xn, xb);
         }
         if (lane == 0) {
             if (outcome) outcome[b] = (uint8_t)((ze ? 1 : 0) | (xe ? 2 : 0));               // (z_err, x_err) of engine.py:117-122
@@ -216,11 +217,11 @@ __global__ __launch_bounds__(256) void circuit_judge_kernel(int64_t B, JudgeSect
             if (xe) atomicAdd(&acc[QLDPC_TALLY_X_ERR], 1ull);
             if (ze || xe) atomicAdd(&acc[QLDPC_TALLY_TOTAL_ERR], 1ull);                       // engine.py:122
             if (Z.conv[b]) atomicAdd(&acc[QLDPC_TALLY_BP_CONV_Z], 1ull);
-            if (X.conv[b]) atomicAdd(&acc[QLDPC_TALLY_BP_CONV_X], 1ull);
+            if (TWO && X.conv[b]) atomicAdd(&acc[QLDPC_TALLY_BP_CONV_X], 1ull);
             atomicAdd(&acc[QLDPC_TALLY_ITERS_Z], (unsigned long long)(Z.iters[b] + 1));
-            atomicAdd(&acc[QLDPC_TALLY_ITERS_X], (unsigned long long)(X.iters[b] + 1));
+            if (TWO) atomicAdd(&acc[QLDPC_TALLY_ITERS_X], (unsigned long long)(X.iters[b] + 1));
             if (!zn) atomicAdd(&acc[QLDPC_TALLY_ZERO_SYND_Z], 1ull);
-            if (!xn) atomicAdd(&acc[QLDPC_TALLY_ZERO_SYND_X], 1ull);
+            if (TWO && !xn) atomicAdd(&acc[QLDPC_TALLY_ZERO_SYND_X], 1ull);
             if (zb) atomicAdd(&acc[QLDPC_TALLY_UNSAT_Z], 1ull);
             if (xb) atomicAdd(&acc[QLDPC_TALLY_UNSAT_X], 1ull);
         }
@@ -266,6 +267,11 @@ struct qldpc_circuit_plan {
         PlanBuf d_flips;                           // Decoder::BP_OSD_CS: workspace of the sweep
     } sec[2];
     int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
+    int nsec = 2, ks[2] = {0, 0};                  // sectors in use (1: a one-sector detector error model, sec[1] stays empty); logicals per sector
+    // dem: the sampler draws from a detector error model (dem.hip).  n_locs then counts its mechanisms, d_ptr / d_idx / d_log of a sector hold their
+    // projection onto it, and d_thr their thresholds (uint32, zero-padded to a multiple of four).
+    bool dem = false;
+    PlanBuf d_thr;
     double p = 0, damping = 1, clip = 20;
     uint32_t thr = 0;
     int64_t batch = 0;
@@ -453,6 +459,37 @@ QLDPC_EXPORT int qldpc_circuit_fault_signatures(const qldpc_circuit_desc *D, int
     return QLDPC_OK;
 }
 
+// One sector of a new plan: the decoder's view (graph, prior, alpha table, column logical masks), the sampler's tables (ptr / idx / log: fault
+// signatures of a circuit, or the projection of a detector error model's mechanisms) and the per-trial buffers.
+static int plan_sector(qldpc_circuit_plan *P, int i, const qldpc_graph *g, int nsyn, int layer_rows, const double *prior, const uint64_t *logmask,
+                       int alpha_mode, double alpha_val, const double *alpha_seq, int alpha_len, const std::vector<int32_t> &sp,
+                       const std::vector<uint16_t> &si, const std::vector<uint64_t> &sl) {
+    Sector &S = P->sec[i];
+    const size_t n = (size_t)g->n, Bz = (size_t)P->batch;
+    int rc;
+    S.g = g; S.nsyn = nsyn; S.layer_rows = layer_rows;
+    if ((rc = build_alpha_table(P->max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, S.h_alpha)) != QLDPC_OK) return rc;
+    S.h_prior.assign(prior, prior + n);
+    // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
+    // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
+    P->nanfree = P->nanfree && inputs_clean(prior, (int)n, P->clip, S.h_alpha.data(), P->max_iter);
+    const std::vector<uint64_t> lm(logmask, logmask + n);
+    if ((rc = up(S.d_ptr, sp)) || (rc = up(S.d_idx, si)) || (rc = up(S.d_log, sl)) || (rc = up(S.d_alpha, S.h_alpha)) || (rc = up(S.d_prior, S.h_prior)) ||
+        (rc = up(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
+        (rc = S.d_llr.ensure(Bz * n * 8)) || (rc = S.d_conv.ensure(Bz)) || (rc = S.d_iter.ensure(Bz * 4)) || (rc = S.d_list.ensure(Bz * 4)))
+        return rc;
+    return QLDPC_OK;
+}
+
+// what a new plan holds once, whatever it samples
+static int plan_common(qldpc_circuit_plan *P) {
+    int rc;
+    if ((rc = P->d_count.ensure(64)) || (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) || (rc = P->d_clk.ensure(2 * kClkSlots * 16))) return rc;
+    if (zero_now(P->d_clk.p, 2 * kClkSlots * 16) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
+    if (zero_now(P->d_tally.p, QLDPC_TALLY_SLOTS * 8) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
+    return QLDPC_OK;
+}
+
 QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const qldpc_graph *gz, const qldpc_graph *gx, const double *prior_z,
                                            const double *prior_x, const uint64_t *logmask_z, const uint64_t *logmask_x, double p, int max_iter,
                                            int alpha_mode, double alpha_val_z, double alpha_val_x, const double *alpha_seq_z, int alpha_len_z,
@@ -475,7 +512,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
 
     qldpc_circuit_plan *P = new qldpc_circuit_plan();
     auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
-    P->device = gz->device; P->k = D->k; P->n_locs = (int)loc_type.size();
+    P->device = gz->device; P->k = P->ks[0] = P->ks[1] = D->k; P->n_locs = (int)loc_type.size();
     P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->p = p; P->damping = damping; P->clip = clip_llr; P->batch = batch;
     P->thr = bernoulli_threshold(p);
     const qldpc_graph *const graph[2] = {gz, gx};
@@ -483,38 +520,80 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
     const double alpha_val[2] = {alpha_val_z, alpha_val_x};
     const uint64_t *const logmask[2] = {logmask_z, logmask_x};
     const int alpha_len[2] = {alpha_len_z, alpha_len_x};
-    const size_t Bz = (size_t)batch;
     P->nanfree = true;
     for (int i = 0; i < 2; i++) {
-        Sector &S = P->sec[i];
-        const size_t n = (size_t)graph[i]->n;
-        S.g = graph[i]; S.nsyn = sd[i].nsyn; S.layer_rows = sd[i].nchk;
-        if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], S.h_alpha)) != QLDPC_OK) return fail(rc);
-        S.h_prior.assign(prior[i], prior[i] + n);
-        // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
-        // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
-        P->nanfree = P->nanfree && inputs_clean(prior[i], (int)n, clip_llr, S.h_alpha.data(), max_iter);
         std::vector<int32_t> sp;
         std::vector<uint16_t> si;
         std::vector<uint64_t> sl;
         if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK) return fail(rc);
-        const std::vector<uint64_t> lm(logmask[i], logmask[i] + n);
-        if ((rc = up(S.d_ptr, sp)) || (rc = up(S.d_idx, si)) || (rc = up(S.d_log, sl)) || (rc = up(S.d_alpha, S.h_alpha)) || (rc = up(S.d_prior, S.h_prior)) ||
-            (rc = up(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
-            (rc = S.d_llr.ensure(Bz * n * 8)) || (rc = S.d_conv.ensure(Bz)) || (rc = S.d_iter.ensure(Bz * 4)) || (rc = S.d_list.ensure(Bz * 4)))
+        if ((rc = plan_sector(P, i, graph[i], sd[i].nsyn, sd[i].nchk, prior[i], logmask[i], alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], sp, si, sl)) != QLDPC_OK)
             return fail(rc);
     }
-    if ((rc = up(P->d_loc_type, loc_type)) || (rc = P->d_count.ensure(64)) || (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) ||
-        (rc = P->d_clk.ensure(2 * kClkSlots * 16)))
-        return fail(rc);
-    if (zero_now(P->d_clk.p, 2 * kClkSlots * 16) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
-    if (zero_now(P->d_tally.p, QLDPC_TALLY_SLOTS * 8) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
+    if ((rc = up(P->d_loc_type, loc_type)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
+    *out = P;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const qldpc_graph *g0, const qldpc_graph *g1, const double *prior0,
+                                               const double *prior1, const uint64_t *logmask0, const uint64_t *logmask1, int max_iter, int alpha_mode,
+                                               double alpha_val0, double alpha_val1, const double *alpha_seq0, int alpha_len0, const double *alpha_seq1,
+                                               int alpha_len1, double damping, double clip_llr, int use_osd, int flags, int64_t batch,
+                                               qldpc_circuit_plan **out) {
+    QLDPC_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    int rc = dem_validate(D);
+    if (rc != QLDPC_OK) return rc;
+    const int nsec = D->n_sectors;
+    QLDPC_REQUIRE(g0 && prior0 && logmask0, "sector 0: NULL graph, prior or logmask");
+    if (nsec == 2) QLDPC_REQUIRE(g1 && prior1 && logmask1, "sector 1: NULL graph, prior or logmask");
+    else QLDPC_REQUIRE(!g1 && !prior1 && !logmask1, "a detector error model with one sector takes no graph, prior or logmask of sector 1");
+    QLDPC_REQUIRE(batch > 0 && batch <= (1 << 24), "batch out of range");
+    QLDPC_REQUIRE(nsec == 1 || g0->device == g1->device, "both sector graphs must live on the same device");
+    const qldpc_graph *const graph[2] = {g0, g1};
+    const double *const prior[2] = {prior0, prior1}, *const alpha_seq[2] = {alpha_seq0, alpha_seq1};
+    const double alpha_val[2] = {alpha_val0, alpha_val1};
+    const uint64_t *const logmask[2] = {logmask0, logmask1};
+    const int alpha_len[2] = {alpha_len0, alpha_len1};
+    for (int i = 0; i < nsec; i++) {
+        QLDPC_REQUIRE(graph[i]->m == D->n_det[i], "sector %d: the decoding matrix has %d rows but the detector error model has %d detectors", i, graph[i]->m,
+                      D->n_det[i]);
+        const uint64_t allowed = D->k[i] == 64 ? ~(uint64_t)0 : (((uint64_t)1 << D->k[i]) - 1);
+        for (int j = 0; j < graph[i]->n; j++)
+            QLDPC_REQUIRE((logmask[i][j] & ~allowed) == 0, "sector %d: the logical mask of column %d has a bit at or above k = %d", i, j, D->k[i]);
+    }
+    QLDPC_USE_DEVICE(g0->device);
+
+    qldpc_circuit_plan *P = new qldpc_circuit_plan();
+    auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
+    P->device = g0->device; P->dem = true; P->nsec = nsec; P->n_locs = (int)D->n_mech;
+    P->k = std::max(D->k[0], nsec == 2 ? D->k[1] : 0);
+    P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->damping = damping; P->clip = clip_llr; P->batch = batch;
+    P->nanfree = true;
+    const size_t nm = (size_t)D->n_mech;
+    for (int i = 0; i < nsec; i++) {
+        P->ks[i] = D->k[i];
+        const std::vector<int32_t> sp(D->det_ptr[i], D->det_ptr[i] + nm + 1);
+        const std::vector<uint16_t> si(D->det_idx[i], D->det_idx[i] + sp[nm]);
+        const std::vector<uint64_t> sl(D->logmask[i], D->logmask[i] + nm);
+        if ((rc = plan_sector(P, i, graph[i], D->n_det[i], D->layer_rows[i], prior[i], logmask[i], alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], sp, si,
+                              sl)) != QLDPC_OK)
+            return fail(rc);
+    }
+    std::vector<uint32_t> thr((nm + 3) / 4 * 4, 0u);                      // zero padding: a padded entry never fires
+    for (size_t l = 0; l < nm; l++) thr[l] = bernoulli_threshold(D->prob[l]);
+    if ((rc = up(P->d_thr, thr)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
     *out = P;
     return QLDPC_OK;
 }
 
 static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, int64_t B, hipStream_t s, bool zero_counts = false) {
     const Sector &Z = P->sec[0], &X = P->sec[1];
+    if (P->dem) {
+        const auto tab = [](const Sector &S) { return DemTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
+        return dem_sample_launch(B, begin, seed, P->n_locs, P->d_thr.as<uint32_t>(), tab(Z), tab(X), Z.nsyn, X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(),
+                                 X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
+                                 zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
+    }
     const auto sig = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
     const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
     const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
@@ -593,22 +672,25 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
     QLDPC_USE_DEVICE(P->device);
     int rc = QLDPC_OK; (void)rc;
     if (outcome && (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK) return rc;
-    const JudgeSector Z = judge_view(P->sec[0]), X = judge_view(P->sec[1]);
-    const auto judge = (Z.m <= 4096 && X.m <= 4096 && Z.colptr && X.colptr) ? circuit_judge_kernel<true> : circuit_judge_kernel<false>;
+    const bool two = P->nsec == 2;
+    const JudgeSector Z = judge_view(P->sec[0]), X = two ? judge_view(P->sec[1]) : JudgeSector{};
+    const bool sparse = Z.m <= 4096 && Z.colptr && (!two || (X.m <= 4096 && X.colptr));
+    const auto judge = two ? (sparse ? circuit_judge_kernel<true, true> : circuit_judge_kernel<false, true>)
+                           : (sparse ? circuit_judge_kernel<true, false> : circuit_judge_kernel<false, false>);
     for (int64_t off = 0; off < count; off += P->batch) {
         const int64_t B = std::min<int64_t>(P->batch, count - off);
         if (P->pending.size() > 256) drain_phases(P, false);         // a caller that never reads phase times: recycle finished brackets (bounded event count)
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, s, true)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
-        for (int sector = 0; sector < 2; sector++)
+        for (int sector = 0; sector < P->nsec; sector++)
             if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, true)) != QLDPC_OK) return rc;
         hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
                            outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
         if ((P->decoder == Decoder::RELAY || P->decim) &&
-            (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), P->sec[1].d_legs.as<int32_t>(), P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
+            (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), two ? P->sec[1].d_legs.as<int32_t>() : nullptr, P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
             return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
         P->batches++;
@@ -650,7 +732,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed,
                                            int8_t *true_z, int8_t *sparse_x, int8_t *true_x) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
-    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x), "NULL output");
+    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && (P->nsec == 1 || (sparse_x && true_x))), "NULL output");
     QLDPC_USE_DEVICE(P->device);
     int rc = QLDPC_OK; (void)rc;
     int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
@@ -660,12 +742,12 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed,
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
         QLDPC_HIP_TRY(hipDeviceSynchronize());
         t.resize(B);
-        for (int i = 0; i < 2; i++) {
+        for (int i = 0; i < P->nsec; i++) {
             const Sector &S = P->sec[i];
             QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
             QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
             for (int64_t b = 0; b < B; b++)
-                for (int r = 0; r < P->k; r++) truth[i][(off + b) * P->k + r] = (int8_t)((t[b] >> r) & 1);
+                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
         }
     }
     return QLDPC_OK;
@@ -723,7 +805,7 @@ static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
 }
 
 static int priors_finite(const qldpc_circuit_plan *P) {
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; i < P->nsec; i++)
         for (double v : P->sec[i].h_prior) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-%c prior is not finite", "ZX"[i]);
     return QLDPC_OK;
 }
@@ -734,11 +816,11 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alph
     if (rc != QLDPC_OK) return rc;
     const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
     if ((rc = relay_check_params(rp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (const Sector &S : P->sec)
-        if (relay_mode(S.g) == 0) return relay_unsupported(S.g);
+    for (int i = 0; i < P->nsec; i++)
+        if (const Sector &S = P->sec[i]; relay_mode(S.g) == 0) return relay_unsupported(S.g);
     QLDPC_USE_DEVICE(P->device);
-    for (Sector &S : P->sec)
-        if ((rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++)
+        if (Sector &S = P->sec[i]; (rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
     P->rp = rp;
     P->decoder = Decoder::RELAY;
     return QLDPC_OK;
@@ -748,11 +830,11 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order)
     int rc = switch_allowed(P, Decoder::BP_OSD_CS);
     if (rc != QLDPC_OK) return rc;
     if ((rc = osdcs_check_order(order)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (const Sector &S : P->sec)
-        if ((rc = osdcs_supported(S.g)) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++)
+        if (const Sector &S = P->sec[i]; (rc = osdcs_supported(S.g)) != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(P->device);
-    for (Sector &S : P->sec)
-        if ((rc = S.d_flips.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++)
+        if (Sector &S = P->sec[i]; (rc = S.d_flips.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
     P->cs_order = order;
     P->decoder = Decoder::BP_OSD_CS;
     return QLDPC_OK;
@@ -762,15 +844,19 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window
     int rc = switch_allowed(P, Decoder::WINDOW);
     if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(P->damping == 1.0, "sliding-window decoding needs damping = 1 (the plan has %g)", P->damping);
+    for (int i = 0; P->dem && i < P->nsec; i++)
+        QLDPC_REQUIRE(P->sec[i].layer_rows > 0 && P->sec[i].nsyn % P->sec[i].layer_rows == 0,
+                      "sector %d of the detector error model has layer_rows = %d, which %s: sliding-window decoding needs the rows of a syndrome cycle", i,
+                      P->sec[i].layer_rows, P->sec[i].layer_rows > 0 ? "does not divide its detectors" : "means no layers were given");
     QLDPC_USE_DEVICE(P->device);
     qldpc_window_decoder *w[2] = {nullptr, nullptr};
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < P->nsec; i++) {
         const Sector &S = P->sec[i];
         rc = window_decoder_create_tab(S.g, S.layer_rows, window, commit, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK,
                                        &w[i]);
         if (rc != QLDPC_OK) { qldpc_window_decoder_destroy(w[0]); return rc; }
     }
-    for (int i = 0; i < 2; i++) P->sec[i].win = w[i];
+    for (int i = 0; i < P->nsec; i++) P->sec[i].win = w[i];
     P->decoder = Decoder::WINDOW;
     return QLDPC_OK;
 }
@@ -786,12 +872,12 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int
     QLDPC_USE_DEVICE(P->device);
     const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
     qldpc_layered_decoder *d[2] = {nullptr, nullptr};
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < P->nsec; i++) {
         const Sector &S = P->sec[i];
         const int rc = layered_decoder_create_tab(S.g, row_layer[i], S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
         if (rc != QLDPC_OK) { qldpc_layered_decoder_destroy(d[0]); return rc; }
     }
-    for (int i = 0; i < 2; i++) { qldpc_layered_decoder_destroy(P->sec[i].lay); P->sec[i].lay = d[i]; }
+    for (int i = 0; i < P->nsec; i++) { qldpc_layered_decoder_destroy(P->sec[i].lay); P->sec[i].lay = d[i]; }
     return QLDPC_OK;
 }
 
@@ -806,11 +892,11 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double
     const DecimParams dp{alpha, P->clip, fix_llr, t_round, max_rounds, per_round};
     int rc;
     if ((rc = decim_check_params(dp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (const Sector &S : P->sec)
-        if (!decim_supported(S.g)) return decim_unsupported(S.g);
+    for (int i = 0; i < P->nsec; i++)
+        if (const Sector &S = P->sec[i]; !decim_supported(S.g)) return decim_unsupported(S.g);
     QLDPC_USE_DEVICE(P->device);
-    for (Sector &S : P->sec)
-        if ((rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++)
+        if (Sector &S = P->sec[i]; (rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
     P->dp = dp;
     P->decim = true;
     return QLDPC_OK;
@@ -827,12 +913,12 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
     if (P->sec[0].f32) return QLDPC_OK;                     // one-way, and nothing to replace
     QLDPC_USE_DEVICE(P->device);
     qldpc_minsum32_decoder *d[2] = {nullptr, nullptr};
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < P->nsec; i++) {
         const Sector &S = P->sec[i];
         const int rc = minsum32_decoder_create_tab(S.g, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
         if (rc != QLDPC_OK) { qldpc_minsum32_decoder_destroy(d[0]); return rc; }
     }
-    for (int i = 0; i < 2; i++) P->sec[i].f32 = d[i];
+    for (int i = 0; i < P->nsec; i++) P->sec[i].f32 = d[i];
     return QLDPC_OK;
 }
 

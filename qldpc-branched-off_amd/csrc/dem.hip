@@ -1,0 +1,109 @@
+// Sampler of a detector error model (DEM) for the circuit plan (circuit.hip): a list of independent error mechanisms, each with a probability, the
+// detectors it flips and the logical observables it flips, in at most two sectors.  New here: the reference has no counterpart.
+//
+// The law (include/qldpc_hip.h, qldpc_circuit_plan_create_dem): trial g = trial_begin + t; mechanism l lives in Philox block q = l >> 2, word w = l & 3 of
+// o = philox4x32_10(counter (lo32(g), hi32(g), q, 3), key (lo32(seed), hi32(seed))) and fires iff o[w] < thr_l = floor(p_l * 2^32).  Domain word 3 is this
+// sampler's (0: code capacity, 1 and 2: the circuit sampler, 0x52......: Relay-BP).  A firing mechanism XORs its detector lists into the sectors' bit
+// sets and its logical masks into the sectors' accumulators, so the result does not depend on grid, block size or lane mapping.
+#include "common.h"
+#include "mc_common.h"
+
+namespace qldpc {
+
+// one workgroup per trial (grid-stride); one lane per Philox block = four mechanisms.  thr is padded with zeros to a multiple of four (a padded
+// entry never fires: no word is < 0), so a lane reads its four thresholds as one 16-byte load; l < n_mech still bounds every table access.
+__global__ __launch_bounds__(256) void dem_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, int n_mech,
+                                                         const uint4 *__restrict__ thr4, DemTab T0, DemTab T1, int n0, int n1, int two,
+                                                         int8_t *__restrict__ syn0, int8_t *__restrict__ syn1, unsigned long long *__restrict__ true0,
+                                                         unsigned long long *__restrict__ true1, int32_t *__restrict__ fail_counts) {
+    extern __shared__ uint32_t sm[];
+    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
+    const int w0 = (n0 + 31) >> 5, w1 = two ? (n1 + 31) >> 5 : 0;
+    uint32_t *b0 = sm, *b1 = sm + w0;
+    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + ((w0 + w1 + 1) & ~1));
+    const int nblk = (n_mech + 3) >> 2;
+    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
+        for (int w = threadIdx.x; w < w0 + w1; w += blockDim.x) sm[w] = 0;
+        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
+        __syncthreads();
+        const uint64_t g = (uint64_t)(trial_begin + t);
+        for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
+            const uint4 th = thr4[blk];
+            if ((th.x | th.y | th.z | th.w) == 0u) continue;                                   // four mechanisms with p = 0 (or padding): nothing to draw
+            uint32_t o[4];
+            philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)blk, 3u, seed_lo, seed_hi, o);
+            const uint32_t tw[4] = {th.x, th.y, th.z, th.w};
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                const int l = 4 * blk + w;
+                if (l < n_mech && o[w] < tw[w]) {
+                    for (int k = T0.ptr[l]; k < T0.ptr[l + 1]; k++) { const int d = T0.idx[k]; atomicXor(&b0[d >> 5], 1u << (d & 31)); }
+                    const unsigned long long l0 = T0.log[l];
+                    if (l0) atomicXor(&lacc[0], l0);
+                    if (two) {
+                        for (int k = T1.ptr[l]; k < T1.ptr[l + 1]; k++) { const int d = T1.idx[k]; atomicXor(&b1[d >> 5], 1u << (d & 31)); }
+                        const unsigned long long l1 = T1.log[l];
+                        if (l1) atomicXor(&lacc[1], l1);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < n0; i += blockDim.x) syn0[t * n0 + i] = (b0[i >> 5] >> (i & 31)) & 1;
+        if (two)
+            for (int i = threadIdx.x; i < n1; i += blockDim.x) syn1[t * n1 + i] = (b1[i >> 5] >> (i & 31)) & 1;
+        if (threadIdx.x == 0) { true0[t] = lacc[0]; if (two) true1[t] = lacc[1]; }
+        __syncthreads();
+    }
+}
+
+int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const DemTab &T0, const DemTab &T1, int n0, int n1,
+                      bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
+                      hipStream_t s) {
+    if (B <= 0) return QLDPC_OK;
+    const int w0 = (n0 + 31) / 32, w1 = two ? (n1 + 31) / 32 : 0;
+    const size_t lds = (size_t)((w0 + w1 + 1) & ~1) * 4 + 16;                                 // n_det < 65536 per sector: at most 16 KiB + 16 B
+    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
+    hipLaunchKernelGGL(dem_sample_kernel, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), n_mech,
+                       reinterpret_cast<const uint4 *>(d_thr), T0, T1, n0, n1, two ? 1 : 0, d_syn0, d_syn1, d_true0, d_true1, d_fail_counts);
+    QLDPC_HIP_TRY(hipGetLastError());
+    return QLDPC_OK;
+}
+
+// Every rule of qldpc_circuit_plan_create_dem that the descriptor alone decides; the error text names the sector or the mechanism.
+int dem_validate(const qldpc_dem_desc *D) {
+    QLDPC_REQUIRE(D != nullptr, "detector error model descriptor is NULL");
+    QLDPC_REQUIRE(D->n_sectors == 1 || D->n_sectors == 2, "n_sectors must be 1 or 2 (got %d)", D->n_sectors);
+    QLDPC_REQUIRE(D->n_mech >= 0 && D->n_mech < ((int64_t)1 << 31) - 4, "n_mech out of range (%lld)", (long long)D->n_mech);
+    QLDPC_REQUIRE(D->prob != nullptr, "detector error model: prob is NULL");
+    for (int s = 0; s < D->n_sectors; s++) {
+        QLDPC_REQUIRE(D->det_ptr[s] && D->det_idx[s] && D->logmask[s], "detector error model: sector %d has a NULL table (det_ptr, det_idx, logmask)", s);
+        QLDPC_REQUIRE(D->k[s] >= 0 && D->k[s] <= 64, "detector error model: sector %d has k = %d (0..64)", s, D->k[s]);
+        QLDPC_REQUIRE(D->n_det[s] >= 1 && D->n_det[s] < 65536, "detector error model: sector %d has %d detectors (1..65535)", s, D->n_det[s]);
+        QLDPC_REQUIRE(D->layer_rows[s] >= 0, "detector error model: sector %d has layer_rows = %d", s, D->layer_rows[s]);
+    }
+    for (int64_t l = 0; l < D->n_mech; l++) {
+        const double p = D->prob[l];
+        QLDPC_REQUIRE(p >= 0.0 && p < 1.0, "detector error model: mechanism %lld has probability %g (0 <= p < 1)", (long long)l, p);   // NaN fails both
+    }
+    for (int s = 0; s < D->n_sectors; s++) {
+        const int32_t *ptr = D->det_ptr[s];
+        const uint64_t allowed = D->k[s] == 64 ? ~(uint64_t)0 : (((uint64_t)1 << D->k[s]) - 1);
+        QLDPC_REQUIRE(ptr[0] == 0, "detector error model: sector %d: det_ptr[0] = %d, not 0", s, ptr[0]);
+        for (int64_t l = 0; l < D->n_mech; l++) {
+            QLDPC_REQUIRE(ptr[l + 1] >= ptr[l], "detector error model: sector %d, mechanism %lld: det_ptr is not monotone", s, (long long)l);
+            for (int32_t e = ptr[l]; e < ptr[l + 1]; e++) {
+                const int d = D->det_idx[s][e];
+                QLDPC_REQUIRE(d < D->n_det[s], "detector error model: sector %d, mechanism %lld: detector %d out of range (%d detectors)", s, (long long)l, d,
+                              D->n_det[s]);
+                QLDPC_REQUIRE(e == ptr[l] || d > (int)D->det_idx[s][e - 1], "detector error model: sector %d, mechanism %lld: detectors not strictly ascending",
+                              s, (long long)l);
+            }
+            QLDPC_REQUIRE((D->logmask[s][l] & ~allowed) == 0, "detector error model: sector %d, mechanism %lld: logmask has a bit at or above k = %d", s,
+                          (long long)l, D->k[s]);
+        }
+    }
+    return QLDPC_OK;
+}
+
+}  // namespace qldpc

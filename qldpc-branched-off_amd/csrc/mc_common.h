@@ -11,6 +11,8 @@
 #include <functional>
 #include <vector>
 
+#include "../../include/qldpc_hip.h"
+
 struct qldpc_graph;
 struct qldpc_window_decoder;
 struct qldpc_layered_decoder;
@@ -97,5 +99,12 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
 int minsum32_lock_and_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                              hipStream_t s);
 int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
+// Detector-error-model sampler of a circuit plan (dem.hip).  DemTab: one sector's projection of the mechanisms (device pointers): ptr int32[n_mech + 1],
+// idx detector indices, log the logical masks.  d_thr: uint32 thresholds, zero-padded to a multiple of four.  two = false: sector 1 is not touched.
+struct DemTab { const int32_t *ptr; const uint16_t *idx; const uint64_t *log; };
+int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const DemTab &T0, const DemTab &T1, int n0, int n1,
+                      bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
+                      hipStream_t s);
+int dem_validate(const qldpc_dem_desc *D);      // QLDPC_OK, or QLDPC_ERR_INVALID with the error text naming the sector or the mechanism
 
 }  // namespace qldpc

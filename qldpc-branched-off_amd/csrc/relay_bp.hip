@@ -169,7 +169,7 @@ int relay_check_params(const RelayParams &P) {
 __global__ void relay_legs_tally_kernel(int64_t B, const int32_t *__restrict__ legs_z, const int32_t *__restrict__ legs_x,
                                         unsigned long long *__restrict__ tally) {
     unsigned long long z = 0, x = 0;
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) { z += legs_z[b]; x += legs_x[b]; }
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) { z += legs_z[b]; if (legs_x) x += legs_x[b]; }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { z += __shfl_xor(z, off, 64); x += __shfl_xor(x, off, 64); }
     if ((threadIdx.x & 63) == 0) {
@@ -178,6 +178,7 @@ __global__ void relay_legs_tally_kernel(int64_t B, const int32_t *__restrict__ l
     }
 }
 
+// d_legs_x NULL: a one-sector plan (the X slot stays as it is)
 int relay_legs_tally_launch(int64_t B, const int32_t *d_legs_z, const int32_t *d_legs_x, unsigned long long *d_tally, hipStream_t stream) {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((B + 255) / 256, 64));
     hipLaunchKernelGGL(relay_legs_tally_kernel, dim3(grid), dim3(256), 0, stream, B, d_legs_z, d_legs_x, d_tally);

@@ -57,6 +57,10 @@ changes; OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_
 f64: the alpha they return is rounded to f32 like any other.  Results differ from ``"f64"`` in some trials (rounding, amplified by the iteration);
 compare logical error rates, not trials.  ``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``osd_order > 0``
 with ``decoder="bp_osd"`` raise ValueError.  The result holds ``precision``.
+
+``simulation/dem.py`` (``run_dem_simulation``: the same pipeline fed by a detector error model instead of a bivariate-bicycle circuit) shares the
+argument rules of the extensions (``_extension_rules``), the choice of devices (``_worker_devices``) and the Worker, round loop, early stop,
+all-reduce and result assembly (``_run_trials``) with ``run_simulation``; the two differ in how a worker's plan is created.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -84,11 +88,14 @@ def _estimation_trials(requested, n_cols, error_rate):
     return requested if requested != 5000 else dynamic
 
 
-def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
-                   alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
-                   num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
-                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", **bb_params):
+class _Rules:
+    """The normalised extension arguments of one call (what _extension_rules lets through)."""
+
+
+def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
+                     maxIter, num_workers):
+    """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision), shared by run_simulation and run_dem_simulation:
+    raises ValueError before any device call, returns the normalised values."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
@@ -174,6 +181,13 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         raise ValueError("relay_params is for decoder='relay_bp'")
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
+    r = _Rules()
+    r.single, r.decimation, r.layered, r.layers, r.window, r.relay, r.osd_cs, r.relay_params = single, decimation, layered, layers, window, relay, osd_cs, relay_params
+    return r
+
+
+def _worker_devices(num_workers, devices, device):
+    """(rank, world, devices): the rank of this process in a torch.distributed launch and which GPU each worker of THIS process drives."""
     rank, world = 0, 1
     try:
         import torch.distributed as _dist
@@ -195,72 +209,21 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if world > 1 and _dist.get_backend() == "nccl":
         import torch
         torch.cuda.set_device(device)              # RCCL collectives run on the rank's own GPU
-    if base_seed is None:
-        base_seed = int(np.random.randint(0, 2 ** 31))
-    if alpha_mode is None:
-        alpha_mode = "dynamical" if (use_dynamic_alpha or relay) else "alvarado"
-    if alpha_mode not in ("dynamical", "alvarado", "alvarado-autoregressive"):
-        raise ValueError(f"Unsupported alpha_mode: {alpha_mode}")
-    if alpha_mode == "alvarado-autoregressive" and alvarado_alpha is not None:
-        raise ValueError("alvarado_alpha must be None for alvarado-autoregressive")                       # engine.py:294-295
-    if estimation_plot_dir is not None:
-        os.makedirs(estimation_plot_dir, exist_ok=True)
+    return rank, world, devices
 
-    cb = BBCodeCircuit(Hx, Hz, num_cycles=num_cycles, **bb_params)
-    m = precomputed_matrices or build_decoding_matrices(cb, Lx, Lz, error_rate, verbose=False)          # engine.py:207-208
-    compiled = CompiledCircuit(base_circuit=cb.get_full_circuit(), noiseless_suffix=cb.cycle * 2, lin_order=cb.lin_order,
-                               data_qubits=cb.data_qubits, Xchecks=cb.Xchecks, Zchecks=cb.Zchecks)
-    llrs_z, llrs_x = prior_llrs(np.asarray(m["channel_probsZ"], dtype=np.float64)), prior_llrs(np.asarray(m["channel_probsX"], dtype=np.float64))
-    k = np.asarray(Lx).shape[0]
-    graphs, masks = [], []
-    for s in ("Z", "X"):
-        Hdec = m[f"Hdec{s}"]
-        ip, ix, shape = _lib.canonical_csr(Hdec)
-        graphs.append(_lib.Graph(ip, ix, shape[1], device=device))
-        if f"H{s}_logical" in m:                     # compact form: the k logical rows only (dense or (indptr, indices))
-            masks.append(_lib.logical_column_masks(m[f"H{s}_logical"], shape[1]))
-        else:
-            flr = int(m[f"first_logical_row{s}"])
-            masks.append(_lib.logical_column_masks(np.asarray(m[f"H{s}_full"])[flr:flr + k], shape[1]))    # engine.py:412-413
 
-    # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
-    # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
-    extra = {}
-    est_rng = np.random.default_rng(base_seed)
-    rate_tag = f"{error_rate:.6g}".replace(".", "p")
-    if alpha_mode == "alvarado":
-        if alvarado_alpha is None:
-            fits = [estimate_alpha_alvarado(g, error_rate, trials=_estimation_trials(alpha_estimation_trials, g.n, error_rate),
-                                            bins=alpha_estimation_bins, rng=est_rng, plot_dir=estimation_plot_dir,
-                                            plot_prefix=f"alvarado_{rate_tag}_{tag}", llrs=llr)
-                    for g, llr, tag in ((graphs[0], llrs_z, "z"), (graphs[1], llrs_x, "x"))]
-            (alpha_z, r2_z), (alpha_x, r2_x) = fits
-        elif isinstance(alvarado_alpha, (list, tuple, np.ndarray)) and len(alvarado_alpha) == 2:
-            alpha_z, alpha_x, r2_z, r2_x = float(alvarado_alpha[0]), float(alvarado_alpha[1]), None, None
-        else:
-            alpha_z = alpha_x = float(alvarado_alpha)
-            r2_z = r2_x = None
-        extra.update(alpha_r2_z=r2_z, alpha_r2_x=r2_x)                                                      # engine.py:479-481
-    elif alpha_mode == "alvarado-autoregressive":
-        fits = [estimate_alpha_alvarado_autoregressive(g, error_rate, maxIter=maxIter, trials=_estimation_trials(alpha_estimation_trials, g.n, error_rate),
-                                                       bins=alpha_estimation_bins, rng=est_rng, plot_dir=estimation_plot_dir,
-                                                       plot_prefix=f"autoregressive_{rate_tag}_{tag}", llrs=llr)
-                for g, llr, tag in ((graphs[0], llrs_z, "z"), (graphs[1], llrs_x, "x"))]
-        (alpha_z, r2s_z), (alpha_x, r2s_x) = fits
-        extra.update(alpha_values_z=alpha_z, alpha_values_x=alpha_x, alpha_r2_values_z=r2s_z, alpha_r2_values_x=r2s_x)   # engine.py:474-478
-    else:
-        alpha_z = alpha_x = 1.0
-    if scopt:                                                                                                # engine.py:346-387 (beta is reported, not used)
-        betas = [estimate_scopt_beta(g, error_rate, trials=_estimation_trials(5000, g.n, error_rate), bins=alpha_estimation_bins, alpha=a,
-                                     alpha_mode=alpha_mode, maxIter=maxIter, rng=est_rng, plot_dir=estimation_plot_dir,
-                                     plot_prefix=f"scopt_{rate_tag}_{tag}", llrs=llr)
-                 for g, llr, a, tag in ((graphs[0], llrs_z, alpha_z, "z"), (graphs[1], llrs_x, alpha_x, "x"))]
-        extra.update(beta_z=betas[0][0], beta_x=betas[1][0], beta_r2_z=betas[0][1], beta_r2_x=betas[1][1])   # engine.py:482-486
-
+def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, devices, base_seed, num_trials, max_trials, target_logical_errors, maxIter,
+                osd_order, alpha_mode, batch, decoder, schedule, precision, extra):
+    """The trial loop and the result of run_simulation and run_dem_simulation: one Worker (plan, graphs, stream) per entry of `devices`, rounds of
+    contiguous trial ranges over the workers and ranks, the in-order early stop, one all-reduce of the tally per round, and the result dict.
+    make_plan(graphs, device) creates a worker's plan; graphs / llrs / masks / alphas / ks hold one entry per sector (the first worker uses `graphs`)."""
+    single, decimation, layered, layers, window, relay, osd_cs, relay_params = (rules.single, rules.decimation, rules.layered, rules.layers, rules.window,
+                                                                                rules.relay, rules.osd_cs, rules.relay_params)
+    device = devices[0]
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
     if layered:                          # host code: the layers every worker's plan gets
-        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, layers)]
+        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, layers)] + [None] * (2 - len(csr))
     osdw_pass = osd_order > 0 and not osd_cs          # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
     class Worker:
@@ -270,8 +233,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
             self.device = dev
             self.graphs = own_graphs or [_lib.Graph(ip, ix, n, device=dev) for ip, ix, n in csr]
             self.stream = _lib.Stream(dev)
-            self.plan = _lib.CircuitPlan(compiled, Lx, Lz, self.graphs[0], self.graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
-                                         alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
+            self.plan = make_plan(self.graphs, dev)
             if relay:
                 self.plan.use_relay(**relay_params)
             if osd_cs:
@@ -289,12 +251,13 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
             (verdicts uint8[count] with bit0 = z_err, bit1 = x_err; tally int64[16]).  The literal per-trial pipeline of the reference
             (engine.py:68-122) with every stage batched on the device; used only for batches the fused OSD-0 plan left unsatisfied."""
-            spz, tz, spx, tx = self.plan.sample(base_seed, begin, count)
+            sampled = self.plan.sample(base_seed, begin, count)                          # (sparse, true) per sector
             tally = np.zeros(_lib.TALLY_SLOTS, np.int64)
             verdict = np.zeros(count, np.uint8)
             tally[T["trials"]] = count
-            for sec, (g, llrs, mask, synd, true, alpha) in enumerate(((self.graphs[0], llrs_z, masks[0], spz, tz, alpha_z), (self.graphs[1], llrs_x, masks[1], spx, tx, alpha_x))):
-                det, conv, llr, iters = _lib.minsum_decode_batch(g, synd, llrs, maxIter, alpha_mode, alpha)
+            for sec, (g, prior, mask, alpha, k) in enumerate(zip(self.graphs, llrs, masks, alphas, ks)):
+                synd, true = sampled[2 * sec], sampled[2 * sec + 1]
+                det, conv, llr, iters = _lib.minsum_decode_batch(g, synd, prior, maxIter, alpha_mode, alpha)
                 failed = np.flatnonzero(conv == 0)
                 if failed.size:                                                          # engine.py:96-97 / 115-116
                     det[failed] = _lib.osdw_batch(g, synd[failed], llr[failed], det[failed], osd_order)
@@ -423,10 +386,90 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if window is not None:
         result.update(window=tuple(window))
     if layered:
-        result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]))
+        result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]) if len(csr) > 1 else 0)
     if decimation is not None:
         trials = max(int(total[T["trials"]]), 1)
         result.update(decimation=dict(decimation), mean_rounds_z=float(total[T["legs_z"]]) / trials, mean_rounds_x=float(total[T["legs_x"]]) / trials)
     result["precision"] = precision
     result["tally"] = total
     return result
+
+
+def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
+                   alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
+                   num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
+                   estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
+                   layers=None, decimation=None, precision="f64", **bb_params):
+    rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
+                             use_dynamic_alpha, scopt, maxIter, num_workers)
+    relay = rules.relay
+    rank, world, devices = _worker_devices(num_workers, devices, device)
+    device = devices[0]
+    if base_seed is None:
+        base_seed = int(np.random.randint(0, 2 ** 31))
+    if alpha_mode is None:
+        alpha_mode = "dynamical" if (use_dynamic_alpha or relay) else "alvarado"
+    if alpha_mode not in ("dynamical", "alvarado", "alvarado-autoregressive"):
+        raise ValueError(f"Unsupported alpha_mode: {alpha_mode}")
+    if alpha_mode == "alvarado-autoregressive" and alvarado_alpha is not None:
+        raise ValueError("alvarado_alpha must be None for alvarado-autoregressive")                       # engine.py:294-295
+    if estimation_plot_dir is not None:
+        os.makedirs(estimation_plot_dir, exist_ok=True)
+
+    cb = BBCodeCircuit(Hx, Hz, num_cycles=num_cycles, **bb_params)
+    m = precomputed_matrices or build_decoding_matrices(cb, Lx, Lz, error_rate, verbose=False)          # engine.py:207-208
+    compiled = CompiledCircuit(base_circuit=cb.get_full_circuit(), noiseless_suffix=cb.cycle * 2, lin_order=cb.lin_order,
+                               data_qubits=cb.data_qubits, Xchecks=cb.Xchecks, Zchecks=cb.Zchecks)
+    llrs_z, llrs_x = prior_llrs(np.asarray(m["channel_probsZ"], dtype=np.float64)), prior_llrs(np.asarray(m["channel_probsX"], dtype=np.float64))
+    k = np.asarray(Lx).shape[0]
+    graphs, masks = [], []
+    for s in ("Z", "X"):
+        Hdec = m[f"Hdec{s}"]
+        ip, ix, shape = _lib.canonical_csr(Hdec)
+        graphs.append(_lib.Graph(ip, ix, shape[1], device=device))
+        if f"H{s}_logical" in m:                     # compact form: the k logical rows only (dense or (indptr, indices))
+            masks.append(_lib.logical_column_masks(m[f"H{s}_logical"], shape[1]))
+        else:
+            flr = int(m[f"first_logical_row{s}"])
+            masks.append(_lib.logical_column_masks(np.asarray(m[f"H{s}_full"])[flr:flr + k], shape[1]))    # engine.py:412-413
+
+    # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
+    # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
+    extra = {}
+    est_rng = np.random.default_rng(base_seed)
+    rate_tag = f"{error_rate:.6g}".replace(".", "p")
+    if alpha_mode == "alvarado":
+        if alvarado_alpha is None:
+            fits = [estimate_alpha_alvarado(g, error_rate, trials=_estimation_trials(alpha_estimation_trials, g.n, error_rate),
+                                            bins=alpha_estimation_bins, rng=est_rng, plot_dir=estimation_plot_dir,
+                                            plot_prefix=f"alvarado_{rate_tag}_{tag}", llrs=llr)
+                    for g, llr, tag in ((graphs[0], llrs_z, "z"), (graphs[1], llrs_x, "x"))]
+            (alpha_z, r2_z), (alpha_x, r2_x) = fits
+        elif isinstance(alvarado_alpha, (list, tuple, np.ndarray)) and len(alvarado_alpha) == 2:
+            alpha_z, alpha_x, r2_z, r2_x = float(alvarado_alpha[0]), float(alvarado_alpha[1]), None, None
+        else:
+            alpha_z = alpha_x = float(alvarado_alpha)
+            r2_z = r2_x = None
+        extra.update(alpha_r2_z=r2_z, alpha_r2_x=r2_x)                                                      # engine.py:479-481
+    elif alpha_mode == "alvarado-autoregressive":
+        fits = [estimate_alpha_alvarado_autoregressive(g, error_rate, maxIter=maxIter, trials=_estimation_trials(alpha_estimation_trials, g.n, error_rate),
+                                                       bins=alpha_estimation_bins, rng=est_rng, plot_dir=estimation_plot_dir,
+                                                       plot_prefix=f"autoregressive_{rate_tag}_{tag}", llrs=llr)
+                for g, llr, tag in ((graphs[0], llrs_z, "z"), (graphs[1], llrs_x, "x"))]
+        (alpha_z, r2s_z), (alpha_x, r2s_x) = fits
+        extra.update(alpha_values_z=alpha_z, alpha_values_x=alpha_x, alpha_r2_values_z=r2s_z, alpha_r2_values_x=r2s_x)   # engine.py:474-478
+    else:
+        alpha_z = alpha_x = 1.0
+    if scopt:                                                                                                # engine.py:346-387 (beta is reported, not used)
+        betas = [estimate_scopt_beta(g, error_rate, trials=_estimation_trials(5000, g.n, error_rate), bins=alpha_estimation_bins, alpha=a,
+                                     alpha_mode=alpha_mode, maxIter=maxIter, rng=est_rng, plot_dir=estimation_plot_dir,
+                                     plot_prefix=f"scopt_{rate_tag}_{tag}", llrs=llr)
+                 for g, llr, a, tag in ((graphs[0], llrs_z, alpha_z, "z"), (graphs[1], llrs_x, alpha_x, "x"))]
+        extra.update(beta_z=betas[0][0], beta_x=betas[1][0], beta_r2_z=betas[0][1], beta_r2_x=betas[1][1])   # engine.py:482-486
+
+    def make_plan(own_graphs, dev):
+        return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
+                                alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
+
+    return _run_trials(make_plan, graphs, (llrs_z, llrs_x), masks, (alpha_z, alpha_x), (k, k), rules, rank, world, devices, base_seed, num_trials, max_trials,
+                       target_logical_errors, maxIter, osd_order, alpha_mode, batch, decoder, schedule, precision, extra)
