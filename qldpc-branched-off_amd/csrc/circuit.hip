@@ -247,8 +247,9 @@ struct PlanBuf : DevBuf {
     ~PlanBuf() { release(); }
 };
 
-// The decoder of both sectors.  A plan is created as BP_OSD0 (BP alone with use_osd = 0); qldpc_circuit_plan_use_* moves it (switch_allowed).
-enum class Decoder { BP_OSD0, BP_OSD_CS, RELAY, WINDOW };
+// What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
+enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW };      // who fills the BP bracket and its follow-up
+enum class Osd { OSD0, CS };                                        // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
 
 struct qldpc_circuit_plan {
     // Everything that exists once per sector: sec[0] = Z, sec[1] = X.  A batch decodes Z, then X, on the caller's stream.
@@ -257,14 +258,14 @@ struct qldpc_circuit_plan {
         int nsyn = 0, layer_rows = 0;              // detectors (= rows of g); rows per syndrome cycle
         // on the host: the prior lets the decode dispatch pick the LDS-resident workgroup kernel (minsum_wg2.hip), the window decoder takes both at the switch
         std::vector<double> h_prior, h_alpha;
-        qldpc_window_decoder *win = nullptr;       // Decoder::WINDOW (window.hip)
-        qldpc_layered_decoder *lay = nullptr;      // the layered schedule in the BP bracket (minsum_layered.hip); both sectors or neither
-        qldpc_minsum32_decoder *f32 = nullptr;     // single-precision min-sum in the BP bracket (minsum_f32.hip); both sectors or neither
+        qldpc_window_decoder *win = nullptr;       // Path::WINDOW (window.hip)
+        qldpc_layered_decoder *lay = nullptr;      // Path::LAYERED (minsum_layered.hip)
+        qldpc_minsum32_decoder *f32 = nullptr;     // Path::F32 (minsum_f32.hip)
         PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
         PlanBuf d_alpha, d_prior, d_lm;
         PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
-        PlanBuf d_legs;                            // Decoder::RELAY: legs per trial; guided decimation: rounds per trial
-        PlanBuf d_flips;                           // Decoder::BP_OSD_CS: workspace of the sweep
+        PlanBuf d_legs;                            // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
+        PlanBuf d_flips;                           // Osd::CS: workspace of the sweep
     } sec[2];
     int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
     int nsec = 2, ks[2] = {0, 0};                  // sectors in use (1: a one-sector detector error model, sec[1] stays empty); logicals per sector
@@ -277,11 +278,11 @@ struct qldpc_circuit_plan {
     int64_t batch = 0;
     bool nanfree = false;
     PlanBuf d_loc_type, d_count, d_tally, d_outcome, d_clk;    // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
-    Decoder decoder = Decoder::BP_OSD0;
-    RelayParams rp{};                              // Decoder::RELAY (relay_bp.hip)
-    int cs_order = 0;                              // Decoder::BP_OSD_CS (osd_cs.hip)
-    bool decim = false;                            // guided decimation in the BP bracket of both sectors (decimation.hip); the mode stays BP_OSD0 / BP_OSD_CS
-    DecimParams dp{};
+    Path path = Path::FLOOD;
+    Osd osd = Osd::OSD0;
+    RelayParams rp{};                              // Path::RELAY (relay_bp.hip)
+    DecimParams dp{};                              // Path::DECIM (decimation.hip)
+    int cs_order = 0;                              // Osd::CS (osd_cs.hip)
     // hipEvent brackets of the phases of every batch not yet read by qldpc_circuit_plan_phase_times
     struct Bracket { int phase; hipEvent_t a, b; };
     std::vector<Bracket> pending;
@@ -289,7 +290,7 @@ struct qldpc_circuit_plan {
     double phase_ms[QLDPC_CIRCUIT_PHASES] = {0, 0, 0, 0, 0, 0};
     int64_t batches = 0;
     int32_t *fail_count(int sector) { return d_count.as<int32_t>() + 4 * sector; }
-    bool osd_stage() const { return use_osd && decoder != Decoder::RELAY; }      // the judge then adds d_count to the OSD tally slots
+    bool osd_stage() const { return use_osd && path != Path::RELAY; }            // the judge then adds d_count to the OSD tally slots
 };
 using Sector = qldpc_circuit_plan::Sector;
 static const int kPhaseBp[2] = {QLDPC_PHASE_BP_Z, QLDPC_PHASE_BP_X}, kPhaseOsd[2] = {QLDPC_PHASE_OSD_Z, QLDPC_PHASE_OSD_X};
@@ -461,19 +462,19 @@ QLDPC_EXPORT int qldpc_circuit_fault_signatures(const qldpc_circuit_desc *D, int
 
 // One sector of a new plan: the decoder's view (graph, prior, alpha table, column logical masks), the sampler's tables (ptr / idx / log: fault
 // signatures of a circuit, or the projection of a detector error model's mechanisms) and the per-trial buffers.
-static int plan_sector(qldpc_circuit_plan *P, int i, const qldpc_graph *g, int nsyn, int layer_rows, const double *prior, const uint64_t *logmask,
-                       int alpha_mode, double alpha_val, const double *alpha_seq, int alpha_len, const std::vector<int32_t> &sp,
+struct SectorIn { const qldpc_graph *g; const double *prior; const uint64_t *logmask; double alpha_val; const double *alpha_seq; int alpha_len; };
+static int plan_sector(qldpc_circuit_plan *P, int i, const SectorIn &in, int alpha_mode, int layer_rows, const std::vector<int32_t> &sp,
                        const std::vector<uint16_t> &si, const std::vector<uint64_t> &sl) {
     Sector &S = P->sec[i];
-    const size_t n = (size_t)g->n, Bz = (size_t)P->batch;
+    const size_t n = (size_t)in.g->n, Bz = (size_t)P->batch;
     int rc;
-    S.g = g; S.nsyn = nsyn; S.layer_rows = layer_rows;
-    if ((rc = build_alpha_table(P->max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, S.h_alpha)) != QLDPC_OK) return rc;
-    S.h_prior.assign(prior, prior + n);
+    S.g = in.g; S.nsyn = in.g->m; S.layer_rows = layer_rows;
+    if ((rc = build_alpha_table(P->max_iter, alpha_mode, in.alpha_val, in.alpha_seq, in.alpha_len, S.h_alpha)) != QLDPC_OK) return rc;
+    S.h_prior.assign(in.prior, in.prior + n);
     // "clean" inputs (finite, no -0.0 priors, positive finite clip / alphas) select the lean kernel; graphs with degree-1 checks
     // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
-    P->nanfree = P->nanfree && inputs_clean(prior, (int)n, P->clip, S.h_alpha.data(), P->max_iter);
-    const std::vector<uint64_t> lm(logmask, logmask + n);
+    P->nanfree = P->nanfree && inputs_clean(in.prior, (int)n, P->clip, S.h_alpha.data(), P->max_iter);
+    const std::vector<uint64_t> lm(in.logmask, in.logmask + n);
     if ((rc = up(S.d_ptr, sp)) || (rc = up(S.d_idx, si)) || (rc = up(S.d_log, sl)) || (rc = up(S.d_alpha, S.h_alpha)) || (rc = up(S.d_prior, S.h_prior)) ||
         (rc = up(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
         (rc = S.d_llr.ensure(Bz * n * 8)) || (rc = S.d_conv.ensure(Bz)) || (rc = S.d_iter.ensure(Bz * 4)) || (rc = S.d_list.ensure(Bz * 4)))
@@ -481,7 +482,14 @@ static int plan_sector(qldpc_circuit_plan *P, int i, const qldpc_graph *g, int n
     return QLDPC_OK;
 }
 
-// what a new plan holds once, whatever it samples
+// what a new plan holds once, whatever it samples: the arguments of both creation entry points, then (after the sectors) the buffers
+static qldpc_circuit_plan *plan_new(int device, int nsec, int n_locs, int max_iter, double damping, double clip_llr, int use_osd, int flags, int64_t batch) {
+    qldpc_circuit_plan *P = new qldpc_circuit_plan();
+    P->device = device; P->nsec = nsec; P->n_locs = n_locs;
+    P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->damping = damping; P->clip = clip_llr; P->batch = batch;
+    P->nanfree = true;
+    return P;
+}
 static int plan_common(qldpc_circuit_plan *P) {
     int rc;
     if ((rc = P->d_count.ensure(64)) || (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) || (rc = P->d_clk.ensure(2 * kClkSlots * 16))) return rc;
@@ -510,24 +518,15 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
     QLDPC_USE_DEVICE(gz->device);
     const std::vector<uint8_t> loc_type(D->base_ops, D->base_ops + D->base_len);      // error location l = base op l
 
-    qldpc_circuit_plan *P = new qldpc_circuit_plan();
+    const SectorIn in[2] = {{gz, prior_z, logmask_z, alpha_val_z, alpha_seq_z, alpha_len_z}, {gx, prior_x, logmask_x, alpha_val_x, alpha_seq_x, alpha_len_x}};
+    qldpc_circuit_plan *P = plan_new(gz->device, 2, (int)loc_type.size(), max_iter, damping, clip_llr, use_osd, flags, batch);
     auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
-    P->device = gz->device; P->k = P->ks[0] = P->ks[1] = D->k; P->n_locs = (int)loc_type.size();
-    P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->p = p; P->damping = damping; P->clip = clip_llr; P->batch = batch;
-    P->thr = bernoulli_threshold(p);
-    const qldpc_graph *const graph[2] = {gz, gx};
-    const double *const prior[2] = {prior_z, prior_x}, *const alpha_seq[2] = {alpha_seq_z, alpha_seq_x};
-    const double alpha_val[2] = {alpha_val_z, alpha_val_x};
-    const uint64_t *const logmask[2] = {logmask_z, logmask_x};
-    const int alpha_len[2] = {alpha_len_z, alpha_len_x};
-    P->nanfree = true;
+    P->k = P->ks[0] = P->ks[1] = D->k; P->p = p; P->thr = bernoulli_threshold(p);
     for (int i = 0; i < 2; i++) {
         std::vector<int32_t> sp;
         std::vector<uint16_t> si;
         std::vector<uint64_t> sl;
-        if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK) return fail(rc);
-        if ((rc = plan_sector(P, i, graph[i], sd[i].nsyn, sd[i].nchk, prior[i], logmask[i], alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], sp, si, sl)) != QLDPC_OK)
-            return fail(rc);
+        if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK || (rc = plan_sector(P, i, in[i], alpha_mode, sd[i].nchk, sp, si, sl)) != QLDPC_OK) return fail(rc);
     }
     if ((rc = up(P->d_loc_type, loc_type)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
     *out = P;
@@ -549,35 +548,26 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
     else QLDPC_REQUIRE(!g1 && !prior1 && !logmask1, "a detector error model with one sector takes no graph, prior or logmask of sector 1");
     QLDPC_REQUIRE(batch > 0 && batch <= (1 << 24), "batch out of range");
     QLDPC_REQUIRE(nsec == 1 || g0->device == g1->device, "both sector graphs must live on the same device");
-    const qldpc_graph *const graph[2] = {g0, g1};
-    const double *const prior[2] = {prior0, prior1}, *const alpha_seq[2] = {alpha_seq0, alpha_seq1};
-    const double alpha_val[2] = {alpha_val0, alpha_val1};
-    const uint64_t *const logmask[2] = {logmask0, logmask1};
-    const int alpha_len[2] = {alpha_len0, alpha_len1};
+    const SectorIn in[2] = {{g0, prior0, logmask0, alpha_val0, alpha_seq0, alpha_len0}, {g1, prior1, logmask1, alpha_val1, alpha_seq1, alpha_len1}};
     for (int i = 0; i < nsec; i++) {
-        QLDPC_REQUIRE(graph[i]->m == D->n_det[i], "sector %d: the decoding matrix has %d rows but the detector error model has %d detectors", i, graph[i]->m,
+        QLDPC_REQUIRE(in[i].g->m == D->n_det[i], "sector %d: the decoding matrix has %d rows but the detector error model has %d detectors", i, in[i].g->m,
                       D->n_det[i]);
         const uint64_t allowed = D->k[i] == 64 ? ~(uint64_t)0 : (((uint64_t)1 << D->k[i]) - 1);
-        for (int j = 0; j < graph[i]->n; j++)
-            QLDPC_REQUIRE((logmask[i][j] & ~allowed) == 0, "sector %d: the logical mask of column %d has a bit at or above k = %d", i, j, D->k[i]);
+        for (int j = 0; j < in[i].g->n; j++)
+            QLDPC_REQUIRE((in[i].logmask[j] & ~allowed) == 0, "sector %d: the logical mask of column %d has a bit at or above k = %d", i, j, D->k[i]);
     }
     QLDPC_USE_DEVICE(g0->device);
 
-    qldpc_circuit_plan *P = new qldpc_circuit_plan();
+    qldpc_circuit_plan *P = plan_new(g0->device, nsec, (int)D->n_mech, max_iter, damping, clip_llr, use_osd, flags, batch);
     auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
-    P->device = g0->device; P->dem = true; P->nsec = nsec; P->n_locs = (int)D->n_mech;
-    P->k = std::max(D->k[0], nsec == 2 ? D->k[1] : 0);
-    P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->damping = damping; P->clip = clip_llr; P->batch = batch;
-    P->nanfree = true;
+    P->dem = true; P->k = std::max(D->k[0], nsec == 2 ? D->k[1] : 0);
     const size_t nm = (size_t)D->n_mech;
     for (int i = 0; i < nsec; i++) {
         P->ks[i] = D->k[i];
         const std::vector<int32_t> sp(D->det_ptr[i], D->det_ptr[i] + nm + 1);
         const std::vector<uint16_t> si(D->det_idx[i], D->det_idx[i] + sp[nm]);
         const std::vector<uint64_t> sl(D->logmask[i], D->logmask[i] + nm);
-        if ((rc = plan_sector(P, i, graph[i], D->n_det[i], D->layer_rows[i], prior[i], logmask[i], alpha_mode, alpha_val[i], alpha_seq[i], alpha_len[i], sp, si,
-                              sl)) != QLDPC_OK)
-            return fail(rc);
+        if ((rc = plan_sector(P, i, in[i], alpha_mode, D->layer_rows[i], sp, si, sl)) != QLDPC_OK) return fail(rc);
     }
     std::vector<uint32_t> thr((nm + 3) / 4 * 4, 0u);                      // zero padding: a padded entry never fires
     for (size_t l = 0; l < nm; l++) thr[l] = bernoulli_threshold(D->prob[l]);
@@ -609,30 +599,37 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
 static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s, uint64_t seed, int64_t trial_begin) {
     Sector &S = P->sec[sector];
     const qldpc_graph *g = S.g;
-    int rc;
+    int rc = QLDPC_OK;
     int32_t *count = P->fail_count(sector);
     const int ph_bp = kPhaseBp[sector], ph_osd = kPhaseOsd[sector];
-    if (P->decoder == Decoder::WINDOW) {  // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
+    unsigned long long *clk = (P->flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr;
+    if (P->path != Path::WINDOW && (rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;      // (the window loop marks its own brackets)
+    switch (P->path) {
+    case Path::WINDOW: {  // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
         const WindowPlanSlots slots{S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), count};
         const std::function<int(int, bool)> mark = [&](int part, bool open) { return phase_mark(P, part ? ph_osd : ph_bp, s, open); };
         return window_decoder_lock_and_launch(S.win, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), &slots, &mark, s);
     }
-    unsigned long long *clk = (P->flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr;
-    if ((rc = phase_mark(P, ph_bp, s, true)) != QLDPC_OK) return rc;
-    if (P->decoder == Decoder::RELAY) {   // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
+    case Path::RELAY: {   // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
         std::lock_guard<std::mutex> lk(g->mu);
         // iter_bias -1: the judge adds one per trial, so the ITERS slots sum the Relay-BP iterations
         rc = relay_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->rp, seed, trial_begin, sector, -1, S.d_det.as<int8_t>(),
                                  S.d_conv.as<uint8_t>(), S.d_legs.as<int32_t>(), S.d_iter.as<int32_t>(), nullptr, s);
-    } else if (S.lay) {                   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
+        break;
+    }
+    case Path::LAYERED:   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
         rc = layered_lock_and_launch(S.lay, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
-    } else if (S.f32) {                   // single precision: same outputs (the posteriors widened to f64)
+        break;
+    case Path::F32:       // single precision: same outputs (the posteriors widened to f64)
         rc = minsum32_lock_and_launch(S.f32, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
-    } else if (P->decim) {                // guided decimation: same outputs too; iter_bias -1 as for Relay-BP, the rounds go where its legs go
+        break;
+    case Path::DECIM: {   // guided decimation: same outputs too; iter_bias -1 as for Relay-BP, the rounds go where its legs go
         std::lock_guard<std::mutex> lk(g->mu);
         rc = decim_decode_launch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->dp, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(),
                                  S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), S.d_legs.as<int32_t>(), nullptr, s);
-    } else {
+        break;
+    }
+    case Path::FLOOD: {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk : nullptr;                  // sector Z carries the probe (one writer per buffer)
         rc = minsum_decode_dispatch(g, B, S.d_syn.as<int8_t>(), S.d_prior.as<double>(), P->max_iter, S.d_alpha.as<double>(), P->damping, P->clip,
@@ -640,6 +637,8 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
                                     S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s,
                                     S.h_prior.empty() ? nullptr : S.h_prior.data());
         g->clk_probe = nullptr;
+        break;
+    }
     }
     if (rc != QLDPC_OK) return rc;
     if ((rc = phase_mark(P, ph_bp, s, false)) != QLDPC_OK || !P->osd_stage()) return rc;
@@ -648,7 +647,7 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
     {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk + 2 * kClkSlots : nullptr;
-        if (P->decoder == Decoder::BP_OSD_CS)
+        if (P->osd == Osd::CS)
             rc = osdcs_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(),
                                      S.d_prior.as<double>(), P->cs_order, S.d_det.as<int8_t>(), S.d_flips.as<int32_t>(), s);
         else
@@ -689,7 +688,7 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
                            outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
-        if ((P->decoder == Decoder::RELAY || P->decim) &&
+        if ((P->path == Path::RELAY || P->path == Path::DECIM) &&
             (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), two ? P->sec[1].d_legs.as<int32_t>() : nullptr, P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
             return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
@@ -778,148 +777,130 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
     return QLDPC_OK;
 }
 
-// May a plan that decodes with P->decoder switch to `to`?  (QLDPC_OK, or QLDPC_ERR_INVALID with the error text set)
-//
-//   from \ to      RELAY                   BP_OSD_CS                  WINDOW
-//   BP_OSD0        yes, also use_osd = 0   yes, needs use_osd         yes, needs use_osd
-//   RELAY          yes: new parameters     no                         no
-//   BP_OSD_CS      no                      yes: new order             no
-//   WINDOW         no                      no                         no
-//
-// The layered schedule (qldpc_circuit_plan_use_layered) replaces the launch inside the BP bracket and leaves the mode alone: it goes with BP_OSD0 and
-// BP_OSD_CS in either order, and a plan that has it moves to neither RELAY nor WINDOW (nor gets it once there).
-// Guided decimation (qldpc_circuit_plan_use_decimation) is a second replacement of that launch under the same rules; a plan has at most one of the two.
-// Single precision (qldpc_circuit_plan_use_f32) is a third replacement of that launch under the same rules; a plan has at most one of the three.
-// Each switch then checks its own arguments and what its kernels need: finite priors and a supported graph (RELAY, BP_OSD_CS, decimation), damping = 1
-// (WINDOW, layered, decimation, f32).
-static int switch_allowed(const qldpc_circuit_plan *P, Decoder to) {
-    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
+// The switch rules, once.  A plan decodes on two axes, and qldpc_circuit_plan_use_* moves it along one of them:
+//   Path: who fills the BP bracket and its follow-up -- flooding min-sum (as created), the layered schedule, guided decimation, single precision (f32),
+//     Relay-BP or sliding windows.  A plan leaves flooding at most once.  Asking again for the path it is on brings new arguments (Relay-BP, layered,
+//     decimation), changes nothing (f32) or is refused (windows).
+//   OSD stage: OSD-0 (as created; none with use_osd = 0) or OSD-CS.  OSD-CS needs use_osd, goes with flooding, layered, decimation and f32 whichever came
+//     first, and may be asked for again with a new order.  It goes with neither Relay-BP nor windows, whichever came first.
+//   Windows need use_osd as well; Relay-BP, layered, decimation and f32 do not.  Windows, layered, decimation and f32 need damping = 1.
+// Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation: finite priors and a supported graph).
+// `to`: the path asked for; Path::FLOOD stands for the one request on the other axis, OSD-CS (no call asks for flooding).
+// QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
+static int switch_allowed(const qldpc_circuit_plan *P, Path to) {
+    static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding"};
+    static const char osd_cs_name[] = "BP + OSD-CS";
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(!P->sec[0].lay || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to the layered schedule: %s cannot follow", name[(int)to]);
-    QLDPC_REQUIRE(!P->decim || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to guided decimation: %s cannot follow", name[(int)to]);
-    QLDPC_REQUIRE(!P->sec[0].f32 || to == Decoder::BP_OSD_CS, "the plan's BP stage was switched to single precision (f32): %s cannot follow", name[(int)to]);
-    QLDPC_REQUIRE(to == Decoder::RELAY || P->use_osd, "the plan was created with use_osd = 0: %s needs its OSD stage", name[(int)to]);
-    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || (P->decoder == to && to != Decoder::WINDOW), "the plan was switched to %s: %s cannot follow",
-                  name[(int)P->decoder], name[(int)to]);
+    const bool cs = to == Path::FLOOD;
+    const auto without_cs = [](Path p) { return p == Path::RELAY || p == Path::WINDOW; };
+    const char *now = P->path == Path::FLOOD && P->osd == Osd::CS ? osd_cs_name : path_name[(int)P->path], *asked = cs ? osd_cs_name : path_name[(int)to];
+    const bool follows = cs ? !without_cs(P->path) : P->path == Path::FLOOD ? !(P->osd == Osd::CS && without_cs(to)) : (P->path == to && to != Path::WINDOW);
+    QLDPC_REQUIRE(follows, "the plan was switched to %s: %s cannot follow", now, asked);
+    QLDPC_REQUIRE(P->use_osd || !(cs || to == Path::WINDOW), "the plan was created with use_osd = 0: %s needs its OSD stage", asked);
+    QLDPC_REQUIRE(P->damping == 1.0 || cs || to == Path::RELAY, "%s needs damping = 1 (the plan has %g)", asked, P->damping);
     return QLDPC_OK;
 }
 
-static int priors_finite(const qldpc_circuit_plan *P) {
+// What Relay-BP, OSD-CS and decimation check after their own arguments (params_rc): finite priors, then a graph their kernels support in every sector.
+template <class F>
+static int inputs_supported(const qldpc_circuit_plan *P, int params_rc, F graph_rc) {
+    if (params_rc != QLDPC_OK) return params_rc;
     for (int i = 0; i < P->nsec; i++)
         for (double v : P->sec[i].h_prior) QLDPC_REQUIRE(std::isfinite(v), "the plan's sector-%c prior is not finite", "ZX"[i]);
+    for (int i = 0; i < P->nsec; i++)
+        if (const int rc = graph_rc(P->sec[i].g); rc != QLDPC_OK) return rc;
+    return QLDPC_OK;
+}
+
+// `bytes` in one buffer of every sector in use
+static int ensure_each(qldpc_circuit_plan *P, PlanBuf Sector::*buf, size_t bytes) {
+    QLDPC_USE_DEVICE(P->device);
+    for (int i = 0; i < P->nsec; i++)
+        if (const int rc = (P->sec[i].*buf).ensure(bytes); rc != QLDPC_OK) return rc;
+    return QLDPC_OK;
+}
+
+// One handle per sector in use, all or none: create(S, i, &h) builds sector i's; if one fails, what was built is destroyed and the plan keeps what it
+// had.  Then every sector's `slot` takes its new handle and the one it held (if any) is destroyed.
+template <class H, class Create>
+static int build_handles(qldpc_circuit_plan *P, H *Sector::*slot, void (*destroy)(H *), Create create) {
+    QLDPC_USE_DEVICE(P->device);
+    H *h[2] = {nullptr, nullptr};
+    for (int i = 0; i < P->nsec; i++)
+        if (const int rc = create(P->sec[i], i, &h[i]); rc != QLDPC_OK) { destroy(h[0]); return rc; }
+    for (int i = 0; i < P->nsec; i++) { destroy(P->sec[i].*slot); P->sec[i].*slot = h[i]; }
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *P, double alpha, double gamma0, double gamma_min, double gamma_max, int t0, int tr,
                                              int max_legs, int stop_after) {
-    int rc = switch_allowed(P, Decoder::RELAY);
+    int rc = switch_allowed(P, Path::RELAY);
     if (rc != QLDPC_OK) return rc;
     const RelayParams rp{alpha, P->clip, gamma0, gamma_min, gamma_max, t0, tr, max_legs, stop_after};
-    if ((rc = relay_check_params(rp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (int i = 0; i < P->nsec; i++)
-        if (const Sector &S = P->sec[i]; relay_mode(S.g) == 0) return relay_unsupported(S.g);
-    QLDPC_USE_DEVICE(P->device);
-    for (int i = 0; i < P->nsec; i++)
-        if (Sector &S = P->sec[i]; (rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    if ((rc = inputs_supported(P, relay_check_params(rp), [](const qldpc_graph *g) { return relay_mode(g) ? QLDPC_OK : relay_unsupported(g); })) != QLDPC_OK ||
+        (rc = ensure_each(P, &Sector::d_legs, (size_t)P->batch * 4)) != QLDPC_OK)
+        return rc;
     P->rp = rp;
-    P->decoder = Decoder::RELAY;
+    P->path = Path::RELAY;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order) {
-    int rc = switch_allowed(P, Decoder::BP_OSD_CS);
+    int rc = switch_allowed(P, Path::FLOOD);
     if (rc != QLDPC_OK) return rc;
-    if ((rc = osdcs_check_order(order)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (int i = 0; i < P->nsec; i++)
-        if (const Sector &S = P->sec[i]; (rc = osdcs_supported(S.g)) != QLDPC_OK) return rc;
-    QLDPC_USE_DEVICE(P->device);
-    for (int i = 0; i < P->nsec; i++)
-        if (Sector &S = P->sec[i]; (rc = S.d_flips.ensure((size_t)P->batch * 8)) != QLDPC_OK) return rc;
+    if ((rc = inputs_supported(P, osdcs_check_order(order), osdcs_supported)) != QLDPC_OK ||
+        (rc = ensure_each(P, &Sector::d_flips, (size_t)P->batch * 8)) != QLDPC_OK)
+        return rc;
     P->cs_order = order;
-    P->decoder = Decoder::BP_OSD_CS;
+    P->osd = Osd::CS;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window, int commit) {
-    int rc = switch_allowed(P, Decoder::WINDOW);
+    int rc = switch_allowed(P, Path::WINDOW);
     if (rc != QLDPC_OK) return rc;
-    QLDPC_REQUIRE(P->damping == 1.0, "sliding-window decoding needs damping = 1 (the plan has %g)", P->damping);
     for (int i = 0; P->dem && i < P->nsec; i++)
         QLDPC_REQUIRE(P->sec[i].layer_rows > 0 && P->sec[i].nsyn % P->sec[i].layer_rows == 0,
                       "sector %d of the detector error model has layer_rows = %d, which %s: sliding-window decoding needs the rows of a syndrome cycle", i,
                       P->sec[i].layer_rows, P->sec[i].layer_rows > 0 ? "does not divide its detectors" : "means no layers were given");
-    QLDPC_USE_DEVICE(P->device);
-    qldpc_window_decoder *w[2] = {nullptr, nullptr};
-    for (int i = 0; i < P->nsec; i++) {
-        const Sector &S = P->sec[i];
-        rc = window_decoder_create_tab(S.g, S.layer_rows, window, commit, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK,
-                                       &w[i]);
-        if (rc != QLDPC_OK) { qldpc_window_decoder_destroy(w[0]); return rc; }
-    }
-    for (int i = 0; i < P->nsec; i++) P->sec[i].win = w[i];
-    P->decoder = Decoder::WINDOW;
-    return QLDPC_OK;
+    rc = build_handles(P, &Sector::win, qldpc_window_decoder_destroy, [&](const Sector &S, int, qldpc_window_decoder **out) {
+        return window_decoder_create_tab(S.g, S.layer_rows, window, commit, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
+    });
+    if (rc == QLDPC_OK) P->path = Path::WINDOW;
+    return rc;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int32_t *row_layer_z, const int32_t *row_layer_x) {
-    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: the layered schedule cannot follow",
-                  name[(int)P->decoder]);
-    QLDPC_REQUIRE(!P->decim, "the plan's BP stage was switched to guided decimation: the layered schedule cannot follow");
-    QLDPC_REQUIRE(!P->sec[0].f32, "the plan's BP stage was switched to single precision (f32): the layered schedule cannot follow");
-    QLDPC_REQUIRE(P->damping == 1.0, "the layered schedule needs damping = 1 (the plan has %g)", P->damping);
-    QLDPC_USE_DEVICE(P->device);
+    int rc = switch_allowed(P, Path::LAYERED);
+    if (rc != QLDPC_OK) return rc;
     const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
-    qldpc_layered_decoder *d[2] = {nullptr, nullptr};
-    for (int i = 0; i < P->nsec; i++) {
-        const Sector &S = P->sec[i];
-        const int rc = layered_decoder_create_tab(S.g, row_layer[i], S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
-        if (rc != QLDPC_OK) { qldpc_layered_decoder_destroy(d[0]); return rc; }
-    }
-    for (int i = 0; i < P->nsec; i++) { qldpc_layered_decoder_destroy(P->sec[i].lay); P->sec[i].lay = d[i]; }
-    return QLDPC_OK;
+    rc = build_handles(P, &Sector::lay, qldpc_layered_decoder_destroy, [&](const Sector &S, int i, qldpc_layered_decoder **out) {
+        return layered_decoder_create_tab(S.g, row_layer[i], S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
+    });
+    if (rc == QLDPC_OK) P->path = Path::LAYERED;
+    return rc;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double alpha, int t_round, int max_rounds, int per_round, double fix_llr) {
-    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: guided decimation cannot follow",
-                  name[(int)P->decoder]);
-    QLDPC_REQUIRE(!P->sec[0].lay, "the plan's BP stage was switched to the layered schedule: guided decimation cannot follow");
-    QLDPC_REQUIRE(!P->sec[0].f32, "the plan's BP stage was switched to single precision (f32): guided decimation cannot follow");
-    QLDPC_REQUIRE(P->damping == 1.0, "guided decimation needs damping = 1 (the plan has %g)", P->damping);
+    int rc = switch_allowed(P, Path::DECIM);
+    if (rc != QLDPC_OK) return rc;
     const DecimParams dp{alpha, P->clip, fix_llr, t_round, max_rounds, per_round};
-    int rc;
-    if ((rc = decim_check_params(dp)) != QLDPC_OK || (rc = priors_finite(P)) != QLDPC_OK) return rc;
-    for (int i = 0; i < P->nsec; i++)
-        if (const Sector &S = P->sec[i]; !decim_supported(S.g)) return decim_unsupported(S.g);
-    QLDPC_USE_DEVICE(P->device);
-    for (int i = 0; i < P->nsec; i++)
-        if (Sector &S = P->sec[i]; (rc = S.d_legs.ensure((size_t)P->batch * 4)) != QLDPC_OK) return rc;
+    if ((rc = inputs_supported(P, decim_check_params(dp), [](const qldpc_graph *g) { return decim_supported(g) ? QLDPC_OK : decim_unsupported(g); })) != QLDPC_OK ||
+        (rc = ensure_each(P, &Sector::d_legs, (size_t)P->batch * 4)) != QLDPC_OK)
+        return rc;
     P->dp = dp;
-    P->decim = true;
+    P->path = Path::DECIM;
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
-    static const char *const name[] = {"BP + OSD-0", "BP + OSD-CS", "Relay-BP", "sliding-window decoding"};
-    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    QLDPC_REQUIRE(P->decoder == Decoder::BP_OSD0 || P->decoder == Decoder::BP_OSD_CS, "the plan was switched to %s: single precision (f32) cannot follow",
-                  name[(int)P->decoder]);
-    QLDPC_REQUIRE(!P->sec[0].lay, "the plan's BP stage was switched to the layered schedule: single precision (f32) cannot follow");
-    QLDPC_REQUIRE(!P->decim, "the plan's BP stage was switched to guided decimation: single precision (f32) cannot follow");
-    QLDPC_REQUIRE(P->damping == 1.0, "single precision (f32) needs damping = 1 (the plan has %g)", P->damping);
-    if (P->sec[0].f32) return QLDPC_OK;                     // one-way, and nothing to replace
-    QLDPC_USE_DEVICE(P->device);
-    qldpc_minsum32_decoder *d[2] = {nullptr, nullptr};
-    for (int i = 0; i < P->nsec; i++) {
-        const Sector &S = P->sec[i];
-        const int rc = minsum32_decoder_create_tab(S.g, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, &d[i]);
-        if (rc != QLDPC_OK) { qldpc_minsum32_decoder_destroy(d[0]); return rc; }
-    }
-    for (int i = 0; i < P->nsec; i++) P->sec[i].f32 = d[i];
-    return QLDPC_OK;
+    int rc = switch_allowed(P, Path::F32);
+    if (rc != QLDPC_OK || P->path == Path::F32) return rc;                  // asked again: nothing to replace
+    rc = build_handles(P, &Sector::f32, qldpc_minsum32_decoder_destroy, [&](const Sector &S, int, qldpc_minsum32_decoder **out) {
+        return minsum32_decoder_create_tab(S.g, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
+    });
+    if (rc == QLDPC_OK) P->path = Path::F32;
+    return rc;
 }
 
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {

@@ -288,12 +288,12 @@ def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode
         alphas = (float(alvarado_alpha[0]), float(alvarado_alpha[1]))
     else:
         alphas = (float(alvarado_alpha),) * 2
-    if rules.window is not None:
+    if rules.path == "window":
         for s, S in enumerate(dem.sectors):
             if S.layer_rows <= 0 or S.n_det % S.layer_rows:
                 raise ValueError(f"window={window!r} needs the model's layer_rows (rows of one syndrome cycle): sector {s} has layer_rows={S.layer_rows} "
                                  f"for {S.n_det} detectors")
-    if rules.layered and dem.n_sectors == 1 and rules.layers[1] is not None:
+    if rules.path == "layered" and dem.n_sectors == 1 and rules.layers[1] is not None:
         raise ValueError("layers: the model has one sector, so the second row_layer must be None")
     rank, world, devices = engine._worker_devices(num_workers, devices, device)
     if base_seed is None:

@@ -22,6 +22,11 @@ Differences that are deliberate and documented:
     the plans of that rank, default 1) and one all-reduce of the tally follows; with the RCCL backend it runs on device tensors;
   * ``target_logical_errors`` stops at the exact trial the reference would (in-order prefix cut over per-trial verdicts).
 
+The extensions below choose what a worker's plan decodes with, on the plan's two axes.  The path: at most one of
+``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``precision="f32"`` leaves flooding min-sum, and none of them
+goes with the reference's OSD-w pass (``osd_order > 0`` with ``decoder="bp_osd"``).  The OSD stage: ``decoder="bp_osd_cs"`` puts OSD-CS in the place
+of OSD-0; it goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
+
 ``decoder="relay_bp"`` (an extension; ``"bp_osd"`` is the default) decodes both sectors with Relay-BP (``decoding/relay.py``) instead of
 min-sum + OSD-0, with ``relay_params`` over ``_lib.RELAY_DEFAULTS``.  Relay-BP uses its own constant alpha, so the alpha / beta estimators do not run,
 and the arguments that only mean something for BP+OSD (``alpha_mode``, ``alvarado_alpha``, ``scopt=True``, ``osd_order > 0``) raise ValueError.
@@ -33,7 +38,7 @@ reliable non-pivot columns), not the reference's OSD-w order.  The alpha / SCOPT
 ValueError.  OSD-CS returns OSD-0's answer wherever the syndrome is not reproducible, so no OSD-w pass follows.  The result also holds
 ``decoder`` and ``osd_order``.
 
-``window=(W, C)`` (an extension; ``decoder="bp_osd"`` with ``osd_order=0`` only, anything else raises ValueError) decodes both sectors with the
+``window=(W, C)`` (an extension; ``decoder="bp_osd"`` with ``osd_order=0`` only) decodes both sectors with the
 sliding-window decoder (``decoding/window.py``): W syndrome cycles at a time, the first C of them committed, min-sum + OSD-0 per window.  The
 window graphs do not grow with ``num_cycles``.  The result also holds ``window``.
 
@@ -41,22 +46,20 @@ window graphs do not grow with ``num_cycles``.  The result also holds ``window``
 schedule (``decoding/layered.py``); only that stage changes, OSD-0 (``decoder="bp_osd"``) or OSD-CS (``decoder="bp_osd_cs"``) follows as before.
 ``layers=(row_layer_z, row_layer_x)`` names the layers (either may be None = the greedy colouring).  The alpha / SCOPT estimators measure flooding
 messages, so anything that would run one raises ValueError (``alpha_mode="alvarado"`` without ``alvarado_alpha``, ``"alvarado-autoregressive"``,
-``scopt=True``), as do ``decoder="relay_bp"``, ``window=...`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``schedule`` and ``layers_z`` / ``layers_x`` (layer counts).
+``scopt=True``).  The result also holds ``schedule`` and ``layers_z`` / ``layers_x`` (layer counts).
 
 ``decimation={...}`` (an extension; None is today's behaviour) runs the BP stage of both sectors as BP with guided decimation
 (``decoding/decimation.py``); the dict holds any of ``alpha, t_round, max_rounds, per_round, fix_llr`` (``_lib.DECIM_DEFAULTS`` for the rest).  Only
 that stage changes: OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_osd_cs"``) follows on the unconverged trials as before.  Its
 alpha is the constant of the dict and ``maxIter`` is not used by it, so every argument that selects or estimates another alpha raises ValueError
-(``alpha_mode``, ``alvarado_alpha``, ``use_dynamic_alpha=False``, ``scopt=True``), as do ``decoder="relay_bp"``, ``window=...``,
-``schedule="layered"`` and ``osd_order > 0`` with ``decoder="bp_osd"``.  The result also holds ``decimation`` (the parameters used) and
+(``alpha_mode``, ``alvarado_alpha``, ``use_dynamic_alpha=False``, ``scopt=True``).  The result also holds ``decimation`` (the parameters used) and
 ``mean_rounds_z`` / ``mean_rounds_x``.
 
 ``precision="f32"`` (an extension; ``"f64"`` is the default and today's behaviour) runs the BP stage of both sectors in single precision
 (``decoding/single.py``): the plan's priors, alpha table, ``maxIter`` and clip rounded to f32, every operation one f32 operation.  Only that stage
 changes; OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_osd_cs"``) follows as before.  The alpha / SCOPT estimators stay
 f64: the alpha they return is rounded to f32 like any other.  Results differ from ``"f64"`` in some trials (rounding, amplified by the iteration);
-compare logical error rates, not trials.  ``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``osd_order > 0``
-with ``decoder="bp_osd"`` raise ValueError.  The result holds ``precision``.
+compare logical error rates, not trials.  The result holds ``precision``.
 
 ``simulation/dem.py`` (``run_dem_simulation``: the same pipeline fed by a detector error model instead of a bivariate-bicycle circuit) shares the
 argument rules of the extensions (``_extension_rules``), the choice of devices (``_worker_devices``) and the Worker, round loop, early stop,
@@ -64,6 +67,7 @@ all-reduce and result assembly (``_run_trials``) with ``run_simulation``; the tw
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -88,42 +92,47 @@ def _estimation_trials(requested, n_cols, error_rate):
     return requested if requested != 5000 else dynamic
 
 
-class _Rules:
-    """The normalised extension arguments of one call (what _extension_rules lets through)."""
-
-
 def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
                      maxIter, num_workers):
     """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision), shared by run_simulation and run_dem_simulation:
-    raises ValueError before any device call, returns the normalised values."""
+    raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered", "decimation", "f32", "relay" or
+    "window": who decodes the BP stage) and ``osd_cs`` (OSD-CS instead of OSD-0 in the OSD stage) -- with the normalised parameters of that path
+    (``layers``, ``decimation``, ``relay_params``, ``window``; None where the path is another)."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
         raise ValueError(f"Unsupported precision: {precision!r} (expected 'f64' or 'f32')")
-    single = precision == "f32"
-    if single:                           # (before any device call: these are argument rules)
-        if decoder == "relay_bp":
-            raise ValueError("precision='f32' goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
-        if window is not None:
-            raise ValueError(f"precision='f32' does not go with window={window!r}")
-        if schedule == "layered":
-            raise ValueError("precision='f32' does not go with schedule='layered' (both replace the BP stage)")
-        if decimation is not None:
-            raise ValueError("precision='f32' does not go with decimation=... (both replace the BP stage)")
-        if decoder == "bp_osd" and osd_order > 0:
-            raise ValueError(f"precision='f32' goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes in f64)")
+    if schedule not in ("flooding", "layered"):
+        raise ValueError(f"Unsupported schedule: {schedule!r} (expected 'flooding' or 'layered')")
+    if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs"):
+        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp' or 'bp_osd_cs')")
+    osd_cs = decoder == "bp_osd_cs"
+    # the path: at most one argument leaves flooding min-sum (the plan's own rule, qldpc_circuit_plan_use_*) ...
+    asked = [(path, text) for path, text, given in (("f32", "precision='f32'", precision == "f32"), ("decimation", "decimation=...", decimation is not None),
+                                                     ("layered", "schedule='layered'", schedule == "layered"),
+                                                     ("window", f"window={window!r}", window is not None), ("relay", "decoder='relay_bp'", decoder == "relay_bp"))
+             if given]
+    if len(asked) > 1:
+        (_, one), (_, other) = asked[:2]
+        raise ValueError(f"{one} does not go with {other}: {one} goes with none of the others of decoder='relay_bp', window=(W, C), schedule='layered', "
+                         "decimation=... and precision='f32' (each decodes the BP stage its own way)")
+    path, text = asked[0] if asked else ("flooding", None)
+    # ... and none of them goes with the OSD-w pass, which decodes again with flooding min-sum in f64
+    if path != "flooding" and decoder == "bp_osd" and osd_order > 0:
+        raise ValueError(f"{text} goes with osd_order=0{'' if path == 'window' else ' or decoder=%r' % 'bp_osd_cs'} (with decoder='bp_osd', "
+                         f"osd_order={osd_order} asks for the OSD-w pass, which decodes with flooding min-sum in f64)")
+    if layers is not None and path != "layered":
+        raise ValueError("layers is for schedule='layered'")
+    if relay_params is not None and path != "relay":
+        raise ValueError("relay_params is for decoder='relay_bp'")
+    if osd_cs and not 0 <= int(osd_order) <= _lib.OSDCS_MAX_ORDER:
+        raise ValueError(f"decoder='bp_osd_cs': osd_order is the combination-sweep order, 0..{_lib.OSDCS_MAX_ORDER} (got {osd_order})")
+    # what is particular to a path (before any device call: these are argument rules)
+    if path == "f32":
         _lib.check_minsum32_args(maxIter, 20.0)
-    if decimation is not None:           # (before any device call: these are argument rules)
+    elif path == "decimation":
         if not isinstance(decimation, dict):
             raise ValueError("decimation must be a dict of guided-decimation parameters (or None)")
-        if decoder == "relay_bp":
-            raise ValueError("decimation=... goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
-        if window is not None:
-            raise ValueError(f"decimation=... does not go with window={window!r}")
-        if schedule == "layered":
-            raise ValueError("decimation=... does not go with schedule='layered' (both replace the BP stage)")
-        if decoder == "bp_osd" and osd_order > 0:
-            raise ValueError(f"decimation=... goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes with flooding min-sum)")
         bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None),
                                         ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
         if bad:
@@ -131,44 +140,24 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         if "clip_llr" in decimation:
             raise ValueError("decimation: the circuit plan's clip_llr is fixed (20)")
         decimation = _lib.decim_params(decimation, with_clip=False)
-    if schedule not in ("flooding", "layered"):
-        raise ValueError(f"Unsupported schedule: {schedule!r} (expected 'flooding' or 'layered')")
-    layered = schedule == "layered"
-    if layers is not None and not layered:
-        raise ValueError("layers is for schedule='layered'")
-    if layered:                          # (before any device call: these are argument rules)
-        if decoder == "relay_bp":
-            raise ValueError("schedule='layered' goes with decoder='bp_osd' or 'bp_osd_cs', not with decoder='relay_bp'")
-        if window is not None:
-            raise ValueError(f"schedule='layered' does not go with window={window!r}")
+    elif path == "layered":
         mode = alpha_mode if alpha_mode is not None else ("dynamical" if use_dynamic_alpha else "alvarado")
         if mode == "alvarado-autoregressive" or (mode == "alvarado" and alvarado_alpha is None):
             raise ValueError(f"schedule='layered' has no alpha estimator (alpha_mode={mode!r} would run the flooding one): pass alvarado_alpha or use 'dynamical'")
         if scopt:
             raise ValueError("schedule='layered' has no SCOPT estimator (scopt=True would run the flooding one)")
-        if decoder == "bp_osd" and osd_order > 0:
-            raise ValueError(f"schedule='layered' goes with OSD-0 or decoder='bp_osd_cs' (osd_order={osd_order} asks for the OSD-w pass, which decodes with the flooding schedule)")
         _lib.check_layered_args(maxIter, 20.0)
         if layers is None:
             layers = (None, None)
         if not isinstance(layers, (tuple, list)) or len(layers) != 2:
             raise ValueError("layers must be a pair (row_layer_z, row_layer_x); either may be None")
-    if window is not None:
-        if decoder != "bp_osd" or osd_order != 0:
+    elif path == "window":
+        if osd_cs:
             raise ValueError("window=(W, C) goes with decoder='bp_osd' and osd_order=0 only")
         if not isinstance(window, (tuple, list)) or len(window) != 2:
             raise ValueError("window must be a pair (W, C)")
         window = _lib.check_window_args(1, window[0], window[1])[1:]
-    if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs"):
-        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp' or 'bp_osd_cs')")
-    relay = decoder == "relay_bp"
-    osd_cs = decoder == "bp_osd_cs"
-    if osd_cs:
-        if relay_params is not None:
-            raise ValueError("relay_params is for decoder='relay_bp'")
-        if not 0 <= int(osd_order) <= _lib.OSDCS_MAX_ORDER:
-            raise ValueError(f"decoder='bp_osd_cs': osd_order is the combination-sweep order, 0..{_lib.OSDCS_MAX_ORDER} (got {osd_order})")
-    if relay:
+    elif path == "relay":
         bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None), ("scopt", bool(scopt)),
                                         ("osd_order", osd_order > 0)) if given]
         if bad:
@@ -177,13 +166,9 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         if "clip_llr" in relay_params:
             raise ValueError("relay_params: the circuit plan's clip_llr is fixed (20)")
         relay_params = _lib.relay_params(relay_params, with_clip=False)
-    elif relay_params is not None:
-        raise ValueError("relay_params is for decoder='relay_bp'")
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
-    r = _Rules()
-    r.single, r.decimation, r.layered, r.layers, r.window, r.relay, r.osd_cs, r.relay_params = single, decimation, layered, layers, window, relay, osd_cs, relay_params
-    return r
+    return SimpleNamespace(path=path, osd_cs=osd_cs, layers=layers, decimation=decimation, relay_params=relay_params, window=window)
 
 
 def _worker_devices(num_workers, devices, device):
@@ -217,14 +202,16 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     """The trial loop and the result of run_simulation and run_dem_simulation: one Worker (plan, graphs, stream) per entry of `devices`, rounds of
     contiguous trial ranges over the workers and ranks, the in-order early stop, one all-reduce of the tally per round, and the result dict.
     make_plan(graphs, device) creates a worker's plan; graphs / llrs / masks / alphas / ks hold one entry per sector (the first worker uses `graphs`)."""
-    single, decimation, layered, layers, window, relay, osd_cs, relay_params = (rules.single, rules.decimation, rules.layered, rules.layers, rules.window,
-                                                                                rules.relay, rules.osd_cs, rules.relay_params)
     device = devices[0]
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
-    if layered:                          # host code: the layers every worker's plan gets
-        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, layers)] + [None] * (2 - len(csr))
-    osdw_pass = osd_order > 0 and not osd_cs          # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
+    if rules.path == "layered":          # host code: the layers every worker's plan gets
+        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
+    # how a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules)
+    to_path = {"flooding": lambda plan: None, "relay": lambda plan: plan.use_relay(**rules.relay_params), "window": lambda plan: plan.use_window(*rules.window),
+               "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
+               "f32": lambda plan: plan.use_f32()}[rules.path]
+    osdw_pass = osd_order > 0 and not rules.osd_cs    # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
     class Worker:
         """One worker = the reference's pool process (engine.py:433-435) as a device plan: graphs, masks, buffers and a stream of its own on one GPU."""
@@ -234,18 +221,9 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
             self.graphs = own_graphs or [_lib.Graph(ip, ix, n, device=dev) for ip, ix, n in csr]
             self.stream = _lib.Stream(dev)
             self.plan = make_plan(self.graphs, dev)
-            if relay:
-                self.plan.use_relay(**relay_params)
-            if osd_cs:
+            if rules.osd_cs:
                 self.plan.use_osd_cs(int(osd_order))
-            if window is not None:
-                self.plan.use_window(*window)
-            if layered:
-                self.plan.use_layered(*layers)
-            if decimation is not None:
-                self.plan.use_decimation(**decimation)
-            if single:
-                self.plan.use_f32()
+            to_path(self.plan)
 
         def osdw_batch(self, begin, count):
             """One trial range through sample -> decode -> OSD-w (order = osd_order) on the shots BP failed on -> logical comparison:
@@ -377,19 +355,17 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     else:
         result = parallel.tally_to_result(total)
     result.update(extra)
-    if relay:
-        trials = max(int(total[T["trials"]]), 1)
-        result.update(decoder=decoder, relay_params=dict(relay_params), mean_legs_z=float(total[T["legs_z"]]) / trials,
-                      mean_legs_x=float(total[T["legs_x"]]) / trials)
-    if osd_cs:
+    if rules.osd_cs:
         result.update(decoder=decoder, osd_order=int(osd_order))
-    if window is not None:
-        result.update(window=tuple(window))
-    if layered:
+    per_trial = [float(total[T[slot]]) / max(int(total[T["trials"]]), 1) for slot in ("legs_z", "legs_x")]      # Relay-BP: legs; decimation: rounds
+    if rules.path == "relay":
+        result.update(decoder=decoder, relay_params=dict(rules.relay_params), mean_legs_z=per_trial[0], mean_legs_x=per_trial[1])
+    elif rules.path == "window":
+        result.update(window=tuple(rules.window))
+    elif rules.path == "layered":
         result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]) if len(csr) > 1 else 0)
-    if decimation is not None:
-        trials = max(int(total[T["trials"]]), 1)
-        result.update(decimation=dict(decimation), mean_rounds_z=float(total[T["legs_z"]]) / trials, mean_rounds_x=float(total[T["legs_x"]]) / trials)
+    elif rules.path == "decimation":
+        result.update(decimation=dict(rules.decimation), mean_rounds_z=per_trial[0], mean_rounds_x=per_trial[1])
     result["precision"] = precision
     result["tally"] = total
     return result
@@ -402,13 +378,12 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    layers=None, decimation=None, precision="f64", **bb_params):
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
                              use_dynamic_alpha, scopt, maxIter, num_workers)
-    relay = rules.relay
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:
         base_seed = int(np.random.randint(0, 2 ** 31))
     if alpha_mode is None:
-        alpha_mode = "dynamical" if (use_dynamic_alpha or relay) else "alvarado"
+        alpha_mode = "dynamical" if (use_dynamic_alpha or rules.path == "relay") else "alvarado"
     if alpha_mode not in ("dynamical", "alvarado", "alvarado-autoregressive"):
         raise ValueError(f"Unsupported alpha_mode: {alpha_mode}")
     if alpha_mode == "alvarado-autoregressive" and alvarado_alpha is not None:
