@@ -285,9 +285,9 @@ int qldpc_osd0_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndro
                          const int32_t *d_ordering, const int32_t *d_select, const int32_t *d_select_count, int flags, int8_t *d_solution,
                          void *stream);
 /* Which OSD-0 kernel the last OSD-0 launch on this handle took: qldpc_osd0_batch[_dev], or the OSD-0 stage of a plan or window decoder that owns the
- * handle.  Launches nothing; the values are written by the launch code itself at the point where it starts each kernel, so the query cannot drift
- * from what ran.  Results never depend on the form.  With several threads on one handle it reports whichever call enqueued last.  New here (the
- * reference has no counterpart); for tests and tools.
+ * handle.  Launches nothing; the values are those of the plan (csrc/osd_plan.h) the launch code executed, written by that code once it has
+ * enqueued the plan's kernels, so the query cannot drift from what ran.  Results never depend on the form.  With several threads on one handle it
+ * reports whichever call enqueued last.  New here (the reference has no counterpart); for tests and tools.
  *   path    QLDPC_OSD_PATH_*: the kernel that was given every listed shot.  NONE: nothing was launched (no call yet, m == 0 or n == 0, or the call
  *           was refused); SMALL csrc/osd_small.hip (one wave per shot, m <= 128 and n <= 1024); GJ csrc/osd_gj.hip (free pivot rows, row transform in
  *           LDS, m <= 1024); GJG csrc/osd_gjg.hip (the same with the transform in HBM / L2, m <= 4096); REFORDER_LDS / REFORDER_UG osd0_lds_kernel of

@@ -36,7 +36,6 @@ __device__ inline ElimShared carve_elim(unsigned char *base, int m, int nwords) 
     S.dead = reinterpret_cast<uint8_t *>(S.cnt + 2);
     return S;
 }
-static size_t elim_lds_bytes(int m, int nwords) { return 16 + (size_t)nwords * 8 + (size_t)m * 4 + 8 + (size_t)m + 16; }
 
 // In-place elimination of A[m][nwords] (global), b[m].  Returns the number of pivots (uniform).
 template <class PIdx>
@@ -194,36 +193,10 @@ __global__ __launch_bounds__(1024) void osd0_kernel(OsdArgs P) {
     }
 }
 
-int osd0_lds_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                    const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled, OsdJudge *judge);
-
-static int osd0_global_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, const int8_t *d_synd, const double *d_llr,
-                              const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, hipStream_t stream);
-
-// callers hold g->mu; the graph's device workspaces are handed over in stream order (common.h)
-int osd0_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                       const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, OsdJudge *judge) {
-    g->osd_path = QLDPC_OSD_PATH_NONE; g->osd_detail = 0;      // what qldpc_osd0_last_path reports: written below, where each launch is made
-    if (g->m == 0 || g->n == 0) return QLDPC_OK;
-    int rc = g->ws_acquire(stream);                 // (a no-op for a caller that already holds the workspaces on this stream)
-    if (rc != QLDPC_OK) return rc;
-    bool handled = false;           // LDS-resident kernels for m <= 4096; the global-memory kernel is the general fallback
-    rc = osd0_lds_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, handled, judge);
-    if (rc == QLDPC_OK && !handled) {
-        rc = osd0_global_launch(g, d_list, d_count, d_synd, d_llr, d_hard, d_ordering, d_solution, stream);
-        if (rc == QLDPC_OK) {
-            // (a free-pivot kernel that found no reference-order form for its redo list is followed by this kernel on EVERY shot)
-            if (g->osd_path == QLDPC_OSD_PATH_NONE) g->osd_path = QLDPC_OSD_PATH_GLOBAL; else g->osd_detail |= QLDPC_OSD_DETAIL_REDO;
-        }
-    }
-    const int rel = g->ws_release(stream);          // always: a failing call may have enqueued launches the next stream has to wait for
-    return rc != QLDPC_OK ? rc : rel;
-}
-
-static int osd0_global_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, const int8_t *d_synd, const double *d_llr,
-                              const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, hipStream_t stream) {
+// the general fallback; the plan (osd_plan.h) has checked its LDS scratch against kOsdElimMax
+static int osd0_global_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream) {
     const int m = g->m, n = g->n;
-    const int nwords = ((n + 7) / 8 + 7) / 8;
+    const int nwords = osd_global_nwords(n);
     const int maxp = m < n ? m : n;
     const size_t slab = (size_t)m * nwords * 8 + (size_t)m + (size_t)n * 8 + (size_t)maxp * 8 + (size_t)n * 8 + 64;
     int grid = 512;
@@ -236,7 +209,7 @@ static int osd0_global_launch(const qldpc_graph *g, const int32_t *d_list, const
     unsigned char *base = g->ws_misc.as<unsigned char>();
     OsdArgs P;
     P.m = m; P.n = n; P.nwords = nwords; P.indptr = g->d_indptr; P.indices = g->d_indices;
-    P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.ordering = d_ordering; P.solution = d_solution;
+    P.list = S.list; P.count = S.count; P.synd = S.synd; P.llr = S.llr; P.hard = S.hard; P.ordering = S.ordering; P.solution = S.solution;
     P.A = reinterpret_cast<uint64_t *>(base);
     P.keys = reinterpret_cast<double *>(base + szA);
     P.ord = reinterpret_cast<int32_t *>(base + szA + szK);
@@ -244,10 +217,7 @@ static int osd0_global_launch(const qldpc_graph *g, const int32_t *d_list, const
     P.prow = reinterpret_cast<int32_t *>(base + szA + szK + 2 * szO);
     P.pcol = reinterpret_cast<int32_t *>(base + szA + szK + 2 * szO + szP);
     P.b = reinterpret_cast<uint8_t *>(base + szA + szK + 2 * szO + 2 * szP);
-    const size_t lds = elim_lds_bytes(m, nwords);
-    if (lds > 150 * 1024) { set_error("OSD-0: matrix too large for the LDS scratch (m=%d nwords=%d)", m, nwords); return QLDPC_ERR_UNSUPPORTED; }
-    const int block = (m >= 512 || n >= 2048) ? 1024 : 256;
-    hipLaunchKernelGGL(osd0_kernel, dim3(grid), dim3(block), lds, stream, P);
+    hipLaunchKernelGGL(osd0_kernel, dim3(grid), dim3(L.block), L.lds, stream, P);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }
@@ -452,6 +422,9 @@ __global__ void iota_list_kernel(int64_t B, int32_t *list, int32_t *count) {
     if (t < B) list[t] = (int32_t)t;
     if (t == 0) *count = (int32_t)B;
 }
+void iota_list_launch(int64_t B, int32_t *list, int32_t *count, hipStream_t s) {
+    hipLaunchKernelGGL(iota_list_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, list, count);
+}
 
 }  // namespace qldpc
 
@@ -469,7 +442,7 @@ QLDPC_EXPORT int qldpc_gf2_eliminate_packed(int64_t B, int m, int n, int nwords,
     QLDPC_REQUIRE(A && b && pivot_rows && pivot_cols, "NULL buffer");
     const int maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
-    QLDPC_REQUIRE(lds <= 150 * 1024, "matrix too large for the LDS scratch");
+    QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
     DevTmp dA, db, dpr, dpc, dn;
     if ((rc = dA.alloc((size_t)B * m * nwords * 8)) || (rc = db.alloc((size_t)B * m)) || (rc = dpr.alloc((size_t)B * maxp * 8)) ||
         (rc = dpc.alloc((size_t)B * maxp * 8)) || (rc = dn.alloc((size_t)B * 4)))
@@ -503,7 +476,7 @@ QLDPC_EXPORT int qldpc_gf2_eliminate(int64_t B, int m, int n, uint8_t *A, uint8_
     QLDPC_REQUIRE(A && b && pivot_rows && pivot_cols, "NULL buffer");
     const int nwords = ((n + 7) / 8 + 7) / 8, maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
-    QLDPC_REQUIRE(lds <= 150 * 1024, "matrix too large for the LDS scratch");
+    QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
     DevTmp dA8, dA, db, dpr, dpc, dn;
     const int64_t rows = B * m;
     if ((rc = dA8.alloc((size_t)rows * n)) || (rc = dA.alloc((size_t)rows * nwords * 8)) || (rc = db.alloc((size_t)rows)) ||
@@ -547,7 +520,7 @@ QLDPC_EXPORT int qldpc_osd0_batch(const qldpc_graph *g, int64_t B, const int8_t 
     QLDPC_HIP_TRY(hipMemcpy(dl.p, llr, B * n * 8, hipMemcpyHostToDevice));
     QLDPC_HIP_TRY(hipMemcpy(dh.p, hard, B * n, hipMemcpyHostToDevice));
     if (ordering) QLDPC_HIP_TRY(hipMemcpy(dord.p, ordering, B * n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(iota_list_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, nullptr, B, dlist.as<int32_t>(), dcnt.as<int32_t>());
+    iota_list_launch(B, dlist.as<int32_t>(), dcnt.as<int32_t>(), nullptr);
     {
         std::lock_guard<std::mutex> lk(g->mu);
         rc = osd0_listed_launch(g, dlist.as<int32_t>(), dcnt.as<int32_t>(), B, ds.as<int8_t>(), dl.as<double>(), dh.as<int8_t>(),
@@ -579,7 +552,7 @@ QLDPC_EXPORT int qldpc_osd0_batch_dev(const qldpc_graph *g, int64_t B, const int
         if ((rc = g->ws_acquire(s)) != QLDPC_OK) return rc;
         if ((rc = g->ws_list.ensure((size_t)B * 4 + 16)) != QLDPC_OK) { (void)g->ws_release(s); return rc; }
         int32_t *cnt = g->ws_list.as<int32_t>(), *list = cnt + 4;
-        hipLaunchKernelGGL(iota_list_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, list, cnt);
+        iota_list_launch(B, list, cnt, s);
         d_select = list; d_select_count = cnt;
     }
     return osd0_listed_launch(g, d_select, d_select_count, B, d_syndromes, d_llr, d_hard, d_ordering, d_solution, flags & QLDPC_FLAG_PUBLIC_MASK, s);
@@ -611,7 +584,7 @@ QLDPC_EXPORT int qldpc_osdw_batch(const qldpc_graph *g, int64_t B, const int8_t 
     }
     const int nwords = ((n + 7) / 8 + 7) / 8, maxp = m < n ? m : n, block = 256;
     const size_t lds = elim_lds_bytes(m, nwords);
-    if (lds > 150 * 1024) { set_error("OSD-w: matrix too large for the LDS scratch (m=%d nwords=%d)", m, nwords); return QLDPC_ERR_UNSUPPORTED; }
+    if (lds > (size_t)kOsdElimMax) { set_error("OSD-w: matrix too large for the LDS scratch (m=%d nwords=%d)", m, nwords); return QLDPC_ERR_UNSUPPORTED; }
     const size_t slab = (size_t)m * nwords * 8 + (size_t)m + (size_t)n * 18 + (size_t)maxp * 8 + (size_t)block * n + (size_t)kOsdwMaxCand * 12 + 256;
     int grid = (int)std::min<int64_t>(B, 64);
     while (grid > 1 && (size_t)grid * slab > ((size_t)2 << 30)) grid /= 2;
@@ -628,7 +601,7 @@ QLDPC_EXPORT int qldpc_osdw_batch(const qldpc_graph *g, int64_t B, const int8_t 
     QLDPC_HIP_TRY(hipMemcpy(dl.p, llr, (size_t)B * n * 8, hipMemcpyHostToDevice));
     QLDPC_HIP_TRY(hipMemcpy(dh.p, hard, (size_t)B * n, hipMemcpyHostToDevice));
     if (ordering) QLDPC_HIP_TRY(hipMemcpy(dord.p, ordering, (size_t)B * n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(iota_list_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, nullptr, B, dlist.as<int32_t>(), dcnt.as<int32_t>());
+    iota_list_launch(B, dlist.as<int32_t>(), dcnt.as<int32_t>(), nullptr);
     OsdwArgs W;
     W.base.m = m; W.base.n = n; W.base.nwords = nwords; W.base.indptr = g->d_indptr; W.base.indices = g->d_indices;
     W.base.list = dlist.as<int32_t>(); W.base.count = dcnt.as<int32_t>(); W.base.synd = ds.as<int8_t>(); W.base.llr = dl.as<double>();
@@ -682,10 +655,6 @@ struct OsdLdsArgs {
     int offIdx, offAlive, offRows, offPc, offR, offBlk, offMisc, offSort;
 };
 
-#ifndef QLDPC_OSD_BLOCK
-#define QLDPC_OSD_BLOCK 16
-#endif
-constexpr int kOsdBlock = QLDPC_OSD_BLOCK;      // columns resolved per block (4 per register of the resolving wave)
 static_assert(kOsdBlock <= 16, "one wave per column, at most 4 columns per wave with 256-thread blocks");
 
 // Position-space formulation.  T (current rows = T * original rows, rows in their CURRENT physical order, i.e. after the
@@ -1103,9 +1072,6 @@ int ensure_col_rows(const qldpc_graph *g) {
     return QLDPC_OK;
 }
 
-int osd0_small_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, const int8_t *d_synd, const double *d_llr,
-                      const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled, OsdJudge *judge);
-
 // rank of H over GF(2) (host, once per graph): the sweep above can stop as soon as this many pivots exist
 int host_gf2_rank(const qldpc_graph *g) {
     const int m = g->m, n = g->n, nw = (n + 63) / 64;
@@ -1127,101 +1093,80 @@ int host_gf2_rank(const qldpc_graph *g) {
     return rank;
 }
 
-// 0: not applicable (use the global-memory elimination), 1: U in LDS (m <= 1024), 2: U in HBM/L2 (m <= 4096, "UG")
-static int plan_osd_lds(const qldpc_graph *g, OsdLdsArgs &P, size_t &lds, int flags) {
-    if (g->m > 4096 || g->n >= 65535 || g->m < 1) return 0;
-    P.m = g->m; P.n = g->n; P.mw = (g->m + 63) / 64; P.K = 1024; P.cdeg = std::max(g->max_col_deg, 1);
-    P.npad = 1;
-    while (P.npad < g->n) P.npad <<= 1;
-    for (int mode = (g->m <= 1024 && !(flags & QLDPC_FLAG_OSD_UG)) ? 1 : 2; mode <= 2; mode++) {
-        const size_t sort_cnt = (size_t)256 * 16 * 4 + 16 * 4 + 64;                         // [256][waves] radix counters + per-wave sums
-        size_t off = (mode == 1) ? std::max((size_t)(g->m + 2) * P.mw * 8, (size_t)g->n * 12 + 16 + sort_cnt) : 0;     // U, aliased by the sort scratch
-        off = (size_t)round_up((int64_t)off, 16);
-        P.offIdx = (int)off; off += (size_t)P.K * 2;
-        P.offAlive = (int)off; off += (size_t)P.K;
-        P.offRows = (int)off; off += (size_t)P.K * P.cdeg * 2;
-        P.offPc = (int)off; off += round_up((int64_t)g->m * 2, 8);
-        P.offR = (int)off; off += (size_t)kOsdBlock * P.mw * 8;
-        P.offBlk = (int)off; off += (4 + 6 * kOsdBlock + 4) * 4;
-        P.offMisc = (int)off; off += 64;
-        P.offSort = (int)off; off += (mode == 2) ? sort_cnt : 0;
-        lds = off + 16;
-        if (lds <= 160 * 1024) return mode;
-    }
-    return 0;
+// g->ws_misc per workgroup: the column order in flight [n] and, for the kernels that keep U in HBM / L2 (ug), U [(m + 2) * mw] and the sort's keys + indices [n + (n + 1) / 2]
+int osd_ug_slabs(const qldpc_graph *g, int grid, bool ug, uint16_t *&ordws, unsigned long long *&U, unsigned long long *&keys) {
+    const size_t sz_ord = (size_t)round_up((int64_t)grid * g->n * 2 + 64, 16);
+    const size_t sz_u = ug ? (size_t)grid * (size_t)(g->m + 2) * ((g->m + 63) / 64) * 8 : 0, sz_k = ug ? (size_t)grid * ((size_t)g->n + (size_t)(g->n + 1) / 2) * 8 : 0;
+    if (const int rc = g->ws_misc.ensure(sz_ord + sz_u + sz_k)) return rc;
+    unsigned char *base = g->ws_misc.as<unsigned char>();
+    ordws = reinterpret_cast<uint16_t *>(base);
+    U = reinterpret_cast<unsigned long long *>(base + sz_ord);
+    keys = reinterpret_cast<unsigned long long *>(base + sz_ord + sz_u);
+    return QLDPC_OK;
 }
 
-int osd0_gj_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                   const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled);
-
-int osd0_gjg_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                    const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, hipStream_t stream, size_t ws_offset, bool &handled);
-
-int osd0_lds_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                    const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled, OsdJudge *judge) {
+// the reference-order kernel in the form the plan (osd_plan.h) chose: L.kernel REFORDER_LDS = mode 1 (U in LDS), REFORDER_UG = mode 2 (U in HBM / L2)
+static int osd0_reforder_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream) {
+    const int mode = (L.kernel == QLDPC_OSD_PATH_REFORDER_UG) ? 2 : 1;
     OsdLdsArgs P;
-    size_t lds = 0;
-    handled = false;
-    if (!(flags & (QLDPC_FLAG_OSD_LDS | QLDPC_FLAG_OSD_UG | QLDPC_FLAG_OSD_GLOBAL))) {      // small matrices: the literal elimination, one wave per shot
-        const int rcs = osd0_small_launch(g, d_list, d_count, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, handled, judge);
-        if (rcs == QLDPC_OK && handled) g->osd_path = QLDPC_OSD_PATH_SMALL;
-        if (rcs != QLDPC_OK || handled) return rcs;
-    }
-#ifndef QLDPC_EXPERIMENTS
-    if (flags & QLDPC_FLAG_OSD_QUEUE) {
-        set_error("this OSD-0 variant (flags %#x) is a measured-and-rejected experiment: it exists in libqldpc_hip_experiments.so only (make experiments)", flags);
-        return QLDPC_ERR_UNSUPPORTED;
-    }
-#endif
-    if (!(flags & (QLDPC_FLAG_OSD_REFORDER | QLDPC_FLAG_OSD_GLOBAL))) {
-        // the free-pivot kernels take every shot -- osd_gj.hip with the row transform in LDS (m <= 1024), osd_gjg.hip with it in HBM / L2 (m <= 4096, or
-        // asked for by QLDPC_FLAG_OSD_UG); the shots they list (right-hand side outside the column space, where the answer depends on the reference's row
-        // choice) go through the reference-order kernel below, behind them on the same stream
-        bool took = false;
-        if (!(flags & QLDPC_FLAG_OSD_UG)) {
-            const int rcg = osd0_gj_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, flags, stream, took);
-            if (rcg != QLDPC_OK) return rcg;
-            if (took) g->osd_path = QLDPC_OSD_PATH_GJ;
-        }
-        if (!took) {
-            const int rcg = osd0_gjg_launch(g, d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution, stream, 0, took);
-            if (rcg != QLDPC_OK) return rcg;
-            if (took) g->osd_path = QLDPC_OSD_PATH_GJG;
-        }
-        if (took) { d_count = g->ws_redo.as<int32_t>(); d_list = d_count + 4; }
-    }
-    const int mode = (flags & QLDPC_FLAG_OSD_GLOBAL) ? 0 : plan_osd_lds(g, P, lds, flags);
-    g->osd_detail = mode & QLDPC_OSD_DETAIL_MODE_MASK;
-    if (mode == 0) return QLDPC_OK;
-    if (g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);      // callers hold g->mu
+    P.m = g->m; P.n = g->n; P.mw = (g->m + 63) / 64; P.K = kOsdChunk; P.cdeg = std::max(g->max_col_deg, 1);
+    P.npad = 1;
+    while (P.npad < g->n) P.npad <<= 1;
+    osd_ref_layout(P.m, P.n, P.cdeg, mode, P);
     P.rankH = g->gf2_rank;
     const int grid = 512;
-    const size_t sz_ord = (size_t)round_up((int64_t)grid * g->n * 2 + 64, 16);
-    const size_t sz_u = (mode == 2) ? (size_t)grid * (size_t)(g->m + 2) * P.mw * 8 : 0;
-    const size_t per_keys = (size_t)g->n + (size_t)(g->n + 1) / 2;                       // u64 units: n keys + 2 x n u16 indices
-    const size_t sz_k = (mode == 2) ? (size_t)grid * per_keys * 8 : 0;
-    int rc = g->ws_misc.ensure(sz_ord + sz_u + sz_k);
+    int rc = osd_ug_slabs(g, grid, mode == 2, P.ordws, P.ug, P.ugkeys);
     if (rc != QLDPC_OK) return rc;
-    P.ordws = g->ws_misc.as<uint16_t>();
-    P.ug = reinterpret_cast<unsigned long long *>(g->ws_misc.as<unsigned char>() + sz_ord);
-    P.ugkeys = reinterpret_cast<unsigned long long *>(g->ws_misc.as<unsigned char>() + sz_ord + sz_u);
     P.indptr = g->d_indptr; P.indices = g->d_indices; P.colptr = g->d_colptr; P.rowidx = g->d_rowidx;
-    P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.ordering = d_ordering; P.solution = d_solution;
+    P.list = S.list; P.count = S.count; P.synd = S.synd; P.llr = S.llr; P.hard = S.hard; P.ordering = S.ordering; P.solution = S.solution;
     P.clk = g->clk_probe;
     P.dbg = osd_timer_buffer();      // NULL unless built with -DQLDPC_OSD_TIMERS (make timers)
-    const int block = (int)std::min<int64_t>(1024, round_up(std::max(g->m + 2, 256), 64));
     if ((rc = g->ws_queue.ensure(16)) != QLDPC_OK) return rc;
     P.queue = g->ws_queue.as<int>() + 2;
     QLDPC_HIP_TRY(hipMemsetAsync(P.queue, 0, 4, stream));
-    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_lds_kernel<false>), 160 * 1024)) != QLDPC_OK) return rc;
-    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_lds_kernel<true>), 160 * 1024)) != QLDPC_OK) return rc;
-    if (mode == 2) hipLaunchKernelGGL(osd0_lds_kernel<true>, dim3(grid), dim3(1024), lds, stream, P);
-    else hipLaunchKernelGGL(osd0_lds_kernel<false>, dim3(grid), dim3(block), lds, stream, P);
+    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_lds_kernel<false>), kOsdLdsMax)) != QLDPC_OK) return rc;
+    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_lds_kernel<true>), kOsdLdsMax)) != QLDPC_OK) return rc;
+    if (mode == 2) hipLaunchKernelGGL(osd0_lds_kernel<true>, dim3(grid), dim3(L.block), L.lds, stream, P);
+    else hipLaunchKernelGGL(osd0_lds_kernel<false>, dim3(grid), dim3(L.block), L.lds, stream, P);
     QLDPC_HIP_TRY(hipGetLastError());
-    if (g->osd_path == QLDPC_OSD_PATH_NONE) g->osd_path = (mode == 2) ? QLDPC_OSD_PATH_REFORDER_UG : QLDPC_OSD_PATH_REFORDER_LDS;
-    else g->osd_detail |= QLDPC_OSD_DETAIL_REDO;       // behind a free-pivot kernel, on the shots it listed in ws_redo
-    handled = true;
     return QLDPC_OK;
+}
+
+// OSD-0 on the listed shots: builds the plan (osd_plan.h has the rule) and executes it; a refused call launches no kernel.  Callers hold g->mu; the graph's
+// device workspaces are handed over in stream order (common.h).
+int osd0_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
+                       const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, OsdJudge *judge) {
+    const Osd0Plan plan = osd0_plan(g->m, g->n, g->max_col_deg, flags);      // (an empty matrix: no kernel, nothing refused)
+    const OsdShots all{d_list, d_count, max_listed, d_synd, d_llr, d_hard, d_ordering, d_solution};
+    auto launch = [&](const OsdLaunch &L, const OsdShots &S) -> int {
+        switch (L.kernel) {
+            case QLDPC_OSD_PATH_SMALL: return osd0_small_launch(g, L, S, stream, flags, judge);
+            case QLDPC_OSD_PATH_GJ: return osd0_gj_launch(g, L, S, stream, plan.w16, plan.queue_first);
+            case QLDPC_OSD_PATH_GJG: return osd0_gjg_launch(g, L, S, stream);
+            case QLDPC_OSD_PATH_GLOBAL: return osd0_global_launch(g, L, S, stream);
+            default: return osd0_reforder_launch(g, L, S, stream);
+        }
+    };
+    int rc = QLDPC_OK;
+    // acquired before a refusal too: the caller may have enqueued on the workspaces (qldpc_osd0_batch_dev's iota list), and only a stream that waited may release
+    if (g->m > 0 && g->n > 0 && (rc = g->ws_acquire(stream)) == QLDPC_OK) {      // (a no-op for a caller that holds the workspaces on this stream)
+        if (plan.refused == kOsdRefusedQueue) set_error("this OSD-0 variant (flags %#x) is a measured-and-rejected experiment: it exists in libqldpc_hip_experiments.so only (make experiments)", flags);
+        if (plan.refused == kOsdRefusedSize) set_error("OSD-0: matrix too large for the LDS scratch (m=%d nwords=%d)", g->m, osd_global_nwords(g->n));
+        if (plan.refused) rc = QLDPC_ERR_UNSUPPORTED;      // nothing is launched
+        else if (plan.first.kernel != QLDPC_OSD_PATH_GLOBAL && g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);      // every sweep but the global kernel's stops at rank(H)
+        if (rc == QLDPC_OK) rc = launch(plan.first, all);
+        if (rc == QLDPC_OK && plan.second.kernel != QLDPC_OSD_PATH_NONE) {
+            OsdShots redo = all;      // the reference-order kernel takes the shots the free-pivot kernel listed in ws_redo; GLOBAL (the route no shape reaches) every shot again
+            if (plan.second.kernel != QLDPC_OSD_PATH_GLOBAL) { redo.count = g->ws_redo.as<int32_t>(); redo.list = redo.count + 4; }
+            rc = launch(plan.second, redo);
+        }
+        const int rel = g->ws_release(stream);      // always: a failing call may have enqueued launches the next stream has to wait for
+        if (rc == QLDPC_OK) rc = rel;
+    }
+    // what qldpc_osd0_last_path reports: the plan that was executed; (NONE, 0) for an empty matrix (its plan says so), a refused call and a failed one
+    g->osd_path = (rc == QLDPC_OK) ? plan.path() : QLDPC_OSD_PATH_NONE;
+    g->osd_detail = (rc == QLDPC_OK) ? plan.detail() : 0;
+    return rc;
 }
 
 }  // namespace qldpc

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "mc_common.h"
 #include "minsum_common.h"
+#include "osd_common.h"
 
 #include <cmath>
 #include <vector>

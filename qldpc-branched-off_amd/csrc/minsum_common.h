@@ -79,7 +79,6 @@ int mc_regular_fill_cold(void *d_cold, unsigned long long *d_tally, int32_t *d_f
 size_t mc_regular_cold_bytes();
 int judge_failed_launch(const qldpc_graph *g, int32_t *d_count, bool reset_counters, int *d_osd_queue, const uint64_t *d_Lmask, const int8_t *f_err, const int8_t *f_synd,
                         const int8_t *f_dec, unsigned long long *d_tally, hipStream_t stream);
-int osd_small_queue(const qldpc_graph *g, int **queue);      // osd_small.hip
 // wave-private kernel for (6,3)-regular graphs and clean inputs (minsum_wave.hip); option "regular_kernel" selects between the two
 bool wave_supported(const qldpc_graph *g, double damping, bool clean);
 int wave_kernel_choice();     // 0 automatic, 1 team kernel, 2 wave kernel (qldpc_set_option)

@@ -30,9 +30,6 @@
 
 namespace qldpc {
 
-int host_gf2_rank(const qldpc_graph *g);
-int ensure_col_rows(const qldpc_graph *g);
-
 constexpr int kCsChunk = 64;
 constexpr int kCsMaxOrder = 64;
 
@@ -359,33 +356,17 @@ __global__ __launch_bounds__(1024) void osd_cs_kernel(OsdCsArgs P) {
     }
 }
 
-__global__ void osdcs_iota_kernel(int64_t B, int32_t *list, int32_t *count) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B) list[i] = (int32_t)i;
-    if (i == 0) *count = (int32_t)B;
-}
-
-static void iota_list_launch(int64_t B, int32_t *list, int32_t *count, hipStream_t s) {
-    hipLaunchKernelGGL(osdcs_iota_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, list, count);
-}
-
 // LDS layout; gsort = true when the column sort has to run in global memory (it does not fit beside nothing in LDS)
 static int osdcs_layout(const qldpc_graph *g, int order, OsdCsArgs &P, size_t &lds, bool &gsort) {
     const int m = g->m, n = g->n;
     P.m = m; P.n = n; P.mw = (m + 63) / 64; P.cdeg = std::max(g->max_col_deg, 1); P.order = order;
-    const size_t sort_cnt = (size_t)256 * 16 * 4 + 16 * 4 + 64;
-    const size_t u_bytes = (size_t)(m + 2) * P.mw * 8, sort_bytes = (size_t)n * 12 + 16 + sort_cnt;
     for (int lsort = 1; lsort >= 0; lsort--) {
-        size_t off = (size_t)round_up((int64_t)(lsort ? std::max(u_bytes, sort_bytes) : u_bytes), 16);
-        P.offUsed = (int)off; off += 16 * 8;
-        P.offPc = (int)off; off += round_up((int64_t)m * 2, 8);
-        P.offPr = (int)off; off += round_up((int64_t)m * 2, 8);
-        P.offR = (int)off; off += (size_t)kCsChunk * P.mw * 8;              // (>= m * 8: the signed pivot weights of the scoring phase)
-        P.offTR = (int)off; off += (size_t)std::max(order, 1) * P.mw * 8;
-        P.offPf = (int)off; off += round_up((int64_t)((n + 31) / 32) * 4, 16);
-        P.offMisc = (int)off; off += 2048;
-        lds = off + 16;
-        if (lds <= 160 * 1024) { gsort = !lsort; return QLDPC_OK; }
+        OsdCarve c{lsort ? osd_u_or_sort_bytes(m, n, P.mw) : osd_align((size_t)(m + 2) * P.mw * 8, 16)};      // U, aliased by the sort scratch if that fits
+        P.offUsed = c.take(16 * 8); P.offPc = c.take(osd_align(m * 2, 8)); P.offPr = c.take(osd_align(m * 2, 8));
+        P.offR = c.take((size_t)kCsChunk * P.mw * 8);              // (>= m * 8: the signed pivot weights of the scoring phase)
+        P.offTR = c.take((size_t)std::max(order, 1) * P.mw * 8); P.offPf = c.take(osd_align((size_t)((n + 31) / 32) * 4, 16)); P.offMisc = c.take(2048);
+        lds = c.off + 16;
+        if (lds <= (size_t)kOsdLdsMax) { gsort = !lsort; return QLDPC_OK; }
     }
     set_error("OSD-CS: %d x %d matrix needs more LDS than the 160 KiB of a workgroup", m, n);
     return QLDPC_ERR_UNSUPPORTED;
@@ -435,9 +416,8 @@ int osdcs_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32
         P.col_rows = g->d_col_rows; P.indptr = g->d_indptr; P.indices = g->d_indices;
         P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.weights = d_weights;
         P.solution = d_solution; P.flips = d_flips;
-        const int block = (int)std::min<int64_t>(1024, round_up(std::max(g->m + 2, 256), 64));
-        if ((rcl = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd_cs_kernel), 160 * 1024)) != QLDPC_OK) return rcl;
-        hipLaunchKernelGGL(osd_cs_kernel, dim3(grid), dim3(block), lds, stream, P);
+        if ((rcl = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd_cs_kernel), kOsdLdsMax)) != QLDPC_OK) return rcl;
+        hipLaunchKernelGGL(osd_cs_kernel, dim3(grid), dim3(osd_wide_block(g->m)), lds, stream, P);
         QLDPC_HIP_TRY(hipGetLastError());
         return QLDPC_OK;
     };

@@ -24,11 +24,12 @@ struct OsdGjArgs {
     size_t sortws_words;
 };
 
-int osd_presort_choice();          // option "osd_presort" (options.hip)
+int osd_presort_choice();          // option "osd_presort" (options.hip); osd_presort_columns (osd_plan.h) turns it into P.presort
+int osd_gj_fill(const qldpc_graph *g, const OsdShots &S, hipStream_t stream, OsdGjArgs &P);      // osd_gj.hip: what GJ and GJG fill alike
+#ifdef QLDPC_EXPERIMENTS
+int osd0_gjq_launch(const qldpc_graph *g, const OsdGjArgs &base, int grid, hipStream_t stream, bool &launched);      // osd_gjq.hip
+#endif
 
-int host_gf2_rank(const qldpc_graph *g);
-
-constexpr int kGjBlock = 16;
 #ifndef QLDPC_GJ_DENSELANES
 #define QLDPC_GJ_DENSELANES 40
 #endif

@@ -471,66 +471,49 @@ __global__ __launch_bounds__(1024) void osd0_gj_kernel(OsdGjArgs P) {
     clk_end(P.clk, clk0);
 }
 
-// handled = true when this kernel took the shots.  The shots it could not answer (right-hand side outside the column space) are left in
-// g->ws_redo ([0] count, [4..] shot indices) for the reference-order kernel, which the caller launches behind this one on the same stream.
-int osd0_gjq_launch(const qldpc_graph *g, const OsdGjArgs &base, int grid, hipStream_t stream, bool &launched);
-
-int osd0_gj_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                   const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled) {
-    handled = false;
-    if (g->m > 1024 || g->m < 1 || g->n >= 65535 || g->n < 1) return QLDPC_OK;
-    OsdGjArgs P;
-    P.m = g->m; P.n = g->n; P.mw = (g->m + 63) / 64; P.K = 1024; P.cdeg = std::max(g->max_col_deg, 1);
-    const size_t sort_cnt = (size_t)256 * 16 * 4 + 16 * 4 + 64;
-    size_t off = std::max((size_t)(g->m + 2) * P.mw * 8, (size_t)g->n * 12 + 16 + sort_cnt);       // U, aliased by the sort scratch
-    off = (size_t)round_up((int64_t)off, 16);
-    P.offIdx = (int)off; off += (size_t)P.K * 2;
-    P.offAlive = (int)off; off += (size_t)P.K;
-    P.offRows = (int)off; off += (size_t)round_up((int64_t)P.K * P.cdeg * 2, 8);
-    P.offPc = (int)off; off += round_up((int64_t)g->m * 2, 8);
-    P.offPr = (int)off; off += round_up((int64_t)g->m * 2, 8);
-    P.offR = (int)off; off += (size_t)3 * kGjBlock * P.mw * 8;
-    P.offUsed = (int)off; off += 32 * 8;
-    P.offBlk = (int)off; off += (4 + 5 * kGjBlock + 8) * 4;
-    P.offTl = (int)off; off += (size_t)round_up((int64_t)(g->m + 2) * 4, 16);
-    const size_t lds = off + 16;
-    if (lds > 160 * 1024) return QLDPC_OK;
-    if (g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);      // callers hold g->mu
-    P.rankH = g->gf2_rank;
-    const int grid = 512;
-    // per workgroup: the column order in flight, and global scratch for ordering the columns behind the sorted head (keys, two index arrays, counters)
-    const size_t ord_bytes = (size_t)round_up((int64_t)grid * g->n * 2 + 64, 16);
-    P.sortws_words = (size_t)g->n + (size_t)(g->n + 3) / 2 + (256 * 16 + 64) / 2 + 8;
-    int rc = g->ws_misc.ensure(ord_bytes + (size_t)grid * P.sortws_words * 8);
-    if (rc != QLDPC_OK) return rc;
-    P.sortws = reinterpret_cast<unsigned long long *>(g->ws_misc.as<unsigned char>() + ord_bytes);
-    P.presort = osd_presort_choice() < 0 ? (int)round_up(std::max(g->m, 1024), 1024) : osd_presort_choice();      // (automatic: about m columns, whole chunks)
-    if ((rc = g->ws_redo.ensure((size_t)(max_listed + 4) * 4)) != QLDPC_OK) return rc;
-    if ((rc = g->ws_queue.ensure(16)) != QLDPC_OK) return rc;
-    P.ordws = g->ws_misc.as<uint16_t>();
+// what both free-pivot launchers (this file, osd_gjg.hip) fill alike; the ticket counter and the count of the redo list in g->ws_redo are zeroed on the stream
+int osd_gj_fill(const qldpc_graph *g, const OsdShots &S, hipStream_t stream, OsdGjArgs &P) {
+    P = OsdGjArgs{};
+    P.m = g->m; P.n = g->n; P.mw = (g->m + 63) / 64; P.K = kOsdChunk; P.cdeg = std::max(g->max_col_deg, 1); P.rankH = g->gf2_rank;
+    P.presort = osd_presort_columns(g->m, osd_presort_choice());
     P.colptr = g->d_colptr; P.rowidx = g->d_rowidx; P.indptr = g->d_indptr; P.indices = g->d_indices;
-    P.ell_col = (g->d_ell_col && g->d_deg_of_row) ? g->d_ell_col : nullptr; P.deg_of_row = g->d_deg_of_row;
-    P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.ordering = d_ordering; P.solution = d_solution;
-    P.clk = g->clk_probe;
+    P.list = S.list; P.count = S.count; P.synd = S.synd; P.llr = S.llr; P.hard = S.hard; P.ordering = S.ordering; P.solution = S.solution;
     P.dbg = osd_timer_buffer();
+    int rc = g->ws_redo.ensure((size_t)(S.max_listed + 4) * 4);
+    if (rc != QLDPC_OK || (rc = g->ws_queue.ensure(16)) != QLDPC_OK) return rc;
     P.queue = g->ws_queue.as<int>() + 3;
     P.redo_count = g->ws_redo.as<int32_t>(); P.redo_list = P.redo_count + 4;
     QLDPC_HIP_TRY(hipMemsetAsync(P.queue, 0, 4, stream));
     QLDPC_HIP_TRY(hipMemsetAsync(P.redo_count, 0, 4, stream));
-    const int block = (int)std::min<int64_t>(1024, round_up(std::max(g->m + 2, 256), 64));
-    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gj_kernel<true>), 160 * 1024)) != QLDPC_OK) return rc;
-    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gj_kernel<false>), 160 * 1024)) != QLDPC_OK) return rc;
+    return QLDPC_OK;
+}
+
+// the plan (osd_plan.h) chose this kernel: m <= 1024 and osd_gj_layout fits LDS
+int osd0_gj_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream, bool w16, bool queue_first) {
+    OsdGjArgs P;
+    int rc = osd_gj_fill(g, S, stream, P);
+    if (rc != QLDPC_OK) return rc;
+    osd_gj_layout(P.m, P.n, P.cdeg, P);
+    const int grid = 512;
+    // per workgroup: the column order in flight, and global scratch for ordering the columns behind the sorted head (keys, two index arrays, counters)
+    const size_t ord_bytes = (size_t)round_up((int64_t)grid * g->n * 2 + 64, 16);
+    P.sortws_words = (size_t)g->n + (size_t)(g->n + 3) / 2 + (256 * 16 + 64) / 2 + 8;
+    if ((rc = g->ws_misc.ensure(ord_bytes + (size_t)grid * P.sortws_words * 8)) != QLDPC_OK) return rc;
+    P.ordws = g->ws_misc.as<uint16_t>();
+    P.sortws = reinterpret_cast<unsigned long long *>(g->ws_misc.as<unsigned char>() + ord_bytes);
+    P.ell_col = (g->d_ell_col && g->d_deg_of_row) ? g->d_ell_col : nullptr; P.deg_of_row = g->d_deg_of_row;
+    P.clk = g->clk_probe;
+    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gj_kernel<true>), kOsdLdsMax)) != QLDPC_OK) return rc;
+    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gj_kernel<false>), kOsdLdsMax)) != QLDPC_OK) return rc;
 #ifdef QLDPC_EXPERIMENTS
-    if (P.mw == 16 && block == 1024 && (flags & QLDPC_FLAG_OSD_QUEUE)) {      // the look-ahead-queue form (osd_gjq.hip): measured 25 % slower (profiles/r03_experiments.txt item 12)
+    if (queue_first) {      // the look-ahead-queue form (osd_gjq.hip): measured 25 % slower (profiles/r03_experiments.txt item 12)
         bool launched = false;
-        if ((rc = osd0_gjq_launch(g, P, grid, stream, launched)) != QLDPC_OK) return rc;
-        if (launched) { handled = true; return QLDPC_OK; }
+        if ((rc = osd0_gjq_launch(g, P, grid, stream, launched)) != QLDPC_OK || launched) return rc;
     }
 #endif
-    if (P.mw == 16 && block == 1024) hipLaunchKernelGGL(osd0_gj_kernel<true>, dim3(grid), dim3(block), lds, stream, P);
-    else hipLaunchKernelGGL(osd0_gj_kernel<false>, dim3(grid), dim3(block), lds, stream, P);
+    if (w16) hipLaunchKernelGGL(osd0_gj_kernel<true>, dim3(grid), dim3(L.block), L.lds, stream, P);
+    else hipLaunchKernelGGL(osd0_gj_kernel<false>, dim3(grid), dim3(L.block), L.lds, stream, P);
     QLDPC_HIP_TRY(hipGetLastError());
-    handled = true;
     return QLDPC_OK;
 }
 

@@ -328,57 +328,18 @@ __global__ __launch_bounds__(1024) void osd0_gjg_kernel(OsdGjgArgs PP) {
     }
 }
 
-// handled = true when this kernel took the shots; the ones it lists in g->ws_redo go through the reference-order kernel (osd0_lds_kernel<UG = true>)
-int osd0_gjg_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
-                    const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, hipStream_t stream, size_t ws_offset, bool &handled) {
-    handled = false;
-    if (g->m > 4096 || g->m < 1 || g->n >= 65535 || g->n < 1) return QLDPC_OK;
+// the plan (osd_plan.h) chose this kernel: m <= 4096 and osd_gjg_layout fits LDS; the shots it lists in g->ws_redo go through the reference-order kernel
+int osd0_gjg_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream) {
     OsdGjgArgs PP;
     OsdGjArgs &P = PP.A;
-    P = OsdGjArgs{};
-    P.m = g->m; P.n = g->n; P.mw = (g->m + 63) / 64; P.K = 1024; P.cdeg = std::max(g->max_col_deg, 1);
-    P.presort = osd_presort_choice() < 0 ? (int)round_up(std::max(g->m, 1024), 1024) : osd_presort_choice();      // (automatic: about m columns, whole chunks)
-    const size_t sort_cnt = (size_t)256 * 16 * 4 + 16 * 4 + 64;
-    size_t off = 0;
-    PP.offSort = (int)off; off += sort_cnt;
-    off = (size_t)round_up((int64_t)off, 16);
-    P.offIdx = (int)off; off += (size_t)P.K * 2;
-    PP.offAlive = (int)off; off += (size_t)P.K;
-    P.offRows = (int)off; off += (size_t)round_up((int64_t)P.K * P.cdeg * 2, 8);
-    P.offPc = (int)off; off += round_up((int64_t)g->m * 2, 8);
-    P.offPr = (int)off; off += round_up((int64_t)g->m * 2, 8);
-    P.offR = (int)off; off += (size_t)kGjBlock * P.mw * 8;
-    P.offUsed = (int)off; off += 128 * 8;
-    P.offBlk = (int)off; off += (4 + 2 * kGjBlock + 4) * 4;
-    const size_t lds = off + 16;
-    if (lds > 160 * 1024) return QLDPC_OK;
-    if (g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);      // callers hold g->mu
-    P.rankH = g->gf2_rank;
-    const int grid = 512;
-    const size_t sz_ord = (size_t)round_up((int64_t)grid * g->n * 2 + 64, 16);
-    const size_t sz_u = (size_t)grid * (size_t)(g->m + 2) * P.mw * 8;
-    const size_t per_keys = (size_t)g->n + (size_t)(g->n + 1) / 2;
-    const size_t sz_k = (size_t)grid * per_keys * 8;
-    int rc = g->ws_misc.ensure(ws_offset + sz_ord + sz_u + sz_k);
+    int rc = osd_gj_fill(g, S, stream, P);      // (no slot-major row view, no clock probe here: both stay NULL)
     if (rc != QLDPC_OK) return rc;
-    if ((rc = g->ws_redo.ensure((size_t)(max_listed + 4) * 4)) != QLDPC_OK) return rc;
-    if ((rc = g->ws_queue.ensure(16)) != QLDPC_OK) return rc;
-    unsigned char *base = g->ws_misc.as<unsigned char>() + ws_offset;
-    P.ordws = reinterpret_cast<uint16_t *>(base);
-    PP.ug = reinterpret_cast<unsigned long long *>(base + sz_ord);
-    PP.ugkeys = reinterpret_cast<unsigned long long *>(base + sz_ord + sz_u);
-    P.colptr = g->d_colptr; P.rowidx = g->d_rowidx; P.indptr = g->d_indptr; P.indices = g->d_indices;
-    P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.ordering = d_ordering; P.solution = d_solution;
-    P.clk = nullptr;
-    P.dbg = osd_timer_buffer();
-    P.queue = g->ws_queue.as<int>() + 3;
-    P.redo_count = g->ws_redo.as<int32_t>(); P.redo_list = P.redo_count + 4;
-    QLDPC_HIP_TRY(hipMemsetAsync(P.queue, 0, 4, stream));
-    QLDPC_HIP_TRY(hipMemsetAsync(P.redo_count, 0, 4, stream));
-    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gjg_kernel), 160 * 1024)) != QLDPC_OK) return rc;
-    hipLaunchKernelGGL(osd0_gjg_kernel, dim3(grid), dim3(1024), lds, stream, PP);
+    osd_gjg_layout(P.m, P.cdeg, P, PP);
+    const int grid = 512;
+    if ((rc = osd_ug_slabs(g, grid, true, P.ordws, PP.ug, PP.ugkeys)) != QLDPC_OK) return rc;
+    if ((rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gjg_kernel), kOsdLdsMax)) != QLDPC_OK) return rc;
+    hipLaunchKernelGGL(osd0_gjg_kernel, dim3(grid), dim3(L.block), L.lds, stream, PP);
     QLDPC_HIP_TRY(hipGetLastError());
-    handled = true;
     return QLDPC_OK;
 }
 

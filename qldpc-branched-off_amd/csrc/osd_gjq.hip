@@ -334,29 +334,22 @@ __global__ __launch_bounds__(1024) void osd0_gjq_kernel(OsdGjqArgs PP) {
 }
 
 
-// tried first for rows of 16 words; P comes filled by osd0_gj_launch (pointers, sizes, rank); launched = false when the LDS carve does not fit
+// tried first for rows of 16 words (Osd0Plan::queue_first) on arguments osd0_gj_launch filled; launched = false when its own carve fits LDS at no chunk size
 int osd0_gjq_launch(const qldpc_graph *g, const OsdGjArgs &base, int grid, hipStream_t stream, bool &launched) {
     launched = false;
-    if (base.mw != 16) return QLDPC_OK;
     OsdGjqArgs PP;
     PP.A = base;
     OsdGjArgs &P = PP.A;
-    const size_t sort_cnt = (size_t)256 * 16 * 4 + 16 * 4 + 64;
-    for (int K = 1024; K >= 256 && !launched; K >>= 1) {
+    for (int K = kOsdChunk; K >= 256 && !launched; K >>= 1) {
         P.K = K;
-        size_t off = std::max((size_t)(g->m + 2) * 16 * 8, (size_t)g->n * 12 + 16 + sort_cnt);       // U, aliased by the sort scratch
-        off = (size_t)round_up((int64_t)off, 16);
-        P.offIdx = (int)off; off += (size_t)K * 2;
-        P.offRows = (int)off; off += (size_t)round_up((int64_t)K * P.cdeg * 2, 8);
-        P.offPc = (int)off; off += round_up((int64_t)g->m * 2, 8);
-        P.offPr = (int)off; off += round_up((int64_t)g->m * 2, 8);
-        PP.offQ = (int)off; off += (size_t)kNQ * 16 * 8;
-        PP.offC = (int)off; off += (size_t)2 * kGjBlock * 16 * 8;
-        P.offUsed = (int)off; off += 32 * 8;
-        PP.offInts = (int)off; off += (32 + 2 * kNQ + 16 + 8) * 4;
-        const size_t lds = off + 16;
-        if (lds > 160 * 1024) continue;
-        int rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gjq_kernel), 160 * 1024);
+        OsdCarve c{osd_u_or_sort_bytes(g->m, g->n, 16)};
+        P.offIdx = c.take((size_t)K * 2); P.offRows = c.take(osd_align((size_t)K * P.cdeg * 2, 8));
+        P.offPc = c.take(osd_align(g->m * 2, 8)); P.offPr = c.take(osd_align(g->m * 2, 8));
+        PP.offQ = c.take((size_t)kNQ * 16 * 8); PP.offC = c.take((size_t)2 * kGjBlock * 16 * 8);
+        P.offUsed = c.take(32 * 8); PP.offInts = c.take((32 + 2 * kNQ + 16 + 8) * 4);
+        const size_t lds = c.off + 16;
+        if (lds > (size_t)kOsdLdsMax) continue;
+        int rc = ensure_max_lds(g->device, reinterpret_cast<const void *>(osd0_gjq_kernel), kOsdLdsMax);
         if (rc != QLDPC_OK) return rc;
         hipLaunchKernelGGL(osd0_gjq_kernel, dim3(grid), dim3(1024), lds, stream, PP);
         QLDPC_HIP_TRY(hipGetLastError());

@@ -275,8 +275,6 @@ __global__ __launch_bounds__(64) void osd0_small_reg_kernel(OsdSmallArgs P) {
     if (P.jerr) osd_small_judge_finish(P, total, lane);
 }
 
-int host_gf2_rank(const qldpc_graph *g);
-
 // the ticket counter of the one-wave kernels: a buffer of its own on the handle, zeroed when it is created
 int osd_small_queue(const qldpc_graph *g, int **queue) {
     const bool fresh = g->ws_squeue.p == nullptr;
@@ -287,17 +285,13 @@ int osd_small_queue(const qldpc_graph *g, int **queue) {
     return QLDPC_OK;
 }
 
-// handled = true when the matrix is small enough for this kernel (callers hold g->mu)
-int osd0_small_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, const int8_t *d_synd, const double *d_llr,
-                      const int8_t *d_hard, const int32_t *d_ordering, int8_t *d_solution, int flags, hipStream_t stream, bool &handled, OsdJudge *judge) {
-    handled = false;
-    if (g->m > 128 || g->n > 1024 || g->m < 1 || g->n < 1) return QLDPC_OK;
+// m <= 128 and n <= 1024: the plan (osd_plan.h) chose this kernel
+int osd0_small_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream, int flags, OsdJudge *judge) {
     OsdSmallArgs P;
     P.m = g->m; P.n = g->n; P.nw = (g->n + 63) / 64;
-    if (g->gf2_rank < 0) g->gf2_rank = host_gf2_rank(g);
     P.rankH = g->gf2_rank;
     P.indptr = g->d_indptr; P.indices = g->d_indices;
-    P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard; P.ordering = d_ordering; P.solution = d_solution;
+    P.list = S.list; P.count = S.count; P.synd = S.synd; P.llr = S.llr; P.hard = S.hard; P.ordering = S.ordering; P.solution = S.solution;
     P.clk = g->clk_probe;
     int rc;
     if ((rc = osd_small_queue(g, &P.queue)) != QLDPC_OK) return rc;
@@ -305,23 +299,20 @@ int osd0_small_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t
     if (!(flags & QLDPC_FLAG_INTERNAL_OSD_QUEUE_CLEAN)) QLDPC_HIP_TRY(hipMemsetAsync(P.queue, 0, 4, stream));
     P.jerr = nullptr; P.jLmask = nullptr; P.jtally = nullptr; P.jcount = nullptr;
     unsigned grid = 2048;
-    if (judge && !d_ordering) {             // the caller's judge rides on this launch (it owns the ticket counter: QLDPC_FLAG_INTERNAL_OSD_QUEUE_CLEAN)
+    if (judge && !S.ordering) {            // the caller's judge rides on this launch (it owns the ticket counter: QLDPC_FLAG_INTERNAL_OSD_QUEUE_CLEAN)
         P.jerr = judge->err; P.jLmask = judge->Lmask; P.jtally = judge->tally; P.jcount = judge->count;
         // every workgroup ends on one atomic (the counter reset belongs to the last one): a grid for the piece, not for the worst case of any piece
         grid = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(32, judge->max_listed / 32));
         judge->fused = true;
     }
-    const size_t lds = (size_t)g->m * (P.nw + 1) * 8 + (size_t)g->n * 8 + (size_t)g->n * 2 + (size_t)g->m * 2 + (size_t)g->n + 16;
-    const size_t lds_reg = (size_t)g->n * 8 + (size_t)g->n * 2 + (size_t)g->m * 2 + (size_t)g->n + 16;
-    switch (P.nw) {                                                  // n <= 256: the rows fit registers
-        case 1: hipLaunchKernelGGL(osd0_small_reg_kernel<1>, dim3(grid), dim3(64), lds_reg, stream, P); break;
-        case 2: hipLaunchKernelGGL(osd0_small_reg_kernel<2>, dim3(grid), dim3(64), lds_reg, stream, P); break;
-        case 3: hipLaunchKernelGGL(osd0_small_reg_kernel<3>, dim3(grid), dim3(64), lds_reg, stream, P); break;
-        case 4: hipLaunchKernelGGL(osd0_small_reg_kernel<4>, dim3(grid), dim3(64), lds_reg, stream, P); break;
-        default: hipLaunchKernelGGL(osd0_small_kernel, dim3(grid), dim3(64), lds, stream, P);
+    switch (P.nw) {                                                  // n <= 256: the rows fit registers (osd_small_lds has no matrix in LDS then)
+        case 1: hipLaunchKernelGGL(osd0_small_reg_kernel<1>, dim3(grid), dim3(L.block), L.lds, stream, P); break;
+        case 2: hipLaunchKernelGGL(osd0_small_reg_kernel<2>, dim3(grid), dim3(L.block), L.lds, stream, P); break;
+        case 3: hipLaunchKernelGGL(osd0_small_reg_kernel<3>, dim3(grid), dim3(L.block), L.lds, stream, P); break;
+        case 4: hipLaunchKernelGGL(osd0_small_reg_kernel<4>, dim3(grid), dim3(L.block), L.lds, stream, P); break;
+        default: hipLaunchKernelGGL(osd0_small_kernel, dim3(grid), dim3(L.block), L.lds, stream, P);
     }
     QLDPC_HIP_TRY(hipGetLastError());
-    handled = true;
     return QLDPC_OK;
 }
 

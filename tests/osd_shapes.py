@@ -3,12 +3,11 @@ tests/test_osd_domain_cpu.py checks with the oracle alone that the cases have th
 hand-computed points; tests/test_osd_domain_gpu.py runs them and asserts after every call that qldpc_osd0_last_path reports the labelled kernel.
 Plain module (no pytest hooks); deterministic from SEED.
 
-`rule_path` restates the dispatch of osd0_listed_launch / osd0_lds_launch (csrc/gf2.hip) in plain arithmetic, with the LDS budgets of the three
-launchers it falls through: it is an independent statement of the rules, not a copy the library reads.  A family's label (`path`, `w16`, `rank`) is
-written in TABLE by hand; the CPU module asserts that the mirror and the oracle agree with it, the GPU module that the library does.
-
-One route is not in the dispatch's own comments: a column too heavy for osd_gjg's LDS budget can still fit plan_osd_lds' mode 2 (its budget is
-2 m + 704 bytes smaller), and then the reference-order kernel osd0_lds_kernel<UG> takes EVERY shot; the global kernel follows one degree later."""
+`rule_path` restates the library's rule -- osd0_plan and the three LDS layouts of csrc/osd_plan.h, which osd0_listed_launch (csrc/gf2.hip) executes; DESIGN.md 4
+has it as a table -- in plain arithmetic: an independent statement of it, not a copy the library reads (tests/test_osd_plan_cpu.py holds the two
+against each other over the whole range).  A family's label (`path`, `w16`, `rank`) is written in TABLE by hand; the CPU module asserts that the mirror
+and the oracle agree with it, the GPU module that the library does.  ("plan_osd_lds' mode 2" in a TABLE note is mode 2 of the reference-order kernel:
+`reforder_lds(.., 2)` here, osd_ref_layout in the library.)"""
 from types import SimpleNamespace
 
 import numpy as np
@@ -23,9 +22,9 @@ UNSUPPORTED_TEXT = "matrix too large for the LDS scratch"
 
 # ---------------------------------------------------------------------------------------------------------------- the mirror
 LDS_MAX = 160 * 1024               # what every OSD-0 launcher allows itself of the CU's LDS
-ELIM_MAX = 150 * 1024              # osd0_global_launch, csrc/gf2.hip:248
+ELIM_MAX = 150 * 1024              # kOsdElimMax (csrc/osd_plan.h): the global kernel's LDS scratch
 CHUNK = 1024                       # P.K: columns per chunk
-BLOCK_COLS = 16                    # kGjBlock (csrc/osd_gj.h:31) and kOsdBlock (csrc/gf2.hip:688)
+BLOCK_COLS = 16                    # kGjBlock and kOsdBlock (csrc/osd_plan.h)
 SORT_CNT = 256 * 16 * 4 + 16 * 4 + 64
 
 
@@ -34,7 +33,7 @@ def _ru(x, a):
 
 
 def gj_lds(m, n, cd):
-    """dynamic LDS of osd0_gj_kernel: osd0_gj_launch, csrc/osd_gj.hip:469-482"""
+    """dynamic LDS of osd0_gj_kernel: osd_gj_layout, csrc/osd_plan.h"""
     mw = (m + 63) // 64
     off = _ru(max((m + 2) * mw * 8, n * 12 + 16 + SORT_CNT), 16)            # U, aliased by the sort scratch
     off += CHUNK * 2 + CHUNK + _ru(CHUNK * cd * 2, 8)                       # sidx, alive, colrows
@@ -45,7 +44,7 @@ def gj_lds(m, n, cd):
 
 
 def gjg_lds(m, n, cd):
-    """dynamic LDS of osd0_gjg_kernel: osd0_gjg_launch, csrc/osd_gjg.hip:339-353 (n does not enter: the sort scratch is in global memory)"""
+    """dynamic LDS of osd0_gjg_kernel: osd_gjg_layout, csrc/osd_plan.h (n does not enter: the sort scratch is in global memory)"""
     mw = (m + 63) // 64
     off = _ru(SORT_CNT, 16)
     off += CHUNK * 2 + CHUNK + _ru(CHUNK * cd * 2, 8)
@@ -55,7 +54,7 @@ def gjg_lds(m, n, cd):
 
 
 def reforder_lds(m, n, cd, mode):
-    """dynamic LDS of osd0_lds_kernel<mode == 2>: plan_osd_lds, csrc/gf2.hip:1136-1149"""
+    """dynamic LDS of osd0_lds_kernel<mode == 2>: osd_ref_layout, csrc/osd_plan.h"""
     mw = (m + 63) // 64
     off = _ru(max((m + 2) * mw * 8, n * 12 + 16 + SORT_CNT), 16) if mode == 1 else 0
     off += CHUNK * 2 + CHUNK + CHUNK * cd * 2
@@ -66,7 +65,7 @@ def reforder_lds(m, n, cd, mode):
 
 
 def plan_mode(m, n, cd, flags):
-    """plan_osd_lds, csrc/gf2.hip:1131-1152 -> 0 (no reference-order form), 1 (row transform in LDS), 2 (in HBM / L2)"""
+    """the reference-order form osd0_plan (csrc/osd_plan.h) settles on -> 0 (no reference-order form), 1 (row transform in LDS), 2 (in HBM / L2)"""
     if m > 4096 or n >= 65535 or m < 1:
         return 0
     for mode in ((1, 2) if m <= 1024 and not flags & FLAG_OSD_UG else (2,)):
@@ -76,13 +75,13 @@ def plan_mode(m, n, cd, flags):
 
 
 def elim_lds(m, n):
-    """elim_lds_bytes, csrc/gf2.hip:39, with the row words of osd0_global_launch, csrc/gf2.hip:226"""
+    """elim_lds_bytes with the row words osd_global_nwords, csrc/osd_plan.h"""
     nwords = ((n + 7) // 8 + 7) // 8
     return 16 + nwords * 8 + m * 4 + 8 + m + 16
 
 
 def _wide_block(m):
-    return min(1024, _ru(max(m + 2, 256), 64))           # csrc/osd_gj.hip:506 and csrc/gf2.hip:1212
+    return min(1024, _ru(max(m + 2, 256), 64))           # osd_wide_block, csrc/osd_plan.h
 
 
 def rule_path(m, n, max_col_deg, flags=0):
@@ -93,27 +92,27 @@ def rule_path(m, n, max_col_deg, flags=0):
     out = SimpleNamespace(path="NONE", w16=False, block=0, mode=0, redo=False, refused=False)
     if m < 1 or n < 1:
         return out
-    if not flags & (FLAG_OSD_LDS | FLAG_OSD_UG | FLAG_OSD_GLOBAL) and m <= 128 and n <= 1024:       # csrc/gf2.hip:1165, csrc/osd_small.hip:294
+    if not flags & (FLAG_OSD_LDS | FLAG_OSD_UG | FLAG_OSD_GLOBAL) and m <= 128 and n <= 1024:       # osd0_plan: the one-wave kernel
         out.path, out.block = "SMALL", 64
         return out
     took = None
-    if not flags & (FLAG_OSD_REFORDER | FLAG_OSD_GLOBAL):                                           # csrc/gf2.hip:1176-1192
-        if not flags & FLAG_OSD_UG and m <= 1024 and n < 65535 and gj_lds(m, n, cd) <= LDS_MAX:     # csrc/osd_gj.hip:467,483
+    if not flags & (FLAG_OSD_REFORDER | FLAG_OSD_GLOBAL):                                           # osd0_plan: the free-pivot kernels
+        if not flags & FLAG_OSD_UG and m <= 1024 and n < 65535 and gj_lds(m, n, cd) <= LDS_MAX:     # GJ: m <= 1024, osd_gj_layout fits
             took = "GJ"
-        if took is None and m <= 4096 and n < 65535 and gjg_lds(m, n, cd) <= LDS_MAX:               # csrc/osd_gjg.hip:335,354
+        if took is None and m <= 4096 and n < 65535 and gjg_lds(m, n, cd) <= LDS_MAX:               # GJG: m <= 4096, osd_gjg_layout fits
             took = "GJG"
     out.mode = 0 if flags & FLAG_OSD_GLOBAL else plan_mode(m, n, cd, flags)
     if took:
-        out.path, out.redo = took, True          # (mode 0 cannot happen here: both free-pivot budgets are larger than plan_osd_lds')
+        out.path, out.redo = took, True          # (mode 0 cannot happen here: both free-pivot layouts are larger than the reference-order kernel's mode 2)
         out.block = _wide_block(m) if took == "GJ" else 1024
-        out.w16 = took == "GJ" and (m + 63) // 64 == 16 and out.block == 1024                       # csrc/osd_gj.hip:516
+        out.w16 = took == "GJ" and (m + 63) // 64 == 16 and out.block == 1024                       # Osd0Plan::w16
     elif out.mode:
         out.path = "REFORDER_LDS" if out.mode == 1 else "REFORDER_UG"
         out.block = _wide_block(m) if out.mode == 1 else 1024
     elif elim_lds(m, n) > ELIM_MAX:
         out.refused = True
     else:
-        out.path, out.block = "GLOBAL", 1024 if m >= 512 or n >= 2048 else 256                      # csrc/gf2.hip:249
+        out.path, out.block = "GLOBAL", 1024 if m >= 512 or n >= 2048 else 256                      # osd0_plan: the global kernel's threads
     return out
 
 

@@ -143,7 +143,7 @@ def test_oracle_equals_the_restated_reference_on_small_families(oracle, name):
 
 
 def test_rule_path_at_hand_computed_points():
-    """Both sides of every boundary of the dispatch, worked out on paper from the launchers' formulas (the byte totals are in the comments)."""
+    """Both sides of every boundary of the dispatch, worked out on paper from the formulas of csrc/osd_plan.h (the byte totals are in the comments)."""
     R, LDS, UG, RE, GL = OS.rule_path, OS.FLAG_OSD_LDS, OS.FLAG_OSD_UG, OS.FLAG_OSD_REFORDER, OS.FLAG_OSD_GLOBAL
 
     def what(m, n, cd, flags=0):
@@ -178,7 +178,7 @@ def test_rule_path_at_hand_computed_points():
     # the uint16 tables: n < 65535
     assert what(200, 65534, 4) == ("GJG", False, 1024, 2, True)
     assert what(200, 65535, 4) == ("GLOBAL", False, 1024, 0, False) and what(129, 65535, 4)[0] == "GLOBAL"
-    # a heavy column at m = 300, n = 700: osd_gj 32976 + 2048 d, osd_gjg 22624 + 2048 d, plan_osd_lds mode 2 21320 + 2048 d
+    # a heavy column at m = 300, n = 700: osd_gj 32976 + 2048 d, osd_gjg 22624 + 2048 d, the reference-order kernel's mode 2 21320 + 2048 d
     assert (OS.gj_lds(300, 700, 63), OS.gj_lds(300, 700, 64)) == (162000, 164048)
     assert (OS.gjg_lds(300, 700, 68), OS.gjg_lds(300, 700, 69)) == (161888, 163936)
     assert (OS.reforder_lds(300, 700, 69, 2), OS.reforder_lds(300, 700, 70, 2)) == (162632, 164680)
@@ -197,7 +197,7 @@ def test_rule_path_at_hand_computed_points():
 
 
 def test_mirror_reproduces_the_three_budgets_at_circ144():
-    """the production Z sector, 1008 x 8785 with columns of weight <= 6: the totals worked out by hand from the three launchers"""
+    """the production Z sector, 1008 x 8785 with columns of weight <= 6: the totals worked out by hand from the three layouts of csrc/osd_plan.h"""
     import qldpc_amd  # noqa: F401
     from qldpc_amd.data import load_circuit_matrices
     d = load_circuit_matrices("circ144")
@@ -208,7 +208,7 @@ def test_mirror_reproduces_the_three_budgets_at_circ144():
     assert OS.gj_lds(m, n, cd) == 159504
     # osd_gjg: 16512 + 3072 + 12288 + 4032 + 2048 + 1024 + 160 + 16
     assert OS.gjg_lds(m, n, cd) == 39152
-    # plan_osd_lds: mode 1 129280 + 3072 + 12288 + 2016 + 2048 + 416 + 64 + 16; mode 2 the same without U plus 16512
+    # osd_ref_layout: mode 1 129280 + 3072 + 12288 + 2016 + 2048 + 416 + 64 + 16; mode 2 the same without U plus 16512
     assert (OS.reforder_lds(m, n, cd, 1), OS.reforder_lds(m, n, cd, 2)) == (149200, 36432)
     r = OS.rule_path(m, n, cd)
     assert (r.path, r.w16, r.block, r.mode, r.redo) == ("GJ", True, 1024, 1, True)
