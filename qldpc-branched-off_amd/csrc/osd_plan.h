@@ -68,6 +68,23 @@ template <class Args> size_t osd_ref_layout(int m, int n, int cdeg, int mode, Ar
     return c.off + 16;
 }
 
+// ---- OSD-CS (osd_cs.hip): one kernel, two forms of its column sort.  U (m + 2 rows) is aliased by the 12 n bytes of sort scratch while the whole layout
+// still fits beside it; beyond that the sort runs in global memory and U stands alone (global_sort).  TR is carved per order, so the edge moves with it.
+// Returns the dynamic LDS bytes of the form taken, 0 when neither fits ----
+constexpr int kCsChunk = 64;                  // columns per chunk of the OSD-CS sweep
+constexpr int kCsMaxOrder = 64;
+template <class Args> size_t osd_cs_layout(int m, int n, int order, Args &P, bool &global_sort) {
+    const int mw = (m + 63) / 64;
+    for (int lsort = 1; lsort >= 0; lsort--) {
+        OsdCarve c{lsort ? osd_u_or_sort_bytes(m, n, mw) : osd_align((size_t)(m + 2) * mw * 8, 16)};
+        P.offUsed = c.take(16 * 8); P.offPc = c.take(osd_align(m * 2, 8)); P.offPr = c.take(osd_align(m * 2, 8));
+        P.offR = c.take((size_t)kCsChunk * mw * 8);                // (>= m * 8: the signed pivot weights of the scoring phase)
+        P.offTR = c.take((size_t)(order > 1 ? order : 1) * mw * 8); P.offPf = c.take(osd_align((size_t)((n + 31) / 32) * 4, 16)); P.offMisc = c.take(2048);
+        if (c.off + 16 <= (size_t)kOsdLdsMax) { global_sort = !lsort; return c.off + 16; }
+    }
+    return 0;
+}
+
 // ---- the plan ----
 struct OsdLaunch { int kernel = QLDPC_OSD_PATH_NONE, block = 0; size_t lds = 0; };      // QLDPC_OSD_PATH_* of the kernel, threads, dynamic LDS bytes
 enum OsdRefusal { kOsdAccepted = 0, kOsdRefusedQueue, kOsdRefusedSize };

@@ -59,9 +59,9 @@ def _unpack(words, m):
     return b[:, :m].astype(bool)
 
 
-def osd_cs(G, syndrome, llr, hard, weights, order, ordering=None):
-    """One shot -> dict(solution int8[n], flips (int, int), outside bool, osd0 int8[n], cost int, pivots list, T list).
-    outside = True: s + H hard is not in the column space (the library then returns qldpc_osd0_batch's answer; solution is None here)."""
+def eliminate(G, syndrome, llr, hard, ordering=None):
+    """The part of one shot that knows neither the weights nor the order: the sweep over the whole column order -> dict(outside bool, osd0 int8[n], pivots
+    [(column, row)], and for the scoring U, hard, seq)."""
     m, n, mw = G.m, G.n, G.mw
     hard = np.asarray(hard, np.int8) & 1
     U = np.zeros((m + 2, mw), np.uint64)
@@ -98,6 +98,25 @@ def osd_cs(G, syndrome, llr, hard, weights, order, ordering=None):
     x0 = hard.copy()
     for j, p in pivots:
         x0[j] = hard[j] ^ _bit(bvec, p)
+    return dict(outside=outside, osd0=x0, pivots=pivots, U=U, hard=hard, seq=seq)
+
+
+def reduced_columns(G, E):
+    """the non-pivot columns of an elimination in the column order and their reduced columns against its final transform -> (T list, BT bool[len(T)][m]);
+    kept in E: they depend on neither the weights nor the order"""
+    if "BT" not in E:
+        is_piv = np.zeros(G.n, bool)
+        is_piv[[j for j, _ in E["pivots"]]] = True
+        T = [int(j) for j in E["seq"] if not is_piv[j]]
+        RT = _reduced(G, E["U"], T)
+        E["T"], E["BT"] = T, _unpack(RT, G.m) if T else np.zeros((0, G.m), bool)
+    return E["T"], E["BT"]
+
+
+def score(G, E, weights, order):
+    """The combination sweep on an elimination E of eliminate() -> the dict of osd_cs."""
+    m = G.m
+    outside, x0, pivots, hard = E["outside"], E["osd0"], E["pivots"], E["hard"]
     res = dict(outside=outside, osd0=x0, pivots=pivots)
     if outside:
         res.update(solution=None, flips=(-1, -1), cost=None, T=None)
@@ -108,11 +127,7 @@ def osd_cs(G, syndrome, llr, hard, weights, order, ordering=None):
     for j, p in pivots:
         sq[p] = -q[j] if x0[j] else q[j]
         pc[p] = j
-    is_piv = np.zeros(n, bool)
-    is_piv[[j for j, _ in pivots]] = True
-    T = [int(j) for j in seq if not is_piv[j]]
-    RT = _reduced(G, U, T)
-    BT = _unpack(RT, m) if T else np.zeros((0, m), bool)
+    T, BT = reduced_columns(G, E)
     sig = np.where(hard[T] == 1, -1, 1).astype(np.int64) if T else np.zeros(0, np.int64)
     d1 = sig * q[T] + BT.astype(np.int64) @ sq if T else np.zeros(0, np.int64)
     lam = min(int(order), len(T))
@@ -135,6 +150,12 @@ def osd_cs(G, syndrome, llr, hard, weights, order, ordering=None):
             x[pc[r]] ^= 1
     res.update(solution=x.astype(np.int8), flips=flips, cost=int(q[x0 == 1].sum() + deltas[k]), T=T, deltas=deltas, pairs=pairs)
     return res
+
+
+def osd_cs(G, syndrome, llr, hard, weights, order, ordering=None):
+    """One shot -> dict(solution int8[n], flips (int, int), outside bool, osd0 int8[n], cost int, pivots list, T list).
+    outside = True: s + H hard is not in the column space (the library then returns qldpc_osd0_batch's answer; solution is None here)."""
+    return score(G, eliminate(G, syndrome, llr, hard, ordering), weights, order)
 
 
 def osd_cs_batch(G, syndromes, llr, hard, weights, order, ordering=None):

@@ -226,7 +226,12 @@ def _csr(r, c, m):
 
 
 def _build(name):
-    kind, m, n, extra = TABLE[name][:4]
+    path, w16, rank, note = TABLE[name][4:]
+    return SimpleNamespace(**vars(build_matrix(name, *TABLE[name][:4])), path=path, w16=w16, rank=rank, note=note, refused=path == "NONE")
+
+
+def build_matrix(name, kind, m, n, extra=None):
+    """the matrix of a family without its labels (tests/osd_cs_shapes.py builds its own families with this): seeded by the name"""
     rng = _rng(name)
     null_rows = None
     if kind in ("dep", "heavy", "doubled"):
@@ -257,9 +262,7 @@ def _build(name):
         r, c = _columns(rng, np.arange(m), n, 2, 4)
     ip, ix = _csr(np.asarray(r, np.int64), np.asarray(c, np.int64), m)
     cdeg = int(np.bincount(ix, minlength=n).max()) if ix.size else 0
-    path, w16, rank, note = TABLE[name][4:]
-    return SimpleNamespace(name=name, kind=kind, m=m, n=n, indptr=ip, indices=ix, max_col_deg=cdeg, null_rows=null_rows, path=path, w16=w16, rank=rank,
-                           note=note, refused=path == "NONE")
+    return SimpleNamespace(name=name, kind=kind, m=m, n=n, indptr=ip, indices=ix, max_col_deg=cdeg, null_rows=null_rows)
 
 
 def family(name):
