@@ -306,7 +306,7 @@ int qldpc_osd0_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndro
 #define QLDPC_OSD_DETAIL_MODE_MASK 0x3
 #define QLDPC_OSD_DETAIL_REDO 0x4
 int qldpc_osd0_last_path(const qldpc_graph *g, int *path, int *detail);
-/* Phase counters of the OSD-0 kernels and of the workgroup BP kernel on the current device (uint64[32]; layout in csrc/osd_common.h).  Only the diagnostic build
+/* Phase counters of the OSD-0 kernels and of the workgroup BP kernel on the current device (uint64[32]; layout in csrc/clocks.h).  Only the diagnostic build
  * (make -C csrc timers) counts; the product build carries no clock reads and returns QLDPC_ERR_UNSUPPORTED. */
 int qldpc_osd_timers_read(uint64_t *out32, int reset);
 /* f1: performOSD_enhanced(H, syndrome, llr, hard, order, max_combinations) (src/decoding/osd.py:5-77), batched.  The OSD-0 solution is

@@ -740,7 +740,7 @@ class Minsum32Decoder:
 
 
 def osd_timers(reset=True):
-    """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/osd_common.h) -> uint64[32]."""
+    """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/clocks.h) -> uint64[32]."""
     out = np.zeros(32, np.uint64)
     check(lib().qldpc_osd_timers_read(ptr(out, C.c_uint64), int(reset)))
     return out

@@ -24,19 +24,6 @@ inline SlotGraph slot_graph(const qldpc_graph *g) {
     return SlotGraph{g->m, g->n, g->max_col_deg, g->d_row_of_slot, g->d_col_of_slot, g->d_deg_of_rslot, g->d_ell_col_s, g->d_ell_var_s};
 }
 
-// The record of a check is (alpha*min1, alpha*min2) and one word: bits 0-55 input signs, 56-62 argmin (127 = none), 63 total sign.
-__device__ __forceinline__ int rec_argmin(unsigned long long w) { return (int)((w >> 56) & 127); }
-__device__ __forceinline__ bool rec_total_sign(unsigned long long w) { return (w >> 63) & 1; }
-__device__ __forceinline__ bool rec_sign_bit(unsigned long long w, int k) { return (w >> k) & 1; }
-__device__ __forceinline__ unsigned long long rec_pack(unsigned long long negbits, int arg, bool sp) {
-    return negbits | ((unsigned long long)arg << 56) | ((unsigned long long)sp << 63);
-}
-// the message the check sent to its position k
-__device__ __forceinline__ double rec_message(double a1, double a2, unsigned long long w, int k) {
-    const double mag = (k == (int)((w >> 56) & 127)) ? a2 : a1;
-    return ((bool)((w >> 63) & 1) != (bool)((w >> k) & 1)) ? -mag : mag;
-}
-
 struct LegResult { bool conv; int itc; };
 
 // One leg of at most T iterations on shot b, from the marginals V as they stand (the first check pass takes Q = V, nothing subtracted):

@@ -10,8 +10,9 @@
 // Random draws of trial g: location l faulty iff word (l&3) of Philox(g, block l>>2, domain 1) < thr; its Pauli choice
 // is word 0 of Philox(g, l, domain 2) mod 3 (IDLE, noise/kernels.py:260-272) or mod 15 (CNOT, :274-344).
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "mc_common.h"
-#include "minsum_common.h"
 
 #include <algorithm>
 #include <cmath>

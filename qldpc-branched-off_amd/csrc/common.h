@@ -127,24 +127,9 @@ struct StreamHandover {
 // d_err, d_llr, d_conv, d_iter) on the null stream under `mu`, wait, results out.  `what` names the decoder in the error text.
 int decode_batch_via_device(std::mutex &mu, const char *what, int64_t B, int m, int n, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
                             int32_t *iter, const std::function<int(const int8_t *, int8_t *, double *, uint8_t *, int32_t *)> &launch);
-
-// Shader-clock probe (QLDPC_FLAG_CLOCK_PROBE): thread 0 of a workgroup stamps the shader-clock counter (s_memtime) and the constant
-// 100 MHz counter (s_memrealtime) when it starts and when it ends; clock held under this kernel's load = delta ratio x 100 MHz
-// (MI355X_MICROARCH.md, DVFS give-back item 6).  Buffer: kClkSlots pairs (delta memtime, delta memrealtime) indexed by blockIdx.x.
-constexpr int kClkSlots = 512;
-struct ClkStamp { unsigned long long t = 0, r = 0; };
-__device__ __forceinline__ ClkStamp clk_begin(const unsigned long long *clk) {
-    ClkStamp s;
-    if (clk) { s.t = __builtin_amdgcn_s_memtime(); s.r = __builtin_amdgcn_s_memrealtime(); }
-    return s;
-}
-__device__ __forceinline__ void clk_end(unsigned long long *clk, const ClkStamp &s) {
-    if (clk && threadIdx.x == 0 && blockIdx.x < kClkSlots) {
-        clk[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - s.t;
-        clk[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - s.r;
-    }
-}
+// clocks.h: what the shader-clock probe stamped
 double clock_probe_median(const unsigned long long *pairs, int slots);   // MHz; 0 when nothing was stamped
+
 
 }  // namespace qldpc
 

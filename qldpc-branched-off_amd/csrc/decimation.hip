@@ -15,6 +15,7 @@
 // compare of the magnitude bits, then the column), so lane and wave order cannot matter.  Every loop is bounded by per_round, n, t_round and
 // max_rounds; workgroup barriers are the only synchronisation.
 #include "bp_leg.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <climits>

@@ -1,6 +1,6 @@
 // C-ABI entry points of the batched min-sum decoder (a1/a2) and kernel selection.
 #include "common.h"
-#include "minsum_common.h"
+#include "launchers.h"
 
 #include <cmath>
 #include <cstring>

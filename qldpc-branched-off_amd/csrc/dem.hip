@@ -6,6 +6,7 @@
 // sampler's (0: code capacity, 1 and 2: the circuit sampler, 0x52......: Relay-BP).  A firing mechanism XORs its detector lists into the sectors' bit
 // sets and its logical masks into the sectors' accumulators, so the result does not depend on grid, block size or lane mapping.
 #include "common.h"
+#include "launchers.h"
 #include "mc_common.h"
 
 namespace qldpc {

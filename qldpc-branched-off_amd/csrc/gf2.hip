@@ -7,9 +7,10 @@
 // The pivot row has only zeros left of its pivot column (all earlier columns were either eliminated or had no
 // one at/below `row`), so XOR-ing words >= pivot_col/64 reproduces the reference's full-row XOR bit for bit.
 #include "common.h"
-#include "mc_common.h"
-#include "minsum_common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "osd_common.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1180,7 +1181,7 @@ QLDPC_EXPORT int qldpc_osd0_last_path(const qldpc_graph *g, int *path, int *deta
     return QLDPC_OK;
 }
 
-// ---- diagnostic phase counters (see osd_common.h) ----
+// ---- diagnostic phase counters (see clocks.h) ----
 namespace qldpc {
 unsigned long long *osd_timer_buffer() {
 #ifdef QLDPC_OSD_TIMERS
@@ -1201,7 +1202,7 @@ unsigned long long *osd_timer_buffer() {
 }  // namespace qldpc
 
 // Phase counters of the OSD-0 kernels ([0..15]) and of the workgroup BP kernel ([16..31]) accumulated on the CURRENT device since the last reset
-// (uint64[32], layout in osd_common.h).
+// (uint64[32], layout in clocks.h).
 // Only the diagnostic build (make timers) counts; the default build returns QLDPC_ERR_UNSUPPORTED.  Synchronises the device.
 QLDPC_EXPORT int qldpc_osd_timers_read(uint64_t *out, int reset) {
     QLDPC_REQUIRE(out != nullptr, "out is NULL");

@@ -1,6 +1,6 @@
 // Error state, device selection and the Tanner-graph handle of libqldpc_hip.
 #include "common.h"
-#include "minsum_common.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstring>

@@ -2,9 +2,9 @@
 // failed-shot collection for OSD-0, logical-error judge and the int64 tally (replaces the Python tally loop
 // src/simulation/engine.py:450-457).  Sampling law: src/decoding/alpha.py:127-128; failure rule: engine.py:99-100.
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "mc_common.h"
-#include "minsum_common.h"
-#include "osd_common.h"
 
 #include <cmath>
 #include <vector>

@@ -20,8 +20,9 @@
 // Sampling law and stream: mc_common.h (bit j of shot g = word j & 3 of Philox block (g, j >> 2) < thr): 36 Philox calls per shot
 // are the floor of this kernel (~85 % of its instructions).
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "mc_common.h"
-#include "minsum_common.h"
 
 #include <algorithm>
 #include <cmath>

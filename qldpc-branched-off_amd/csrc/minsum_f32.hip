@@ -14,8 +14,7 @@
 // CLEAN (host-verified: no degree-1 row, finite priors, bounded alpha -- no NaN or inf can arise): the NaN test goes and the clip is one v_med3_f32.
 // Every loop is bounded by the host tables and max_iter; workgroup barriers are the only synchronisation.
 #include "common.h"
-#include "mc_common.h"
-#include "minsum_common.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cmath>

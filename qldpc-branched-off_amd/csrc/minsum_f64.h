@@ -1,4 +1,7 @@
-// f64 building blocks shared by the register-resident min-sum kernels (minsum_regular.hip, minsum_wave.hip).
+// f64 building blocks shared by the min-sum kernels: the register-resident ones (minsum_regular.hip, minsum_wave.hip) and, for the v_min / v_max
+// wrappers, the workgroup ones (minsum_wg.hip, minsum_wg2.hip).
+// Device header: only what can reach a kernel's instruction stream (device functions, kernel argument structs shared between files, constants
+// and macros kernel bodies name).  Prototypes and host-only structs live in launchers.h; tools/isa_mix.py RECORDED lists this file per kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,6 +25,12 @@ __device__ __forceinline__ double vmin_abs(double a, double b) { double r; asm("
 // by a wave-uniform condition): the "s" constraint makes the compiler read a divergent b from its first active lane without a diagnostic.
 __device__ __forceinline__ double vmin_abs_u(double a, double b) { double r; asm("v_min_f64 %0, |%1|, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
 __device__ __forceinline__ double vmax_abs(double a, double b) { double r; asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// a as it is (a magnitude already), |b|
+__device__ __forceinline__ double vmin_abs2(double a, double b) { double r; asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double vmax_abs2(double a, double b) { double r; asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// second operand wave-uniform (see vmin_abs_u): no vector copy of a clip bound per edge
+__device__ __forceinline__ double vmin_u(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
+__device__ __forceinline__ double vmax_u(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
 
 // The two smallest magnitudes (with multiplicity) of x[0..D): pairs -> (min,max), then merge (lo,hi) sets:
 // lo = min(l1,l2), hi = min(max(l1,l2), min(h1,h2)).  min1/min2 of kernels.py:301-306 are exactly these values.

@@ -15,7 +15,7 @@
 // the layer table and -- when n <= 65535 and they still fit -- the column indices as u16 in slot order (else int32 in L2).
 // Every loop is bounded by the host tables and max_iter.
 #include "common.h"
-#include "mc_common.h"
+#include "launchers.h"
 #include "minsum_common.h"
 
 #include <algorithm>
@@ -96,8 +96,8 @@ __global__ __launch_bounds__(1024) void minsum_layered_kernel(LayeredArgs A) {
                     const int deg = (int)(ES[slot + 1] - e0);
                     const double2 old = SP[slot];
                     const unsigned long long ip = SI[slot];
-                    const int argp = (int)((ip >> 56) & 127);
-                    const bool spp = (ip >> 63) & 1;
+                    const int argp = rec_argmin(ip);
+                    const bool spp = (ip >> 63) & 1;                                 // (rec_total_sign / rec_message here change the compiler's schedule of the edge loop: spelled out)
                     double q[kLayeredLaneEdges];
                     int cols[kLayeredLaneEdges];
                     double min1 = INFINITY, min2 = INFINITY;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(1024) void minsum_layered_kernel(LayeredArgs A) {
                     const double a1 = alpha * min1, a2 = alpha * min2;
                     if (sub == 0) {
                         SP[slot] = make_double2(a1, a2);
-                        SI[slot] = negbits | ((unsigned long long)pos << 56) | ((unsigned long long)sp << 63);
+                        SI[slot] = rec_pack(negbits, pos, sp);
                     }
 #pragma unroll
                     for (int t = 0; t < kLayeredLaneEdges; t++) {

@@ -47,6 +47,8 @@
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "mc_common.h"
 #include "minsum_common.h"
 #include "minsum_f64.h"

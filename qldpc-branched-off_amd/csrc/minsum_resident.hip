@@ -17,6 +17,7 @@
 //     workgroup leaves the loop when all its shots are frozen (unless QLDPC_FLAG_FIXED_ITERS).
 // No global-memory traffic inside the iteration loop: HBM sees syndromes in, (err, llr, conv, iter) out.
 #include "common.h"
+#include "launchers.h"
 #include "mc_common.h"
 #include "minsum_common.h"
 #include "minsum_f64.h"

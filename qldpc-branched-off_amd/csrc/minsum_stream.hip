@@ -9,6 +9,7 @@
 // (16*nnz bytes/shot/iteration, the algorithmic figure of SURVEY 8d).  Floating-point expressions keep the
 // reference's operand order; the file is compiled with -ffp-contract=off.
 #include "common.h"
+#include "launchers.h"
 #include "minsum_common.h"
 
 namespace qldpc {

@@ -16,7 +16,7 @@
 //   * fixed-work mode (QLDPC_FLAG_FIXED_ITERS): all max_iter iterations for every shot, outputs frozen at the first converged one.
 //
 // Inputs must be "clean" (host-verified: every prior finite and not -0.0, |prior| <= clip, clip finite > 0, every alpha finite > 0,
-// damping == 1): then no message or posterior is NaN, no posterior or variable-to-check message is -0.0 (minsum_common.h), so
+// damping == 1): then no message or posterior is NaN, no posterior or variable-to-check message is -0.0 (inputs_clean, launchers.h), so
 //   x < 0  <=>  sign bit of x           (signs, parities and hard decisions are integer XORs of the high words),
 //   clip(prior - 0.0) == prior          (iteration 0 needs no special case: Q_{-1} = prior, kernels.py:263-265),
 // and the NaN test of kernels.py:328 can never fire.  Everything else goes to minsum_regular.hip.
@@ -24,8 +24,9 @@
 // msg = +-(alpha_0 |p0|) (see minsum_regular.hip), and the sampled error e_j is parked in V[j] as -1.0 / +1.0 so that the
 // syndrome s = H e (a6) is the same sign-parity gather as the convergence test.
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "mc_common.h"
-#include "minsum_common.h"
 #include "minsum_f64.h"
 
 #include <atomic>

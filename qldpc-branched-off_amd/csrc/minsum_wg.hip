@@ -15,8 +15,10 @@
 // thread owns one row for the whole launch (m <= 1024) its column indices stay in registers (RIDX: no index loads in the check pass), and the
 // variable pass switches on the wave's column degree into a predicate-free body (wg_lean_col_edges).
 #include "common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "minsum_common.h"
-#include "osd_common.h"      // OSD_CLOCK / osd_timer_buffer: the diagnostic build (make timers) also times the phases of the lean kernel
+#include "minsum_f64.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -83,8 +85,6 @@ __global__ __launch_bounds__(1024) void minsum_wg_kernel(WgArgs A) {
                     double p1p = 0.0, p2p = 0.0;
                     unsigned long long ip = 0ull;
                     if (it > 0 && deg > 0) { const double2 t = SP[i]; p1p = t.x; p2p = t.y; ip = SI[i]; }
-                    const int argp = (int)((ip >> 56) & 127);
-                    const bool spp = (ip >> 63) & 1;
                     bool par = csyn, sp = csyn;
                     double min1 = INFINITY, min2 = INFINITY;
                     int arg = 127;
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(1024) void minsum_wg_kernel(WgArgs A) {
                         par ^= (v < 0.0);                                                    // kernels.py:349,356
                         double x = v;
                         if (it > 0) {
-                            const double mag = (k == argp) ? p2p : p1p;                      // kernels.py:313
-                            const double r = (spp != (bool)((ip >> k) & 1)) ? -mag : mag;    // R_{it-1}[e], kernels.py:311-314
+                            const double r = rec_message(p1p, p2p, ip, k);                   // R_{it-1}[e], kernels.py:311-314
                             x = clip_nan(v - r, clip);                                       // kernels.py:325-333
                             if (DAMP) x = clip_only(damping * x + one_minus_d * Qo[(size_t)k * m + i], clip);   // kernels.py:336-342
                             else if (A.nfcheck && prior_not_finite(A.prior[col])) x = NAN;   // kernels.py:336 with Q_old = +-inf (see minsum_common.h)
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(1024) void minsum_wg_kernel(WgArgs A) {
                     if (it >= 1 && !done && par) unsat[it & 1] = 1;                          // kernels.py:357-359
                     if (it < max_iter && deg > 0) {                                          // kernels.py:285-286
                         SP[i] = make_double2(alpha * min1, alpha * min2);
-                        SI[i] = negbits | ((unsigned long long)arg << 56) | ((unsigned long long)sp << 63);
+                        SI[i] = rec_pack(negbits, arg, sp);
                     }
                 }
             }
@@ -144,8 +143,7 @@ __global__ __launch_bounds__(1024) void minsum_wg_kernel(WgArgs A) {
                     const int i = (int)(e >> 8), k = (int)(e & 255u);
                     const double2 pp = SP[i];
                     const unsigned long long inf = SI[i];
-                    const double mag = (k == (int)((inf >> 56) & 127)) ? pp.y : pp.x;
-                    s += ((bool)((inf >> 63) & 1) != (bool)((inf >> k) & 1)) ? -mag : mag;   // kernels.py:316, ascending check order
+                    s += rec_message(pp.x, pp.y, inf, k);                                    // kernels.py:316, ascending check order
                 }
                 V[j] = s + A.prior_s[c];                                                     // kernels.py:320
             }
@@ -165,13 +163,6 @@ __global__ __launch_bounds__(1024) void minsum_wg_kernel(WgArgs A) {
 //   * the state stores the products already signed by the row's total sign, so both passes rebuild R with one XOR.
 // NANSEL keeps the NaN -> 0 test of kernels.py:328 for graphs with degree-1 checks (their messages are +-inf).
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wmin(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double wmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// second operand uniform (held in scalar registers): avoids a VGPR copy of the clip bound per edge
-__device__ __forceinline__ double wmin_s(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
-__device__ __forceinline__ double wmax_s(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
-__device__ __forceinline__ double wmin_abs2(double a, double b) { double r; asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double wmax_abs2(double a, double b) { double r; asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double flip_sign(double x, uint32_t signword) { return __hiloint2double(__double2hiint(x) ^ (int)signword, __double2loint(x)); }
 
 // One row of the check pass, edges taken 8 at a time: the 8 index loads (slot-major table, coalesced), then the 8 posterior
@@ -206,15 +197,15 @@ __device__ __forceinline__ void wg_lean_chunk_cols(const uint32_t (&c)[8], int m
                 const double r = flip_sign(mag, (pw >> u) << 31);                            // R_{it-1}[e], kernels.py:311-314
                 x = v[u] - r;                                                                // kernels.py:325
                 if (NANSEL) x = (x != x) ? 0.0 : x;                                          // kernels.py:328-329
-                x = wmax_s(wmin_s(x, clip), nclip);                                          // kernels.py:330-333
-                if (DAMP) x = wmax_s(wmin_s(damping * x + one_minus_d * qprev[u], clip), nclip);   // kernels.py:336-342 (finite operands)
+                x = vmax_u(vmin_u(x, clip), nclip);                                          // kernels.py:330-333
+                if (DAMP) x = vmax_u(vmin_u(damping * x + one_minus_d * qprev[u], clip), nclip);   // kernels.py:336-342 (finite operands)
             }
             if (DAMP && store_q) qo[(size_t)(k0 + u) * m] = x;                               // kernels.py:344-345
             // without damping x is never -0.0 or NaN here (see above); a damped x may underflow to -0.0, which counts as positive
             cb |= (DAMP ? (x < 0.0 ? 1u : 0u) : ((uint32_t)__double2hiint(x) >> 31)) << u;
             if (fabs(x) < min1) arg = k0 + u;                                                // kernels.py:301-304 (strict: first minimum wins)
-            min2 = wmin(min2, wmax_abs2(min1, x));                                           // kernels.py:302,305-306
-            min1 = wmin_abs2(min1, x);
+            min2 = vmin(min2, vmax_abs2(min1, x));                                           // kernels.py:302,305-306
+            min1 = vmin_abs2(min1, x);
         }
     }
     par ^= (pxw >> 31) != 0u;
@@ -377,7 +368,7 @@ __global__ __launch_bounds__(1024) void minsum_wg_lean_kernel(WgArgs A) {
                                     const uint32_t pwb = (k < 32) ? (ip_lo >> k) : (ip_hi >> (k - 32));
                                     x = v - flip_sign(mag, pwb << 31);                       // kernels.py:311-314, 325
                                     if (NANSEL) x = (x != x) ? 0.0 : x;                      // kernels.py:328-329
-                                    x = wmax_s(wmin_s(x, clip), nclip);                      // kernels.py:330-333
+                                    x = vmax_u(vmin_u(x, clip), nclip);                      // kernels.py:330-333
                                 }
                                 xneg = ((uint32_t)__double2hiint(x) >> 31) != 0u;
                                 const double a = fabs(x);
@@ -394,7 +385,7 @@ __global__ __launch_bounds__(1024) void minsum_wg_lean_kernel(WgArgs A) {
                             const bool take = (om1 < m1) || (om1 == m1 && ok1 < k1);
                             const double lose1 = take ? m1 : om1, win2 = take ? om2 : m2;
                             m1 = take ? om1 : m1; k1 = take ? ok1 : k1;
-                            m2 = wmin(win2, lose1);
+                            m2 = vmin(win2, lose1);
                         }
                         if (gl == 0 && live) {
                             const bool par = csyn ^ (bool)(__popc(parbits) & 1);
@@ -574,17 +565,19 @@ int wg_check_variant(int flags) {
     return QLDPC_OK;
 }
 
+Deg1 deg1_checks(const qldpc_graph *g) {
+    Deg1 d{false, 1};
+    std::vector<uint8_t> hit(g->n, 0);
+    for (int i = 0; i < g->m; i++)
+        if (g->indptr[i + 1] - g->indptr[i] == 1) { d.any = true; const int j = g->indices[g->indptr[i]]; if (hit[j]++) d.nan_deg1_only = 0; }
+    return d;
+}
+
 WgChoice wg_choose(const qldpc_graph *g, double damping, int flags, bool clean) {
     WgChoice C;
     C.vg = (wg_mode(g, damping, flags) == 2); C.damp = (damping != 1.0);
-    C.has_deg1 = false;
-    for (int i = 0; i < g->m; i++) C.has_deg1 = C.has_deg1 || (g->indptr[i + 1] - g->indptr[i] == 1);
-    C.nan_deg1_only = 1;
-    if (C.has_deg1) {
-        std::vector<uint8_t> hit(g->n, 0);
-        for (int i = 0; i < g->m && C.nan_deg1_only; i++)
-            if (g->indptr[i + 1] - g->indptr[i] == 1) { const int j = g->indices[g->indptr[i]]; if (hit[j]++) C.nan_deg1_only = 0; }
-    }
+    const Deg1 d1 = deg1_checks(g);
+    C.has_deg1 = d1.any; C.nan_deg1_only = d1.nan_deg1_only;
     C.block = (g->m > 512 || g->n > 4096) ? 1024 : 512;
     C.edge_lanes = ((flags & QLDPC_FLAG_WG_EDGE_LANES) && g->max_row_deg <= 48) ? 1 : 0;
     C.lean = clean && std::isfinite(damping) && !(flags & QLDPC_FLAG_WG_GENERIC);

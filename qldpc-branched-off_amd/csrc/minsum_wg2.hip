@@ -17,11 +17,12 @@
 //   * sign bits are collected with one v_alignbit per edge;
 //   * the last chunk of a row runs a body specialised on the number of edges the wave's rows have left (degree 35 = 4 x 8 + 3: the predicated
 //     8-edge body spent 40 edge-slots on 35 edges).
-// Eligibility (wg2_prepare): clean inputs (minsum_common.h), damping == 1, m <= 1024, row degree <= 40, column degree <= 8, n < 65536, the three
+// Eligibility (wg2_prepare): clean inputs (inputs_clean, launchers.h), damping == 1, m <= 1024, row degree <= 40, column degree <= 8, n < 65536, the three
 // arrays fit 160 KB of LDS, and at most a quarter of the 64-slot chunks mix classes.  Everything else takes minsum_wg.hip.
 #include "common.h"
-#include "minsum_common.h"
-#include "osd_common.h"      // OSD_CLOCK / osd_timer_buffer: the diagnostic build (make timers) stamps the phases
+#include "launchers.h"
+#include "clocks.h"
+#include "minsum_f64.h"
 
 #include <algorithm>
 #include <cmath>
@@ -61,11 +62,6 @@ constexpr int kWg2Chunks = 5;      // 8 edges each: row degree <= 40
 // then the posteriors V [n] at kWg2OffV, the edge list, the flags and the chunk records
 constexpr int kWg2OffSI = 16 * 1025, kWg2OffV = kWg2OffSI + 8 * 1025 + 8;
 
-__device__ __forceinline__ double w2min(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double w2min_s(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
-__device__ __forceinline__ double w2max_s(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
-__device__ __forceinline__ double w2min_abs2(double a, double b) { double r; asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double w2max_abs2(double a, double b) { double r; asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // sign of `t` (bit 31) on the magnitude `mag`: (+-alpha) * mag of kernels.py:311-314 as one bit-field insert
 __device__ __forceinline__ double signed_mag(double mag, uint32_t t) {
     uint32_t hi;
@@ -116,14 +112,14 @@ __device__ __forceinline__ void wg2_chunk(const uint32_t (&idx)[4 * kWg2Chunks],
                 const uint32_t t = (k & 31) ? (word << (k & 31)) : word;                         // the edge's sign (times the row sign) at bit 31
                 x = v[u] - signed_mag(mag, t);                                               // kernels.py:311-314, 325
                 if (NANSEL) x = (x != x) ? 0.0 : x;                                          // kernels.py:328-329
-                x = w2max_s(w2min_s(x, clip), nclip);                                        // kernels.py:330-333
+                x = vmax_u(vmin_u(x, clip), nclip);                                          // kernels.py:330-333
             }
             // x is never -0.0 or NaN here (clean inputs): its sign bit is kernels.py:296-299
             if (k < 32) a.nA = __builtin_amdgcn_alignbit(a.nA, (uint32_t)__double2hiint(x), 31);
             else a.nB = __builtin_amdgcn_alignbit(a.nB, (uint32_t)__double2hiint(x), 31);
             if (fabs(x) < a.min1) a.arg = k;                                                 // kernels.py:301-304 (strict: the first minimum wins)
-            a.min2 = w2min(a.min2, w2max_abs2(a.min1, x));                                   // kernels.py:302,305-306
-            a.min1 = w2min_abs2(a.min1, x);
+            a.min2 = vmin(a.min2, vmax_abs2(a.min1, x));                                     // kernels.py:302,305-306
+            a.min1 = vmin_abs2(a.min1, x);
         }
     }
 }
@@ -464,12 +460,8 @@ static int wg2_build(const qldpc_graph *g, const double *prior, Wg2Prep &P) {
     }
     std::vector<double> prior_s(n);
     for (int c = 0; c < n; c++) prior_s[c] = prior[cos[c]];
-    P.has_deg1 = 0; P.nan_deg1_only = 1;
-    {
-        std::vector<uint8_t> hit(n, 0);
-        for (int i = 0; i < m; i++)
-            if (rdeg(i) == 1) { P.has_deg1 = 1; const int j = g->indices[g->indptr[i]]; if (hit[j]++) P.nan_deg1_only = 0; }
-    }
+    const Deg1 d1 = deg1_checks(g);
+    P.has_deg1 = d1.any; P.nan_deg1_only = d1.nan_deg1_only;
     int rc;
     if ((rc = up(P.row_of_slot, ros)) || (rc = up(P.degr, degr)) || (rc = up(P.ell_cs, ell_cs)) || (rc = up(P.el, el)) || (rc = up(P.chunks, chunks)) ||
         (rc = up(P.prior_s, prior_s)) || (rc = up(P.degc, degc)) || (rc = up(P.slot_of_col, slot_of_col)))

@@ -1,6 +1,6 @@
 // Process-wide kernel-selection switches (qldpc_set_option): state and the entry point.  Results never depend on them.
 #include "common.h"
-#include "minsum_common.h"
+#include "launchers.h"
 
 #include <atomic>
 #include <cstring>

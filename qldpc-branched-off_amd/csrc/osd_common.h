@@ -1,36 +1,12 @@
 // Shared pieces of the OSD-0 kernels (gf2.hip, osd_gj.hip, osd_gjg.hip, osd_small.hip) and of OSD-CS (osd_cs.hip).
+// Device header: only what can reach a kernel's instruction stream (device functions, kernel argument structs shared between files, constants
+// and macros kernel bodies name).  Prototypes and host-only structs live in launchers.h; tools/isa_mix.py RECORDED lists this file per kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "osd_plan.h"
-
-// Phase timers of the OSD kernels exist only in the diagnostic build (`make timers` -> libqldpc_hip_timers.so, -DQLDPC_OSD_TIMERS);
-// the default build carries no clock reads.  Counters (uint64[32]; [16..22] belong to the workgroup BP kernel: wave-iterations, check pass, its barrier, freeze, variable pass, its barrier): [0] shots, [1] chunks, [2] columns taken into blocks, [3] pivots,
-// [4] cycles, [5] kill passes, [6] blocks, [8] sort, [9] phase 1 (reduce columns), [10] phase 2 (block pivots), [11] phase 3 (row updates),
-// [12] dependent-column tests, [13] back-substitution.
-#ifdef QLDPC_OSD_TIMERS
-#define OSD_CLOCK() clock64()
-#else
-#define OSD_CLOCK() 0ll
-#endif
-
 namespace qldpc {
-unsigned long long *osd_timer_buffer();      // device buffer of the current device, NULL in the default build
-
-// ---- host side (after common.h): the launchers osd0_listed_launch (gf2.hip) calls for the kernels its plan chose, and what they share.  Callers hold g->mu.
-// the shots of a launch: list [0 .. *count) on the device, *count <= max_listed; the arrays are indexed by shot
-struct OsdShots { const int32_t *list, *count; int64_t max_listed; const int8_t *synd; const double *llr; const int8_t *hard; const int32_t *ordering; int8_t *solution; };
-int osd0_small_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream, int flags, struct OsdJudge *judge);      // osd_small.hip (OsdJudge: mc_common.h)
-int osd0_gj_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream, bool w16, bool queue_first);        // osd_gj.hip
-int osd0_gjg_launch(const qldpc_graph *g, const OsdLaunch &L, const OsdShots &S, hipStream_t stream);                                   // osd_gjg.hip
-int osd_ug_slabs(const qldpc_graph *g, int grid, bool ug, uint16_t *&ordws, unsigned long long *&U, unsigned long long *&keys);          // gf2.hip
-int host_gf2_rank(const qldpc_graph *g);      // gf2.hip: rank of H over GF(2), what g->gf2_rank caches
-int ensure_col_rows(const qldpc_graph *g);    // gf2.hip: g->d_col_rows on first use
-int osd_small_queue(const qldpc_graph *g, int **queue);      // osd_small.hip: the ticket counter of the one-wave kernels
-void iota_list_launch(int64_t B, int32_t *list, int32_t *count, hipStream_t s);      // gf2.hip: list = 0 .. B - 1, *count = B
-
 __device__ __forceinline__ unsigned long long osd_key(double x) {
     double a = fabs(x);
     if (a != a) a = INFINITY;

@@ -20,9 +20,10 @@
 //     in the column order), n + 1 + lexicographic pair index (pairs) -- the same order as the candidate list of the header.
 // A right-hand side outside the column space puts the shot on a list; the caller runs qldpc_osd0_batch's kernels on it behind this one.
 #include "common.h"
-#include "mc_common.h"
+#include "launchers.h"
 #include "minsum_common.h"
 #include "osd_common.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 #include <cmath>

@@ -1,8 +1,9 @@
 // Shared device pieces of the free-pivot OSD-0 kernels (osd_gj.hip: the pipelined kernel for any m <= 1024; osd_gjq.hip: its look-ahead-queue form for
 // rows of 16 words).  See osd_gj.hip for the algorithm.
+// Device header: only what can reach a kernel's instruction stream (device functions, kernel argument structs shared between files, constants
+// and macros kernel bodies name).  Prototypes and host-only structs live in launchers.h; tools/isa_mix.py RECORDED lists this file per kernel.
 #pragma once
-#include "common.h"
-#include "mc_common.h"
+#include "clocks.h"
 #include "osd_common.h"
 
 namespace qldpc {
@@ -23,12 +24,6 @@ struct OsdGjArgs {
     unsigned long long *sortws;    // [grid][sortws_words] global scratch for the order of the columns behind the head
     size_t sortws_words;
 };
-
-int osd_presort_choice();          // option "osd_presort" (options.hip); osd_presort_columns (osd_plan.h) turns it into P.presort
-int osd_gj_fill(const qldpc_graph *g, const OsdShots &S, hipStream_t stream, OsdGjArgs &P);      // osd_gj.hip: what GJ and GJG fill alike
-#ifdef QLDPC_EXPERIMENTS
-int osd0_gjq_launch(const qldpc_graph *g, const OsdGjArgs &base, int grid, hipStream_t stream, bool &launched);      // osd_gjq.hip
-#endif
 
 #ifndef QLDPC_GJ_DENSELANES
 #define QLDPC_GJ_DENSELANES 40

@@ -21,7 +21,10 @@
 //   * dependent columns are dropped in parallel batches and the sweep stops at rank(H), as in the reference-order kernel.
 // A right-hand side outside the column space (only a caller's own syndromes can be) shows as a one of the reduced b in an unused row; such a
 // shot is put on a list and solved by the reference-order kernel (gf2.hip) afterwards, so every input still gets the reference's answer.
+#include "common.h"
+#include "launchers.h"
 #include "osd_gj.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 

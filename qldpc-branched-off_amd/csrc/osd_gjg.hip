@@ -10,7 +10,10 @@
 //     bit) and a wave-wide XOR -- no barrier inside the chain (the replaced kernel: sixteen waves and a workgroup barrier per pivot);
 //   * dependent-column tests on a window of the next columns only, four lanes per column, only words with unused rows.
 // Right-hand sides outside the column space go on the list the reference-order kernel solves afterwards, as for m <= 1024.
+#include "common.h"
+#include "launchers.h"
 #include "osd_gj.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 

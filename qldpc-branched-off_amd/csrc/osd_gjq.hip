@@ -12,7 +12,10 @@
 // Levels: at the start of iteration c the chains 0 .. c-1 are done, U has seen the blocks 0 .. c-2 ("level c-1", the block c-1 is pending), and so
 // has every queue entry.  The selectors lift the entries to level c; the chain of block c starts; the others apply block c-1 to U and then add
 // new entries at level c.
+#include "common.h"
+#include "launchers.h"
 #include "osd_gj.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 

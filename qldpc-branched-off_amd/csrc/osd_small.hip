@@ -8,9 +8,10 @@
 // at or below the current rank with a one (kernels.py:71-75), rows are physically swapped (kernels.py:79-82) and every other row with a one
 // is added to (kernels.py:88-92).  A lane owns rows lane and lane + 64; one wave, so no barrier: LDS operations of a wave execute in order.
 #include "common.h"
-#include "mc_common.h"
-#include "minsum_common.h"
+#include "launchers.h"
+#include "clocks.h"
 #include "osd_common.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 

@@ -1,7 +1,7 @@
 // Single check-node passes on the CSR edge layout (a3 minsum_core_sparse, a5 bp_core) and the sum-product
 // driver performBeliefPropagationFast (a5).  Edge messages are laid out [shot][edge] as in the reference call.
 #include "common.h"
-#include "mc_common.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstring>

@@ -15,6 +15,7 @@
 // LDS: V[n] f64 (or a per-workgroup slab in HBM/L2 when it does not fit: VG), the check states, the memory draws as u16 per column and
 // a few words of flags and the weight accumulator.  Every loop is bounded by the iteration and leg counts.
 #include "bp_leg.h"
+#include "launchers.h"
 #include "mc_common.h"
 
 #include <algorithm>

@@ -11,8 +11,7 @@
 // columns XORed into the running syndrome, per-shot counters).  The two kernels here are the gather and the commit; both are bounded by the
 // host's tables, and the commit accumulates its parity flips in LDS (32-bit atomicXor) before it touches the running syndrome with plain stores.
 #include "common.h"
-#include "mc_common.h"
-#include "minsum_common.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cmath>

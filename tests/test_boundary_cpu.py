@@ -254,7 +254,7 @@ def test_flag_constants_follow_the_header():
         v = int(val, 16)
         assert getattr(_lib, "FLAG_" + name) == v, name
         assert v & (v - 1) == 0 and v not in seen, (name, seen.get(v))
-        assert v < 0x10000000                      # the public mask (csrc/minsum_common.h: QLDPC_FLAG_PUBLIC_MASK)
+        assert v < 0x10000000                      # the public mask (csrc/launchers.h: QLDPC_FLAG_PUBLIC_MASK)
         seen[v] = name
 
 

@@ -13,6 +13,7 @@ basic block of the loop once: for the branch-free decoder loops that is the dyna
 the share of the rare paths -- the PMC instruction totals (SQ_INSTS_VALU / SALU / LDS) stay the measured side of the roofline.
 """
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -279,18 +280,23 @@ def analyse(src, pattern, loop_pick=None):
     return res
 
 
-# the kernels bench.py prices: key -> (source file, kernel name pattern, which loop: None = the innermost loop with most VALU instructions,
-# "whole" = the whole kernel body (kernels whose time is spread over many loops), files whose text fixes the instruction stream)
+# The one table of the kernels bench.py prices (tools/pmc_summarise.py and tests/test_kernel_sources_cpu.py read it): key -> (source file, the ONE kernel
+# instantiation counted, which loop: None = the innermost loop with most VALU instructions, "whole" = the whole kernel body (kernels whose time is spread over
+# many loops), the files whose text fixes the instruction stream: the .hip file and every device header it reaches through #include "..." -- csrc/launchers.h,
+# csrc/common.h and include/qldpc_hip.h hold nothing a kernel reads and are in no list.  osd_plan.h is host planning code, listed because the
+# OSD kernels name its block and chunk constants.
+_REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h"]
 RECORDED = {
-    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true>", None, ["minsum_regular.hip", "minsum_common.h", "minsum_f64.h", "mc_common.h"]),
-    "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "mc_common.h"]),
-    "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<false>", "whole", ["minsum_wg2.hip", "minsum_common.h"]),
-    "circ144_osd": ("osd_gj.hip", "osd0_gj_kernel<true>", "whole", ["osd_gj.hip", "osd_gj.h", "osd_common.h"]),
+    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true>", None, _REGULAR),
+    "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "clocks.h", "mc_common.h"]),
+    "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<true>", "whole", ["minsum_wg2.hip", "clocks.h", "minsum_f64.h"]),      # <true>: the shipped circ144 matrices have degree-1 checks
+    "circ144_osd": ("osd_gj.hip", "osd0_gj_kernel<true>", "whole", ["osd_gj.hip", "osd_gj.h", "osd_common.h", "clocks.h", "osd_plan.h"]),
 }
+# PMC records of a second instantiation of a kernel above (no static mix of their own): key -> file list
+RECORDED_ALSO = {"cc_bb144_early_exit_full": _REGULAR}
 
 
 def digest(files):
-    import hashlib
     h = hashlib.sha256()
     for f in files:
         with open(os.path.join(CSRC, f), "rb") as fh:

@@ -8,22 +8,13 @@ HBM bytes: (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (FETCH_SIZE / WRITE_SIZE are in 
 MI355X_MICROARCH.md "HBM") -- an upper estimate for narrow reads."""
 import csv
 import glob
-import hashlib
 import json
 import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qldpc-branched-off_amd", "csrc")
-
-
-def digest(files):
-    h = hashlib.sha256()
-    for f in files:
-        with open(os.path.join(CSRC, f), "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()[:16]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_mix import RECORDED, RECORDED_ALSO, ROOT, digest  # noqa: E402  (the file lists per kernel are written once, there)
 
 
 def regular_args(kernel_name):
@@ -54,30 +45,35 @@ def main():
     for p in ("sq_a", "sq_b", "sq_c", "fetch", "write", "grbm"):
         counters.update(load_pass(os.path.join(src, p)))
     cl = wl["circuit_level"]
-    regular = ["minsum_regular.hip", "minsum_common.h", "minsum_f64.h", "mc_common.h"]        # (the same lists as tools/isa_mix.py RECORDED)
-    specs = {   # key: (kernel-name match, counted launches, units per launch, unit, sources)
-        f"cc_{wl['code']}_fixed": (lambda k: (regular_args(k) or [""] * 6)[4:6] == ["true", "true"], 2,
-                                   wl["cc_fixed"]["shots_per_launch"] * wl["cc_fixed"]["max_iter"], "shot_iteration", regular),
+    files = {k: v[3] for k, v in RECORDED.items()}
+    files.update(RECORDED_ALSO)
+    inst = {k: v[1] for k, v in RECORDED.items()}
+    specs = {   # key: (kernel-name match, units of each counted launch in launch order, unit); the key's file list and instantiation are tools/isa_mix.py's
+        f"cc_{wl['code']}_fixed": (lambda k: (regular_args(k) or [""] * 6)[4:6] == ["true", "true"],
+                                   [wl["cc_fixed"]["shots_per_launch"] * wl["cc_fixed"]["max_iter"]] * 2, "shot_iteration"),
         # reference semantics: the bit-sliced first iteration sees every shot (the full decoder only the few it lists: cc_..._early_exit_full)
-        f"cc_{wl['code']}_early_exit": (lambda k: "mc_first_kernel" in k, 2, wl["cc_early_exit"]["shots_per_launch"], "shot", ["mc_first.hip", "mc_common.h"]),
-        f"cc_{wl['code']}_early_exit_full": (lambda k: (regular_args(k) or [""] * 6)[4:6] == ["true", "false"], 2,
-                                             wl["cc_early_exit"]["shots_per_launch"], "shot", regular),
-        f"{wl['circuit']}_bp": (lambda k: "minsum_wg2_kernel" in k, 2, (cl["iters_z"] + cl["iters_x"]) / 2.0, "decode_iteration",
-                                ["minsum_wg2.hip", "minsum_common.h"]),
-        f"{wl['circuit']}_osd": (lambda k: "osd0_gj_kernel" in k, 2, (cl["osd_z"] + cl["osd_x"]) / 2.0, "osd_shot",
-                                 ["osd_gj.hip", "osd_gj.h", "osd_common.h"]),
+        f"cc_{wl['code']}_early_exit": (lambda k: "mc_first_kernel" in k, [wl["cc_early_exit"]["shots_per_launch"]] * 2, "shot"),
+        f"cc_{wl['code']}_early_exit_full": (lambda k: (regular_args(k) or [""] * 6)[4:6] == ["true", "false"],
+                                             [wl["cc_early_exit"]["shots_per_launch"]] * 2, "shot"),
+        # the counted batch launches sector Z, then sector X; a sector whose matrix has degree-1 checks takes minsum_wg2_kernel<true>, the other <false>:
+        # of the two launches the entry keeps those of the ONE instantiation the table names, with their own units
+        f"{wl['circuit']}_bp": (lambda k: "minsum_wg2_kernel" in k, [cl["iters_z"], cl["iters_x"]], "decode_iteration"),
+        f"{wl['circuit']}_osd": (lambda k: "osd0_gj_kernel" in k, [cl["osd_z"], cl["osd_x"]], "osd_shot"),
     }
     entries, lines = {}, []
-    for key, (match, nl, units, unit, sources) in specs.items():
-        e = {"unit": unit, "units_per_launch": units, "sources": sources, "source_digest": digest(sources), "counted_launches": nl,
+    for key, (match, launch_units, unit) in specs.items():
+        sources = files[key]
+        e = {"unit": unit, "sources": sources, "source_digest": digest(sources),
              "source": f"profiles/{tag}_pmc.txt (rocprofv3 --pmc, tools/pmc_passes.sh, collected {time.strftime('%Y-%m-%d')})"}
         for cname, rows in counters.items():
-            vals = [(did, k, v) for did, k, v in rows if match(k)]
-            if not vals:
+            vals = [(k, v) for _, k, v in rows if match(k)][-len(launch_units):]
+            kept = [(k, v, u) for (k, v), u in zip(vals, launch_units) if inst.get(key, "") in k]
+            if not kept:
                 continue
-            e["kernel"] = vals[-1][1]
-            last = vals[-nl:]
-            e[cname] = sum(v for _, _, v in last) / len(last)
+            e["kernel"] = kept[-1][0]
+            e["counted_launches"] = len(kept)
+            e["units_per_launch"] = units = sum(u for _, _, u in kept) / len(kept)
+            e[cname] = sum(v for _, v, _ in kept) / len(kept)
         if "SQ_INSTS_VALU" not in e:
             continue
         if "SQ_WAVE_CYCLES" in e and e["SQ_WAVE_CYCLES"] > 0:
