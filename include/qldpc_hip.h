@@ -41,6 +41,8 @@
  *        additive, same version: qldpc_osd0_last_path (which OSD-0 kernel the last call on a handle took), QLDPC_OSD_PATH_* and QLDPC_OSD_DETAIL_*
  *        additive, same version (the suites pin 101): circuit plans that sample a detector error model, qldpc_dem_desc and
  *        qldpc_circuit_plan_create_dem
+ *        additive, same version: recorded detection events in place of a plan's sampler, qldpc_circuit_plan_set_event_layout,
+ *        qldpc_circuit_plan_decode_events[_dev] and qldpc_circuit_plan_unpack_events
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -670,6 +672,40 @@ int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *dem, const qldpc_graph *
                                   int alpha_mode, double alpha_val0, double alpha_val1, const double *alpha_seq0, int alpha_len0,
                                   const double *alpha_seq1, int alpha_len1, double damping, double clip_llr, int use_osd, int flags, int64_t batch,
                                   qldpc_circuit_plan **out);
+
+/* ---- recorded detection events in place of the sampler: events -> decode -> OSD -> predict.  New here: the reference has no counterpart. ---------
+ * The second front door of a circuit plan, for plans of qldpc_circuit_plan_create and _create_dem alike: the syndromes come from the caller's records
+ * (Stim samples, hardware shots) and the predicted observable flips go back, the `decode_batch` of other DEM decoders.  Everything between is the plan's:
+ * the same buffers, the same decode of a sector, every qldpc_circuit_plan_use_* switch.  Nothing here touches the tally, the sampled truth or the outcomes,
+ * and _run, _run_outcomes and _sample are unaffected by calls made before them.
+ *
+ * The record format: shot i starts at byte i * stride of `events`; bit d of a record is (rec[d >> 3] >> (d & 7)) & 1 (Stim's "b8").  n_bits is the number of
+ * bits rows may name; a record holds at least ceil(n_bits / 8) bytes (stride may be larger: the bytes beyond, and the high bits of the last byte, are never
+ * used; bytes beyond are never read).
+ * The layout: row r of sector s (a row of that sector's graph; what _sample calls sparse_z / sparse_x) reads bit bit_of_row<s>[r]; -1 makes the row
+ * constant 0; a bit no row names is ignored; two rows may name one bit.  Without a call the layout is the default: sector 0's rows, then sector 1's
+ * (n_bits = rows of g0 + rows of g1).  _set_event_layout may be called again; NULL for a sector = a contiguous run at that sector's default base (0, and
+ * the rows of g0); the tables are copied.  bit_of_row1 is ignored on a one-sector plan.  QLDPC_ERR_INVALID: n_bits outside 1..131070, a table entry outside
+ * [-1, n_bits), n_bits too small for a default run. */
+int qldpc_circuit_plan_set_event_layout(qldpc_circuit_plan *plan, int32_t n_bits, const int32_t *bit_of_row0, const int32_t *bit_of_row1);
+/* Decodes `count` records (host memory) in pieces of the plan's batch: per batch, copy to the device and unpack (inside the QLDPC_PHASE_SAMPLE bracket),
+ * decode + OSD of every sector inside their brackets exactly as _run does, predict (inside QLDPC_PHASE_JUDGE), copy the results back, synchronise `stream`.
+ *   pred0[i] / pred1[i]: bit r = the correction of shot i flips observable r of sector 0 / 1 (the XOR of the logical masks of the correction's ones);
+ *   flags[i]: bit 0 / 1 = BP (or whatever the plan's path is) converged in sector 0 / 1, bit 2 / 3 = the correction does NOT reproduce the sector's
+ *   syndrome, bit 4 / 5 = the sector's syndrome was all zero.
+ * A one-sector plan leaves the odd flag bits 0; pred1 may then be NULL and is zeroed otherwise.
+ * seed and shot_begin + i go where _run passes its seed and trial index: Relay-BP draws from them, every other path ignores them.  So the result for a
+ * shot is a pure function of (record, seed, shot_begin + i): it depends neither on the plan's batch nor on how a range is split over calls.
+ * QLDPC_ERR_INVALID, with qldpc_last_error naming the argument: plan, events, pred0, flags (pred1 with two sectors) NULL; count or shot_begin negative;
+ * stride below ceil(n_bits / 8) (or above 2^30).  count == 0 returns QLDPC_OK and touches nothing. */
+int qldpc_circuit_plan_decode_events(qldpc_circuit_plan *plan, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events,
+                                     int64_t stride, void *stream, uint64_t *pred0, uint64_t *pred1, uint8_t *flags);
+/* The same on device pointers: everything is enqueued on `stream`, nothing is copied and nothing synchronised. */
+int qldpc_circuit_plan_decode_events_dev(qldpc_circuit_plan *plan, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
+                                         int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags);
+/* The unpacker alone, the counterpart of qldpc_circuit_plan_sample: sparse0 int8[count][rows of g0], sparse1 int8[count][rows of g1] (host; values
+ * 0 / 1; sparse1 may be NULL on a one-sector plan). */
+int qldpc_circuit_plan_unpack_events(qldpc_circuit_plan *plan, int64_t count, const uint8_t *events, int64_t stride, int8_t *sparse0, int8_t *sparse1);
 
 /* ---- (e) multi-GPU: the one collective of the path, natively on RCCL --------------------------------------------------------
  * Sum of the int64[QLDPC_TALLY_SLOTS] tally over the GPUs of a node; replaces the Python loop that sums the workers' results in

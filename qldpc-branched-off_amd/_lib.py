@@ -952,6 +952,22 @@ class MessageStats:
             pass
 
 
+def pack_events(bits):
+    """bool / 0-1 array [count, n_bits] -> bit-packed records uint8[count, ceil(n_bits / 8)], bit d of a record = (rec[d >> 3] >> (d & 7)) & 1 (Stim's b8)."""
+    bits = np.asarray(bits)
+    if bits.ndim != 2:
+        raise ValueError(f"bits must be [count, n_bits], got shape {bits.shape}")
+    return np.packbits(bits != 0, axis=1, bitorder="little")
+
+
+def unpack_bits(packed, n_bits):
+    """The inverse of pack_events: uint8[count, >= ceil(n_bits / 8)] -> uint8[count, n_bits] of 0 / 1."""
+    packed = np.asarray(packed, np.uint8)
+    if packed.ndim != 2 or packed.shape[1] * 8 < n_bits:
+        raise ValueError(f"packed must be uint8[count, >= {(n_bits + 7) // 8}], got shape {packed.shape}")
+    return np.unpackbits(packed, axis=1, count=int(n_bits), bitorder="little")
+
+
 class CircuitPlan:
     """Circuit-level Monte-Carlo plan (qldpc_circuit_plan_*): Philox fault sampling through precomputed fault signatures,
     decode of both sectors, OSD-0, logical comparison and tally, all on the device."""
@@ -1057,6 +1073,54 @@ class CircuitPlan:
         check(lib().qldpc_circuit_plan_sample(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), ptr(spz, C.c_int8),
                                               ptr(tz, C.c_int8), ptr(spx, C.c_int8), ptr(tx, C.c_int8)))
         return spz, tz, spx, tx
+
+    def set_event_layout(self, n_bits, rows0=None, rows1=None):
+        """Which bit of an event record every row reads (qldpc_circuit_plan_set_event_layout): rows<s>[r] = the bit of row r of sector s, -1 = the row is
+        constant 0, None = a contiguous run at the sector's default base.  Without a call: sector 0's rows, then sector 1's."""
+        tabs = []
+        for s, (rows, m) in enumerate(((rows0, self.nsx), (rows1, self.nsz))):
+            if rows is None or (s == 1 and getattr(self, "n_sectors", 2) == 1):
+                tabs.append(None)
+                continue
+            rows = i32(rows).ravel()
+            if rows.size != m:
+                raise ValueError(f"rows{s} has {rows.size} entries, sector {s} has {m} rows")
+            tabs.append(rows)
+        check(lib().qldpc_circuit_plan_set_event_layout(self._h, C.c_int32(int(n_bits)), *(ptr(x, C.c_int32) if x is not None else None for x in tabs)))
+        self.event_bits = int(n_bits)
+
+    def _events(self, events):
+        """uint8[count, stride] records (C order) of at least ceil(event_bits / 8) bytes each"""
+        events = u8(events)
+        if events.ndim != 2:
+            raise ValueError(f"events must be uint8[count, stride], got shape {events.shape}")
+        return events
+
+    def decode_events(self, events, seed=0, shot_begin=0, stream=0):
+        """Bit-packed records uint8[count, stride] (pack_events) -> (pred0 uint64[count], pred1 uint64[count], flags uint8[count]): the predicted observable
+        flips per sector (bit r = observable r) and, per shot, bit 0 / 1 = converged, 2 / 3 = correction does not reproduce the syndrome, 4 / 5 = zero
+        syndrome of sector 0 / 1 (qldpc_circuit_plan_decode_events).  A one-sector plan returns zeros for sector 1."""
+        events = self._events(events)
+        count = events.shape[0]
+        pred0, pred1, flags = np.zeros(count, np.uint64), np.zeros(count, np.uint64), np.zeros(count, np.uint8)
+        check(lib().qldpc_circuit_plan_decode_events(self._h, C.c_uint64(seed), C.c_int64(shot_begin), C.c_int64(count), ptr(events, C.c_uint8),
+                                                     C.c_int64(events.shape[1]), C.c_void_p(stream), ptr(pred0, C.c_uint64), ptr(pred1, C.c_uint64),
+                                                     ptr(flags, C.c_uint8)))
+        return pred0, pred1, flags
+
+    def decode_events_dev(self, d_events, count, stride, d_pred0, d_pred1, d_flags, seed=0, shot_begin=0, stream=0):
+        """decode_events on device addresses (e.g. torch data_ptr()): enqueued on `stream`, nothing synchronised (qldpc_circuit_plan_decode_events_dev)."""
+        check(lib().qldpc_circuit_plan_decode_events_dev(self._h, C.c_uint64(seed), C.c_int64(shot_begin), C.c_int64(count), C.c_void_p(d_events),
+                                                         C.c_int64(stride), C.c_void_p(stream), C.c_void_p(d_pred0), C.c_void_p(d_pred1), C.c_void_p(d_flags)))
+
+    def unpack_events(self, events):
+        """The unpacker alone (qldpc_circuit_plan_unpack_events): records -> (sparse0 int8[count, rows of sector 0], sparse1), the syndromes a decode sees."""
+        events = self._events(events)
+        count = events.shape[0]
+        sp0, sp1 = np.zeros((count, self.nsx), np.int8), np.zeros((count, self.nsz), np.int8)
+        check(lib().qldpc_circuit_plan_unpack_events(self._h, C.c_int64(count), ptr(events, C.c_uint8), C.c_int64(events.shape[1]), ptr(sp0, C.c_int8),
+                                                     ptr(sp1, C.c_int8)))
+        return sp0, sp1
 
     def close(self):
         if self._h is not None and self._h.value:

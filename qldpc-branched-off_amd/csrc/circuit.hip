@@ -13,6 +13,7 @@
 #include "launchers.h"
 #include "clocks.h"
 #include "mc_common.h"
+#include "judge.h"
 
 #include <algorithm>
 #include <cmath>
@@ -115,77 +116,7 @@ __global__ __launch_bounds__(256) void circuit_sample_kernel(int64_t B, int64_t 
     }
 }
 
-// per trial (32 lanes): decoded logical action H_logical @ det (engine.py:99,119) vs the true logical flips, both sectors
-struct JudgeSector {
-    int m, n;
-    const int32_t *indptr, *indices, *colptr, *rowidx;
-    const uint64_t *logmask;
-    const int8_t *synd, *det;
-    const uint8_t *conv;
-    const int32_t *iters;
-    const unsigned long long *true_log;
-};
-
-__device__ __forceinline__ void judge_sector(const JudgeSector &S, int64_t b, int lane, bool &err, bool &nz, bool &bad) {
-    const int8_t *d = S.det + b * S.n, *s = S.synd + b * S.m;
-    uint64_t lm = 0;
-    for (int j = lane; j < S.n; j += 32) if (d[j] & 1) lm ^= S.logmask[j];
-    int bd = 0, z = 0;
-    for (int i = lane; i < S.m; i += 32) {
-        int p = 0;
-        for (int k = S.indptr[i]; k < S.indptr[i + 1]; k++) p ^= d[S.indices[k]];
-        bd |= ((p ^ s[i]) & 1);
-        z |= (s[i] & 1);
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) { lm ^= __shfl_xor(lm, off, 32); bd |= __shfl_xor(bd, off, 32); z |= __shfl_xor(z, off, 32); }
-    err = (lm != S.true_log[b]);
-    nz = z != 0;
-    bad = bd != 0;
-}
-
-// The same verdicts from the ONES of the correction: a decoded error has ~100 ones among ~8 800 columns, so H @ det is ~600 parity flips (the columns' rows, CSC) into a bit
-// set of the trial in LDS instead of the ~31 000 byte gathers per sector of the row-wise form above (1.15 ms per 16 384-trial batch of config 5); the scan of det -- aligned
-// dwords, the ragged head and tail as bytes -- is what is left.  `par`: m bits of LDS owned by the trial's 32 lanes.
-__device__ __forceinline__ void judge_sector_sparse(const JudgeSector &S, int64_t b, int lane, uint32_t *par, bool &err, bool &nz, bool &bad) {
-    const uint8_t *d = reinterpret_cast<const uint8_t *>(S.det) + b * S.n;
-    const int8_t *s = S.synd + b * S.m;
-    const int mwords = (S.m + 31) >> 5;
-    for (int w = lane; w < mwords; w += 32) par[w] = 0u;
-    __builtin_amdgcn_wave_barrier();
-    uint64_t lm = 0;
-    auto one = [&](int j) {
-        lm ^= S.logmask[j];
-        for (int e = S.colptr[j]; e < S.colptr[j + 1]; e++) { const int r = S.rowidx[e]; atomicXor(&par[r >> 5], 1u << (r & 31)); }
-    };
-    const int head = (int)((4 - (reinterpret_cast<uintptr_t>(d) & 3)) & 3), nhead = head < S.n ? head : S.n;
-    if (lane < nhead && (d[lane] & 1)) one(lane);
-    const int nw = (S.n - nhead) >> 2;
-    const uint32_t *dw = reinterpret_cast<const uint32_t *>(d + nhead);
-    for (int w = lane; w < nw; w += 32) {
-        uint32_t x = dw[w] & 0x01010101u;
-        while (x) {                                                        // (rare: a correction is sparse)
-            const int byte = (__builtin_ctz(x)) >> 3;
-            x &= x - 1u;
-            one(nhead + 4 * w + byte);
-        }
-    }
-    const int tail0 = nhead + 4 * nw;
-    if (tail0 + lane < S.n && (d[tail0 + lane] & 1)) one(tail0 + lane);
-    __builtin_amdgcn_wave_barrier();
-    int bd = 0, z = 0;
-    for (int i = lane; i < S.m; i += 32) {
-        const int si = s[i] & 1;
-        bd |= (int)((par[i >> 5] >> (i & 31)) & 1u) ^ si;
-        z |= si;
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) { lm ^= __shfl_xor(lm, off, 32); bd |= __shfl_xor(bd, off, 32); z |= __shfl_xor(z, off, 32); }
-    err = (lm != S.true_log[b]);
-    nz = z != 0;
-    bad = bd != 0;
-}
-
+// per trial (32 lanes): decoded logical action H_logical @ det (engine.py:99,119) (judge.h) vs the true logical flips, both sectors
 // TWO = false: a one-sector plan (a detector error model with n_sectors = 1): X is not read, its slots and outcome bit 1 stay 0
 template <bool SPARSE, bool TWO>
 __global__ __launch_bounds__(256) void circuit_judge_kernel(int64_t B, JudgeSector Z, JudgeSector X, unsigned long long *__restrict__ tally,
@@ -205,11 +136,11 @@ __global__ __launch_bounds__(256) void circuit_judge_kernel(int64_t B, JudgeSect
         bool ze, zn, zb, xe = false, xn = false, xb = false;
         if (SPARSE) {
             uint32_t *par = parbits + (threadIdx.x >> 5) * 256;
-            judge_sector_sparse(Z, b, lane, par, ze, zn, zb);
-            if (TWO) judge_sector_sparse(X, b, lane, par + 128, xe, xn, xb);
+            ze = judge_sector_sparse(Z, b, lane, par, zn, zb) != Z.true_log[b];
+            if (TWO) xe = judge_sector_sparse(X, b, lane, par + 128, xn, xb) != X.true_log[b];
         } else {
-            judge_sector(Z, b, lane, ze, zn, zb);
-            if (TWO) judge_sector(X, b, lane, xe, xn, xb);
+            ze = judge_sector(Z, b, lane, zn, zb) != Z.true_log[b];
+            if (TWO) xe = judge_sector(X, b, lane, xn, xb) != X.true_log[b];
         }
         if (lane == 0) {
             if (outcome) outcome[b] = (uint8_t)((ze ? 1 : 0) | (xe ? 2 : 0));               // (z_err, x_err) of engine.py:117-122
@@ -267,6 +198,10 @@ struct qldpc_circuit_plan {
         PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
         PlanBuf d_legs;                            // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
         PlanBuf d_flips;                           // Osd::CS: workspace of the sweep
+        // decode of recorded events (events.hip): the record bit of every row (ev_tab, else the contiguous run at ev_base); the predictions of a batch
+        PlanBuf d_evtab, d_pred;
+        bool ev_tab = false;
+        int ev_base = 0;
     } sec[2];
     int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
     int nsec = 2, ks[2] = {0, 0};                  // sectors in use (1: a one-sector detector error model, sec[1] stays empty); logicals per sector
@@ -279,6 +214,8 @@ struct qldpc_circuit_plan {
     int64_t batch = 0;
     bool nanfree = false;
     PlanBuf d_loc_type, d_count, d_tally, d_outcome, d_clk;    // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
+    int ev_bits = 0;                               // bits of an event record that rows may name; 0: the default layout (sector 0's rows, then sector 1's)
+    PlanBuf d_events, d_evflags;                   // qldpc_circuit_plan_decode_events: the records of a batch (staging), its flags
     Path path = Path::FLOOD;
     Osd osd = Osd::OSD0;
     RelayParams rp{};                              // Path::RELAY (relay_bp.hip)
@@ -902,6 +839,146 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
     });
     if (rc == QLDPC_OK) P->path = Path::F32;
     return rc;
+}
+
+// ---- recorded detection events in place of the sampler (kernels: events.hip) ----
+static const int kMaxEventBits = 131070;           // two sectors of at most 65535 detectors
+
+static int event_bits(const qldpc_circuit_plan *P) { return P->ev_bits ? P->ev_bits : P->sec[0].nsyn + (P->nsec == 2 ? P->sec[1].nsyn : 0); }
+static EventsSector events_view(const qldpc_circuit_plan *P, int i) {
+    const Sector &S = P->sec[i];
+    if (i >= P->nsec) return EventsSector{0, 0, nullptr, nullptr};
+    const int base = P->ev_bits ? S.ev_base : (i ? P->sec[0].nsyn : 0);
+    return EventsSector{S.nsyn, base, S.ev_tab ? S.d_evtab.as<int32_t>() : (const int32_t *)nullptr, S.d_syn.as<int8_t>()};
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_set_event_layout(qldpc_circuit_plan *P, int32_t n_bits, const int32_t *bit_of_row0, const int32_t *bit_of_row1) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(n_bits >= 1 && n_bits <= kMaxEventBits, "n_bits = %d is outside 1..%d", n_bits, kMaxEventBits);
+    const int32_t *const tab[2] = {bit_of_row0, bit_of_row1};
+    bool is_tab[2] = {false, false};
+    int base[2] = {0, P->sec[0].nsyn};
+    for (int i = 0; i < P->nsec; i++) {
+        const int nsyn = P->sec[i].nsyn;
+        if (!tab[i]) {
+            QLDPC_REQUIRE(base[i] + nsyn <= n_bits, "n_bits = %d is too small for the default layout of sector %d (bits %d..%d)", n_bits, i, base[i], base[i] + nsyn - 1);
+            continue;
+        }
+        bool run = tab[i][0] >= 0;
+        for (int r = 0; r < nsyn; r++) {
+            QLDPC_REQUIRE(tab[i][r] >= -1 && tab[i][r] < n_bits, "bit_of_row%d[%d] = %d is outside -1..%d (n_bits = %d)", i, r, tab[i][r], n_bits - 1, n_bits);
+            run = run && tab[i][r] == tab[i][0] + r;
+        }
+        is_tab[i] = !run;                                              // a contiguous run of bits needs no table
+        if (run) base[i] = tab[i][0];
+    }
+    QLDPC_USE_DEVICE(P->device);
+    int rc = QLDPC_OK;
+    QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a decode that is still enqueued reads the tables replaced here
+    for (int i = 0; i < P->nsec; i++)
+        if (is_tab[i] && (rc = up(P->sec[i].d_evtab, std::vector<int32_t>(tab[i], tab[i] + P->sec[i].nsyn))) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++) { P->sec[i].ev_tab = is_tab[i]; P->sec[i].ev_base = base[i]; }
+    P->ev_bits = n_bits;
+    return QLDPC_OK;
+}
+
+// what decode_events and unpack_events check alike
+static int events_args(const qldpc_circuit_plan *P, const uint8_t *events, int64_t stride) {
+    QLDPC_REQUIRE(events != nullptr, "events is NULL");
+    const int nbytes = (event_bits(P) + 7) / 8;
+    QLDPC_REQUIRE(stride >= nbytes, "stride = %lld is below the %d bytes of a record (n_bits = %d)", (long long)stride, nbytes, event_bits(P));
+    QLDPC_REQUIRE(stride <= ((int64_t)1 << 30), "stride = %lld is above 2^30 bytes", (long long)stride);
+    return QLDPC_OK;
+}
+
+// one pass over the records [0, count): copy (host records) + unpack in the sampler's bracket, the sectors' decode as in a run, predict in the judge's bracket.
+// host = true: events / pred0 / pred1 / flags are host pointers, and every batch is copied back and waited for (as circuit_run does for its outcomes);
+// host = false: device pointers, everything is enqueued on s and nothing is waited for.
+static int decode_events(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events, int64_t stride, hipStream_t s,
+                         uint64_t *pred0, uint64_t *pred1, uint8_t *flags, bool host) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(count >= 0, "count is negative");
+    QLDPC_REQUIRE(shot_begin >= 0, "shot_begin is negative");
+    if (count == 0) return QLDPC_OK;
+    int rc = events_args(P, events, stride);
+    if (rc != QLDPC_OK) return rc;
+    const bool two = P->nsec == 2;
+    QLDPC_REQUIRE(pred0 != nullptr, "pred0 is NULL");
+    QLDPC_REQUIRE(pred1 != nullptr || !two, "pred1 is NULL (the plan has two sectors)");
+    QLDPC_REQUIRE(flags != nullptr, "flags is NULL");
+    QLDPC_USE_DEVICE(P->device);
+    const size_t Bz = (size_t)P->batch;
+    if (host) {
+        if ((rc = P->d_events.ensure(Bz * (size_t)stride)) || (rc = P->d_evflags.ensure(Bz)) || (rc = ensure_each(P, &Sector::d_pred, Bz * 8))) return rc;
+        if (!two && pred1) std::memset(pred1, 0, (size_t)count * 8);
+    } else if (!two && pred1) {
+        QLDPC_HIP_TRY(hipMemsetAsync(pred1, 0, (size_t)count * 8, s));
+    }
+    const JudgeSector Z = judge_view(P->sec[0]), X = two ? judge_view(P->sec[1]) : JudgeSector{};
+    const EventsSector E0 = events_view(P, 0), E1 = events_view(P, 1);
+    const int n_bits = event_bits(P);
+    for (int64_t off = 0; off < count; off += P->batch) {
+        const int64_t B = std::min<int64_t>(P->batch, count - off);
+        if (P->pending.size() > 256) drain_phases(P, false);
+        if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
+        const uint8_t *d_rec = events + off * stride;
+        if (host) {
+            QLDPC_HIP_TRY(hipMemcpyAsync(P->d_events.p, d_rec, (size_t)B * (size_t)stride, hipMemcpyHostToDevice, s));
+            d_rec = P->d_events.as<uint8_t>();
+        }
+        if ((rc = events_unpack_launch(B, d_rec, stride, n_bits, E0, E1, two, P->d_count.as<int32_t>(), s)) != QLDPC_OK) return rc;
+        if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
+        for (int sector = 0; sector < P->nsec; sector++)
+            if ((rc = decode_sector(P, sector, B, s, seed, shot_begin + off)) != QLDPC_OK) return rc;
+        if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, true)) != QLDPC_OK) return rc;
+        unsigned long long *p0 = host ? P->sec[0].d_pred.as<unsigned long long>() : reinterpret_cast<unsigned long long *>(pred0) + off;
+        unsigned long long *p1 = !two ? nullptr : host ? P->sec[1].d_pred.as<unsigned long long>() : reinterpret_cast<unsigned long long *>(pred1) + off;
+        uint8_t *fl = host ? P->d_evflags.as<uint8_t>() : flags + off;
+        if ((rc = events_predict_launch(B, Z, X, two, p0, p1, fl, s)) != QLDPC_OK) return rc;
+        if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
+        P->batches++;
+        if (host) {
+            QLDPC_HIP_TRY(hipMemcpyAsync(pred0 + off, p0, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+            if (two) QLDPC_HIP_TRY(hipMemcpyAsync(pred1 + off, p1, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+            QLDPC_HIP_TRY(hipMemcpyAsync(flags + off, fl, (size_t)B, hipMemcpyDeviceToHost, s));
+            QLDPC_HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_decode_events(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events,
+                                                  int64_t stride, void *stream, uint64_t *pred0, uint64_t *pred1, uint8_t *flags) {
+    return decode_events(P, seed, shot_begin, count, events, stride, reinterpret_cast<hipStream_t>(stream), pred0, pred1, flags, true);
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_decode_events_dev(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
+                                                      int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags) {
+    return decode_events(P, seed, shot_begin, count, d_events, stride, reinterpret_cast<hipStream_t>(stream), d_pred0, d_pred1, d_flags, false);
+}
+
+// the unpacker alone, the counterpart of qldpc_circuit_plan_sample: sparse0 int8[count][nsyn0], sparse1 int8[count][nsyn1] (host; sparse1 may be NULL on one sector)
+QLDPC_EXPORT int qldpc_circuit_plan_unpack_events(qldpc_circuit_plan *P, int64_t count, const uint8_t *events, int64_t stride, int8_t *sparse0, int8_t *sparse1) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(count >= 0, "count is negative");
+    if (count == 0) return QLDPC_OK;
+    int rc = events_args(P, events, stride);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(sparse0 != nullptr, "sparse0 is NULL");
+    QLDPC_REQUIRE(sparse1 != nullptr || P->nsec == 1, "sparse1 is NULL (the plan has two sectors)");
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_events.ensure((size_t)P->batch * (size_t)stride)) != QLDPC_OK) return rc;
+    int8_t *const sparse[2] = {sparse0, sparse1};
+    const EventsSector E0 = events_view(P, 0), E1 = events_view(P, 1);
+    for (int64_t off = 0; off < count; off += P->batch) {
+        const int64_t B = std::min<int64_t>(P->batch, count - off);
+        QLDPC_HIP_TRY(hipMemcpy(P->d_events.p, events + off * stride, (size_t)B * (size_t)stride, hipMemcpyHostToDevice));
+        if ((rc = events_unpack_launch(B, P->d_events.as<uint8_t>(), stride, event_bits(P), E0, E1, P->nsec == 2, nullptr, nullptr)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(hipDeviceSynchronize());
+        for (int i = 0; i < P->nsec; i++)
+            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * P->sec[i].nsyn, P->sec[i].d_syn.p, (size_t)B * P->sec[i].nsyn, hipMemcpyDeviceToHost));
+    }
+    return QLDPC_OK;
 }
 
 QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {

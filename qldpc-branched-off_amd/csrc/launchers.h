@@ -15,6 +15,8 @@ namespace qldpc {
 struct OsdLaunch;      // osd_plan.h
 struct OsdGjArgs;      // osd_gj.h
 struct DemTab;         // mc_common.h
+struct JudgeSector;    // judge.h
+struct EventsSector;   // judge.h
 
 // internal flag (upper half of `flags`): the caller verified on the host that every prior is finite
 #define QLDPC_FLAG_PUBLIC_MASK 0x0FFFFFFF          // flag bits callers may set (include/qldpc_hip.h)
@@ -162,6 +164,14 @@ int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech,
                       bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
                       hipStream_t s);
 int dem_validate(const qldpc_dem_desc *D);      // QLDPC_OK, or QLDPC_ERR_INVALID with the error text naming the sector or the mechanism
+// Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
+// only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
+// predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does
+// not reproduce the syndrome, 4 / 5 = zero syndrome, of sector 0 / 1.  two = false: sector 1 is not touched and its bits stay 0.
+int events_unpack_launch(int64_t B, const uint8_t *d_events, int64_t stride, int n_bits, const EventsSector &S0, const EventsSector &S1, bool two,
+                         int32_t *d_fail_counts, hipStream_t s);
+int events_predict_launch(int64_t B, const JudgeSector &Z, const JudgeSector &X, bool two, unsigned long long *d_pred0, unsigned long long *d_pred1,
+                          uint8_t *d_flags, hipStream_t s);
 
 unsigned long long *osd_timer_buffer();      // device buffer of the current device, NULL in the default build
 

@@ -12,6 +12,9 @@ The sampler's law (``include/qldpc_hip.h``): mechanism l of trial g fires iff wo
 The mechanisms are the truth that is sampled; what the decoders see is the DECODER VIEW of a sector: a parity-check matrix over detectors, a prior per
 column and a logical mask per column.  ``from_decoding_matrices`` keeps the matrices it was given as that view (the graphs and priors of today's
 ``run_simulation`` plan); otherwise ``decoder_view`` derives one by merging the mechanisms that look alike inside the sector.
+
+``DemDecoder`` is the other front door of the same plan: recorded detection events in (Stim samples, hardware shots, in the model's own detector
+numbering), predicted observable flips out -- events -> decode -> OSD -> predict, with the same decoders and switches and no sampler.
 """
 import re
 from collections import namedtuple
@@ -39,9 +42,13 @@ def _columns_of(indptr, indices, n):
 class DetectorErrorModel:
     """prob f64[n_mech] and, per sector, the projection of the mechanisms onto it: ``det_ptr`` int32[n_mech + 1] / ``det_idx`` uint16 (the detectors of
     every mechanism, strictly ascending) and ``logmask`` uint64[n_mech] (bit r = observable r), with ``n_det``, ``k`` and an optional ``layer_rows`` (rows
-    of one syndrome cycle, for ``window=``).  ``views``: an explicit DecoderView per sector, or None to derive it."""
+    of one syndrome cycle, for ``window=``).  ``views``: an explicit DecoderView per sector, or None to derive it.
 
-    def __init__(self, prob, sectors, views=None):
+    ``detector_map``: per sector, an int array with the MODEL's detector number of every row of that sector -- the numbering recorded detection events
+    come in (``DemDecoder``); ``n_detectors`` is the width of such a record.  None = the concatenated default: sector 0's rows are detectors
+    0 .. n_det[0] - 1, sector 1's follow."""
+
+    def __init__(self, prob, sectors, views=None, detector_map=None, n_detectors=None):
         self.prob = np.ascontiguousarray(prob, np.float64)
         if not 1 <= len(sectors) <= 2:
             raise ValueError(f"a detector error model has 1 or 2 sectors, got {len(sectors)}")
@@ -61,6 +68,17 @@ class DetectorErrorModel:
                 raise ValueError(f"sector {s}: {sec.n_det} detectors (1..65535)")
             self.sectors.append(sec)
         self._views = list(views) if views is not None else [None] * len(self.sectors)
+        if detector_map is None:
+            first = np.concatenate([[0], np.cumsum([S.n_det for S in self.sectors])])
+            detector_map = [first[s] + np.arange(S.n_det) for s, S in enumerate(self.sectors)]
+            n_detectors = int(first[-1]) if n_detectors is None else n_detectors
+        self.detector_map = [np.ascontiguousarray(x, np.int64).ravel() for x in detector_map]
+        if len(self.detector_map) != len(self.sectors) or any(x.size != S.n_det for x, S in zip(self.detector_map, self.sectors)):
+            raise ValueError("detector_map needs one detector number per row of every sector")
+        top = max(int(x.max()) for x in self.detector_map) + 1
+        self.n_detectors = top if n_detectors is None else int(n_detectors)
+        if self.n_detectors < top or min(int(x.min()) for x in self.detector_map) < 0:
+            raise ValueError(f"detector_map names detectors outside 0..{self.n_detectors - 1}")
 
     n_mech = property(lambda self: int(self.prob.size))
     n_sectors = property(lambda self: len(self.sectors))
@@ -74,11 +92,12 @@ class DetectorErrorModel:
         return S.det_idx[S.det_ptr[l]:S.det_ptr[l + 1]].astype(np.int64), int(S.logmask[l])
 
     def sector(self, s):
-        """The one-sector model that keeps sector s alone (every mechanism stays, so the draws of a trial do not change)."""
-        return DetectorErrorModel(self.prob, [self.sectors[s]], [self._views[s]])
+        """The one-sector model that keeps sector s alone (every mechanism stays, so the draws of a trial do not change).  It keeps its sector's
+        detector_map and the model's n_detectors: its events stay in the model's numbering."""
+        return DetectorErrorModel(self.prob, [self.sectors[s]], [self._views[s]], [self.detector_map[s]], self.n_detectors)
 
     @classmethod
-    def from_columns(cls, prob, columns, n_det, k, layer_rows=None, views=None):
+    def from_columns(cls, prob, columns, n_det, k, layer_rows=None, views=None, detector_map=None, n_detectors=None):
         """prob[l] and columns[l] = one (detectors, logmask) pair per sector, for every mechanism; detectors are XOR-ed (a repeated one cancels)."""
         nsec = len(n_det)
         layer_rows = (layer_rows,) * nsec if layer_rows is None or np.ndim(layer_rows) == 0 else tuple(layer_rows)
@@ -98,7 +117,7 @@ class DetectorErrorModel:
                 ptr.append(ptr[-1] + det.size)
                 lm.append(int(mask))
             sectors.append((n_det[s], k[s], layer_rows[s], ptr, np.concatenate(idx) if idx else np.zeros(0, np.int64), np.array(lm, np.uint64)))
-        return cls(prob, sectors, views)
+        return cls(prob, sectors, views, detector_map, n_detectors)
 
     @classmethod
     def from_decoding_matrices(cls, m, layer_rows=None):
@@ -161,7 +180,9 @@ class DetectorErrorModel:
         sector_of_detector None: one sector with every detector.  Otherwise an int array over the detectors with values 0 or 1: detector d goes to that
         sector and is renumbered inside it in ascending order.  Convention for the observables: every sector has all of them (k = the number of
         observables), and a mechanism's observable flips count in every sector in which it flips a detector; a mechanism without detectors (only L
-        targets: an undetectable logical flip) counts in sector 0.  With one sector that is the usual memory experiment."""
+        targets: an undetectable logical flip) counts in sector 0.  With one sector that is the usual memory experiment.
+
+        ``detector_map[s]`` keeps the text's detector number of every row of sector s, so ``DemDecoder`` takes events in the text's numbering."""
         prob, targets, n_det, n_obs = [], [], 0, 0
         for lineno, raw in enumerate(text.splitlines(), 1):
             line = raw.split("#", 1)[0].strip()
@@ -203,18 +224,19 @@ class DetectorErrorModel:
                 raise ValueError("sector_of_detector holds 0 or 1 per detector")
         nsec = 1 if sector_of_detector is None else 2
         local = np.zeros(sod.size, np.int64)
-        counts = []
+        counts, dmap = [], []
         for s in range(nsec):
             mine = np.flatnonzero(sod == s)
             local[mine] = np.arange(mine.size)
             counts.append(int(mine.size))
+            dmap.append(mine)
         columns = []
         for det, obs in targets:
             det = np.asarray(det, np.int64)
             per = [local[det[sod[det] == s]] for s in range(nsec)]
             vis = [np.count_nonzero(np.unique(d, return_counts=True)[1] % 2) > 0 for d in per]
             columns.append([(per[s], obs if (vis[s] or (s == 0 and not any(vis))) else 0) for s in range(nsec)])
-        return cls.from_columns(prob, columns, counts, (n_obs,) * nsec)
+        return cls.from_columns(prob, columns, counts, (n_obs,) * nsec, detector_map=dmap, n_detectors=int(sod.size))
 
     def decoder_view(self, sector):
         """DecoderView of a sector: the explicit one when the model has it.  Otherwise derived: the mechanisms with p > 0, in index order, projected onto
@@ -256,30 +278,23 @@ class DetectorErrorModel:
                             alphas=alphas, alpha_mode=alpha_mode, batch=batch, flags=flags, use_osd=use_osd, **kw)
 
 
-def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode=None, alvarado_alpha=None, base_seed=None, target_logical_errors=None,
-                       max_trials=None, batch=16384, device=None, devices=None, num_workers=None, flags=0, decoder="bp_osd", relay_params=None, window=None,
-                       schedule="flooding", layers=None, decimation=None, precision="f64"):
-    """``run_simulation`` for a DetectorErrorModel: the same result keys, in-order early stop (``target_logical_errors``), ``num_workers`` / ``devices`` and
-    extensions (``decoder``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``) under the same argument rules; sector 0 fills the ``z``
-    keys, sector 1 the ``x`` keys (0 for a one-sector model).  ``window=(W, C)`` needs the model's ``layer_rows``.
-
-    Out of scope (ValueError before any device call): the alpha / SCOPT estimators, which draw errors at one error rate -- use ``alpha_mode="dynamical"``
-    (the default) or ``"alvarado"`` with an explicit ``alvarado_alpha`` (a number or a pair) -- and ``osd_order > 0`` with ``decoder="bp_osd"`` (the
-    reference's OSD-w pass; ``decoder="bp_osd_cs"`` is the higher-order OSD of the fused pipeline)."""
+def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers, decimation, precision, num_workers=None):
+    """The argument rules run_dem_simulation and DemDecoder share, raised as ValueError before any device call -> (rules of engine._extension_rules,
+    alpha_mode, (alpha of sector 0, alpha of sector 1))."""
     if not isinstance(dem, DetectorErrorModel):
         raise ValueError("dem must be a DetectorErrorModel (from_decoding_matrices, from_text, from_columns)")
     rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, True, False,
                                     maxIter, num_workers)
     if decoder == "bp_osd" and osd_order > 0:
-        raise ValueError(f"run_dem_simulation: osd_order={osd_order} with decoder='bp_osd' asks for the OSD-w pass, which is not available on detector error "
+        raise ValueError(f"{who}: osd_order={osd_order} with decoder='bp_osd' asks for the OSD-w pass, which is not available on detector error "
                          "models; use decoder='bp_osd_cs' (osd_order is then the combination-sweep order)")
     if alpha_mode is None:
         alpha_mode = "dynamical"
     if alpha_mode not in ("dynamical", "alvarado"):
-        raise ValueError(f"run_dem_simulation: alpha_mode={alpha_mode!r} would run an alpha estimator, which draws errors at one error_rate; "
+        raise ValueError(f"{who}: alpha_mode={alpha_mode!r} would run an alpha estimator, which draws errors at one error_rate; "
                          "use 'dynamical', or 'alvarado' with an explicit alvarado_alpha")
     if alpha_mode == "alvarado" and alvarado_alpha is None:
-        raise ValueError("run_dem_simulation: alpha_mode='alvarado' needs an explicit alvarado_alpha (the estimator draws errors at one error_rate)")
+        raise ValueError(f"{who}: alpha_mode='alvarado' needs an explicit alvarado_alpha (the estimator draws errors at one error_rate)")
     if alpha_mode == "dynamical" and alvarado_alpha is not None:
         raise ValueError("alvarado_alpha is for alpha_mode='alvarado'")
     if alvarado_alpha is None:
@@ -295,6 +310,21 @@ def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode
                                  f"for {S.n_det} detectors")
     if rules.path == "layered" and dem.n_sectors == 1 and rules.layers[1] is not None:
         raise ValueError("layers: the model has one sector, so the second row_layer must be None")
+    return rules, alpha_mode, alphas
+
+
+def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode=None, alvarado_alpha=None, base_seed=None, target_logical_errors=None,
+                       max_trials=None, batch=16384, device=None, devices=None, num_workers=None, flags=0, decoder="bp_osd", relay_params=None, window=None,
+                       schedule="flooding", layers=None, decimation=None, precision="f64"):
+    """``run_simulation`` for a DetectorErrorModel: the same result keys, in-order early stop (``target_logical_errors``), ``num_workers`` / ``devices`` and
+    extensions (``decoder``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``) under the same argument rules; sector 0 fills the ``z``
+    keys, sector 1 the ``x`` keys (0 for a one-sector model).  ``window=(W, C)`` needs the model's ``layer_rows``.
+
+    Out of scope (ValueError before any device call): the alpha / SCOPT estimators, which draw errors at one error rate -- use ``alpha_mode="dynamical"``
+    (the default) or ``"alvarado"`` with an explicit ``alvarado_alpha`` (a number or a pair) -- and ``osd_order > 0`` with ``decoder="bp_osd"`` (the
+    reference's OSD-w pass; ``decoder="bp_osd_cs"`` is the higher-order OSD of the fused pipeline)."""
+    rules, alpha_mode, alphas = _dem_rules("run_dem_simulation", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers,
+                                           decimation, precision, num_workers)
     rank, world, devices = engine._worker_devices(num_workers, devices, device)
     if base_seed is None:
         base_seed = int(np.random.randint(0, 2 ** 31))
@@ -306,3 +336,104 @@ def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode
 
     return engine._run_trials(make_plan, graphs, [v.prior for v in views], [v.logmask for v in views], alphas[:dem.n_sectors], dem.k, rules, rank, world, devices,
                               base_seed, num_trials, max_trials, target_logical_errors, maxIter, osd_order, alpha_mode, batch, decoder, schedule, precision, {})
+
+
+def read_b8(path, n_bits):
+    """A file of bit-packed records (Stim's ``b8``: ceil(n_bits / 8) bytes per shot, bit d = (rec[d >> 3] >> (d & 7)) & 1) -> uint8[count, ceil(n_bits / 8)]."""
+    width = (int(n_bits) + 7) // 8
+    return np.fromfile(path, np.uint8).reshape(-1, width)
+
+
+def _packed_events(events, n_detectors, bit_packed):
+    """decode_batch's input rule -> bit-packed records uint8[count, >= ceil(n_detectors / 8)].  bool arrays are one detector per entry; uint8 arrays are
+    told apart by their width when bit_packed is None (n_detectors wide: one detector per byte, values 0 / 1; ceil(n_detectors / 8) wide: packed)."""
+    events = np.asarray(events)
+    width = (n_detectors + 7) // 8
+    if events.ndim != 2:
+        raise ValueError(f"events must be [count, n_detectors] or bit-packed [count, {width}], got shape {events.shape}")
+    if events.dtype == np.bool_:
+        if bit_packed:
+            raise ValueError("bit_packed=True needs uint8 records, got a bool array")
+        bit_packed = False
+    elif events.dtype != np.uint8:
+        raise ValueError(f"events must be bool or uint8, got {events.dtype}")
+    if bit_packed is None:
+        fits = (events.shape[1] == n_detectors, events.shape[1] == width)
+        if all(fits):
+            raise ValueError(f"uint8 events of width {events.shape[1]} could be {n_detectors} detectors or {width} packed bytes: pass bit_packed=True or False")
+        if not any(fits):
+            raise ValueError(f"events are {events.shape[1]} wide: the model has {n_detectors} detectors ({width} bytes when bit-packed)")
+        bit_packed = fits[1]
+    if bit_packed:
+        if events.shape[1] < width:
+            raise ValueError(f"bit-packed events are {events.shape[1]} bytes wide: {n_detectors} detectors need {width}")
+        return np.ascontiguousarray(events)
+    if events.shape[1] != n_detectors:
+        raise ValueError(f"events are {events.shape[1]} wide: the model has {n_detectors} detectors")
+    if events.dtype == np.uint8 and events.size and events.max() > 1:
+        raise ValueError("unpacked uint8 events hold 0 or 1 per detector")
+    return _lib.pack_events(events)
+
+
+class DemDecoder:
+    """Decodes recorded detection events of a DetectorErrorModel on the fused device pipeline: events -> decode -> OSD -> predict
+    (``qldpc_circuit_plan_decode_events``), the ``decode_batch`` of other DEM decoders.  The arguments are ``run_dem_simulation``'s, under the same rules
+    (ValueError before any device call); the plan is created on the first decode.
+
+    Events come in the MODEL's detector numbering (``dem.detector_map``; for ``from_text`` the text's ``D<i>``), ``dem.n_detectors`` per shot.  ``seed`` and
+    the global shot index (``shot_begin`` + row) are what Relay-BP draws from; every other decoder ignores them.  So a prediction is a function of
+    (record, seed, shot index) and depends neither on ``batch`` nor on how the shots are split over calls."""
+
+    def __init__(self, dem, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding", layers=None, decimation=None, precision="f64",
+                 relay_params=None, alpha_mode=None, alvarado_alpha=None, batch=16384, device=None, seed=0, flags=0):
+        self._rules, self._alpha_mode, self._alphas = _dem_rules("DemDecoder", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window,
+                                                                 schedule, layers, decimation, precision)
+        if int(batch) < 1:
+            raise ValueError("batch must be >= 1")
+        self.dem, self.seed, self.batch, self.device = dem, int(seed), int(batch), device
+        self._max_iter, self._osd_order, self._flags = maxIter, osd_order, flags
+        self._plan = self._graphs = None
+
+    def _ensure_plan(self):
+        if self._plan is None:
+            dem = self.dem
+            dev = 0 if self.device is None else int(self.device)
+            views = [dem.decoder_view(s) for s in range(dem.n_sectors)]
+            switch, _ = engine._plan_switch(self._rules, [(v.indptr, v.indices, v.shape[1]) for v in views], self._osd_order)
+            self._graphs = [_lib.Graph(v.indptr, v.indices, v.shape[1], device=dev) for v in views]
+            plan = dem.plan(self._graphs, max_iter=self._max_iter, alphas=self._alphas, alpha_mode=self._alpha_mode, batch=self.batch, flags=self._flags)
+            try:
+                switch(plan)
+                plan.set_event_layout(dem.n_detectors, *dem.detector_map)
+            except Exception:
+                plan.close()
+                raise
+            self._plan = plan
+        return self._plan
+
+    def decode_to_flags(self, events, bit_packed=None, shot_begin=0):
+        """decode_batch and the flags uint8[count]: bit 0 / 1 = converged, 2 / 3 = the correction does not reproduce the syndrome, 4 / 5 = zero syndrome,
+        of sector 0 / 1."""
+        packed = _packed_events(events, self.dem.n_detectors, bit_packed)
+        if int(shot_begin) < 0:
+            raise ValueError("shot_begin must be >= 0")
+        pred = self._ensure_plan().decode_events(packed, seed=self.seed, shot_begin=int(shot_begin))
+        out = tuple(((pred[s][:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool) for s, k in enumerate(self.dem.k))
+        return (out[0] if self.dem.n_sectors == 1 else out), pred[2]
+
+    def decode_batch(self, events, bit_packed=None, shot_begin=0):
+        """events: bool or uint8 [count, n_detectors] (0 / 1 per detector), or bit-packed uint8 [count, ceil(n_detectors / 8)] (``_lib.pack_events``,
+        ``read_b8``); bit_packed None = told apart by dtype and width.  Returns the predicted observable flips bool[count, k] per sector -- a pair for a
+        two-sector model, the array itself for a one-sector model (column r = ``L<r>`` of the text)."""
+        return self.decode_to_flags(events, bit_packed, shot_begin)[0]
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

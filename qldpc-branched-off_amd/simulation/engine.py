@@ -197,6 +197,25 @@ def _worker_devices(num_workers, devices, device):
     return rank, world, devices
 
 
+def _plan_switch(rules, csr, osd_order):
+    """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
+    dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` in the OSD stage when the rules ask for it, then moves the BP stage to
+    rules.path.  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
+    layers = None
+    if rules.path == "layered":
+        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
+    to_path = {"flooding": lambda plan: None, "relay": lambda plan: plan.use_relay(**rules.relay_params), "window": lambda plan: plan.use_window(*rules.window),
+               "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
+               "f32": lambda plan: plan.use_f32()}[rules.path]
+
+    def switch(plan):
+        if rules.osd_cs:
+            plan.use_osd_cs(int(osd_order))
+        to_path(plan)
+
+    return switch, layers
+
+
 def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, devices, base_seed, num_trials, max_trials, target_logical_errors, maxIter,
                 osd_order, alpha_mode, batch, decoder, schedule, precision, extra):
     """The trial loop and the result of run_simulation and run_dem_simulation: one Worker (plan, graphs, stream) per entry of `devices`, rounds of
@@ -205,12 +224,7 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     device = devices[0]
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
-    if rules.path == "layered":          # host code: the layers every worker's plan gets
-        layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
-    # how a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules)
-    to_path = {"flooding": lambda plan: None, "relay": lambda plan: plan.use_relay(**rules.relay_params), "window": lambda plan: plan.use_window(*rules.window),
-               "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
-               "f32": lambda plan: plan.use_f32()}[rules.path]
+    to_path, layers = _plan_switch(rules, csr, osd_order)
     osdw_pass = osd_order > 0 and not rules.osd_cs    # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
     class Worker:
@@ -221,8 +235,6 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
             self.graphs = own_graphs or [_lib.Graph(ip, ix, n, device=dev) for ip, ix, n in csr]
             self.stream = _lib.Stream(dev)
             self.plan = make_plan(self.graphs, dev)
-            if rules.osd_cs:
-                self.plan.use_osd_cs(int(osd_order))
             to_path(self.plan)
 
         def osdw_batch(self, begin, count):
