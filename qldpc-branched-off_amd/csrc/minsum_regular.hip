@@ -52,6 +52,7 @@
 #include "mc_common.h"
 #include "minsum_common.h"
 #include "minsum_f64.h"
+#include "regular_plan.h"
 
 #include <cstdlib>
 
@@ -72,8 +73,36 @@ struct RegArgs {
     const int32_t *shot_list, *shot_count;   // Monte-Carlo mode: decode only the listed shots (offsets from shot_begin; device-resident count), else NULL
     const struct RegCold *cold;     // rarely used pointers live in device memory to keep scalar registers free
     // LDS carve (byte offsets)
-    int offV, offE, offL, offI, offA, offT;
+    int offV, offE, offL, offI, offA, offT, offD;
 };
+
+// The compare-free message words of one check (header comment): x holds the gathered posteriors and becomes the unclipped t_k = x_k - Rprev_k
+// (`later`: iteration 0 reads priors, nothing to subtract), the clip sits in the two chain seeds (cmin), the words go to Rprev and to the check's row.
+template <int CDEG>
+__device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev)[CDEG], bool later, double alpha, double cmin, unsigned synw, double *row) {
+    unsigned spw = synw;                                                       // sign of the whole row in bit 31
+#pragma unroll
+    for (int k = 0; k < CDEG; k++) {
+        if (later) x[k] = x[k] - Rprev[k];                                     // kernels.py:325
+        spw ^= (unsigned)__double2hiint(x[k]);
+    }
+    double suf[CDEG];                                                          // suf[k] = min(|t_k|, .., |t_{CDEG-1}|, cmin), k = CDEG-1 .. 1
+    suf[CDEG - 1] = vmin_abs_u(x[CDEG - 1], cmin);
+#pragma unroll
+    for (int k = CDEG - 2; k >= 1; k--) suf[k] = vmin_abs(x[k], suf[k + 1]);
+    double pre = 0.0;                                                          // pre = min(|t_0|, .., |t_{k-1}|, cmin) from k = 1 on
+#pragma unroll
+    for (int k = 0; k < CDEG; k++) {
+        const double mag = (k == 0) ? suf[1] : (k == CDEG - 1) ? pre : vmin(pre, suf[k + 1]);   // the minimum over the other edges (kernels.py:301-313)
+        const unsigned sgn = spw ^ (unsigned)__double2hiint(x[k]);             // the row's sign without the edge itself (kernels.py:311-314)
+        if (k < CDEG - 1) pre = (k == 0) ? vmin_abs_u(x[0], cmin) : vmin_abs(x[k], pre);
+        const double prod = alpha * mag;                                       // >= 0: (alpha * sign) * mag == sign * (alpha * mag)
+        const unsigned hi = ((unsigned)__double2hiint(prod) & 0x7fffffffu) | (sgn & 0x80000000u);
+        const double msg = __hiloint2double((int)hi, __double2loint(prod));
+        Rprev[k] = msg;
+        row[k] = msg;
+    }
+}
 
 #ifndef QLDPC_LB_T
 #define QLDPC_LB_T 512
@@ -90,8 +119,14 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     const int slot = threadIdx.x / TS, member = threadIdx.x - slot * TS;
     const bool in_team = slot < S;
     const int sl = in_team ? slot : 0;
-    double *Rl = reinterpret_cast<double *>(lds) + (size_t)sl * m * RST;
-    double *Vl = reinterpret_cast<double *>(lds + A.offV) + (size_t)sl * n;
+    constexpr bool CLIPMIN = NANFREE && !DAMP;      // compare-free message words with the clip in the two chain seeds (header comment); needs clip > 0, which NANFREE includes
+    // ALL: the iteration body of the clean form runs with every lane enabled.  plan_regular takes n == 2 m only, so TS == m and every lane of a team owns
+    // a check and two columns; a team without a shot (b >= nshots) works on its own slot, which nobody else touches, and the lanes of the block that
+    // belong to no team work on the dummy region Dl: a row of RST doubles, two posteriors, one parity word.  Nothing they compute is ever read.
+    constexpr bool ALL = CLIPMIN;
+    double *Dl = reinterpret_cast<double *>(lds + A.offD);
+    double *Rl = (ALL && !in_team) ? Dl : reinterpret_cast<double *>(lds) + (size_t)sl * m * RST;
+    double *Vl = (ALL && !in_team) ? Dl + RST : reinterpret_cast<double *>(lds + A.offV) + (size_t)sl * n;
     uint32_t *El = reinterpret_cast<uint32_t *>(lds + A.offE) + (size_t)sl * nq;
     unsigned long long *lacc = reinterpret_cast<unsigned long long *>(lds + A.offL) + sl;
     int *I = reinterpret_cast<int *>(lds + A.offI);
@@ -100,7 +135,6 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     int *sres = I + 2 * S + 2 + 4 * sl; // conv, final_iter, nonzero syndrome, failure index
     const double *Al = reinterpret_cast<const double *>(lds + A.offA);                  // alpha_k staged in LDS
     unsigned long long *Tl = reinterpret_cast<unsigned long long *>(lds + A.offT);      // block tally (MC)
-    constexpr bool CLIPMIN = NANFREE && !DAMP;      // compare-free message words with the clip in the two chain seeds (header comment); needs clip > 0, which NANFREE includes
     static_assert(CDEG >= 3, "the prefix / suffix chains need a middle edge");
     const double clip = A.clip, nclip = -A.clip, damping = A.damping, one_minus_d = 1.0 - A.damping;
     for (int k = threadIdx.x; k < max_iter; k += blockDim.x) reinterpret_cast<double *>(lds + A.offA)[k] = A.alpha[k];
@@ -113,7 +147,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     const bool has_check = in_team && member < m;
     int coff[CDEG];
 #pragma unroll
-    for (int k = 0; k < CDEG; k++) coff[k] = has_check ? A.indices[A.indptr[member] + k] : 0;
+    for (int k = 0; k < CDEG; k++) coff[k] = has_check ? A.indices[A.indptr[member] + k] : (ALL ? (k & 1) : 0);
     unsigned cnf = 0u;                                     // bit k: the prior of the row's k-th column is not finite (see minsum_common.h)
     if (!NANFREE && !DAMP) {
 #pragma unroll
@@ -127,11 +161,11 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     for (int v = 0; v < 2; v++) {
         const int j = member + v * TS;
         has_var[v] = in_team && j < n;
-        vj[v] = has_var[v] ? j : 0;
+        vj[v] = has_var[v] ? j : (ALL ? v : 0);
         vprior[v] = has_var[v] ? A.prior[j] : 0.0;
 #pragma unroll
         for (int d = 0; d < VDEG; d++) {
-            voff[v][d] = 0;
+            voff[v][d] = ALL ? d : 0;
             if (has_var[v]) {
                 const int k = A.colptr[j] + d, row = A.rowidx[k];
                 voff[v][d] = row * RST + (A.csc2csr[k] - A.indptr[row]);
@@ -176,15 +210,16 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
         for (int k = 0; k < CDEG; k++) { Rprev[k] = 0.0; Qold[k] = 0.0; }
 #pragma unroll
-        for (int v = 0; v < 2; v++) if (has_var[v]) Vl[vj[v]] = vprior[v];             // Q_{-1} = prior[col] (kernels.py:263-265)
+        for (int v = 0; v < 2; v++) if (ALL || has_var[v]) Vl[vj[v]] = vprior[v];      // Q_{-1} = prior[col] (kernels.py:263-265)
         if (in_team && member == 0) { unsat[0] = 0; unsat[1] = 0; }
         if (threadIdx.x == 0) { const int64_t left = nshots - base; active[0] = (int)(left < S ? left : S); }
         bool done = !valid;
         __syncthreads();
 
-        for (int it = 0; it <= max_iter; it++) {
+        int it = 0;
+        for (; it <= max_iter; it++) {
             // ======== check phase: syndrome test of values_{it-1}, then R_it from Q_{it-1} ========
-            const bool in_check = (FIXED ? valid : !done) && has_check;
+            const bool in_check = ALL ? (FIXED || !done) : (FIXED ? valid : !done) && has_check;
             double x[CDEG];
             if (in_check) {
                 bool par = csyn;
@@ -224,31 +259,8 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 }
             } else if (in_check && !skip_msg) {
                 if (CLIPMIN && it < max_iter) {
-                    // compare-free form (header comment): x becomes the unclipped t_k, the clip sits in the two chain seeds
-                    const double alpha = Al[it];
-                    const double cmin = (it > 0) ? clip : INFINITY;                            // iteration 0 reads priors: no clip (kernels.py:263-265)
-                    unsigned spw = synw;                                                       // sign of the whole row in bit 31
-#pragma unroll
-                    for (int k = 0; k < CDEG; k++) {
-                        if (it > 0) x[k] = x[k] - Rprev[k];                                    // kernels.py:325
-                        spw ^= (unsigned)__double2hiint(x[k]);
-                    }
-                    double suf[CDEG];                                                          // suf[k] = min(|t_k|, .., |t_{CDEG-1}|, cmin), k = CDEG-1 .. 1
-                    suf[CDEG - 1] = vmin_abs_u(x[CDEG - 1], cmin);
-#pragma unroll
-                    for (int k = CDEG - 2; k >= 1; k--) suf[k] = vmin_abs(x[k], suf[k + 1]);
-                    double pre = 0.0;                                                          // pre = min(|t_0|, .., |t_{k-1}|, cmin) from k = 1 on
-#pragma unroll
-                    for (int k = 0; k < CDEG; k++) {
-                        const double mag = (k == 0) ? suf[1] : (k == CDEG - 1) ? pre : vmin(pre, suf[k + 1]);   // the minimum over the other edges (kernels.py:301-313)
-                        const unsigned sgn = spw ^ (unsigned)__double2hiint(x[k]);             // the row's sign without the edge itself (kernels.py:311-314)
-                        if (k < CDEG - 1) pre = (k == 0) ? vmin_abs_u(x[0], cmin) : vmin_abs(x[k], pre);
-                        const double prod = alpha * mag;                                       // >= 0: (alpha * sign) * mag == sign * (alpha * mag)
-                        const unsigned hi = ((unsigned)__double2hiint(prod) & 0x7fffffffu) | (sgn & 0x80000000u);
-                        const double msg = __hiloint2double((int)hi, __double2loint(prod));
-                        Rprev[k] = msg;
-                        Rl[roff + k] = msg;
-                    }
+                    // compare-free form (header comment); iteration 0 reads priors: no clip (kernels.py:263-265)
+                    clean_messages<CDEG>(x, Rprev, it > 0, Al[it], (it > 0) ? clip : INFINITY, synw, Rl + roff);
                 } else if (it < max_iter) {
                     const double alpha = Al[it];
                     if (it > 0) {
@@ -335,10 +347,10 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 }
             }
             if (in_team && member == 0) unsat[(it + 1) & 1] = 0;
-            if (it < max_iter && (FIXED ? valid : !done)) {
+            if (it < max_iter && (ALL ? (FIXED || !done) : (FIXED ? valid : !done))) {
 #pragma unroll
                 for (int v = 0; v < 2; v++)
-                    if (has_var[v]) {
+                    if (ALL || has_var[v]) {
                         double s = 0.0;                                                        // kernels.py:279
 #pragma unroll
                         for (int d = 0; d < VDEG; d++) s += Rl[voff[v][d]];                    // kernels.py:316, ascending check order
@@ -347,7 +359,47 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
             }
             __syncthreads();
-            if (!FIXED && active[0] == 0) break;
+            if ((!FIXED || ALL) && active[0] == 0) { it++; break; }       // block-uniform: early exit is finished; fixed work goes on below
+        }
+        if (ALL && FIXED) {
+            // Every shot of the workgroup is frozen (a workgroup that holds a BP failure never gets here before it == max_iter): nothing computed from
+            // here on is observable, and the remaining passes keep the arithmetic of a pass -- gather, hard-decision parity, message update, variable
+            // update -- without its control: no unsat word, no freeze test, no `done`, no first-iteration case (it >= 2 here).  The parities are kept
+            // alive by one OR per pass and one store per shot into the dummy region.
+            unsigned parity = 0u;
+            for (; it < max_iter; it++) {
+                double x[CDEG];
+                unsigned ph = synw;
+#pragma unroll
+                for (int k = 0; k < CDEG; k++) x[k] = Vl[coff[k]];
+#pragma unroll
+                for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(x[k]);               // kernels.py:349,356
+                parity |= ph;
+                clean_messages<CDEG>(x, Rprev, true, Al[it], clip, synw, Rl + roff);
+                __syncthreads();
+                __builtin_amdgcn_s_setprio(1);                                                     // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
+                double r[2][VDEG];
+#pragma unroll
+                for (int v = 0; v < 2; v++)
+#pragma unroll
+                    for (int d = 0; d < VDEG; d++) r[v][d] = Rl[voff[v][d]];
+#pragma unroll
+                for (int v = 0; v < 2; v++) {
+                    double s = 0.0;                                                                // kernels.py:279
+#pragma unroll
+                    for (int d = 0; d < VDEG; d++) s += r[v][d];                                   // kernels.py:316, ascending check order
+                    Vl[vj[v]] = s + vprior[v];                                                     // kernels.py:320
+                }
+                __builtin_amdgcn_s_setprio(0);
+                __syncthreads();
+            }
+            if (it == max_iter) {                                                                  // the syndrome test of values_{max_iter-1}
+                unsigned ph = synw;
+#pragma unroll
+                for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(Vl[coff[k]]);
+                parity |= ph;
+            }
+            reinterpret_cast<unsigned *>(Dl + RST + 2)[0] = parity;
         }
         __syncthreads();
         if (MC) {
@@ -438,39 +490,16 @@ __global__ __launch_bounds__(256) void cc_judge_failed_kernel(int32_t *__restric
 }
 
 // ------------------------------------------------------------------------------------------ host side
-struct RegPlan { int cdeg, vdeg, TS, S, offV, offE, offL, offI, offA, offT; size_t lds; unsigned block; };
-static const int kMaxIterLds = 1024;
-
+// RegPlan and the carve itself: regular_plan.h (host arithmetic only)
 static int g_list_shots = 0;          // qldpc_set_option("mc_list_shots"): shots per workgroup of the shot-list launch (0 = as the full launch)
 void regular_set_list_shots(int s) { g_list_shots = s; }
 
 static bool plan_regular(const qldpc_graph *g, int max_iter, RegPlan &P, int force_S = 0) {
-    if (g->m <= 0 || g->n <= 0 || max_iter > kMaxIterLds) return false;
+    if (g->m <= 0 || g->n <= 0) return false;
     const int cdeg = g->max_row_deg, vdeg = g->max_col_deg;
-    if (!((cdeg == 6 && vdeg == 3) || (cdeg == 4 && vdeg == 2) || (cdeg == 8 && vdeg == 4))) return false;
     for (int i = 0; i < g->m; i++) if (g->indptr[i + 1] - g->indptr[i] != cdeg) return false;
     for (int j = 0; j < g->n; j++) if (g->colptr[j + 1] - g->colptr[j] != vdeg) return false;
-    const int ts = std::max(g->m, (g->n + 1) / 2);
-    if (ts > QLDPC_LB_T) return false;
-    const int rst = (cdeg % 2 == 0) ? cdeg + 1 : cdeg;
-    const int nq = (g->n + 3) / 4;
-    int S = QLDPC_LB_T / ts;                           // 4 blocks per CU fill its 32 wave slots
-    if (force_S > 0 && force_S < S) S = force_S;
-    auto layout = [&](int s) {
-        P.offV = s * g->m * rst * 8;
-        P.offE = P.offV + s * g->n * 8;
-        P.offL = (P.offE + s * nq * 4 + 7) / 8 * 8;
-        P.offI = P.offL + s * 8;
-        P.offA = (P.offI + (6 * s + 2) * 4 + 7) / 8 * 8;
-        P.offT = P.offA + (max_iter > 0 ? max_iter : 1) * 8;
-        P.lds = (size_t)P.offT + 6 * 8 + 16;
-    };
-    layout(S);
-    while (S > 1 && P.lds > 39 * 1024) { S--; layout(S); }      // 4 blocks per CU within 160 KiB
-    if (P.lds > 150 * 1024) return false;
-    P.cdeg = cdeg; P.vdeg = vdeg; P.TS = ts; P.S = S;
-    P.block = (unsigned)round_up((int64_t)S * ts, 64);
-    return true;
+    return plan_regular_shape(cdeg, vdeg, g->m, g->n, max_iter, QLDPC_LB_T, force_S, P);
 }
 
 bool regular_supported(const qldpc_graph *g, double clip, int max_iter) {
@@ -512,7 +541,7 @@ static void fill_common(const qldpc_graph *g, const RegPlan &P, RegArgs &A, int6
     A.S = P.S; A.TS = P.TS;
     A.indptr = g->d_indptr; A.indices = g->d_indices; A.colptr = g->d_colptr; A.rowidx = g->d_rowidx; A.csc2csr = g->d_csc2csr;
     A.B = B; A.prior = d_prior; A.alpha = d_alpha; A.damping = damping; A.clip = clip;
-    A.offV = P.offV; A.offE = P.offE; A.offL = P.offL; A.offI = P.offI; A.offA = P.offA; A.offT = P.offT;
+    A.offV = P.offV; A.offE = P.offE; A.offL = P.offL; A.offI = P.offI; A.offA = P.offA; A.offT = P.offT; A.offD = P.offD;
 }
 
 static unsigned persistent_grid(int64_t B, int S) {

@@ -281,13 +281,14 @@ def analyse(src, pattern, loop_pick=None):
 
 
 # The one table of the kernels bench.py prices (tools/pmc_summarise.py and tests/test_kernel_sources_cpu.py read it): key -> (source file, the ONE kernel
-# instantiation counted, which loop: None = the innermost loop with most VALU instructions, "whole" = the whole kernel body (kernels whose time is spread over
-# many loops), the files whose text fixes the instruction stream: the .hip file and every device header it reaches through #include "..." -- csrc/launchers.h,
+# instantiation counted, which loop: None = the innermost loop with most VALU instructions, "straight" = the innermost loop of ONE basic block with most VALU
+# instructions (the fixed-work regular kernel spends its time in the branch-free loop it runs once a workgroup's shots are frozen; the loop with the freeze
+# bookkeeping has more instructions and runs a pass or two), "whole" = the whole kernel body (kernels whose time is spread over many loops), the files whose text fixes the instruction stream: the .hip file and every device header it reaches through #include "..." -- csrc/launchers.h,
 # csrc/common.h and include/qldpc_hip.h hold nothing a kernel reads and are in no list.  osd_plan.h is host planning code, listed because the
 # OSD kernels name its block and chunk constants.
 _REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h"]
 RECORDED = {
-    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true>", None, _REGULAR),
+    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true>", "straight", _REGULAR),
     "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "clocks.h", "mc_common.h"]),
     "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<true>", "whole", ["minsum_wg2.hip", "clocks.h", "minsum_f64.h"]),      # <true>: the shipped circ144 matrices have degree-1 checks
     "circ144_osd": ("osd_gj.hip", "osd0_gj_kernel<true>", "whole", ["osd_gj.hip", "osd_gj.h", "osd_common.h", "clocks.h", "osd_plan.h"]),
@@ -308,6 +309,8 @@ def record(path):
     out = {"rates": "profiles/r03_issue_rate.txt (tools/microbench/issue_rate.hip on the GPU box)", "entries": {}}
     for key, (src, pat, which, files) in RECORDED.items():
         r = analyse(src, pat)
+        if which == "straight":
+            r["steady_state"] = max((l for l in r["loops"] if l["innermost"] and l["blocks"] == 1), key=lambda l: l["valu"])
         if which == "whole" or "steady_state" not in r:
             m, scope = r["whole"], "whole kernel (static)"
         else:
