@@ -43,6 +43,7 @@
  *        qldpc_circuit_plan_create_dem
  *        additive, same version: recorded detection events in place of a plan's sampler, qldpc_circuit_plan_set_event_layout,
  *        qldpc_circuit_plan_decode_events[_dev] and qldpc_circuit_plan_unpack_events
+ *        additive, same version: qldpc_minsum_decode_path names the resident kernel's instantiation, QLDPC_DETAIL_RES_CDEG8 and QLDPC_DETAIL_RES_CPT2
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -180,7 +181,8 @@ int qldpc_minsum_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t 
  * share one selection function, and results never depend on the form.  New here (the reference has no counterpart).
  *   path    QLDPC_PATH_*: REGULAR csrc/minsum_regular.hip, RESIDENT minsum_resident.hip, WG2 minsum_wg2.hip (workgroup per shot, every table in LDS),
  *           WG minsum_wg.hip (workgroup per shot, tables in HBM / L2), STREAM minsum_stream.hip, WAVE minsum_wave.hip (experiments build only)
- *   detail  QLDPC_DETAIL_* bits of the two workgroup forms (0 for the others) */
+ *   detail  QLDPC_DETAIL_* bits of the two workgroup forms; for QLDPC_PATH_RESIDENT the kernel instantiation (QLDPC_DETAIL_RES_* and
+ *           QLDPC_DETAIL_DAMPING); 0 for the others */
 #define QLDPC_PATH_REGULAR 0
 #define QLDPC_PATH_RESIDENT 1
 #define QLDPC_PATH_WG2 2
@@ -194,6 +196,8 @@ int qldpc_minsum_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t 
 #define QLDPC_DETAIL_BLOCK_1024 0x10     /* 1024 threads per workgroup (else 512; WG2: always) */
 #define QLDPC_DETAIL_DEG1 0x20           /* the graph has degree-1 checks: the kernel instance that carries their +-inf messages */
 #define QLDPC_DETAIL_NAN_DEG1_ONLY 0x40  /* no column meets two degree-1 checks: only they can make a NaN, and only their waves test for it */
+#define QLDPC_DETAIL_RES_CDEG8 0x80      /* resident kernel: the (8,4) instance (a row of degree 7 or 8, or a column of degree 4), else (6,3) */
+#define QLDPC_DETAIL_RES_CPT2 0x100      /* resident kernel: a thread owns two rows and four columns (team beyond 256 threads), else one and two */
 int qldpc_minsum_decode_path(const qldpc_graph *g, const double *prior, int max_iter, int alpha_mode, double alpha_val, const double *alpha_seq,
                              int alpha_len, double damping, double clip_llr, int flags, int *path, int *detail);
 

@@ -35,6 +35,7 @@ FLAG_WG_VGLOBAL, FLAG_WG_GENERIC, FLAG_OSD_UG, FLAG_OSD_GLOBAL, FLAG_CLOCK_PROBE
 # qldpc_minsum_decode_path: the decoder form a call takes (QLDPC_PATH_*) and the QLDPC_DETAIL_* bits of the workgroup forms
 PATH_REGULAR, PATH_RESIDENT, PATH_WG2, PATH_WG, PATH_STREAM, PATH_WAVE = 0, 1, 2, 3, 4, 5
 DETAIL_LEAN, DETAIL_REG_INDICES, DETAIL_VGLOBAL, DETAIL_DAMPING, DETAIL_BLOCK_1024, DETAIL_DEG1, DETAIL_NAN_DEG1_ONLY = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+DETAIL_RES_CDEG8, DETAIL_RES_CPT2 = 0x80, 0x100         # PATH_RESIDENT: the kernel instantiation (with DETAIL_DAMPING)
 # qldpc_osd0_last_path: the OSD-0 kernel the last call on a graph handle took (QLDPC_OSD_PATH_*) and its QLDPC_OSD_DETAIL_* bits
 OSD_PATH_NONE, OSD_PATH_SMALL, OSD_PATH_GJ, OSD_PATH_GJG, OSD_PATH_REFORDER_LDS, OSD_PATH_REFORDER_UG, OSD_PATH_GLOBAL = -1, 0, 1, 2, 3, 4, 5
 OSD_DETAIL_MODE_MASK, OSD_DETAIL_REDO = 0x3, 0x4

@@ -53,7 +53,7 @@ int select_decode_path(const qldpc_graph *g, int max_iter, double damping, doubl
                   g->max_row_deg, g->max_col_deg);
         return QLDPC_ERR_UNSUPPORTED;
     }
-    if (!want_stream && can_res) { out.path = QLDPC_PATH_RESIDENT; return QLDPC_OK; }
+    if (!want_stream && can_res) { out.path = QLDPC_PATH_RESIDENT; out.detail = resident_detail(g, damping); return QLDPC_OK; }
     if (!want_stream && wg_supported(g, damping)) {
         // the prior is known on the host and the inputs are clean: the form with every table in LDS (minsum_wg2.hip), unless a flag asks for a form of the
         // table kernel (QLDPC_FLAG_WG_TABLES and the layout / experiment selectors)

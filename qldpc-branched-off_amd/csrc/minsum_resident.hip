@@ -21,6 +21,7 @@
 #include "mc_common.h"
 #include "minsum_common.h"
 #include "minsum_f64.h"
+#include "resident_plan.h"
 
 #include <cstdlib>
 
@@ -317,30 +318,16 @@ __global__ __launch_bounds__(1024) void minsum_resident_kernel(ResidentArgs A) {
     }
 }
 
-struct ResidentPlan { int cdeg, vdeg, cpt, vpt, TS, S; size_t lds; };
-
+// the team shape and the LDS size: resident_plan.h (pure arithmetic, printed by tests/resident_plan_main.cpp)
 static bool plan_resident(const qldpc_graph *g, ResidentPlan &P) {
-    if (g->m <= 0 || g->n <= 0 || g->nnz <= 0) return false;
-    if (g->max_row_deg > 8 || g->max_col_deg > 4) return false;
-    P.cdeg = g->max_row_deg <= 6 ? 6 : 8;
-    P.vdeg = g->max_col_deg <= 3 ? 3 : 4;
-    if (P.cdeg == 8 || P.vdeg == 4) { P.cdeg = 8; P.vdeg = 4; }
-    const int rst = (P.cdeg % 2 == 0) ? P.cdeg + 1 : P.cdeg;
-    const size_t per_slot = ((size_t)g->m * rst + g->n) * 8 + 8 + 16 + 8 + (size_t)((g->n + 3) / 4) * 4;      // R, V, flags + Monte-Carlo state (results, logical accumulator, error bytes)
-    if (per_slot > 60 * 1024) return false;
-    // one check / two variables per thread when the team then fits 1024 threads, else two / four
-    P.cpt = 1; P.vpt = 2;
-    int ts = std::max(g->m, (g->n + 1) / 2);
-    if (ts > 256) { P.cpt = 2; P.vpt = 4; ts = std::max((g->m + 1) / 2, (g->n + 3) / 4); }
-    if (ts > 1024) return false;
-    P.TS = ts;
-    int S = 1024 / ts;
-    const size_t lds_budget = 64 * 1024;   // two workgroups per CU
-    while (S > 1 && (size_t)S * per_slot + 96 > lds_budget) S--;
-    if (S < 1) return false;
-    P.S = S;
-    P.lds = (size_t)S * per_slot + 16 + 16 + 48 + 16;      // + active[2], the block tally, alignment
-    return true;
+    return plan_resident_shape(g->m, g->n, g->nnz, g->max_row_deg, g->max_col_deg, P);
+}
+
+// QLDPC_DETAIL_* bits of a resident launch: which of the instantiations below serves the graph (0 where the kernel refuses it)
+int resident_detail(const qldpc_graph *g, double damping) {
+    ResidentPlan P;
+    if (!plan_resident(g, P)) return 0;
+    return (P.cdeg == 8 ? QLDPC_DETAIL_RES_CDEG8 : 0) | (P.cpt == 2 ? QLDPC_DETAIL_RES_CPT2 : 0) | (damping != 1.0 ? QLDPC_DETAIL_DAMPING : 0);
 }
 
 bool resident_supported(const qldpc_graph *g, double damping) {
@@ -375,7 +362,7 @@ int minsum_resident_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd
     A.indptr = g->d_indptr; A.indices = g->d_indices; A.colptr = g->d_colptr; A.rowidx = g->d_rowidx; A.csc2csr = g->d_csc2csr;
     A.B = B; A.synd = d_synd; A.prior = d_prior; A.alpha = d_alpha; A.damping = damping; A.clip = clip;
     A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
-    const unsigned block = (unsigned)round_up((int64_t)P.S * P.TS, 64);
+    const unsigned block = P.block;
     int64_t groups = (B + P.S - 1) / P.S;
     const int64_t max_grid = 256 * 2 * 8;   // persistent: a few waves of workgroups per CU
     const unsigned grid = (unsigned)(groups < max_grid ? groups : max_grid);
@@ -398,7 +385,7 @@ int mc_resident_launch(const qldpc_graph *g, int64_t B, const double *d_prior, i
     A.B = B; A.prior = d_prior; A.alpha = d_alpha; A.damping = 1.0; A.clip = clip;
     A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.thr = thr; A.use_osd = use_osd; A.shot_begin = shot_begin;
     A.Lmask = d_Lmask; A.cold = reinterpret_cast<const RegCold *>(d_cold);
-    const unsigned block = (unsigned)round_up((int64_t)P.S * P.TS, 64);
+    const unsigned block = P.block;
     const int64_t groups = (B + P.S - 1) / P.S, max_grid = 256 * 2 * 8;
     const unsigned grid = (unsigned)(groups < max_grid ? (groups > 0 ? groups : 1) : max_grid);
     if (P.cdeg == 6 && P.cpt == 1) return launch_mc_t<6, 3, 1, 2>(A, grid, block, P.lds, stream);

@@ -269,7 +269,10 @@ def test_path_and_detail_constants_follow_the_header():
     paths = {k: int(v) for k, v in re.findall(r"#define\s+QLDPC_PATH_(\w+)\s+(\d+)\b", text)}
     bits = {k: int(v, 16) for k, v in re.findall(r"#define\s+QLDPC_DETAIL_(\w+)\s+(0x[0-9a-fA-F]+)", text)}
     assert set(paths) == {"REGULAR", "RESIDENT", "WG2", "WG", "STREAM", "WAVE"} and sorted(paths.values()) == list(range(6))
-    assert len(bits) == 7 and all(v & (v - 1) == 0 and v for v in bits.values()) and len(set(bits.values())) == 7
+    assert len(bits) == 9 and all(v & (v - 1) == 0 and v for v in bits.values()) and len(set(bits.values())) == 9
+    # the seven bits of the workgroup forms keep their values; the two of the resident kernel lie above them
+    assert [bits[k] for k in ("LEAN", "REG_INDICES", "VGLOBAL", "DAMPING", "BLOCK_1024", "DEG1", "NAN_DEG1_ONLY")] == [1 << i for i in range(7)]
+    assert sorted(k for k, v in bits.items() if v > 0x40) == ["RES_CDEG8", "RES_CPT2"]
     for name, v in paths.items():
         assert getattr(_lib, "PATH_" + name) == v, name
     for name, v in bits.items():

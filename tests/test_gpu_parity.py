@@ -1149,6 +1149,7 @@ def test_random_irregular_graphs_all_kernels(Lb, oracle, monkeypatch):
     rng = np.random.default_rng(2026)
     shapes = [(5, 9, 3), (12, 30, 4), (40, 90, 5), (64, 200, 7), (150, 600, 6), (300, 2100, 9), (700, 5000, 12), (1100, 9000, 20)]
     ran = {"vg": 0, "stream": 0}
+    resident_details = set()                                           # which instantiations of the resident kernel the query named
     for gi, (m, n, rd) in enumerate(shapes):
         rows = []
         for i in range(m):
@@ -1186,11 +1187,14 @@ def test_random_irregular_graphs_all_kernels(Lb, oracle, monkeypatch):
                 if path == L.PATH_WG:
                     form = "wg " + ("lean" if detail & L.DETAIL_LEAN else "generic") + (" vglobal" if detail & L.DETAIL_VGLOBAL else "")
                 ran[form] = ran.get(form, 0) + 1
+                if path == L.PATH_RESIDENT:
+                    resident_details.add(detail)
                 assert (path == L.PATH_STREAM) == (flags == L.FLAG_KERNEL_STREAM) and bool(detail & L.DETAIL_VGLOBAL) == bool(vg), (gi, trial, flags, path, detail)
                 out = L.minsum_decode_batch(graph, synd, prior, iters, mode, alpha, damping=damping, clip_llr=clip, flags=flags)
                 ran["stream"] += flags == L.FLAG_KERNEL_STREAM
                 for name, a, b in zip(("err", "conv", "llr", "iter"), (out[0], out[1].astype(bool), out[2], out[3]), (ref[0], ref[1].astype(bool), ref[2], ref[3])):
                     assert np.array_equal(a, b, equal_nan=True), (gi, trial, flags, vg, name, mode, damping, clip, iters)
+    print("ran", ran, "distinct resident detail values", len(resident_details))
     assert L.BUILD == "experiments" or (ran["vg"] >= 6 and ran["stream"] >= 20)
     assert "wg2" not in ran and "regular" not in ran, ran
     for form in ("wg lean", "wg generic") + (() if L.BUILD == "experiments" else ("resident", "wg lean vglobal", "wg generic vglobal", "path stream")):
