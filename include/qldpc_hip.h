@@ -44,6 +44,8 @@
  *        additive, same version: recorded detection events in place of a plan's sampler, qldpc_circuit_plan_set_event_layout,
  *        qldpc_circuit_plan_decode_events[_dev] and qldpc_circuit_plan_unpack_events
  *        additive, same version: qldpc_minsum_decode_path names the resident kernel's instantiation, QLDPC_DETAIL_RES_CDEG8 and QLDPC_DETAIL_RES_CPT2
+ *        additive, same version (the suites pin 101): fixed-weight fault sampling on a circuit plan, qldpc_circuit_plan_use_fixed_weight,
+ *        QLDPC_FIXED_WEIGHT_MAX and QLDPC_FIXED_WEIGHT_MAX_LOCS
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -676,6 +678,36 @@ int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *dem, const qldpc_graph *
                                   int alpha_mode, double alpha_val0, double alpha_val1, const double *alpha_seq0, int alpha_len0,
                                   const double *alpha_seq1, int alpha_len1, double damping, double clip_llr, int use_osd, int flags, int64_t batch,
                                   qldpc_circuit_plan **out);
+
+/* ---- fixed-weight fault sampling: the plan's sampler draws exactly `weight` faults per trial.  New here: the reference has no counterpart. ---------
+ * The sampler axis of a plan, beside its decode path and its OSD stage: it is not one of the qldpc_circuit_plan_use_* decode switches, goes with every
+ * one of them in either call order, and is two-way.  The plan's own sampler draws each of its N fault locations (circuit: the base ops; detector error
+ * model: the mechanisms) independently with one probability p, so the number of faults is Binomial(N, p) and, given that number, the faulty set is
+ * uniform.  The fixed-weight sampler draws that conditional law for one weight w: the failure fraction f_w it measures does not depend on p, and
+ * LER(p) = sum_w C(N, w) p^w (1 - p)^(N - w) f_w (simulation/strata.py sweeps w on ONE plan).
+ *
+ * The law, a pure function of (seed, global trial index g = trial_begin + t, w): the faulty set S is built by Floyd's algorithm, for i = 0 .. w - 1:
+ *   j = N - w + i;
+ *   o_i = word (i & 3) of Philox4x32-10(counter = (lo32(g), hi32(g), i >> 2, 4), key = (lo32(seed), hi32(seed)));
+ *   t = the high 32 bits of the 64-bit product o_i * (j + 1);
+ *   S gets j if t is already in S, t otherwise.
+ * Counter word 3 is the domain: 4 is new (0 = the code-capacity samplers, 1 and 2 = the circuit sampler, 3 = the DEM sampler, 0x52...... = Relay-BP).
+ * S is a uniformly distributed w-subset of 0 .. N - 1 (Bentley and Floyd 1987) up to the 2^-32 granularity of t: the probability of a value of t
+ * differs from 1 / (j + 1) by at most 2^-32, a relative bias of at most N / 2^32 per step (4e-6 for the 17 280 locations of the [[144,12,12]] circuit).
+ * A member l of S then does what a faulty location does today: on a circuit plan it draws its Pauli component from domain 2, counter (g, l), exactly as
+ * the independent sampler does (measurements and preparations have one component) and XORs the same fault signatures; on a DEM plan mechanism l XORs
+ * its detectors and logical masks.  XOR is order-free, so the result does not depend on grid, block size, lane mapping or how a range is cut into batches.
+ *
+ * weight >= 0: from now on the plan's sampler draws exactly `weight` faulty locations per trial (law above);
+ * weight == -1: back to the independent draws the plan was created with.  Two-way, any number of times.
+ * qldpc_circuit_plan_run, _run_outcomes and _sample honour it; _decode_events* and _unpack_events do not sample and are untouched.
+ * QLDPC_ERR_INVALID: weight < -1, weight > QLDPC_FIXED_WEIGHT_MAX (binomial mass beyond is of no use) or weight > N; a DEM plan whose mechanisms
+ * do not all have the same threshold floor(p_l * 2^32) (qldpc_last_error names the first mechanism that differs from mechanism 0: a non-uniform model
+ * has no weight strata of this kind).  QLDPC_ERR_UNSUPPORTED: N > QLDPC_FIXED_WEIGHT_MAX_LOCS (the membership bit set of S lives in LDS, 64 KiB).
+ * A refused call leaves the plan as it was. */
+#define QLDPC_FIXED_WEIGHT_MAX 4096
+#define QLDPC_FIXED_WEIGHT_MAX_LOCS 524288
+int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *plan, int weight);
 
 /* ---- recorded detection events in place of the sampler: events -> decode -> OSD -> predict.  New here: the reference has no counterpart. ---------
  * The second front door of a circuit plan, for plans of qldpc_circuit_plan_create and _create_dem alike: the syndromes come from the caller's records

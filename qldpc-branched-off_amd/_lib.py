@@ -969,6 +969,21 @@ def unpack_bits(packed, n_bits):
     return np.unpackbits(packed, axis=1, count=int(n_bits), bitorder="little")
 
 
+FIXED_WEIGHT_MAX, FIXED_WEIGHT_MAX_LOCS = 4096, 524288      # QLDPC_FIXED_WEIGHT_MAX, QLDPC_FIXED_WEIGHT_MAX_LOCS
+
+
+def check_fixed_weight(weight):
+    """The argument rule of use_fixed_weight, before any device call: None or -1 -> -1 (the independent draws); an integer 0..FIXED_WEIGHT_MAX -> int."""
+    if weight is None:
+        return -1
+    if isinstance(weight, (bool, np.bool_)) or not isinstance(weight, (int, np.integer)):
+        raise ValueError(f"fixed weight must be an integer (or None), got {weight!r}")
+    weight = int(weight)
+    if weight < -1:
+        raise ValueError(f"fixed weight must be >= 0 (None or -1 switches back), got {weight}")
+    return weight
+
+
 class CircuitPlan:
     """Circuit-level Monte-Carlo plan (qldpc_circuit_plan_*): Philox fault sampling through precomputed fault signatures,
     decode of both sectors, OSD-0, logical comparison and tally, all on the device."""
@@ -981,6 +996,8 @@ class CircuitPlan:
         pz, px = f64(prior_z), f64(prior_x)
         lz, lx = np.ascontiguousarray(logmask_z, np.uint64), np.ascontiguousarray(logmask_x, np.uint64)
         self.k, self.nsx, self.nsz = d.k, int(keep["x_syn_ptrs"][-1]), int(keep["z_syn_ptrs"][-1])
+        self.n_locs = int(d.base_len)                       # fault locations: what use_fixed_weight counts
+        self.fixed_weight = None                            # the sampler axis: None = the independent draws, else the weight in force
         self.graph_z, self.graph_x = graph_z, graph_x
         self.flags = flags
         self._h = C.c_void_p()
@@ -1037,6 +1054,14 @@ class CircuitPlan:
         p = decim_params(params, with_clip=False)
         check(lib().qldpc_circuit_plan_use_decimation(self._h, p["alpha"], p["t_round"], p["max_rounds"], p["per_round"], p["fix_llr"]))
         self.decimation = p
+
+    def use_fixed_weight(self, weight):
+        """Draw exactly `weight` faulty locations (mechanisms of a DemPlan) per trial from now on, uniformly among the subsets of that size
+        (qldpc_circuit_plan_use_fixed_weight); None or -1: back to the independent draws.  The sampler axis of the plan: two-way, any number of
+        times, and it goes with every other use_* in either order.  run, run_outcomes and sample honour it."""
+        weight = check_fixed_weight(weight)
+        check(lib().qldpc_circuit_plan_use_fixed_weight(self._h, C.c_int(weight)))
+        self.fixed_weight = None if weight < 0 else weight
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))
@@ -1167,6 +1192,8 @@ class DemPlan(CircuitPlan):
         lms = [np.ascontiguousarray(x, np.uint64) for x in logmasks] + [None] * (2 - nsec)
         nd, ks = [int(x[0]) for x in sectors] + [0, 0], [int(x[1]) for x in sectors] + [0, 0]
         self.n_sectors, self.k, self.ks, self.nsx, self.nsz = nsec, max(ks), (ks[0], ks[1]), nd[0], nd[1]
+        self.n_locs = int(d.n_mech)
+        self.fixed_weight = None
         self.graph_z, self.graph_x = g[0], g[1]
         self.flags = flags
         opt = lambda a, t: ptr(a, t) if a is not None else None

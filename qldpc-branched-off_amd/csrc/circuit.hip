@@ -12,7 +12,7 @@
 #include "common.h"
 #include "launchers.h"
 #include "clocks.h"
-#include "mc_common.h"
+#include "sampler_common.h"
 #include "judge.h"
 
 #include <algorithm>
@@ -21,8 +21,6 @@
 #include <vector>
 
 namespace qldpc {
-
-enum { C_OP_CNOT = 1, C_OP_PREP_X = 2, C_OP_PREP_Z = 3, C_OP_MEAS_X = 4, C_OP_MEAS_Z = 5, C_OP_IDLE = 6 };   // noise/constants.py:8-14
 
 // ---- single-fault frame simulation: lane = (location, slot); ops shared; frames laid out [qubit][lane] ----
 template <bool XSECTOR>
@@ -52,21 +50,7 @@ __global__ void fault_signature_kernel(int nl, const int32_t *__restrict__ lane_
     }
 }
 
-struct SigTab {           // signatures of one sector; entry e = 2 * location + slot
-    const int32_t *ptr;   // [2*n_locs + 1]
-    const uint16_t *idx;  // detector indices
-    const uint64_t *log;  // logical flips, bit r = logical row r
-};
-
-// component masks: bit0 = X on slot 0, bit1 = X on slot 1, bit2 = Z on slot 0, bit3 = Z on slot 1
-__constant__ uint8_t c_cnot_comp[15] = {1, 5, 4, 2, 10, 8, 3, 15, 12, 11, 7, 13, 14, 9, 6};   // order of noise/kernels.py:283-343
-__constant__ uint8_t c_idle_comp[3] = {1, 5, 4};                                               // X, Y, Z (kernels.py:263-268)
-
-__device__ __forceinline__ void xor_signature(const SigTab &T, int e, uint32_t *bits, unsigned long long *logacc) {
-    for (int k = T.ptr[e]; k < T.ptr[e + 1]; k++) { const int d = T.idx[k]; atomicXor(&bits[d >> 5], 1u << (d & 31)); }
-    const unsigned long long lm = T.log[e];
-    if (lm) atomicXor(logacc, lm);
-}
+// SigTab, the component masks, xor_signature and fire_location: sampler_common.h (shared with fixed_weight.hip)
 
 // one workgroup per trial (grid-stride): draw faults, accumulate both sectors' detector bit-sets in LDS, write them out
 __global__ __launch_bounds__(256) void circuit_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, uint32_t thr,
@@ -91,21 +75,7 @@ __global__ __launch_bounds__(256) void circuit_sample_kernel(int64_t B, int64_t 
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
-                if (l < n_locs && o[w] < thr) {
-                    const int ty = loc_type[l];
-                    int comp;
-                    if (ty == C_OP_MEAS_X || ty == C_OP_PREP_X) comp = 4;            // Z flip (kernels.py:211-216, 241-246)
-                    else if (ty == C_OP_MEAS_Z || ty == C_OP_PREP_Z) comp = 1;       // X flip (kernels.py:224-229, 253-258)
-                    else {
-                        uint32_t r[4];
-                        philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)l, 2u, seed_lo, seed_hi, r);
-                        comp = (ty == C_OP_IDLE) ? c_idle_comp[r[0] % 3u] : c_cnot_comp[r[0] % 15u];
-                    }
-                    if (comp & 1) xor_signature(X, 2 * l, bx, &lacc[1]);
-                    if (comp & 2) xor_signature(X, 2 * l + 1, bx, &lacc[1]);
-                    if (comp & 4) xor_signature(Z, 2 * l, bz, &lacc[0]);
-                    if (comp & 8) xor_signature(Z, 2 * l + 1, bz, &lacc[0]);
-                }
+                if (l < n_locs && o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, bz, bx, lacc);
             }
         }
         __syncthreads();
@@ -209,6 +179,10 @@ struct qldpc_circuit_plan {
     // projection onto it, and d_thr their thresholds (uint32, zero-padded to a multiple of four).
     bool dem = false;
     PlanBuf d_thr;
+    // the sampler axis (qldpc_circuit_plan_use_fixed_weight): -1 = the independent draws above, w >= 0 = exactly w faults per trial (fixed_weight.hip).
+    // dem_odd: the first mechanism whose threshold differs from mechanism 0's (-1: none), which refuses the switch
+    int fixed_weight = -1;
+    int64_t dem_odd = -1;
     double p = 0, damping = 1, clip = 20;
     uint32_t thr = 0;
     int64_t batch = 0;
@@ -508,7 +482,10 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
         if ((rc = plan_sector(P, i, in[i], alpha_mode, D->layer_rows[i], sp, si, sl)) != QLDPC_OK) return fail(rc);
     }
     std::vector<uint32_t> thr((nm + 3) / 4 * 4, 0u);                      // zero padding: a padded entry never fires
-    for (size_t l = 0; l < nm; l++) thr[l] = bernoulli_threshold(D->prob[l]);
+    for (size_t l = 0; l < nm; l++) {
+        thr[l] = bernoulli_threshold(D->prob[l]);
+        if (P->dem_odd < 0 && thr[l] != thr[0]) P->dem_odd = (int64_t)l;
+    }
     if ((rc = up(P->d_thr, thr)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
     *out = P;
     return QLDPC_OK;
@@ -516,6 +493,12 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
 
 static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, int64_t B, hipStream_t s, bool zero_counts = false) {
     const Sector &Z = P->sec[0], &X = P->sec[1];
+    if (P->fixed_weight >= 0) {
+        const auto tab = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
+        return fixed_weight_sample_launch(P->device, B, begin, seed, P->fixed_weight, P->n_locs, P->dem, P->d_loc_type.as<uint8_t>(), tab(Z), tab(X), Z.nsyn,
+                                          X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(),
+                                          X.d_true.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
+    }
     if (P->dem) {
         const auto tab = [](const Sector &S) { return DemTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
         return dem_sample_launch(B, begin, seed, P->n_locs, P->d_thr.as<uint32_t>(), tab(Z), tab(X), Z.nsyn, X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(),
@@ -839,6 +822,19 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
     });
     if (rc == QLDPC_OK) P->path = Path::F32;
     return rc;
+}
+
+// The sampler axis: not a decode switch (switch_allowed is not asked), two-way, and only read by launch_sampler.  Launch arguments travel by value,
+// so batches already enqueued keep the sampler they were enqueued with.
+QLDPC_EXPORT int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *P, int weight) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    if (weight == -1) { P->fixed_weight = -1; return QLDPC_OK; }
+    const int rc = fixed_weight_check(P->n_locs, weight);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(!P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
+                  "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
+    P->fixed_weight = weight;
+    return QLDPC_OK;
 }
 
 // ---- recorded detection events in place of the sampler (kernels: events.hip) ----

@@ -15,6 +15,7 @@ namespace qldpc {
 struct OsdLaunch;      // osd_plan.h
 struct OsdGjArgs;      // osd_gj.h
 struct DemTab;         // mc_common.h
+struct SigTab;         // sampler_common.h
 struct JudgeSector;    // judge.h
 struct EventsSector;   // judge.h
 
@@ -165,6 +166,13 @@ int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech,
                       bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
                       hipStream_t s);
 int dem_validate(const qldpc_dem_desc *D);      // QLDPC_OK, or QLDPC_ERR_INVALID with the error text naming the sector or the mechanism
+// Fixed-weight sampler of a circuit plan (fixed_weight.hip): exactly `weight` members of 0 .. n_locs - 1 per trial.  dem = false: T0 / T1 are the fault signatures
+// of sectors Z / X (entry 2 * location + slot) and d_loc_type the locations' op types; dem = true: the mechanisms' projections (entry = mechanism), d_loc_type
+// unused.  The other arguments as in dem_sample_launch.  fixed_weight_check: the limits of (n_locs, weight), QLDPC_ERR_INVALID / _UNSUPPORTED with the text set.
+int fixed_weight_check(int64_t n_locs, int weight);
+int fixed_weight_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, int weight, int n_locs, bool dem, const uint8_t *d_loc_type,
+                               const SigTab &T0, const SigTab &T1, int n0, int n1, bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0,
+                               unsigned long long *d_true1, int32_t *d_fail_counts, hipStream_t s);
 // Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
 // only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
 // predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does

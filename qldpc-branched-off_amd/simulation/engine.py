@@ -383,6 +383,34 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     return result
 
 
+def _circuit_problem(Hx, Hz, Lx, Lz, error_rate, num_cycles, precomputed_matrices, device, bb_params):
+    """What a circuit plan is created from, shared by run_simulation and strata.run_weight_strata: the compiled syndrome circuit, the decoding matrices
+    built at ``error_rate`` (or the precomputed ones) as graphs on ``device``, the prior LLRs and logical column masks per sector (Z, X), k, and
+    ``make_plan(graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags)`` -> the _lib.CircuitPlan whose sampler draws at ``error_rate``."""
+    cb = BBCodeCircuit(Hx, Hz, num_cycles=num_cycles, **bb_params)
+    m = precomputed_matrices or build_decoding_matrices(cb, Lx, Lz, error_rate, verbose=False)          # engine.py:207-208
+    compiled = CompiledCircuit(base_circuit=cb.get_full_circuit(), noiseless_suffix=cb.cycle * 2, lin_order=cb.lin_order,
+                               data_qubits=cb.data_qubits, Xchecks=cb.Xchecks, Zchecks=cb.Zchecks)
+    llrs_z, llrs_x = prior_llrs(np.asarray(m["channel_probsZ"], dtype=np.float64)), prior_llrs(np.asarray(m["channel_probsX"], dtype=np.float64))
+    k = np.asarray(Lx).shape[0]
+    graphs, masks = [], []
+    for s in ("Z", "X"):
+        Hdec = m[f"Hdec{s}"]
+        ip, ix, shape = _lib.canonical_csr(Hdec)
+        graphs.append(_lib.Graph(ip, ix, shape[1], device=device))
+        if f"H{s}_logical" in m:                     # compact form: the k logical rows only (dense or (indptr, indices))
+            masks.append(_lib.logical_column_masks(m[f"H{s}_logical"], shape[1]))
+        else:
+            flr = int(m[f"first_logical_row{s}"])
+            masks.append(_lib.logical_column_masks(np.asarray(m[f"H{s}_full"])[flr:flr + k], shape[1]))    # engine.py:412-413
+
+    def make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags):
+        return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
+                                alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
+
+    return SimpleNamespace(compiled=compiled, graphs=graphs, llrs=(llrs_z, llrs_x), masks=masks, k=k, make_plan=make_plan)
+
+
 def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
@@ -403,22 +431,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if estimation_plot_dir is not None:
         os.makedirs(estimation_plot_dir, exist_ok=True)
 
-    cb = BBCodeCircuit(Hx, Hz, num_cycles=num_cycles, **bb_params)
-    m = precomputed_matrices or build_decoding_matrices(cb, Lx, Lz, error_rate, verbose=False)          # engine.py:207-208
-    compiled = CompiledCircuit(base_circuit=cb.get_full_circuit(), noiseless_suffix=cb.cycle * 2, lin_order=cb.lin_order,
-                               data_qubits=cb.data_qubits, Xchecks=cb.Xchecks, Zchecks=cb.Zchecks)
-    llrs_z, llrs_x = prior_llrs(np.asarray(m["channel_probsZ"], dtype=np.float64)), prior_llrs(np.asarray(m["channel_probsX"], dtype=np.float64))
-    k = np.asarray(Lx).shape[0]
-    graphs, masks = [], []
-    for s in ("Z", "X"):
-        Hdec = m[f"Hdec{s}"]
-        ip, ix, shape = _lib.canonical_csr(Hdec)
-        graphs.append(_lib.Graph(ip, ix, shape[1], device=device))
-        if f"H{s}_logical" in m:                     # compact form: the k logical rows only (dense or (indptr, indices))
-            masks.append(_lib.logical_column_masks(m[f"H{s}_logical"], shape[1]))
-        else:
-            flr = int(m[f"first_logical_row{s}"])
-            masks.append(_lib.logical_column_masks(np.asarray(m[f"H{s}_full"])[flr:flr + k], shape[1]))    # engine.py:412-413
+    prob = _circuit_problem(Hx, Hz, Lx, Lz, error_rate, num_cycles, precomputed_matrices, device, bb_params)
+    graphs, masks, k, (llrs_z, llrs_x) = prob.graphs, prob.masks, prob.k, prob.llrs
 
     # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
     # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
@@ -455,8 +469,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         extra.update(beta_z=betas[0][0], beta_x=betas[1][0], beta_r2_z=betas[0][1], beta_r2_x=betas[1][1])   # engine.py:482-486
 
     def make_plan(own_graphs, dev):
-        return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
-                                alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
+        return prob.make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags)
 
     return _run_trials(make_plan, graphs, (llrs_z, llrs_x), masks, (alpha_z, alpha_x), (k, k), rules, rank, world, devices, base_seed, num_trials, max_trials,
                        target_logical_errors, maxIter, osd_order, alpha_mode, batch, decoder, schedule, precision, extra)
