@@ -144,6 +144,8 @@ int qldpc_device_count(void);
  *                         plans with large batches keep the caller's stream), 2 = only OSD-0 + judge on a side stream, 0 = everything on the caller's stream
  *   "mc_big_lanes"        streams whole batches rotate over under reference semantics with large batches: 2 .. 8 (default 3)
  *   "mc_list_shots"       shots per workgroup of the full decoder on listed shots: 0 (default: the kernel's own 7), 1 .. 16
+ *   "regular_own_edges"   read at a launch of the regular min-sum kernel: 1 (default) = on clean inputs and a (6,3)-regular graph the thread of a check is the
+ *                         variable thread of two of its own columns (csrc/regular_own.h), 0 = the body without ownership on every graph
  *   "regular_kernel", "wave_cpl", "wave_rst", "wave_grid"  experiments build only: the wave-private decoder (csrc/minsum_wave.hip); the
  *                         product library accepts 0 and answers anything else with QLDPC_ERR_UNSUPPORTED */
 int qldpc_set_option(const char *name, int value);

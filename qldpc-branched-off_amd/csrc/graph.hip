@@ -1,6 +1,8 @@
 // Error state, device selection and the Tanner-graph handle of libqldpc_hip.
 #include "common.h"
 #include "launchers.h"
+#include "regular_plan.h"
+#include "regular_own.h"
 
 #include <algorithm>
 #include <cstring>
@@ -273,6 +275,11 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         if (rc == QLDPC_OK) rc = upload(&g->d_ell_var_s, evs);
         if (rc == QLDPC_OK) rc = upload(&g->d_identity, ident);
     }
+    if (rc == QLDPC_OK && g->max_row_deg == kRegOwnCdeg && g->max_col_deg == kRegOwnVdeg && n == 2 * m && m <= 1024) {
+        // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL)
+        std::vector<int32_t> own;
+        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own)) rc = upload(&g->d_regown, own);
+    }
     if (rc != QLDPC_OK) { qldpc_graph_destroy(g); return rc; }
     *out = g;
     return QLDPC_OK;
@@ -286,6 +293,7 @@ QLDPC_EXPORT void qldpc_graph_destroy(qldpc_graph *g) {
     if (g->d_ell_col) (void)hipFree(g->d_ell_col);
     if (g->d_ell_var) (void)hipFree(g->d_ell_var);
     if (g->d_col_rows) (void)hipFree(g->d_col_rows);
+    if (g->d_regown) (void)hipFree(g->d_regown);
     for (void *p : {(void *)g->d_row_of_slot, (void *)g->d_col_of_slot, (void *)g->d_deg_of_rslot, (void *)g->d_deg_of_cslot, (void *)g->d_deg_of_row,
                     (void *)g->d_deg_of_col, (void *)g->d_ell_col_s, (void *)g->d_ell_var_s, (void *)g->d_identity})
         if (p) (void)hipFree(p);

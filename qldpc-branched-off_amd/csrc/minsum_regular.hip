@@ -43,6 +43,12 @@
 //     Per check and iteration: CDEG v_sub, 3 * CDEG - 4 v_min_f64 (two of them the seeds), CDEG v_mul_f64, 2 * CDEG + 1 v_xor,
 //     CDEG v_bfi.  The suffix chain is built first, the prefix chain runs forward and each message leaves as soon as its two
 //     inputs exist, so t_k dies edge by edge.
+//   * clean (6,3) graphs with an ownership assignment (OWN; regular_own.h, built once per graph handle): the two columns of a thread are two columns of
+//     its OWN check, edges 0 and 1 of the reordered row (the check update does not depend on edge order: min and XOR are exact and commutative and no
+//     selector exists).  Their two messages never leave Rprev, their posteriors are gathered from registers, the row holds the other four words, and
+//     the variable sum takes its two other messages from LDS in ascending check order with the own one selected into its place: the reference's
+//     ((0 + a) + b) + c word for word.  Per thread and pass 8 words gathered and 6 stored instead of 12 and 8, for eight v_cndmask_b32 -- the LDS pipe,
+//     not VALU issue, bounds the loop (profiles/r20_own_edges.txt).  qldpc_set_option("regular_own_edges", 0) takes the body without ownership.
 // MC = true fuses the sampler (Philox4x32-10 stream of mc_common.h), the GF(2) syndrome (a6), the decode, the logical
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
@@ -53,7 +59,9 @@
 #include "minsum_common.h"
 #include "minsum_f64.h"
 #include "regular_plan.h"
+#include "regular_own.h"
 
+#include <atomic>
 #include <cstdlib>
 
 namespace qldpc {
@@ -61,6 +69,7 @@ namespace qldpc {
 struct RegArgs {
     int m, n, max_iter, fixed, S, TS;
     const int32_t *indptr, *indices, *colptr, *rowidx, *csc2csr;
+    const int32_t *own;             // ownership records of the (6,3) clean form (regular_own.h), NULL = the body without ownership
     int64_t B;
     const double *prior, *alpha;
     double damping, clip;
@@ -78,7 +87,8 @@ struct RegArgs {
 
 // The compare-free message words of one check (header comment): x holds the gathered posteriors and becomes the unclipped t_k = x_k - Rprev_k
 // (`later`: iteration 0 reads priors, nothing to subtract), the clip sits in the two chain seeds (cmin), the words go to Rprev and to the check's row.
-template <int CDEG>
+// SKIP: the first SKIP edges are the thread's own columns (regular_own.h); their words stay in Rprev only, edge k >= SKIP goes to row[k - SKIP].
+template <int CDEG, int SKIP = 0>
 __device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev)[CDEG], bool later, double alpha, double cmin, unsigned synw, double *row) {
     unsigned spw = synw;                                                       // sign of the whole row in bit 31
 #pragma unroll
@@ -100,7 +110,7 @@ __device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev
         const unsigned hi = ((unsigned)__double2hiint(prod) & 0x7fffffffu) | (sgn & 0x80000000u);
         const double msg = __hiloint2double((int)hi, __double2loint(prod));
         Rprev[k] = msg;
-        row[k] = msg;
+        if (k >= SKIP) row[k - SKIP] = msg;
     }
 }
 
@@ -110,7 +120,9 @@ __device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev
 #endif
 // FIXED (all max_iter iterations executed for every shot, outputs frozen at convergence) is a template parameter: the fixed-work and the
 // early-exit forms are distinct kernel symbols, so a rocprofv3 --stats summary lists them separately.
-template <int CDEG, int VDEG, bool DAMP, bool NANFREE, bool MC, bool FIXED>
+// OWN: the thread of a check is the variable thread of two of the check's OWN columns (regular_own.h): edges 0 and 1 of the reordered row.  Their messages
+// stay in Rprev, their posteriors are gathered from registers, and the row holds the other four words in slots 0 .. 3.  Clean (6,3) form only.
+template <int CDEG, int VDEG, bool DAMP, bool NANFREE, bool MC, bool FIXED, bool OWN = false>
 __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(RegArgs A) {
     extern __shared__ unsigned char lds[];
     constexpr int RST = (CDEG % 2 == 0) ? CDEG + 1 : CDEG;
@@ -124,6 +136,8 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     // a check and two columns; a team without a shot (b >= nshots) works on its own slot, which nobody else touches, and the lanes of the block that
     // belong to no team work on the dummy region Dl: a row of RST doubles, two posteriors, one parity word.  Nothing they compute is ever read.
     constexpr bool ALL = CLIPMIN;
+    static_assert(!OWN || (CLIPMIN && CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg), "edge ownership: the clean (6,3) form");
+    constexpr int NOWN = OWN ? kRegOwnOwned : 0;                                   // edges of a row that are not stored
     double *Dl = reinterpret_cast<double *>(lds + A.offD);
     double *Rl = (ALL && !in_team) ? Dl : reinterpret_cast<double *>(lds) + (size_t)sl * m * RST;
     double *Vl = (ALL && !in_team) ? Dl + RST : reinterpret_cast<double *>(lds + A.offV) + (size_t)sl * n;
@@ -147,31 +161,45 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     const bool has_check = in_team && member < m;
     int coff[CDEG];
 #pragma unroll
-    for (int k = 0; k < CDEG; k++) coff[k] = has_check ? A.indices[A.indptr[member] + k] : (ALL ? (k & 1) : 0);
+    for (int k = 0; k < CDEG; k++) {
+        // coff[k]: where the posterior of the row's k-th column lives in V.  It is the column itself, except under OWN: a thread keeps its two posteriors at
+        // member and member + TS, as without ownership (lane-contiguous, conflict-free stores), and the record names those places to the four gathers
+        coff[k] = ALL ? (k & 1) : 0;
+        if (has_check) coff[k] = !OWN ? A.indices[A.indptr[member] + k] : (k < NOWN) ? member + k * TS : A.own[member * kRegOwnWords + kRegOwnGather + k - NOWN];
+    }
+    // the column behind the row's k-th edge / behind the thread's v-th posterior (OWN: read from the record where needed, once or twice per shot, not kept in registers)
+    auto ecol = [&](int k) { return OWN ? A.own[member * kRegOwnWords + kRegOwnCols + k] : coff[k]; };
     unsigned cnf = 0u;                                     // bit k: the prior of the row's k-th column is not finite (see minsum_common.h)
     if (!NANFREE && !DAMP) {
 #pragma unroll
         for (int k = 0; k < CDEG; k++) if (has_check && prior_not_finite(A.prior[coff[k]])) cnf |= 1u << k;
     }
     const int roff = has_check ? member * RST : 0;
-    bool has_var[2];
+    bool has_var[2], vlast[2];
     int vj[2], voff[2][VDEG];
     double vprior[2];
 #pragma unroll
     for (int v = 0; v < 2; v++) {
-        const int j = member + v * TS;
+        const int j = member + v * TS;                                     // the posterior's place in V; the column itself unless OWN (vcol below)
         has_var[v] = in_team && j < n;
+        vlast[v] = false;
         vj[v] = has_var[v] ? j : (ALL ? v : 0);
-        vprior[v] = has_var[v] ? A.prior[j] : 0.0;
+        vprior[v] = has_var[v] ? A.prior[OWN ? ecol(v) : j] : 0.0;
 #pragma unroll
         for (int d = 0; d < VDEG; d++) {
             voff[v][d] = ALL ? d : 0;
-            if (has_var[v]) {
+            if (OWN) {
+                // the two other messages of the column in ascending check order (voff[v][2] is not read); `last`: the own message is the third addend
+                if (has_var[v] && d < 2) voff[v][d] = A.own[member * kRegOwnWords + kRegOwnOffs + 2 * v + d];
+                if (has_var[v] && d == 0) vlast[v] = (A.own[member * kRegOwnWords + kRegOwnLast] >> v) & 1;
+            } else if (has_var[v]) {
                 const int k = A.colptr[j] + d, row = A.rowidx[k];
                 voff[v][d] = row * RST + (A.csc2csr[k] - A.indptr[row]);
             }
         }
     }
+
+    auto vcol = [&](int v) { return OWN ? ecol(v) : vj[v]; };             // OWN: the owned columns are edges 0 and 1 of the reordered row
 
     // a shot list (the shots the bit-sliced first iteration, mc_first.hip, did not finish) replaces the contiguous range
     const int64_t nshots = (MC && A.shot_list) ? (int64_t)*A.shot_count : A.B;
@@ -198,7 +226,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             if (valid && has_check) {
                 int s = 0;
 #pragma unroll
-                for (int k = 0; k < CDEG; k++) s ^= Eb[coff[k]];
+                for (int k = 0; k < CDEG; k++) s ^= Eb[ecol(k)];
                 csyn = s & 1;
                 if (csyn) sres[2] = 1;
             }
@@ -211,6 +239,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
         for (int k = 0; k < CDEG; k++) { Rprev[k] = 0.0; Qold[k] = 0.0; }
 #pragma unroll
         for (int v = 0; v < 2; v++) if (ALL || has_var[v]) Vl[vj[v]] = vprior[v];      // Q_{-1} = prior[col] (kernels.py:263-265)
+        double Vown[2] = {vprior[0], vprior[1]};                                        // OWN: what this thread last wrote to Vl[vj[v]]; the check phase gathers it from here (re-reading it from LDS measured 9 % slower)
         if (in_team && member == 0) { unsat[0] = 0; unsat[1] = 0; }
         if (threadIdx.x == 0) { const int64_t left = nshots - base; active[0] = (int)(left < S ? left : S); }
         bool done = !valid;
@@ -226,7 +255,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 if (CLIPMIN) {                                        // clean inputs: a posterior is never -0.0 (header comment), so x < 0 <=> its sign bit: one XOR per edge
                     unsigned ph = synw;
 #pragma unroll
-                    for (int k = 0; k < CDEG; k++) { x[k] = Vl[coff[k]]; ph ^= (unsigned)__double2hiint(x[k]); }
+                    for (int k = 0; k < CDEG; k++) { x[k] = (OWN && k < NOWN) ? Vown[k] : Vl[coff[k]]; ph ^= (unsigned)__double2hiint(x[k]); }
                     par = (int)ph < 0;                                                            // kernels.py:349,356
                 } else {
 #pragma unroll
@@ -255,12 +284,12 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     const double mag = Al[0] * fabs(p0);
                     const double msg = sneg ? -mag : mag;
 #pragma unroll
-                    for (int k = 0; k < CDEG; k++) { Rprev[k] = msg; Rl[roff + k] = msg; }
+                    for (int k = 0; k < CDEG; k++) { Rprev[k] = msg; if (k >= NOWN) Rl[roff + k - NOWN] = msg; }
                 }
             } else if (in_check && !skip_msg) {
                 if (CLIPMIN && it < max_iter) {
                     // compare-free form (header comment); iteration 0 reads priors: no clip (kernels.py:263-265)
-                    clean_messages<CDEG>(x, Rprev, it > 0, Al[it], (it > 0) ? clip : INFINITY, synw, Rl + roff);
+                    clean_messages<CDEG, NOWN>(x, Rprev, it > 0, Al[it], (it > 0) ? clip : INFINITY, synw, Rl + roff);
                 } else if (it < max_iter) {
                     const double alpha = Al[it];
                     if (it > 0) {
@@ -324,7 +353,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                             unsigned long long lm = 0ull;
 #pragma unroll
                             for (int v = 0; v < 2; v++)
-                                if (has_var[v] && ((Eb[vj[v]] ^ ((it >= 1 && Vl[vj[v]] < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[vj[v]];   // V still holds values_{it-1}
+                                if (has_var[v] && ((Eb[vcol(v)] ^ ((it >= 1 && Vl[vj[v]] < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[vcol(v)];   // V still holds values_{it-1}
                             if (lm) atomicXor(lacc, lm);
                         } else if (member == 0) {
                             active[1] = 1;
@@ -335,8 +364,8 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                         for (int v = 0; v < 2; v++)
                             if (has_var[v]) {
                                 const double xo = (it >= 1) ? Vl[vj[v]] : 0.0;        // V still holds values_{it-1}
-                                A.out_llr[b * n + vj[v]] = xo;
-                                A.out_err[b * n + vj[v]] = (xo < 0.0) ? 1 : 0;                 // kernels.py:349
+                                A.out_llr[b * n + vcol(v)] = xo;
+                                A.out_err[b * n + vcol(v)] = (xo < 0.0) ? 1 : 0;               // kernels.py:349
                             }
                         if (member == 0) {
                             A.out_conv[b] = conv ? 1 : 0;
@@ -352,10 +381,16 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 for (int v = 0; v < 2; v++)
                     if (ALL || has_var[v]) {
                         double s = 0.0;                                                        // kernels.py:279
+                        if (OWN) {
+                            const double o1 = Rl[voff[v][0]], o2 = Rl[voff[v][1]], own = Rprev[v];
+                            s += o1; s += vlast[v] ? o2 : own; s += vlast[v] ? own : o2;       // ascending check order (regular_own.h)
+                        } else {
 #pragma unroll
-                        for (int d = 0; d < VDEG; d++) s += Rl[voff[v][d]];                    // kernels.py:316, ascending check order
+                            for (int d = 0; d < VDEG; d++) s += Rl[voff[v][d]];                // kernels.py:316, ascending check order
+                        }
                         const double xv = s + vprior[v];                                       // kernels.py:320
                         Vl[vj[v]] = xv;
+                        Vown[v] = xv;
                     }
             }
             __syncthreads();
@@ -371,24 +406,30 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 double x[CDEG];
                 unsigned ph = synw;
 #pragma unroll
-                for (int k = 0; k < CDEG; k++) x[k] = Vl[coff[k]];
+                for (int k = 0; k < CDEG; k++) x[k] = (OWN && k < NOWN) ? Vown[k] : Vl[coff[k]];
 #pragma unroll
                 for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(x[k]);               // kernels.py:349,356
                 parity |= ph;
-                clean_messages<CDEG>(x, Rprev, true, Al[it], clip, synw, Rl + roff);
+                clean_messages<CDEG, NOWN>(x, Rprev, true, Al[it], clip, synw, Rl + roff);
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(1);                                                     // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
                 double r[2][VDEG];
 #pragma unroll
                 for (int v = 0; v < 2; v++)
 #pragma unroll
-                    for (int d = 0; d < VDEG; d++) r[v][d] = Rl[voff[v][d]];
+                    for (int d = 0; d < VDEG - (OWN ? 1 : 0); d++) r[v][d] = Rl[voff[v][d]];
 #pragma unroll
                 for (int v = 0; v < 2; v++) {
+                    if (OWN) {                                                                     // r[v] = the three messages in ascending check order (regular_own.h)
+                        const double o2 = r[v][1], own = Rprev[v];
+                        r[v][1] = vlast[v] ? o2 : own;
+                        r[v][2] = vlast[v] ? own : o2;
+                    }
                     double s = 0.0;                                                                // kernels.py:279
 #pragma unroll
                     for (int d = 0; d < VDEG; d++) s += r[v][d];                                   // kernels.py:316, ascending check order
-                    Vl[vj[v]] = s + vprior[v];                                                     // kernels.py:320
+                    Vown[v] = s + vprior[v];                                                       // kernels.py:320
+                    Vl[vj[v]] = Vown[v];
                 }
                 __builtin_amdgcn_s_setprio(0);
                 __syncthreads();
@@ -419,9 +460,9 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     for (int v = 0; v < 2; v++)
                         if (has_var[v]) {
                             const double xo = (max_iter >= 1) ? Vl[vj[v]] : 0.0;
-                            C.f_llr[(int64_t)f * n + vj[v]] = xo;
-                            C.f_hard[(int64_t)f * n + vj[v]] = (xo < 0.0) ? 1 : 0;
-                            C.f_err[(int64_t)f * n + vj[v]] = (int8_t)Eb[vj[v]];
+                            C.f_llr[(int64_t)f * n + vcol(v)] = xo;
+                            C.f_hard[(int64_t)f * n + vcol(v)] = (xo < 0.0) ? 1 : 0;
+                            C.f_err[(int64_t)f * n + vcol(v)] = (int8_t)Eb[vcol(v)];
                         }
                 }
                 __syncthreads();
@@ -493,6 +534,8 @@ __global__ __launch_bounds__(256) void cc_judge_failed_kernel(int32_t *__restric
 // RegPlan and the carve itself: regular_plan.h (host arithmetic only)
 static int g_list_shots = 0;          // qldpc_set_option("mc_list_shots"): shots per workgroup of the shot-list launch (0 = as the full launch)
 void regular_set_list_shots(int s) { g_list_shots = s; }
+static std::atomic<int> g_own_edges{1};   // qldpc_set_option("regular_own_edges"): 1 = the clean (6,3) form keeps two edges of each check inside its thread (regular_own.h)
+void regular_set_own_edges(int v) { g_own_edges = v; }
 
 static bool plan_regular(const qldpc_graph *g, int max_iter, RegPlan &P, int force_S = 0) {
     if (g->m <= 0 || g->n <= 0) return false;
@@ -513,6 +556,13 @@ static int launch_reg2(const RegArgs &A, bool damp, bool nanfree, unsigned grid,
         if (MC) return QLDPC_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, true, false, false, FIXED>), dim3(grid), dim3(block), lds, stream, A);
     } else if (nanfree && A.clip > 0.0) {             // the clean form folds the clip into its two chain seeds: exact for clip > 0 only (inputs_clean() has checked it; kept next to the launch)
+        if constexpr (CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg) {
+            if (A.own) {
+                hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, true, MC, FIXED, true>), dim3(grid), dim3(block), lds, stream, A);
+                QLDPC_HIP_TRY(hipGetLastError());
+                return QLDPC_OK;
+            }
+        }
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, true, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
     } else {
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, false, MC, FIXED>), dim3(grid), dim3(block), lds, stream, A);
@@ -540,6 +590,7 @@ static void fill_common(const qldpc_graph *g, const RegPlan &P, RegArgs &A, int6
     A.m = g->m; A.n = g->n; A.max_iter = max_iter; A.fixed = (flags & QLDPC_FLAG_FIXED_ITERS) ? 1 : 0;
     A.S = P.S; A.TS = P.TS;
     A.indptr = g->d_indptr; A.indices = g->d_indices; A.colptr = g->d_colptr; A.rowidx = g->d_rowidx; A.csc2csr = g->d_csc2csr;
+    A.own = (g_own_edges.load() && P.cdeg == kRegOwnCdeg) ? g->d_regown : nullptr;      // NULL too where the graph has no assignment (graph.hip)
     A.B = B; A.prior = d_prior; A.alpha = d_alpha; A.damping = damping; A.clip = clip;
     A.offV = P.offV; A.offE = P.offE; A.offL = P.offL; A.offI = P.offI; A.offA = P.offA; A.offT = P.offT; A.offD = P.offD;
 }

@@ -3,7 +3,7 @@
 weighted with (a wave64 32-bit VALU instruction issues in 2 cycles, an f64 one in 4; tools/microbench/issue_rate.hip
 measures the classes on the box, profiles/r03_issue_rate.txt).
 
-    python tools/isa_mix.py minsum_regular.hip 'minsum_regular_kernel<6, 3, false, true, true, true>' [--loop N] [--json]
+    python tools/isa_mix.py minsum_regular.hip 'minsum_regular_kernel<6, 3, false, true, true, true, true>' [--loop N] [--json]
 
 Compiles csrc/<file> to assembly for gfx950 with the product flags (hipcc --cuda-device-only -S, a few seconds, no GPU needed), finds
 the kernel by its demangled name (substring match), splits the body into natural loops (a label that a later branch jumps back to) and
@@ -286,9 +286,10 @@ def analyse(src, pattern, loop_pick=None):
 # bookkeeping has more instructions and runs a pass or two), "whole" = the whole kernel body (kernels whose time is spread over many loops), the files whose text fixes the instruction stream: the .hip file and every device header it reaches through #include "..." -- csrc/launchers.h,
 # csrc/common.h and include/qldpc_hip.h hold nothing a kernel reads and are in no list.  osd_plan.h is host planning code, listed because the
 # OSD kernels name its block and chunk constants.
-_REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h"]
+_REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h", "regular_own.h"]      # regular_own.h: host code, listed for the record layout the kernel indexes with
 RECORDED = {
-    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true>", "straight", _REGULAR),
+    # the seventh argument: OWN, two edges of each check inside its thread (the form bench.py's bb144 graph takes by default)
+    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true, true>", "straight", _REGULAR),
     "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "clocks.h", "mc_common.h"]),
     "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<true>", "whole", ["minsum_wg2.hip", "clocks.h", "minsum_f64.h"]),      # <true>: the shipped circ144 matrices have degree-1 checks
     "circ144_osd": ("osd_gj.hip", "osd0_gj_kernel<true>", "whole", ["osd_gj.hip", "osd_gj.h", "osd_common.h", "clocks.h", "osd_plan.h"]),

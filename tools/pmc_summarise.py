@@ -18,7 +18,7 @@ from isa_mix import RECORDED, RECORDED_ALSO, ROOT, digest  # noqa: E402  (the fi
 
 
 def regular_args(kernel_name):
-    """template arguments of minsum_regular_kernel<CDEG, VDEG, DAMP, NANFREE, MC, FIXED> as strings, or None"""
+    """template arguments of minsum_regular_kernel<CDEG, VDEG, DAMP, NANFREE, MC, FIXED, OWN> as strings, or None"""
     import re
     mt = re.search(r"minsum_regular_kernel<([^>]*)>", kernel_name)
     return [x.strip() for x in mt.group(1).split(",")] if mt else None
