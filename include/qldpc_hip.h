@@ -146,6 +146,8 @@ int qldpc_device_count(void);
  *   "mc_list_shots"       shots per workgroup of the full decoder on listed shots: 0 (default: the kernel's own 7), 1 .. 16
  *   "regular_own_edges"   read at a launch of the regular min-sum kernel: 1 (default) = on clean inputs and a (6,3)-regular graph the thread of a check is the
  *                         variable thread of two of its own columns (csrc/regular_own.h), 0 = the body without ownership on every graph
+ *   "regular_own_search"  read by qldpc_graph_create: 1 (default) = of the valid assignments of those columns the one whose gathers the LDS bank model of
+ *                         csrc/regular_own.h prices lowest, 0 = the first matching found
  *   "regular_kernel", "wave_cpl", "wave_rst", "wave_grid"  experiments build only: the wave-private decoder (csrc/minsum_wave.hip); the
  *                         product library accepts 0 and answers anything else with QLDPC_ERR_UNSUPPORTED */
 int qldpc_set_option(const char *name, int value);

@@ -175,7 +175,8 @@ def device_count():
 
 
 def set_option(name, value):
-    """Process-wide kernel-selection switch (include/qldpc_hip.h: qldpc_set_option); results never depend on it."""
+    """Process-wide kernel-selection switch (include/qldpc_hip.h: qldpc_set_option); results never depend on it.
+    Most are read at a launch or at plan creation; "regular_own_search" is read when a Graph is created, so set it before the handle is made."""
     check(lib().qldpc_set_option(name.encode(), int(value)))
 
 

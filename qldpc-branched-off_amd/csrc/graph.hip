@@ -276,9 +276,10 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         if (rc == QLDPC_OK) rc = upload(&g->d_identity, ident);
     }
     if (rc == QLDPC_OK && g->max_row_deg == kRegOwnCdeg && g->max_col_deg == kRegOwnVdeg && n == 2 * m && m <= 1024) {
-        // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL)
+        // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL).
+        // Which valid assignment it is changes LDS bank conflicts only, never a result ("regular_own_search", options.hip).
         std::vector<int32_t> own;
-        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own)) rc = upload(&g->d_regown, own);
+        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) rc = upload(&g->d_regown, own);
     }
     if (rc != QLDPC_OK) { qldpc_graph_destroy(g); return rc; }
     *out = g;

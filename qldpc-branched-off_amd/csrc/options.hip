@@ -7,7 +7,8 @@
 
 namespace qldpc {
 
-static std::atomic<int> g_opt_kernel{0}, g_opt_first{1}, g_opt_tail{1}, g_opt_presort{-1};
+static std::atomic<int> g_opt_kernel{0}, g_opt_first{1}, g_opt_tail{1}, g_opt_presort{-1}, g_opt_own_search{1};
+int regular_own_search_choice() { return g_opt_own_search.load(); }
 int osd_presort_choice() { return g_opt_presort.load(); }
 int wave_kernel_choice() { return g_opt_kernel.load(); }
 int mc_first_choice() { return g_opt_first.load(); }
@@ -28,6 +29,8 @@ extern std::atomic<int> g_opt_wave_cpl, g_opt_wave_rst, g_opt_wave_grid;      //
 //                         chunks of 1024; the columns behind are ordered only if a sweep gets there; 0 = the whole order up front); tests/ use 0 and short heads on purpose
 //   "regular_own_edges"   read at a launch of the regular min-sum kernel: 1 (default) = on a clean (6,3) graph that has an assignment (regular_own.h) the thread of a
 //                         check is the variable thread of two of its own columns, 0 = the body without ownership on every graph
+//   "regular_own_search"  read when a graph handle is created: 1 (default) = of the valid ownership assignments the one the LDS bank model prices lowest
+//                         (regular_own.h: translation-invariant candidates, else a polished matching), 0 = the first matching found
 // experiments build only (libqldpc_hip_experiments.so):
 //   "regular_kernel"      0 / 1 = the 72-thread-team kernel (minsum_regular.hip), 2 = the wave-private kernel (minsum_wave.hip) where eligible
 //   "wave_cpl" / "wave_rst" / "wave_grid"  its checks per lane (0 = automatic, 4, 5, 6, 9), message-row stride in doubles (0, 6, 7), waves per CU (0 .. 32)
@@ -39,6 +42,7 @@ QLDPC_EXPORT int qldpc_set_option(const char *name, int value) {
     if (!std::strcmp(name, "osd_presort")) { QLDPC_REQUIRE(value >= -1 && value <= 65535, "osd_presort: -1 .. 65535"); qldpc::g_opt_presort = value; return QLDPC_OK; }
     if (!std::strcmp(name, "mc_big_lanes")) { QLDPC_REQUIRE(value >= 2 && value <= 8, "mc_big_lanes: 2 .. 8"); qldpc::mc_set_big_lanes(value); return QLDPC_OK; }
     if (!std::strcmp(name, "mc_list_shots")) { QLDPC_REQUIRE(value >= 0 && value <= 16, "mc_list_shots: 0 .. 16"); qldpc::regular_set_list_shots(value); return QLDPC_OK; }
+    if (!std::strcmp(name, "regular_own_search")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_own_search: 0 or 1"); qldpc::g_opt_own_search = value; return QLDPC_OK; }
     if (!std::strcmp(name, "regular_own_edges")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_own_edges: 0 or 1"); qldpc::regular_set_own_edges(value); return QLDPC_OK; }
     const bool wave_opt =!std::strcmp(name, "regular_kernel") || !std::strcmp(name, "wave_cpl") || !std::strcmp(name, "wave_rst") || !std::strcmp(name, "wave_grid");
 #ifdef QLDPC_EXPERIMENTS
