@@ -262,8 +262,13 @@ int qldpc_relay_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *
  *   7. max_rounds = 0 is qldpc_relay_decode_batch(max_legs = 0, gamma0 = 0, t0 = t_round) bit for bit: constant-alpha min-sum.
  * A frozen column is not immune: its marginal is s_j +- fix_llr, and |s_j| <= (column degree) * alpha * clip_llr on a graph without
  * degree-1 checks, so fix_llr above that bound keeps its hard decision for good.
- * QLDPC_ERR_UNSUPPORTED under Relay-BP's conditions (a row degree above 56, a check state that does not fit in LDS); QLDPC_ERR_INVALID
- * for the arguments above.  Results depend only on the inputs: not on batch splits, the grid or the order of the shots. */
+ * QLDPC_ERR_UNSUPPORTED for a graph Relay-BP refuses (a row degree above 56, no slot tables, its own LDS count) and for one whose state does
+ * not fit in 160 KB of LDS by BPGD's own count: 24 bytes per check, two bit planes (fixed, sign) of ceil(n / 32) 32-bit words, each padded to
+ * 16 bytes, 16 bytes of flags and 384 bytes of per-wave selection candidates; 8 bytes per column on top keep the posteriors in LDS, else
+ * they live in global memory.  Relay-BP counts 2 bytes per column (its memory draws, n rounded up to 4) and 32 bytes of flags in place of the
+ * planes and candidates, so the two counts differ in either direction: at m = 300 BPGD keeps the posteriors in LDS up to n = 18938,
+ * Relay-BP up to n = 15660; at n = 64 BPGD accepts m <= 6808, Relay-BP m <= 6820.  QLDPC_ERR_INVALID for the arguments above.  Results
+ * depend only on the inputs: not on batch splits, the grid or the order of the shots. */
 int qldpc_decim_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior, double alpha, double clip_llr,
                              int t_round, int max_rounds, int per_round, double fix_llr, int8_t *err, double *llr, uint8_t *conv,
                              int32_t *iters, int32_t *rounds, int32_t *fixed);
