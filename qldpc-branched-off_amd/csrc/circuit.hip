@@ -281,31 +281,26 @@ static int build_signatures(const qldpc_circuit_desc *D, int sector, std::vector
             lane_q[e] = (s == 0) ? D->base_q1[l] : (op == C_OP_CNOT ? D->base_q2[l] : -1);
         }
     }
-    DevTmp dpos, dafter, dq, dops, dq1, dq2, dstate, dhist;
-    int rc;
     const size_t len = ops.size();
-    if ((rc = dpos.alloc(nl * 4)) || (rc = dafter.alloc(nl)) || (rc = dq.alloc(nl * 4)) || (rc = dops.alloc(len * 4)) || (rc = dq1.alloc(len * 4)) ||
-        (rc = dq2.alloc(len * 4)) || (rc = dstate.alloc((size_t)tq * nl)) || (rc = dhist.alloc((size_t)nsyn * nl)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(dpos.p, lane_pos.data(), nl * 4, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dafter.p, lane_after.data(), nl, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dq.p, lane_q.data(), nl * 4, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dops.p, ops.data(), len * 4, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dq1.p, q1.data(), len * 4, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dq2.p, q2.data(), len * 4, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(zero_now(dhist.p, (size_t)nsyn * nl));
+    std::vector<int8_t> hist((size_t)nsyn * nl), state((size_t)tq * nl);
+    HostStage S;
+    const auto dpos = S.in(lane_pos.data(), nl);
+    const auto dafter = S.in(lane_after.data(), nl);
+    const auto dq = S.in(lane_q.data(), nl);
+    const auto dops = S.in(ops.data(), len), dq1 = S.in(q1.data(), len), dq2 = S.in(q2.data(), len);
+    const auto dstate = S.out(state.data(), tq, nl);
+    const auto dhist = S.out_zeroed(hist.data(), nsyn, nl);
+    int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     const unsigned grid = (unsigned)((nl + 255) / 256);
     if (sector)
-        hipLaunchKernelGGL(fault_signature_kernel<true>, dim3(grid), dim3(256), 0, nullptr, nl, dpos.as<int32_t>(), dafter.as<int8_t>(), dq.as<int32_t>(),
-                           (int64_t)len, dops.as<int32_t>(), dq1.as<int32_t>(), dq2.as<int32_t>(), tq, nsyn, dstate.as<int8_t>(), dhist.as<int8_t>());
+        hipLaunchKernelGGL(fault_signature_kernel<true>, dim3(grid), dim3(256), 0, nullptr, nl, S[dpos], S[dafter], S[dq], (int64_t)len, S[dops], S[dq1],
+                           S[dq2], tq, nsyn, S[dstate], S[dhist]);
     else
-        hipLaunchKernelGGL(fault_signature_kernel<false>, dim3(grid), dim3(256), 0, nullptr, nl, dpos.as<int32_t>(), dafter.as<int8_t>(), dq.as<int32_t>(),
-                           (int64_t)len, dops.as<int32_t>(), dq1.as<int32_t>(), dq2.as<int32_t>(), tq, nsyn, dstate.as<int8_t>(), dhist.as<int8_t>());
+        hipLaunchKernelGGL(fault_signature_kernel<false>, dim3(grid), dim3(256), 0, nullptr, nl, S[dpos], S[dafter], S[dq], (int64_t)len, S[dops], S[dq1],
+                           S[dq2], tq, nsyn, S[dstate], S[dhist]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    std::vector<int8_t> hist((size_t)nsyn * nl), state((size_t)tq * nl);
-    QLDPC_HIP_TRY(hipMemcpy(hist.data(), dhist.p, hist.size(), hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(state.data(), dstate.p, state.size(), hipMemcpyDeviceToHost));
+    if ((rc = S.finish("fault signature kernel", HostStage::kDevice)) != QLDPC_OK) return rc;
     // detectors = XOR of consecutive RAW measurements of the same check (sparsify_syndrome_jit, kernels.py:356-380)
     ptr.assign(nl + 1, 0); idx.clear(); logm.assign(nl, 0);
     std::vector<int32_t> prev(nsyn, -1);
@@ -590,7 +585,7 @@ static JudgeSector judge_view(const Sector &S) {
 // one pass over [trial_begin, trial_begin + count); `outcome` (host, may be NULL) receives bit0 = z_err, bit1 = x_err per trial
 static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, hipStream_t s, uint8_t *outcome) {
     QLDPC_USE_DEVICE(P->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     if (outcome && (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK) return rc;
     const bool two = P->nsec == 2;
     const JudgeSector Z = judge_view(P->sec[0]), X = two ? judge_view(P->sec[1]) : JudgeSector{};
@@ -639,7 +634,6 @@ QLDPC_EXPORT int qldpc_circuit_plan_run_outcomes(qldpc_circuit_plan *P, uint64_t
 QLDPC_EXPORT int qldpc_circuit_plan_read(qldpc_circuit_plan *P, void *stream, int clear, int64_t *tally) {
     QLDPC_REQUIRE(P != nullptr && tally != nullptr, "NULL argument");
     QLDPC_USE_DEVICE(P->device);
-    int rc = QLDPC_OK; (void)rc;
     QLDPC_HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     drain_phases(P, true);                                           // everything enqueued has finished: fold the brackets, recycle their events
     QLDPC_HIP_TRY(hipMemcpy(tally, P->d_tally.p, QLDPC_TALLY_SLOTS * 8, hipMemcpyDeviceToHost));
@@ -654,7 +648,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed,
     QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
     QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && (P->nsec == 1 || (sparse_x && true_x))), "NULL output");
     QLDPC_USE_DEVICE(P->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
     std::vector<unsigned long long> t;
     for (int64_t off = 0; off < count; off += P->batch) {

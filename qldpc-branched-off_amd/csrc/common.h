@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/qldpc_hip.h"
+#include "stage_layout.h"
 
 #define QLDPC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -74,19 +75,6 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// RAII temporary device allocation for the host-pointer entry points.
-struct DevTmp {
-    void *p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (bytes == 0) bytes = 16;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); p = nullptr; return QLDPC_ERR_HIP; }
-        return QLDPC_OK;
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 
 // Replaces the contents of a device buffer with a host vector (synchronous copy; an empty vector still leaves an allocation).
@@ -98,15 +86,57 @@ int upload(DevBuf &b, const std::vector<T> &v) {
     return QLDPC_OK;
 }
 
-// Regions of one device slab (the host-pointer entry points' ws_io): add() hands out 16-aligned offsets in order, ensure() sizes the
-// buffer for all of them, at() is a region's address afterwards.
-struct IoSlab {
-    size_t total = 0;
-    unsigned char *base = nullptr;
-    size_t add(size_t bytes) { const size_t o = total; total += (size_t)round_up((int64_t)bytes, 16); return o; }
-    int ensure(DevBuf &b) { const int rc = b.ensure(total); base = b.as<unsigned char>(); return rc; }
-    template <class T = unsigned char> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+// Device staging of one host-pointer entry point.  A call declares its regions, stage() carves ONE allocation for all of them (stage_layout.h: 256-byte
+// aligned, an address even for an empty region), uploads the inputs and zeroes what asked for it (zero_now), the call launches on the null stream under
+// the lock it needs, and finish() waits and downloads every output that has a host pointer.  A declaration returns a typed handle: S[handle] is the
+// region's device address after stage(), and the default handle stands for "no such buffer" (NULL).  Dimensions multiply to the element count; a byte
+// count that does not fit size_t, a negative dimension or more than StageLayout::kMaxRegions regions make stage() fail with QLDPC_ERR_INVALID.
+// Two backings.  HostStage S;                        one temporary allocation, freed with S.
+//                HostStage S(g->ws_io, g->mu_io);    the regions live in a grow-only slab that stays allocated between calls; S holds the mutex.
+template <class T> struct Staged { int id = -1; };
+class HostStage {
+  public:
+    // kCopies: the blocking downloads are the wait (they run behind the null stream's work); kStream: hipStreamSynchronize(nullptr) first;
+    // kDevice: hipDeviceSynchronize() first -- a launcher may use streams the null stream is not ordered against
+    enum Wait { kCopies, kStream, kDevice };
+    HostStage() = default;
+    HostStage(DevBuf &slab, std::mutex &mu) : slab_(&slab), lock_(mu) {}
+    ~HostStage() { if (!slab_ && base_) (void)hipFree(base_); }
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+
+    template <class T, class... N> Staged<T> in(const T *host, N... dims) { return {add(host, nullptr, false, sizeof(T), {(int64_t)dims...})}; }
+    template <class T, class... N> Staged<T> out(T *host, N... dims) { return {add(nullptr, host, false, sizeof(T), {(int64_t)dims...})}; }          // host == NULL: stays on the device
+    template <class T, class... N> Staged<T> out_zeroed(T *host, N... dims) { return {add(nullptr, host, true, sizeof(T), {(int64_t)dims...})}; }
+    template <class T, class... N> Staged<T> inout(const T *from, T *to, N... dims) { return {add(from, to, false, sizeof(T), {(int64_t)dims...})}; }
+    template <class T, class... N> Staged<T> scratch(N... dims) { return {add(nullptr, nullptr, false, sizeof(T), {(int64_t)dims...})}; }
+    template <class T, class... N> Staged<T> zeroed(N... dims) { return {add(nullptr, nullptr, true, sizeof(T), {(int64_t)dims...})}; }
+    template <class T> T *operator[](Staged<T> h) const { return h.id < 0 ? nullptr : reinterpret_cast<T *>(base_ + layout_.regions[h.id].off); }
+
+    int stage();
+    int finish(const char *what, Wait wait);        // a failed wait: "<what> failed: <hip error string>"
+    // finish() for a latency-bound call: outputs of at most 1 MiB come back in ONE copy through the pinned buffer (grown here) and are scattered on the host
+    int finish_pinned(const char *what, void *&pin, size_t &pin_cap);
+    // one region into a host array, for an output that the call downloads only once it has looked at another (declared as scratch)
+    template <class T> int fetch(Staged<T> h, T *host) const { return fetch_bytes(h.id, host); }
+
+  private:
+    int fetch_bytes(int id, void *host) const;
+    struct Copy { const void *in; void *out; bool zero; };
+    int add(const void *in, void *out, bool zero, size_t elem, std::initializer_list<int64_t> dims) {
+        const int id = layout_.add(dims, elem);
+        if (id >= 0) copies_[id] = {in, out, zero};
+        return id;
+    }
+    StageLayout layout_;
+    Copy copies_[StageLayout::kMaxRegions];
+    DevBuf *slab_ = nullptr;
+    std::unique_lock<std::mutex> lock_;
+    unsigned char *base_ = nullptr;
 };
+
+// The call checks shared by the decoder objects whose outputs are (err, llr, conv, iter): layered and f32.
+int decoder_check_call(const void *decoder, int64_t B, const void *synd, const void *err, const void *llr, const void *conv, const void *iter);
 
 // Compute units of a device (256 when the runtime does not say): what the persistent grids are sized by.
 int cu_count(int device);
@@ -123,10 +153,6 @@ struct StreamHandover {
     void destroy();
 };
 
-// The host-pointer entry of the decoders whose outputs are (err, llr, conv, iter): temporary device buffers, syndromes in, launch(d_synd,
-// d_err, d_llr, d_conv, d_iter) on the null stream under `mu`, wait, results out.  `what` names the decoder in the error text.
-int decode_batch_via_device(std::mutex &mu, const char *what, int64_t B, int m, int n, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
-                            int32_t *iter, const std::function<int(const int8_t *, int8_t *, double *, uint8_t *, int32_t *)> &launch);
 // clocks.h: what the shader-clock probe stamped
 double clock_probe_median(const unsigned long long *pairs, int slots);   // MHz; 0 when nothing was stamped
 

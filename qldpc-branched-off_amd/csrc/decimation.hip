@@ -230,25 +230,19 @@ QLDPC_EXPORT int qldpc_decim_decode_batch(const qldpc_graph *g, int64_t B, const
     for (size_t j = 0; j < n; j++) QLDPC_REQUIRE(std::isfinite(prior[j]), "prior[%zu] is not finite", j);
     QLDPC_USE_DEVICE(g->device);
     if (!decim_supported(g)) return decim_unsupported(g);
-    // one grow-only slab per graph handle:  prior | llr (when asked for) | syndromes | err | conv | iters | rounds | fixed
-    IoSlab S;
-    const size_t o_prior = S.add(n * 8), o_llr = S.add(llr ? B * n * 8 : 0), o_synd = S.add(B * m), o_err = S.add(B * n), o_conv = S.add(B),
-                 o_iters = S.add(B * 4), o_rounds = S.add(B * 4), o_fixed = S.add(B * 4);
-    std::unique_lock<std::mutex> io(g->mu_io);
-    if ((rc = S.ensure(g->ws_io)) != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_synd), syndromes, B * m, hipMemcpyHostToDevice, nullptr));
-    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_prior), prior, n * 8, hipMemcpyHostToDevice, nullptr));
+    HostStage S(g->ws_io, g->mu_io);          // the graph handle's grow-only slab
+    const auto dp = S.in(prior, n);
+    const auto dl = llr ? S.out(llr, B, n) : Staged<double>{};        // not asked for: the launch gets NULL
+    const auto ds = S.in(syndromes, B, m);
+    const auto de = S.out(err, B, n);
+    const auto dc = S.out(conv, B);
+    const auto di = S.out(iters, B);
+    const auto dr = S.out(rounds, B);           // rounds, fixed: NULL stays on the device
+    const auto df = S.out(fixed, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = decim_decode_launch(g, B, S.at<int8_t>(o_synd), S.at<double>(o_prior), P, 0, S.at<int8_t>(o_err), llr ? S.at<double>(o_llr) : nullptr,
-                                 S.at<uint8_t>(o_conv), S.at<int32_t>(o_iters), S.at<int32_t>(o_rounds), S.at<int32_t>(o_fixed), nullptr);
+        rc = decim_decode_launch(g, B, S[ds], S[dp], P, 0, S[de], S[dl], S[dc], S[di], S[dr], S[df], nullptr);
     }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, S.at(o_err), B * n, hipMemcpyDeviceToHost));
-    if (llr) QLDPC_HIP_TRY(hipMemcpy(llr, S.at(o_llr), B * n * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, S.at(o_conv), B, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iters, S.at(o_iters), B * 4, hipMemcpyDeviceToHost));
-    if (rounds) QLDPC_HIP_TRY(hipMemcpy(rounds, S.at(o_rounds), B * 4, hipMemcpyDeviceToHost));
-    if (fixed) QLDPC_HIP_TRY(hipMemcpy(fixed, S.at(o_fixed), B * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return rc != QLDPC_OK ? rc : S.finish("decimation decode", HostStage::kCopies);
 }

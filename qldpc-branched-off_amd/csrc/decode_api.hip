@@ -192,45 +192,20 @@ QLDPC_EXPORT int qldpc_minsum_decode_batch(const qldpc_graph *g, int64_t B, cons
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(g->device);
     if (B == 0) return QLDPC_OK;
-    const size_t m = g->m, n = g->n;
-    // One grow-only device slab per graph handle (no hipMalloc / hipFree per call: the reference-style single-shot call is
-    // latency bound) laid out as  prior | syndromes | llr | iter | err | conv ; small results return in ONE copy through a
-    // pinned staging buffer, large ones directly into the caller's arrays.
-    const size_t o_prior = 0, o_synd = o_prior + round_up((int64_t)n * 8, 16), o_llr = o_synd + round_up((int64_t)B * m, 16),
-                 o_iter = o_llr + round_up((int64_t)B * n * 8, 16), o_err = o_iter + round_up((int64_t)B * 4, 16),
-                 o_conv = o_err + round_up((int64_t)B * n, 16), total = o_conv + round_up(B, 16);
-    std::unique_lock<std::mutex> io(g->mu_io);
-    if ((rc = g->ws_io.ensure(total)) != QLDPC_OK) return rc;
-    unsigned char *base = g->ws_io.as<unsigned char>();
-    if (m) QLDPC_HIP_TRY(hipMemcpyAsync(base + o_synd, syndromes, B * m, hipMemcpyHostToDevice, nullptr));
-    if (n) QLDPC_HIP_TRY(hipMemcpyAsync(base + o_prior, prior, n * 8, hipMemcpyHostToDevice, nullptr));
+    // The graph handle's grow-only slab (no hipMalloc / hipFree per call: the reference-style single-shot call is latency bound); small results
+    // return in ONE copy through the handle's pinned staging buffer, large ones directly into the caller's arrays.
+    HostStage S(g->ws_io, g->mu_io);
+    const auto dp = S.in(prior, g->n);
+    const auto ds = S.in(syndromes, B, g->m);
+    const auto dl = S.out(out_llr, B, g->n);
+    const auto di = S.out(out_iter, B);
+    const auto de = S.out(out_err, B, g->n);
+    const auto dc = S.out(out_conv, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
     bool prior_finite, prior_le_clip;
-    host_prior_facts(prior, n, clip_llr, prior_finite, prior_le_clip);
-    rc = decode_dev_impl(g, B, reinterpret_cast<int8_t *>(base + o_synd), reinterpret_cast<double *>(base + o_prior), max_iter, alpha_mode,
-                         alpha_val, alpha_seq, alpha_len, damping, clip_llr, flags, prior_finite, prior_le_clip, reinterpret_cast<int8_t *>(base + o_err),
-                         reinterpret_cast<double *>(base + o_llr), reinterpret_cast<uint8_t *>(base + o_conv),
-                         reinterpret_cast<int32_t *>(base + o_iter), nullptr, prior);
+    host_prior_facts(prior, (size_t)g->n, clip_llr, prior_finite, prior_le_clip);
+    rc = decode_dev_impl(g, B, S[ds], S[dp], max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, damping, clip_llr, flags, prior_finite, prior_le_clip,
+                         S[de], S[dl], S[dc], S[di], nullptr, prior);
     if (rc != QLDPC_OK) return rc;
-    const size_t out_bytes = total - o_llr;
-    if (out_bytes <= ((size_t)1 << 20) && out_llr) {
-        if (g->pin_cap < out_bytes) {
-            if (g->pin) (void)hipHostFree(g->pin);
-            g->pin = nullptr; g->pin_cap = 0;
-            QLDPC_HIP_TRY(hipHostMalloc(&g->pin, (size_t)1 << 20, hipHostMallocDefault));
-            g->pin_cap = (size_t)1 << 20;
-        }
-        QLDPC_HIP_TRY(hipMemcpyAsync(g->pin, base + o_llr, out_bytes, hipMemcpyDeviceToHost, nullptr));
-        QLDPC_HIP_TRY(hipStreamSynchronize(nullptr));
-        const unsigned char *h = static_cast<const unsigned char *>(g->pin);
-        if (n) std::memcpy(out_llr, h, B * n * 8);
-        std::memcpy(out_iter, h + (o_iter - o_llr), B * 4);
-        if (n) std::memcpy(out_err, h + (o_err - o_llr), B * n);
-        std::memcpy(out_conv, h + (o_conv - o_llr), B);
-    } else {
-        if (n && out_llr) QLDPC_HIP_TRY(hipMemcpy(out_llr, base + o_llr, B * n * 8, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(out_iter, base + o_iter, B * 4, hipMemcpyDeviceToHost));
-        if (n) QLDPC_HIP_TRY(hipMemcpy(out_err, base + o_err, B * n, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(out_conv, base + o_conv, B, hipMemcpyDeviceToHost));
-    }
-    return QLDPC_OK;
+    return out_llr ? S.finish_pinned("min-sum decode", g->pin, g->pin_cap) : S.finish("min-sum decode", HostStage::kCopies);
 }

@@ -436,7 +436,6 @@ QLDPC_EXPORT int qldpc_gf2_eliminate_packed(int64_t B, int m, int n, int nwords,
     QLDPC_REQUIRE(B >= 0 && m >= 0 && n >= 0, "negative size");
     QLDPC_REQUIRE(nwords * 64 >= n, "nwords=%d too small for n=%d", nwords, n);
     QLDPC_USE_DEVICE(0);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE(num_pivots != nullptr, "num_pivots is NULL");
     if (m == 0 || n == 0) { for (int64_t i = 0; i < B; i++) num_pivots[i] = 0; return QLDPC_OK; }
@@ -444,24 +443,18 @@ QLDPC_EXPORT int qldpc_gf2_eliminate_packed(int64_t B, int m, int n, int nwords,
     const int maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
     QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
-    DevTmp dA, db, dpr, dpc, dn;
-    if ((rc = dA.alloc((size_t)B * m * nwords * 8)) || (rc = db.alloc((size_t)B * m)) || (rc = dpr.alloc((size_t)B * maxp * 8)) ||
-        (rc = dpc.alloc((size_t)B * maxp * 8)) || (rc = dn.alloc((size_t)B * 4)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(dA.p, A, (size_t)B * m * nwords * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(db.p, b, (size_t)B * m, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(zero_now(dpr.p, (size_t)B * maxp * 8));
-    QLDPC_HIP_TRY(zero_now(dpc.p, (size_t)B * maxp * 8));
-    hipLaunchKernelGGL(gf2_eliminate_packed_kernel, dim3((unsigned)B), dim3(m >= 512 ? 1024 : 256), lds, nullptr, m, n, nwords,
-                       dA.as<uint64_t>(), db.as<uint8_t>(), dpr.as<int64_t>(), dpc.as<int64_t>(), dn.as<int32_t>());
+    HostStage S;
+    const auto dA = S.inout(A, A, B, m, nwords);
+    const auto db = S.inout(b, b, B, m);
+    const auto dpr = S.out_zeroed(pivot_rows, B, maxp);
+    const auto dpc = S.out_zeroed(pivot_cols, B, maxp);
+    const auto dn = S.out(num_pivots, B);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
+    hipLaunchKernelGGL(gf2_eliminate_packed_kernel, dim3((unsigned)B), dim3(m >= 512 ? 1024 : 256), lds, nullptr, m, n, nwords, S[dA], S[db], S[dpr],
+                       S[dpc], S[dn]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(A, dA.p, (size_t)B * m * nwords * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(b, db.p, (size_t)B * m, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(pivot_rows, dpr.p, (size_t)B * maxp * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(pivot_cols, dpc.p, (size_t)B * maxp * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(num_pivots, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("GF(2) elimination", HostStage::kDevice);
 }
 
 // a7: the byte-matrix elimination (kernels.py:5-34) is the same algorithm on one element per byte; it is run as
@@ -470,7 +463,6 @@ QLDPC_EXPORT int qldpc_gf2_eliminate(int64_t B, int m, int n, uint8_t *A, uint8_
                                      int32_t *num_pivots) {
     QLDPC_REQUIRE(B >= 0 && m >= 0 && n >= 0, "negative size");
     QLDPC_USE_DEVICE(0);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE(num_pivots != nullptr, "num_pivots is NULL");
     if (m == 0 || n == 0) { for (int64_t i = 0; i < B; i++) num_pivots[i] = 0; return QLDPC_OK; }
@@ -478,29 +470,22 @@ QLDPC_EXPORT int qldpc_gf2_eliminate(int64_t B, int m, int n, uint8_t *A, uint8_
     const int nwords = ((n + 7) / 8 + 7) / 8, maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
     QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
-    DevTmp dA8, dA, db, dpr, dpc, dn;
+    HostStage S;
+    const auto dA8 = S.inout(A, A, B, m, n);
+    const auto dA = S.scratch<uint64_t>(B, m, nwords);
+    const auto db = S.inout(b, b, B, m);
+    const auto dpr = S.out_zeroed(pivot_rows, B, maxp);
+    const auto dpc = S.out_zeroed(pivot_cols, B, maxp);
+    const auto dn = S.out(num_pivots, B);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     const int64_t rows = B * m;
-    if ((rc = dA8.alloc((size_t)rows * n)) || (rc = dA.alloc((size_t)rows * nwords * 8)) || (rc = db.alloc((size_t)rows)) ||
-        (rc = dpr.alloc((size_t)B * maxp * 8)) || (rc = dpc.alloc((size_t)B * maxp * 8)) || (rc = dn.alloc((size_t)B * 4)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(dA8.p, A, (size_t)rows * n, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(db.p, b, (size_t)rows, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(zero_now(dpr.p, (size_t)B * maxp * 8));
-    QLDPC_HIP_TRY(zero_now(dpc.p, (size_t)B * maxp * 8));
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((rows * nwords + 255) / 256)), dim3(256), 0, nullptr, rows, n, nwords,
-                       dA8.as<uint8_t>(), dA.as<uint64_t>());
-    hipLaunchKernelGGL(gf2_eliminate_packed_kernel, dim3((unsigned)B), dim3(m >= 512 ? 1024 : 256), lds, nullptr, m, n, nwords,
-                       dA.as<uint64_t>(), db.as<uint8_t>(), dpr.as<int64_t>(), dpc.as<int64_t>(), dn.as<int32_t>());
-    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, nullptr, rows, n, nwords,
-                       dA.as<uint64_t>(), dA8.as<uint8_t>());
+    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((rows * nwords + 255) / 256)), dim3(256), 0, nullptr, rows, n, nwords, S[dA8], S[dA]);
+    hipLaunchKernelGGL(gf2_eliminate_packed_kernel, dim3((unsigned)B), dim3(m >= 512 ? 1024 : 256), lds, nullptr, m, n, nwords, S[dA], S[db], S[dpr],
+                       S[dpc], S[dn]);
+    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, nullptr, rows, n, nwords, S[dA], S[dA8]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(A, dA8.p, (size_t)rows * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(b, db.p, (size_t)rows, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(pivot_rows, dpr.p, (size_t)B * maxp * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(pivot_cols, dpc.p, (size_t)B * maxp * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(num_pivots, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("GF(2) elimination", HostStage::kDevice);
 }
 
 QLDPC_EXPORT int qldpc_osd0_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard,
@@ -508,29 +493,23 @@ QLDPC_EXPORT int qldpc_osd0_batch(const qldpc_graph *g, int64_t B, const int8_t 
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0 || g->n == 0) return QLDPC_OK;
     QLDPC_REQUIRE(llr && hard && solution && (syndromes || g->m == 0), "NULL buffer");
-    const size_t m = g->m, n = g->n;
-    DevTmp ds, dl, dh, dord, dsol, dlist, dcnt;
-    if ((rc = ds.alloc(B * m)) || (rc = dl.alloc(B * n * 8)) || (rc = dh.alloc(B * n)) || (rc = dsol.alloc(B * n)) ||
-        (rc = dlist.alloc(B * 4)) || (rc = dcnt.alloc(16)))
-        return rc;
-    if (ordering && (rc = dord.alloc(B * n * 4))) return rc;
-    if (m) QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, B * m, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dl.p, llr, B * n * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dh.p, hard, B * n, hipMemcpyHostToDevice));
-    if (ordering) QLDPC_HIP_TRY(hipMemcpy(dord.p, ordering, B * n * 4, hipMemcpyHostToDevice));
-    iota_list_launch(B, dlist.as<int32_t>(), dcnt.as<int32_t>(), nullptr);
+    HostStage S;
+    const auto ds = S.in(syndromes, B, g->m);
+    const auto dl = S.in(llr, B, g->n);
+    const auto dh = S.in(hard, B, g->n);
+    const auto dord = ordering ? S.in(ordering, B, g->n) : Staged<int32_t>{};
+    const auto dsol = S.out(solution, B, g->n);
+    const auto dlist = S.scratch<int32_t>(B), dcnt = S.scratch<int32_t>(4);
+    int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
+    iota_list_launch(B, S[dlist], S[dcnt], nullptr);
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = osd0_listed_launch(g, dlist.as<int32_t>(), dcnt.as<int32_t>(), B, ds.as<int8_t>(), dl.as<double>(), dh.as<int8_t>(),
-                                ordering ? dord.as<int32_t>() : nullptr, dsol.as<int8_t>(), flags & QLDPC_FLAG_PUBLIC_MASK, nullptr);
-        if (rc == QLDPC_OK && hipDeviceSynchronize() != hipSuccess) { set_error("OSD-0 kernel failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+        rc = osd0_listed_launch(g, S[dlist], S[dcnt], B, S[ds], S[dl], S[dh], S[dord], S[dsol], flags & QLDPC_FLAG_PUBLIC_MASK, nullptr);
     }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(solution, dsol.p, B * n, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return rc != QLDPC_OK ? rc : S.finish("OSD-0 kernel", HostStage::kDevice);
 }
 
 // device-pointer form of qldpc_osd0_batch: only enqueues on `stream`.  d_select (may be NULL = every shot) lists the shots to solve, e.g. the
@@ -542,7 +521,7 @@ QLDPC_EXPORT int qldpc_osd0_batch_dev(const qldpc_graph *g, int64_t B, const int
     QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
     QLDPC_REQUIRE((d_select == nullptr) == (d_select_count == nullptr), "d_select and d_select_count go together");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     if (B == 0 || g->n == 0) return QLDPC_OK;
     QLDPC_REQUIRE(d_llr && d_hard && d_solution && (d_syndromes || g->m == 0), "NULL buffer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -568,7 +547,6 @@ QLDPC_EXPORT int qldpc_osdw_batch(const qldpc_graph *g, int64_t B, const int8_t 
     QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
     QLDPC_REQUIRE(order <= kOsdwMaxOrder, "OSD order %d above the supported maximum %d", order, kOsdwMaxOrder);
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0 || g->n == 0) return QLDPC_OK;
     QLDPC_REQUIRE(llr && hard && solution && (syndromes || g->m == 0), "NULL buffer");
     const int m = g->m, n = g->n;
@@ -589,33 +567,36 @@ QLDPC_EXPORT int qldpc_osdw_batch(const qldpc_graph *g, int64_t B, const int8_t 
     const size_t slab = (size_t)m * nwords * 8 + (size_t)m + (size_t)n * 18 + (size_t)maxp * 8 + (size_t)block * n + (size_t)kOsdwMaxCand * 12 + 256;
     int grid = (int)std::min<int64_t>(B, 64);
     while (grid > 1 && (size_t)grid * slab > ((size_t)2 << 30)) grid /= 2;
-    DevTmp ds, dl, dh, dord, dsol, dlist, dcnt, dA, dkeys, do_, dinv, dpr, dpc, db, disp, dep, def, dcm, dcw;
-    if ((rc = ds.alloc((size_t)B * m)) || (rc = dl.alloc((size_t)B * n * 8)) || (rc = dh.alloc((size_t)B * n)) || (rc = dsol.alloc((size_t)B * n)) ||
-        (rc = dlist.alloc((size_t)B * 4)) || (rc = dcnt.alloc(16)) || (rc = dA.alloc((size_t)grid * m * nwords * 8)) ||
-        (rc = dkeys.alloc((size_t)grid * n * 8)) || (rc = do_.alloc((size_t)grid * n * 4)) || (rc = dinv.alloc((size_t)grid * n * 4)) ||
-        (rc = dpr.alloc((size_t)grid * maxp * 4)) || (rc = dpc.alloc((size_t)grid * maxp * 4)) || (rc = db.alloc((size_t)grid * m)) ||
-        (rc = disp.alloc((size_t)grid * n)) || (rc = dep.alloc((size_t)grid * n)) || (rc = def.alloc((size_t)grid * block * n)) ||
-        (rc = dcm.alloc((size_t)grid * kOsdwMaxCand * 8)) || (rc = dcw.alloc((size_t)grid * kOsdwMaxCand * 4)))
-        return rc;
-    if (ordering && (rc = dord.alloc((size_t)B * n * 4))) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, (size_t)B * m, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dl.p, llr, (size_t)B * n * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dh.p, hard, (size_t)B * n, hipMemcpyHostToDevice));
-    if (ordering) QLDPC_HIP_TRY(hipMemcpy(dord.p, ordering, (size_t)B * n * 4, hipMemcpyHostToDevice));
-    iota_list_launch(B, dlist.as<int32_t>(), dcnt.as<int32_t>(), nullptr);
+    HostStage S;                                  // temporary: the per-workgroup scratch below can reach 2 GB
+    const auto ds = S.in(syndromes, B, m);
+    const auto dl = S.in(llr, B, n);
+    const auto dh = S.in(hard, B, n);
+    const auto dord = ordering ? S.in(ordering, B, n) : Staged<int32_t>{};
+    const auto dsol = S.out(solution, B, n);
+    const auto dlist = S.scratch<int32_t>(B), dcnt = S.scratch<int32_t>(4);
+    const auto dA = S.scratch<uint64_t>(grid, m, nwords);
+    const auto db = S.scratch<uint8_t>(grid, m);
+    const auto dkeys = S.scratch<double>(grid, n);
+    const auto dord_w = S.scratch<int32_t>(grid, n), dinv = S.scratch<int32_t>(grid, n);
+    const auto dpr = S.scratch<int32_t>(grid, maxp), dpc = S.scratch<int32_t>(grid, maxp);
+    const auto disp = S.scratch<uint8_t>(grid, n), dep = S.scratch<uint8_t>(grid, n);
+    const auto def = S.scratch<int8_t>(grid, block, n);
+    const auto dcm = S.scratch<double>(grid, kOsdwMaxCand);
+    const auto dcw = S.scratch<int32_t>(grid, kOsdwMaxCand);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
+    iota_list_launch(B, S[dlist], S[dcnt], nullptr);
     OsdwArgs W;
     W.base.m = m; W.base.n = n; W.base.nwords = nwords; W.base.indptr = g->d_indptr; W.base.indices = g->d_indices;
-    W.base.list = dlist.as<int32_t>(); W.base.count = dcnt.as<int32_t>(); W.base.synd = ds.as<int8_t>(); W.base.llr = dl.as<double>();
-    W.base.hard = dh.as<int8_t>(); W.base.ordering = ordering ? dord.as<int32_t>() : nullptr; W.base.solution = dsol.as<int8_t>();
-    W.base.A = dA.as<uint64_t>(); W.base.b = db.as<uint8_t>(); W.base.ord = do_.as<int32_t>(); W.base.inv = dinv.as<int32_t>();
-    W.base.prow = dpr.as<int32_t>(); W.base.pcol = dpc.as<int32_t>(); W.base.keys = dkeys.as<double>();
+    W.base.list = S[dlist]; W.base.count = S[dcnt]; W.base.synd = S[ds]; W.base.llr = S[dl];
+    W.base.hard = S[dh]; W.base.ordering = S[dord]; W.base.solution = S[dsol];
+    W.base.A = S[dA]; W.base.b = S[db]; W.base.ord = S[dord_w]; W.base.inv = S[dinv];
+    W.base.prow = S[dpr]; W.base.pcol = S[dpc]; W.base.keys = S[dkeys];
     W.order = order; W.maxc = max_combinations;
-    W.isp = disp.as<uint8_t>(); W.eperm = dep.as<uint8_t>(); W.efull = def.as<int8_t>(); W.cmetric = dcm.as<double>(); W.cweight = dcw.as<int32_t>();
+    W.isp = S[disp]; W.eperm = S[dep]; W.efull = S[def]; W.cmetric = S[dcm]; W.cweight = S[dcw];
     hipLaunchKernelGGL(osdw_kernel, dim3(grid), dim3(block), lds, nullptr, W);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(solution, dsol.p, (size_t)B * n, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("OSD-w kernel", HostStage::kDevice);
 }
 
 // =====================================================================================================================

@@ -112,23 +112,71 @@ void StreamHandover::destroy() {
     event = nullptr;
 }
 
-int decode_batch_via_device(std::mutex &mu, const char *what, int64_t B, int m, int n, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
-                            int32_t *iter, const std::function<int(const int8_t *, int8_t *, double *, uint8_t *, int32_t *)> &launch) {
-    const size_t Bz = (size_t)B, mz = (size_t)m, nz = (size_t)n;
-    DevTmp ds, de, dl, dc, di;
-    int rc;
-    if ((rc = ds.alloc(Bz * mz)) || (rc = de.alloc(Bz * nz)) || (rc = dl.alloc(Bz * nz * 8)) || (rc = dc.alloc(Bz)) || (rc = di.alloc(Bz * 4))) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * mz, hipMemcpyHostToDevice));
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        rc = launch(ds.as<int8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(), di.as<int32_t>());
-        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("%s decode failed: %s", what, hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+int HostStage::stage() {
+    QLDPC_REQUIRE(!layout_.overflow, "a buffer's byte count does not fit size_t, a dimension is negative or there are more than %d buffers", StageLayout::kMaxRegions);
+    if (slab_) {
+        const int rc = slab_->ensure(layout_.bytes());
+        if (rc != QLDPC_OK) return rc;
+        base_ = slab_->as<unsigned char>();
+    } else {
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&base_), layout_.bytes());
+        if (e != hipSuccess) { set_error("hipMalloc(%zu bytes) failed: %s", layout_.bytes(), hipGetErrorString(e)); base_ = nullptr; return QLDPC_ERR_HIP; }
     }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * nz, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(llr, dl.p, Bz * nz * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iter, di.p, Bz * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < layout_.count; i++) {
+        const StageLayout::Region &r = layout_.regions[i];
+        if (r.bytes == 0) continue;
+        // the slab serves latency-bound calls: its uploads are enqueued on the null stream, where the launch follows them
+        if (copies_[i].in && slab_) QLDPC_HIP_TRY(hipMemcpyAsync(base_ + r.off, copies_[i].in, r.bytes, hipMemcpyHostToDevice, nullptr));
+        else if (copies_[i].in) QLDPC_HIP_TRY(hipMemcpy(base_ + r.off, copies_[i].in, r.bytes, hipMemcpyHostToDevice));
+        if (copies_[i].zero) QLDPC_HIP_TRY(zero_now(base_ + r.off, r.bytes));
+    }
+    return QLDPC_OK;
+}
+
+int HostStage::finish(const char *what, Wait wait) {
+    const hipError_t e = wait == kDevice ? hipDeviceSynchronize() : wait == kStream ? hipStreamSynchronize(nullptr) : hipSuccess;
+    if (e != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(e)); return QLDPC_ERR_HIP; }
+    for (int i = 0; i < layout_.count; i++) {
+        const StageLayout::Region &r = layout_.regions[i];
+        if (copies_[i].out && r.bytes) QLDPC_HIP_TRY(hipMemcpy(copies_[i].out, base_ + r.off, r.bytes, hipMemcpyDeviceToHost));
+    }
+    return QLDPC_OK;
+}
+
+int HostStage::fetch_bytes(int id, void *host) const {
+    const StageLayout::Region &r = layout_.regions[id];
+    if (r.bytes) QLDPC_HIP_TRY(hipMemcpy(host, base_ + r.off, r.bytes, hipMemcpyDeviceToHost));
+    return QLDPC_OK;
+}
+
+int HostStage::finish_pinned(const char *what, void *&pin, size_t &pin_cap) {
+    const size_t kPin = (size_t)1 << 20;
+    size_t lo = layout_.total, hi = 0;
+    for (int i = 0; i < layout_.count; i++) {
+        const StageLayout::Region &r = layout_.regions[i];
+        if (copies_[i].out && r.bytes) { lo = std::min(lo, r.off); hi = std::max(hi, r.off + r.bytes); }
+    }
+    if (hi <= lo || hi - lo > kPin) return finish(what, kCopies);
+    if (pin_cap < kPin) {
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr; pin_cap = 0;
+        QLDPC_HIP_TRY(hipHostMalloc(&pin, kPin, hipHostMallocDefault));
+        pin_cap = kPin;
+    }
+    QLDPC_HIP_TRY(hipMemcpyAsync(pin, base_ + lo, hi - lo, hipMemcpyDeviceToHost, nullptr));
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(e)); return QLDPC_ERR_HIP; }
+    for (int i = 0; i < layout_.count; i++) {
+        const StageLayout::Region &r = layout_.regions[i];
+        if (copies_[i].out && r.bytes) std::memcpy(copies_[i].out, static_cast<const unsigned char *>(pin) + (r.off - lo), r.bytes);
+    }
+    return QLDPC_OK;
+}
+
+int decoder_check_call(const void *decoder, int64_t B, const void *synd, const void *err, const void *llr, const void *conv, const void *iter) {
+    QLDPC_REQUIRE(decoder != nullptr, "decoder is NULL");
+    QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
+    if (B > 0) QLDPC_REQUIRE(synd && err && llr && conv && iter, "NULL buffer");
     return QLDPC_OK;
 }
 

@@ -177,7 +177,7 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
     QLDPC_REQUIRE(batch > 0 && batch <= ((int64_t)1 << 30), "batch out of range");
     QLDPC_REQUIRE(max_iter >= 0, "negative max_iter");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     QLDPC_REQUIRE(min_launch >= 0 && min_launch <= ((int64_t)1 << 30), "min_launch out of range");
     // `batch` is taken literally: a piece is three enqueues (decode, OSD-0, judge).  A caller that prefers fewer, larger launches to the memory bound
     // passes a granule for THIS plan (include/qldpc_hip.h); the tallies do not depend on the cut.
@@ -293,7 +293,7 @@ QLDPC_EXPORT int qldpc_cc_plan_run(qldpc_cc_plan *P, uint64_t seed, int64_t shot
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     QLDPC_REQUIRE(count >= 0 && shot_begin >= 0, "negative shot range");
     QLDPC_USE_DEVICE(P->g->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const qldpc_graph *g = P->g;
     const int n = g->n, m = g->m;
@@ -438,7 +438,6 @@ static int drain_events(qldpc_cc_plan *P) {
 QLDPC_EXPORT int qldpc_cc_plan_read(qldpc_cc_plan *P, void *stream, int clear, int64_t *tally) {
     QLDPC_REQUIRE(P != nullptr && tally != nullptr, "NULL argument");
     QLDPC_USE_DEVICE(P->g->device);
-    int rc = QLDPC_OK; (void)rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     QLDPC_HIP_TRY(hipStreamSynchronize(s));
     if (P->side) QLDPC_HIP_TRY(hipStreamSynchronize(P->side));
@@ -522,16 +521,15 @@ QLDPC_EXPORT int qldpc_gf2_spmv_batch(const qldpc_graph *g, int64_t B, const int
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0, "negative batch");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0 || g->m == 0) return QLDPC_OK;
     QLDPC_REQUIRE(vectors != nullptr && out != nullptr, "NULL buffer");
-    DevTmp dv, dout;
-    if ((rc = dv.alloc((size_t)B * g->n)) || (rc = dout.alloc((size_t)B * g->m))) return rc;
-    if (g->n) QLDPC_HIP_TRY(hipMemcpy(dv.p, vectors, (size_t)B * g->n, hipMemcpyHostToDevice));
-    if ((rc = gf2_spmv_launch(g, B, dv.as<int8_t>(), dout.as<int8_t>(), nullptr)) != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(out, dout.p, (size_t)B * g->m, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    HostStage S;
+    const auto dv = S.in(vectors, B, g->n);
+    const auto dout = S.out(out, B, g->m);
+    int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
+    if ((rc = gf2_spmv_launch(g, B, S[dv], S[dout], nullptr)) != QLDPC_OK) return rc;
+    return S.finish("GF(2) product", HostStage::kDevice);
 }
 
 // device-pointer form: only enqueues on `stream`
@@ -539,7 +537,6 @@ QLDPC_EXPORT int qldpc_gf2_spmv_batch_dev(const qldpc_graph *g, int64_t B, const
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0, "negative batch");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0 || g->m == 0) return QLDPC_OK;
     QLDPC_REQUIRE(d_vectors != nullptr && d_out != nullptr, "NULL buffer");
     return gf2_spmv_launch(g, B, d_vectors, d_out, reinterpret_cast<hipStream_t>(stream));

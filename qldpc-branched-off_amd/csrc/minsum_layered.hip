@@ -402,17 +402,9 @@ QLDPC_EXPORT int qldpc_layered_decoder_layers(const qldpc_layered_decoder *D, in
     return QLDPC_OK;
 }
 
-static int layered_check_call(const qldpc_layered_decoder *D, int64_t B, const void *synd, const void *err, const void *llr, const void *conv,
-                              const void *iter) {
-    QLDPC_REQUIRE(D != nullptr, "decoder is NULL");
-    QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
-    if (B > 0) QLDPC_REQUIRE(synd && err && llr && conv && iter, "NULL buffer");
-    return QLDPC_OK;
-}
-
 QLDPC_EXPORT int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *D, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
                                                 uint8_t *d_conv, int32_t *d_iter, void *stream) {
-    int rc = layered_check_call(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter);
+    int rc = decoder_check_call(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter);
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(D->device);
     if (B == 0) return QLDPC_OK;
@@ -421,10 +413,20 @@ QLDPC_EXPORT int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *D, int64_
 
 QLDPC_EXPORT int qldpc_layered_decode_batch(qldpc_layered_decoder *D, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
                                             int32_t *iter) {
-    int rc = layered_check_call(D, B, syndromes, err, llr, conv, iter);
+    int rc = decoder_check_call(D, B, syndromes, err, llr, conv, iter);
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(D->device);
     if (B == 0) return QLDPC_OK;
-    return decode_batch_via_device(D->mu, "layered", B, D->m, D->n, syndromes, err, llr, conv, iter,
-                                   [&](const int8_t *ds, int8_t *de, double *dl, uint8_t *dc, int32_t *di) { return layered_launch(D, B, ds, de, dl, dc, di, nullptr); });
+    HostStage S;
+    const auto ds = S.in(syndromes, B, D->m);
+    const auto de = S.out(err, B, D->n);
+    const auto dl = S.out(llr, B, D->n);
+    const auto dc = S.out(conv, B);
+    const auto di = S.out(iter, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
+    {
+        std::lock_guard<std::mutex> lk(D->mu);
+        rc = layered_launch(D, B, S[ds], S[de], S[dl], S[dc], S[di], nullptr);
+    }
+    return rc != QLDPC_OK ? rc : S.finish("layered decode", HostStage::kStream);
 }

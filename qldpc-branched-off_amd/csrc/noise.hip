@@ -108,44 +108,27 @@ QLDPC_EXPORT int qldpc_noisy_circuit_batch(int64_t B, int64_t len, const int32_t
                                            int32_t *out_ops, int32_t *out_q1, int32_t *out_q2, int64_t *out_len) {
     QLDPC_REQUIRE(B >= 0 && len >= 0 && n_locs >= 0 && cap >= 0, "negative size");
     QLDPC_USE_DEVICE(0);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE((len == 0 || (ops && q1 && q2)) && (n_locs == 0 || (rv && rp && rt)) && out_len && (cap == 0 || (out_ops && out_q1 && out_q2)),
                   "NULL buffer");
     int64_t locs = 0;       // every error location consumes one random triple; never read past n_locs on the device
     for (int64_t i = 0; i < len; i++) locs += (ops[i] >= OP_CNOT && ops[i] <= OP_IDLE) ? 1 : 0;
     QLDPC_REQUIRE(locs <= n_locs, "circuit has %lld error locations but only %lld random values per draw", (long long)locs, (long long)n_locs);
-    DevTmp dops, dq1, dq2, drv, drp, drt, doo, do1, do2, dlen;
-    if ((rc = dops.alloc(len * 4)) || (rc = dq1.alloc(len * 4)) || (rc = dq2.alloc(len * 4)) || (rc = drv.alloc(B * n_locs * 8)) ||
-        (rc = drp.alloc(B * n_locs * 4)) || (rc = drt.alloc(B * n_locs * 4)) || (rc = doo.alloc(B * cap * 4)) ||
-        (rc = do1.alloc(B * cap * 4)) || (rc = do2.alloc(B * cap * 4)) || (rc = dlen.alloc(B * 8)))
-        return rc;
-    if (len) {
-        QLDPC_HIP_TRY(hipMemcpy(dops.p, ops, len * 4, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(dq1.p, q1, len * 4, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(dq2.p, q2, len * 4, hipMemcpyHostToDevice));
-    }
-    if (n_locs) {
-        QLDPC_HIP_TRY(hipMemcpy(drv.p, rv, B * n_locs * 8, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(drp.p, rp, B * n_locs * 4, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(drt.p, rt, B * n_locs * 4, hipMemcpyHostToDevice));
-    }
-    if (cap) {
-        QLDPC_HIP_TRY(zero_now(doo.p, B * cap * 4)); QLDPC_HIP_TRY(zero_now(do1.p, B * cap * 4)); QLDPC_HIP_TRY(zero_now(do2.p, B * cap * 4));
-    }
-    hipLaunchKernelGGL(noisy_circuit_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, len, dops.as<int32_t>(), dq1.as<int32_t>(),
-                       dq2.as<int32_t>(), p, n_locs, drv.as<double>(), drp.as<int32_t>(), drt.as<int32_t>(), cap, doo.as<int32_t>(),
-                       do1.as<int32_t>(), do2.as<int32_t>(), dlen.as<int64_t>());
+    HostStage S;
+    const auto dops = S.in(ops, len), dq1 = S.in(q1, len), dq2 = S.in(q2, len);
+    const auto drv = S.in(rv, B, n_locs);
+    const auto drp = S.in(rp, B, n_locs), drt = S.in(rt, B, n_locs);
+    const auto doo = S.zeroed<int32_t>(B, cap), do1 = S.zeroed<int32_t>(B, cap), do2 = S.zeroed<int32_t>(B, cap);      // fetched once every length fits
+    const auto dlen = S.out(out_len, B);
+    int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
+    hipLaunchKernelGGL(noisy_circuit_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, len, S[dops], S[dq1], S[dq2], p, n_locs, S[drv],
+                       S[drp], S[drt], cap, S[doo], S[do1], S[do2], S[dlen]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(out_len, dlen.p, B * 8, hipMemcpyDeviceToHost));
+    if ((rc = S.finish("noisy circuit kernel", HostStage::kDevice)) != QLDPC_OK) return rc;
     for (int64_t b = 0; b < B; b++)
         QLDPC_REQUIRE(out_len[b] <= cap, "output circuit of draw %lld needs %lld slots, capacity %lld", (long long)b, (long long)out_len[b], (long long)cap);
-    if (cap) {
-        QLDPC_HIP_TRY(hipMemcpy(out_ops, doo.p, B * cap * 4, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(out_q1, do1.p, B * cap * 4, hipMemcpyDeviceToHost));
-        QLDPC_HIP_TRY(hipMemcpy(out_q2, do2.p, B * cap * 4, hipMemcpyDeviceToHost));
-    }
+    if ((rc = S.fetch(doo, out_ops)) || (rc = S.fetch(do1, out_q1)) || (rc = S.fetch(do2, out_q2))) return rc;
     return QLDPC_OK;
 }
 
@@ -153,7 +136,6 @@ QLDPC_EXPORT int qldpc_frame_sim_batch(int sector_is_x, int64_t B, int64_t cap, 
                                        const int32_t *q2, int total_qubits, int max_syn, int8_t *hist, int8_t *state, int64_t *counts) {
     QLDPC_REQUIRE(B >= 0 && cap >= 0 && total_qubits >= 0 && max_syn >= 0, "negative size");
     QLDPC_USE_DEVICE(0);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE(len && counts && (cap == 0 || (ops && q1 && q2)) && (max_syn == 0 || hist) && (total_qubits == 0 || state), "NULL buffer");
     for (int64_t b = 0; b < B; b++) QLDPC_REQUIRE(len[b] >= 0 && len[b] <= cap, "len[%lld] out of range", (long long)b);
@@ -165,56 +147,44 @@ QLDPC_EXPORT int qldpc_frame_sim_batch(int sector_is_x, int64_t B, int64_t cap, 
             const bool two = (op == 1) || (op >= 20 && op <= 28);
             QLDPC_REQUIRE(!two || (c >= 0 && c < total_qubits), "q2 out of range at op %lld", (long long)i);
         }
-    DevTmp dlen, dops, dq1, dq2, dh, ds, dc;
-    if ((rc = dlen.alloc(B * 8)) || (rc = dops.alloc(B * cap * 4)) || (rc = dq1.alloc(B * cap * 4)) || (rc = dq2.alloc(B * cap * 4)) ||
-        (rc = dh.alloc((size_t)B * max_syn)) || (rc = ds.alloc((size_t)B * total_qubits)) || (rc = dc.alloc(B * 16)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(dlen.p, len, B * 8, hipMemcpyHostToDevice));
-    if (cap) {
-        QLDPC_HIP_TRY(hipMemcpy(dops.p, ops, B * cap * 4, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(dq1.p, q1, B * cap * 4, hipMemcpyHostToDevice));
-        QLDPC_HIP_TRY(hipMemcpy(dq2.p, q2, B * cap * 4, hipMemcpyHostToDevice));
-    }
+    HostStage S;
+    const auto dlen = S.in(len, B);
+    const auto dops = S.in(ops, B, cap), dq1 = S.in(q1, B, cap), dq2 = S.in(q2, B, cap);
+    const auto dh = S.out(hist, B, max_syn);
+    const auto ds = S.out(state, B, total_qubits);
+    const auto dc = S.out(counts, B, 2);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     if (sector_is_x)
-        hipLaunchKernelGGL(frame_sim_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, cap, dlen.as<int64_t>(),
-                           dops.as<int32_t>(), dq1.as<int32_t>(), dq2.as<int32_t>(), total_qubits, max_syn, dh.as<int8_t>(), ds.as<int8_t>(),
-                           dc.as<int64_t>());
+        hipLaunchKernelGGL(frame_sim_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, cap, S[dlen], S[dops], S[dq1], S[dq2],
+                           total_qubits, max_syn, S[dh], S[ds], S[dc]);
     else
-        hipLaunchKernelGGL(frame_sim_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, cap, dlen.as<int64_t>(),
-                           dops.as<int32_t>(), dq1.as<int32_t>(), dq2.as<int32_t>(), total_qubits, max_syn, dh.as<int8_t>(), ds.as<int8_t>(),
-                           dc.as<int64_t>());
+        hipLaunchKernelGGL(frame_sim_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, nullptr, B, cap, S[dlen], S[dops], S[dq1], S[dq2],
+                           total_qubits, max_syn, S[dh], S[ds], S[dc]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    if (max_syn) QLDPC_HIP_TRY(hipMemcpy(hist, dh.p, (size_t)B * max_syn, hipMemcpyDeviceToHost));
-    if (total_qubits) QLDPC_HIP_TRY(hipMemcpy(state, ds.p, (size_t)B * total_qubits, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(counts, dc.p, B * 16, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("frame simulation kernel", HostStage::kDevice);
 }
 
 QLDPC_EXPORT int qldpc_sparsify_batch(int64_t B, int64_t stride, const int8_t *hist, const int64_t *syn_count, const int32_t *positions,
                                       const int32_t *ptrs, int num_checks, int8_t *out) {
     QLDPC_REQUIRE(B >= 0 && stride >= 0 && num_checks >= 0, "negative size");
     QLDPC_USE_DEVICE(0);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0 || stride == 0) return QLDPC_OK;
     QLDPC_REQUIRE(hist && syn_count && out && (num_checks == 0 || (positions && ptrs)), "NULL buffer");
     const int64_t npos = num_checks ? ptrs[num_checks] : 0;
     for (int64_t b = 0; b < B; b++) QLDPC_REQUIRE(syn_count[b] >= 0 && syn_count[b] <= stride, "syn_count[%lld] out of range", (long long)b);
     for (int64_t i = 0; i < npos; i++) QLDPC_REQUIRE(positions[i] >= 0, "negative measurement position");
-    DevTmp dh, dsc, dpos, dptr, dout;
-    if ((rc = dh.alloc(B * stride)) || (rc = dsc.alloc(B * 8)) || (rc = dpos.alloc(npos * 4)) || (rc = dptr.alloc((num_checks + 1) * 4)) ||
-        (rc = dout.alloc(B * stride)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(dh.p, hist, B * stride, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dout.p, hist, B * stride, hipMemcpyHostToDevice));        // result = history.copy() (:367)
-    QLDPC_HIP_TRY(hipMemcpy(dsc.p, syn_count, B * 8, hipMemcpyHostToDevice));
-    if (npos) QLDPC_HIP_TRY(hipMemcpy(dpos.p, positions, npos * 4, hipMemcpyHostToDevice));
-    if (num_checks) QLDPC_HIP_TRY(hipMemcpy(dptr.p, ptrs, (num_checks + 1) * 4, hipMemcpyHostToDevice));
+    HostStage S;
+    const auto dh = S.in(hist, B, stride);
+    const auto dout = S.inout(hist, out, B, stride);            // result = history.copy() (:367)
+    const auto dsc = S.in(syn_count, B);
+    const auto dpos = S.in(positions, npos);
+    const auto dptr = S.in(ptrs, num_checks ? num_checks + 1 : 0);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     if (num_checks)
-        hipLaunchKernelGGL(sparsify_kernel, dim3((unsigned)((B * num_checks + 255) / 256)), dim3(256), 0, nullptr, B, stride, dh.as<int8_t>(),
-                           dsc.as<int64_t>(), dpos.as<int32_t>(), dptr.as<int32_t>(), num_checks, dout.as<int8_t>());
+        hipLaunchKernelGGL(sparsify_kernel, dim3((unsigned)((B * num_checks + 255) / 256)), dim3(256), 0, nullptr, B, stride, S[dh], S[dsc], S[dpos],
+                           S[dptr], num_checks, S[dout]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    QLDPC_HIP_TRY(hipMemcpy(out, dout.p, B * stride, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("sparsify kernel", HostStage::kDevice);
 }

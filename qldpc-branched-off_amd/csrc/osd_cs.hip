@@ -474,23 +474,19 @@ QLDPC_EXPORT int qldpc_osdcs_batch(const qldpc_graph *g, int64_t B, const int8_t
         for (int64_t b = 0; b < 2 * B; b++) flips[b] = -1;
         return QLDPC_OK;
     }
-    DevTmp ds, dl, dh, dw, dsol, dfl, dlist, dcnt;
-    if ((rc = ds.alloc(B * m)) || (rc = dl.alloc(B * n * 8)) || (rc = dh.alloc(B * n)) || (rc = dw.alloc(n * 8)) || (rc = dsol.alloc(B * n)) ||
-        (rc = dfl.alloc(B * 8)) || (rc = dlist.alloc(B * 4)) || (rc = dcnt.alloc(16)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, B * m, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dl.p, llr, B * n * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dh.p, hard, B * n, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(hipMemcpy(dw.p, weights, n * 8, hipMemcpyHostToDevice));
-    iota_list_launch(B, dlist.as<int32_t>(), dcnt.as<int32_t>(), nullptr);
+    HostStage S;
+    const auto ds = S.in(syndromes, B, m);
+    const auto dl = S.in(llr, B, n);
+    const auto dh = S.in(hard, B, n);
+    const auto dw = S.in(weights, n);
+    const auto dsol = S.out(solution, B, n);
+    const auto dfl = S.out(flips, B, 2);
+    const auto dlist = S.scratch<int32_t>(B), dcnt = S.scratch<int32_t>(4);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
+    iota_list_launch(B, S[dlist], S[dcnt], nullptr);
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = osdcs_listed_launch(g, dlist.as<int32_t>(), dcnt.as<int32_t>(), B, ds.as<int8_t>(), dl.as<double>(), dh.as<int8_t>(), dw.as<double>(),
-                                 order, dsol.as<int8_t>(), dfl.as<int32_t>(), nullptr);
-        if (rc == QLDPC_OK && hipDeviceSynchronize() != hipSuccess) { set_error("OSD-CS kernel failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+        rc = osdcs_listed_launch(g, S[dlist], S[dcnt], B, S[ds], S[dl], S[dh], S[dw], order, S[dsol], S[dfl], nullptr);
     }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(solution, dsol.p, B * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(flips, dfl.p, B * 8, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return rc != QLDPC_OK ? rc : S.finish("OSD-CS kernel", HostStage::kDevice);
 }

@@ -129,29 +129,27 @@ static int check_pass_host(const qldpc_graph *g, int64_t B, const double *Q, con
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0, "negative batch");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE(Q && ssign && R && Rsum, "NULL buffer");
     const size_t m = g->m, n = g->n, nnz = g->nnz;
-    DevTmp dQ, dS, dR, dRs;
-    if ((rc = dQ.alloc(B * nnz * 8)) || (rc = dS.alloc(B * m * 8)) || (rc = dR.alloc(B * nnz * 8)) || (rc = dRs.alloc(B * n * 8))) return rc;
-    if (nnz) QLDPC_HIP_TRY(hipMemcpy(dQ.p, Q, B * nnz * 8, hipMemcpyHostToDevice));
-    if (m) QLDPC_HIP_TRY(hipMemcpy(dS.p, ssign, B * m * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(zero_now(dR.p, B * nnz * 8 + (nnz ? 0 : 16)));
+    HostStage S;
+    const auto dQ = S.in(Q, B, nnz);
+    const auto dS = S.in(ssign, B, m);
+    const auto dR = S.out_zeroed(R, B, nnz);
+    const auto dRs = S.out(Rsum, B, n);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     if (B * m > 0) {
-        if (bp) hipLaunchKernelGGL(check_pass_kernel<true>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr,
-                                   dQ.as<double>(), dS.as<double>(), (const uint8_t *)nullptr, param, dR.as<double>());
-        else hipLaunchKernelGGL(check_pass_kernel<false>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr,
-                                dQ.as<double>(), dS.as<double>(), (const uint8_t *)nullptr, param, dR.as<double>());
+        if (bp) hipLaunchKernelGGL(check_pass_kernel<true>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr, S[dQ], S[dS],
+                                   (const uint8_t *)nullptr, param, S[dR]);
+        else hipLaunchKernelGGL(check_pass_kernel<false>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr, S[dQ], S[dS],
+                                (const uint8_t *)nullptr, param, S[dR]);
     }
     if (B * n > 0)
-        hipLaunchKernelGGL(column_sum_kernel, dim3(blocks(B * n)), dim3(256), 0, nullptr, B, (int)n, (int)nnz, g->d_colptr, g->d_csc2csr,
-                           dR.as<double>(), (const double *)nullptr, (const uint8_t *)nullptr, dRs.as<double>());
+        hipLaunchKernelGGL(column_sum_kernel, dim3(blocks(B * n)), dim3(256), 0, nullptr, B, (int)n, (int)nnz, g->d_colptr, g->d_csc2csr, S[dR],
+                           (const double *)nullptr, (const uint8_t *)nullptr, S[dRs]);
     QLDPC_HIP_TRY(hipGetLastError());
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    if (nnz) QLDPC_HIP_TRY(hipMemcpy(R, dR.p, B * nnz * 8, hipMemcpyDeviceToHost));
-    if (n) QLDPC_HIP_TRY(hipMemcpy(Rsum, dRs.p, B * n * 8, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("check pass", HostStage::kDevice);
 }
 
 QLDPC_EXPORT int qldpc_minsum_check_pass(const qldpc_graph *g, int64_t B, const double *Q, const double *syndrome_sign, double alpha,
@@ -169,43 +167,38 @@ QLDPC_EXPORT int qldpc_bp_decode_batch(const qldpc_graph *g, int64_t B, const in
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0 && max_iter >= 1, "bad batch / max_iter (performBeliefPropagationFast needs max_iter >= 1)");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
     if (B == 0) return QLDPC_OK;
     QLDPC_REQUIRE(prior && out_err && out_llr && out_conv && out_iter && (syndromes || g->m == 0), "NULL buffer");
     const size_t m = g->m, n = g->n, nnz = g->nnz;
-    DevTmp dsy, dpr, dQ, dR, dS, dV, ddone, dunsat, de, dl, dc, di;
-    if ((rc = dsy.alloc(B * m)) || (rc = dpr.alloc(n * 8)) || (rc = dQ.alloc(B * nnz * 8)) || (rc = dR.alloc(B * nnz * 8)) ||
-        (rc = dS.alloc(B * m * 8)) || (rc = dV.alloc(B * n * 8)) || (rc = ddone.alloc(B)) || (rc = dunsat.alloc(B)) ||
-        (rc = de.alloc(B * n)) || (rc = dl.alloc(B * n * 8)) || (rc = dc.alloc(B)) || (rc = di.alloc(B * 4)))
-        return rc;
-    if (m) QLDPC_HIP_TRY(hipMemcpy(dsy.p, syndromes, B * m, hipMemcpyHostToDevice));
-    if (n) QLDPC_HIP_TRY(hipMemcpy(dpr.p, prior, n * 8, hipMemcpyHostToDevice));
+    HostStage S;                                  // temporary: the [shot][edge] scratch does not belong in the graph handle's slab
+    const auto dsy = S.in(syndromes, B, m);
+    const auto dpr = S.in(prior, n);
+    const auto dQ = S.scratch<double>(B, nnz), dR = S.zeroed<double>(B, nnz), dS = S.scratch<double>(B, m), dV = S.scratch<double>(B, n);
+    const auto ddone = S.scratch<uint8_t>(B), dunsat = S.scratch<uint8_t>(B);
+    const auto de = S.out(out_err, B, n);
+    const auto dl = S.out(out_llr, B, n);
+    const auto dc = S.out(out_conv, B);
+    const auto di = S.out(out_iter, B);
+    const int rc = S.stage();
+    if (rc != QLDPC_OK) return rc;
     size_t tot = B * nnz; if (B * m > tot) tot = B * m; if ((size_t)B > tot) tot = B;
-    hipLaunchKernelGGL(bp_init_kernel, dim3(blocks(tot)), dim3(256), 0, nullptr, B, (int)m, (int)n, (int)nnz, g->d_indices, dpr.as<double>(),
-                       dsy.as<int8_t>(), dQ.as<double>(), dS.as<double>(), ddone.as<uint8_t>(), dunsat.as<uint8_t>());
-    QLDPC_HIP_TRY(zero_now(dR.p, B * nnz * 8 + (nnz ? 0 : 16)));
+    hipLaunchKernelGGL(bp_init_kernel, dim3(blocks(tot)), dim3(256), 0, nullptr, B, (int)m, (int)n, (int)nnz, g->d_indices, S[dpr], S[dsy], S[dQ], S[dS],
+                       S[ddone], S[dunsat]);
     for (int it = 0; it < max_iter; it++) {
         if (B * m > 0)
-            hipLaunchKernelGGL(check_pass_kernel<true>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr,
-                               dQ.as<double>(), dS.as<double>(), ddone.as<uint8_t>(), 0.9999999, dR.as<double>());     // dense.py:84,87
+            hipLaunchKernelGGL(check_pass_kernel<true>, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)nnz, g->d_indptr, S[dQ], S[dS],
+                               S[ddone], 0.9999999, S[dR]);                                                            // dense.py:84,87
         if (B * n > 0)
-            hipLaunchKernelGGL(column_sum_kernel, dim3(blocks(B * n)), dim3(256), 0, nullptr, B, (int)n, (int)nnz, g->d_colptr, g->d_csc2csr,
-                               dR.as<double>(), dpr.as<double>(), ddone.as<uint8_t>(), dV.as<double>());                // dense.py:88-89
+            hipLaunchKernelGGL(column_sum_kernel, dim3(blocks(B * n)), dim3(256), 0, nullptr, B, (int)n, (int)nnz, g->d_colptr, g->d_csc2csr, S[dR],
+                               S[dpr], S[ddone], S[dV]);                                                               // dense.py:88-89
         if (B * m > 0)
-            hipLaunchKernelGGL(bp_update_kernel, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)n, (int)nnz, g->d_indptr,
-                               g->d_indices, dV.as<double>(), dR.as<double>(), dsy.as<int8_t>(), ddone.as<uint8_t>(), dQ.as<double>(),
-                               dunsat.as<uint8_t>());
-        hipLaunchKernelGGL(bp_finalize_kernel, dim3((unsigned)B), dim3(64), 0, nullptr, B, (int)n, it, it == max_iter - 1 ? 1 : 0,
-                           dV.as<double>(), ddone.as<uint8_t>(), dunsat.as<uint8_t>(), de.as<int8_t>(), dl.as<double>(), dc.as<uint8_t>(),
-                           di.as<int32_t>());
+            hipLaunchKernelGGL(bp_update_kernel, dim3(blocks(B * m)), dim3(256), 0, nullptr, B, (int)m, (int)n, (int)nnz, g->d_indptr, g->d_indices,
+                               S[dV], S[dR], S[dsy], S[ddone], S[dQ], S[dunsat]);
+        hipLaunchKernelGGL(bp_finalize_kernel, dim3((unsigned)B), dim3(64), 0, nullptr, B, (int)n, it, it == max_iter - 1 ? 1 : 0, S[dV], S[ddone],
+                           S[dunsat], S[de], S[dl], S[dc], S[di]);
         QLDPC_HIP_TRY(hipGetLastError());
     }
-    QLDPC_HIP_TRY(hipDeviceSynchronize());
-    if (n) QLDPC_HIP_TRY(hipMemcpy(out_err, de.p, B * n, hipMemcpyDeviceToHost));
-    if (n) QLDPC_HIP_TRY(hipMemcpy(out_llr, dl.p, B * n * 8, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(out_conv, dc.p, B, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(out_iter, di.p, B * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return S.finish("BP decode", HostStage::kDevice);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -342,7 +335,7 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
     QLDPC_REQUIRE(kind != QLDPC_STATS_POSTERIOR || iters >= 1, "maxIter must be > 0");                      // scopt.py:52-53
     QLDPC_REQUIRE(B == 0 || (errors != nullptr && (prior != nullptr || g->n == 0)), "NULL buffer");
     QLDPC_USE_DEVICE(g->device);
-    int rc = QLDPC_OK; (void)rc;
+    int rc;
     *out = nullptr;
     const size_t m = g->m, n = g->n, nnz = g->nnz;
     const bool by_edge = (kind == QLDPC_STATS_CHECK_MESSAGES);
@@ -354,42 +347,36 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
     qldpc_msgstats *S = new qldpc_msgstats;
     S->g = g; S->B = B; S->L = (int)L; S->by_edge = by_edge;
     auto fail = [&](int code) { qldpc_msgstats_destroy(S); return code; };
-    DevTmp d_prior, d_red;
-    if ((rc = S->d_samples.ensure((size_t)B * L * 8 + 16)) || (rc = S->d_err.ensure((size_t)B * n + 16)) || (rc = d_prior.alloc(n * 8)) ||
-        (rc = d_red.alloc(32)))
-        return fail(rc);
-    hipError_t he = hipSuccess;
-    if (B * n) he = hipMemcpy(S->d_err.p, errors, (size_t)B * n, hipMemcpyHostToDevice);
-    if (he == hipSuccess && n) he = hipMemcpy(d_prior.p, prior, n * 8, hipMemcpyHostToDevice);
-    if (he != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(he)); return fail(QLDPC_ERR_HIP); }
-
     // trials are independent: process them in chunks so the [trial][edge] temporaries stay below ~6 GB
     const size_t per_trial = by_edge ? (nnz * 16 + n * 8 + m * 9 + 2) : (m + n + 5);
     int64_t chunk = (int64_t)(((size_t)6 << 30) / (per_trial ? per_trial : 1));
     if (chunk < 1) chunk = 1;
     if (chunk > B) chunk = B;
-    DevTmp d_synd, d_Q, d_Qold, d_ss, d_val, d_done, d_unsat, d_hard, d_conv, d_iter;
-    if (B > 0) {
-        if ((rc = d_synd.alloc(chunk * m))) return fail(rc);
-        if (by_edge) {
-            if ((rc = d_Q.alloc(chunk * nnz * 8)) || (rc = d_Qold.alloc(chunk * nnz * 8)) || (rc = d_ss.alloc(chunk * m * 8)) ||
-                (rc = d_val.alloc(chunk * n * 8)) || (rc = d_done.alloc(chunk)) || (rc = d_unsat.alloc(chunk)))
-                return fail(rc);
-        } else if ((rc = d_hard.alloc(chunk * n)) || (rc = d_conv.alloc(chunk)) || (rc = d_iter.alloc(chunk * 4))) {
-            return fail(rc);
-        }
-    }
+    const int64_t ce = by_edge ? chunk : 0, cp = by_edge ? 0 : chunk;          // the chunk of the form in use; the other form's scratch is empty
+    unsigned long long red[4] = {~0ull, 0ull, 0ull, 0ull};
+    HostStage T;                                  // the samples and the errors belong to the returned object, everything else is staged
+    const auto d_prior = T.in(prior, n);
+    const auto d_red = T.inout(red, red, 4);
+    const auto d_synd = T.scratch<int8_t>(chunk, m);
+    const auto d_Q = T.scratch<double>(ce, nnz), d_Qold = T.scratch<double>(ce, nnz), d_ss = T.scratch<double>(ce, m), d_val = T.scratch<double>(ce, n);
+    const auto d_done = T.scratch<uint8_t>(ce), d_unsat = T.scratch<uint8_t>(ce);
+    const auto d_hard = T.scratch<int8_t>(cp, n);
+    const auto d_conv = T.scratch<uint8_t>(cp);
+    const auto d_iter = T.scratch<int32_t>(cp);
+    if ((rc = S->d_samples.ensure((size_t)B * L * 8 + 16)) || (rc = S->d_err.ensure((size_t)B * n + 16)) || (rc = T.stage())) return fail(rc);
+    const hipError_t he = B * n ? hipMemcpy(S->d_err.p, errors, (size_t)B * n, hipMemcpyHostToDevice) : hipSuccess;
+    if (he != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(he)); return fail(QLDPC_ERR_HIP); }
     for (int64_t off = 0; off < B; off += chunk) {
         const int64_t Bc = std::min<int64_t>(chunk, B - off);
         const int8_t *err_c = S->d_err.as<int8_t>() + off * n;
         double *smp_c = S->d_samples.as<double>() + off * L;
-        if ((rc = gf2_spmv_launch(g, Bc, err_c, d_synd.as<int8_t>(), nullptr)) != QLDPC_OK) return fail(rc);      // alpha.py:121 / scopt.py:82
+        if ((rc = gf2_spmv_launch(g, Bc, err_c, T[d_synd], nullptr)) != QLDPC_OK) return fail(rc);      // alpha.py:121 / scopt.py:82
         if (by_edge) {
             size_t tot = Bc * nnz; if (Bc * m > tot) tot = Bc * m; if ((size_t)Bc > tot) tot = Bc;
             hipLaunchKernelGGL(bp_init_kernel, dim3(blocks(tot)), dim3(256), 0, nullptr, Bc, (int)m, (int)n, (int)nnz, g->d_indices,
-                               d_prior.as<double>(), d_synd.as<int8_t>(), d_Q.as<double>(), d_ss.as<double>(), d_done.as<uint8_t>(),
-                               d_unsat.as<uint8_t>());                                                           // alpha.py:122-124
-            if (nnz && hipMemcpyAsync(d_Qold.p, d_Q.p, Bc * nnz * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) {
+                               T[d_prior], T[d_synd], T[d_Q], T[d_ss], T[d_done],
+                               T[d_unsat]);                                                           // alpha.py:122-124
+            if (nnz && hipMemcpyAsync(T[d_Qold], T[d_Q], Bc * nnz * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) {
                 set_error("device copy failed"); return fail(QLDPC_ERR_HIP);
             }
             if (hipMemsetAsync(smp_c, 0, Bc * nnz * 8 + (nnz ? 0 : 8), nullptr) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
@@ -397,32 +384,30 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
                 const double a = (k < iters) ? tab[k] : 1.0;                                                     // alpha.py:214-218, 247-249
                 if (Bc * m > 0)
                     hipLaunchKernelGGL(check_pass_kernel<false>, dim3(blocks(Bc * m)), dim3(256), 0, nullptr, Bc, (int)m, (int)nnz, g->d_indptr,
-                                       d_Q.as<double>(), d_ss.as<double>(), (const uint8_t *)nullptr, a, smp_c);
+                                       T[d_Q], T[d_ss], (const uint8_t *)nullptr, a, smp_c);
                 if (k == iters) break;
                 if (Bc * n > 0)
                     hipLaunchKernelGGL(column_sum_kernel, dim3(blocks(Bc * n)), dim3(256), 0, nullptr, Bc, (int)n, (int)nnz, g->d_colptr,
-                                       g->d_csc2csr, smp_c, d_prior.as<double>(), (const uint8_t *)nullptr, d_val.as<double>());   // alpha.py:220
+                                       g->d_csc2csr, smp_c, T[d_prior], (const uint8_t *)nullptr, T[d_val]);   // alpha.py:220
                 if (Bc * nnz > 0)
                     hipLaunchKernelGGL(stats_q_update_kernel, dim3(blocks(Bc * nnz)), dim3(256), 0, nullptr, Bc, (int)n, (int)nnz, g->d_indices,
-                                       d_val.as<double>(), smp_c, damping, clip_llr, d_Q.as<double>(), d_Qold.as<double>());
+                                       T[d_val], smp_c, damping, clip_llr, T[d_Q], T[d_Qold]);
             }
             if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed"); return fail(QLDPC_ERR_HIP); }
         } else {
-            rc = qldpc_minsum_decode_batch_dev(g, Bc, d_synd.as<int8_t>(), d_prior.as<double>(), iters, alpha_mode, alpha_val, alpha_seq,
-                                               alpha_len, damping, clip_llr, 0, d_hard.as<int8_t>(), smp_c, d_conv.as<uint8_t>(),
-                                               d_iter.as<int32_t>(), nullptr);                                   // scopt.py:88-131
+            rc = qldpc_minsum_decode_batch_dev(g, Bc, T[d_synd], T[d_prior], iters, alpha_mode, alpha_val, alpha_seq,
+                                               alpha_len, damping, clip_llr, 0, T[d_hard], smp_c, T[d_conv],
+                                               T[d_iter], nullptr);                                   // scopt.py:88-131
             if (rc != QLDPC_OK) return fail(rc);
         }
         if (hipDeviceSynchronize() != hipSuccess) { set_error("device synchronisation failed"); return fail(QLDPC_ERR_HIP); }
     }
-    unsigned long long red[4] = {~0ull, 0ull, 0ull, 0ull};
-    if (hipMemcpy(d_red.p, red, 32, hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); return fail(QLDPC_ERR_HIP); }
     if (B * (int64_t)L > 0) {
         const unsigned grid = (unsigned)std::min<int64_t>(4096, (B * (int64_t)L + 255) / 256);
         hipLaunchKernelGGL(stats_range_kernel, dim3(grid), dim3(256), 0, nullptr, B, (int)L, (int)n, by_edge ? g->d_indices : (const int32_t *)nullptr,
-                           S->d_samples.as<double>(), S->d_err.as<int8_t>(), d_red.as<unsigned long long>());
+                           S->d_samples.as<double>(), S->d_err.as<int8_t>(), T[d_red]);
     }
-    if (hipMemcpy(red, d_red.p, 32, hipMemcpyDeviceToHost) != hipSuccess) { set_error("range read-back failed"); return fail(QLDPC_ERR_HIP); }
+    if ((rc = T.finish("range read-back", HostStage::kCopies)) != QLDPC_OK) return fail(rc);
     finite[0] = (int64_t)red[2]; finite[1] = (int64_t)red[3];
     const bool any = (red[2] | red[3]) != 0;
     range[0] = any ? key_f64(red[0]) : 0.0;
@@ -436,11 +421,12 @@ QLDPC_EXPORT int qldpc_msgstats_histogram(qldpc_msgstats *S, const double *edges
     QLDPC_REQUIRE(bins >= 1 && bins <= kStatsMaxBins, "bins must be in [1, %d]", kStatsMaxBins);
     for (int i = 0; i < bins; i++) QLDPC_REQUIRE(edges[i] < edges[i + 1], "bin edges must increase strictly");
     QLDPC_USE_DEVICE(S->g->device);
-    int rc = QLDPC_OK; (void)rc;
-    DevTmp d_edges, d_hist;
-    if ((rc = d_edges.alloc((bins + 1) * 8)) || (rc = d_hist.alloc(2 * bins * 8))) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(d_edges.p, edges, (bins + 1) * 8, hipMemcpyHostToDevice));
-    QLDPC_HIP_TRY(zero_now(d_hist.p, 2 * bins * 8));
+    std::vector<unsigned long long> h(2 * (size_t)bins);
+    HostStage T;
+    const auto d_edges = T.in(edges, bins + 1);
+    const auto d_hist = T.out_zeroed(h.data(), 2, bins);
+    int rc = T.stage();
+    if (rc != QLDPC_OK) return rc;
     const int64_t total = S->B * (int64_t)S->L;
     if (total > 0) {
         // each block counts into 32-bit LDS bins: keep its share of the samples below 2^31
@@ -449,11 +435,10 @@ QLDPC_EXPORT int qldpc_msgstats_histogram(qldpc_msgstats *S, const double *edges
         const size_t lds = (size_t)(bins + 1) * 8 + (size_t)2 * bins * 4;
         hipLaunchKernelGGL(stats_hist_kernel, dim3((unsigned)grid), dim3(256), lds, nullptr, S->B, S->L, S->g->n,
                            S->by_edge ? S->g->d_indices : (const int32_t *)nullptr, S->d_samples.as<double>(), S->d_err.as<int8_t>(),
-                           d_edges.as<double>(), bins, d_hist.as<unsigned long long>());
+                           T[d_edges], bins, T[d_hist]);
         QLDPC_HIP_TRY(hipGetLastError());
     }
-    std::vector<unsigned long long> h(2 * (size_t)bins);
-    QLDPC_HIP_TRY(hipMemcpy(h.data(), d_hist.p, 2 * (size_t)bins * 8, hipMemcpyDeviceToHost));
+    if ((rc = T.finish("histogram", HostStage::kCopies)) != QLDPC_OK) return rc;
     for (int i = 0; i < bins; i++) { hist0[i] = (int64_t)h[i]; hist1[i] = (int64_t)h[bins + i]; }
     return QLDPC_OK;
 }

@@ -228,24 +228,18 @@ QLDPC_EXPORT int qldpc_relay_decode_batch(const qldpc_graph *g, int64_t B, const
     for (size_t j = 0; j < n; j++) QLDPC_REQUIRE(std::isfinite(prior[j]), "prior[%zu] is not finite", j);
     QLDPC_USE_DEVICE(g->device);
     if (relay_mode(g) == 0) return relay_unsupported(g);
-    // one grow-only slab per graph handle:  prior | syndromes | err | conv | legs | iters | solutions
-    IoSlab S;
-    const size_t o_prior = S.add(n * 8), o_synd = S.add(B * m), o_err = S.add(B * n), o_conv = S.add(B), o_legs = S.add(B * 4), o_iters = S.add(B * 4),
-                 o_sol = S.add(B * 4);
-    std::unique_lock<std::mutex> io(g->mu_io);
-    if ((rc = S.ensure(g->ws_io)) != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_synd), syndromes, B * m, hipMemcpyHostToDevice, nullptr));
-    QLDPC_HIP_TRY(hipMemcpyAsync(S.at(o_prior), prior, n * 8, hipMemcpyHostToDevice, nullptr));
+    HostStage S(g->ws_io, g->mu_io);          // the graph handle's grow-only slab
+    const auto dp = S.in(prior, n);
+    const auto ds = S.in(syndromes, B, m);
+    const auto de = S.out(err, B, n);
+    const auto dc = S.out(conv, B);
+    const auto dg = S.out(legs, B);
+    const auto di = S.out(iters, B);
+    const auto dn = S.out(solutions, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = relay_decode_launch(g, B, S.at<int8_t>(o_synd), S.at<double>(o_prior), P, seed, shot_begin, tag, 0, S.at<int8_t>(o_err), S.at<uint8_t>(o_conv),
-                                 S.at<int32_t>(o_legs), S.at<int32_t>(o_iters), S.at<int32_t>(o_sol), nullptr);
+        rc = relay_decode_launch(g, B, S[ds], S[dp], P, seed, shot_begin, tag, 0, S[de], S[dc], S[dg], S[di], S[dn], nullptr);
     }
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_HIP_TRY(hipMemcpy(err, S.at(o_err), B * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, S.at(o_conv), B, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(legs, S.at(o_legs), B * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iters, S.at(o_iters), B * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(solutions, S.at(o_sol), B * 4, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return rc != QLDPC_OK ? rc : S.finish("Relay-BP decode", HostStage::kCopies);
 }

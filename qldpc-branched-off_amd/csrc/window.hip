@@ -371,22 +371,17 @@ QLDPC_EXPORT int qldpc_window_decode_batch(qldpc_window_decoder *D, int64_t B, c
     if (rc != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(D->device);
     if (B == 0) return QLDPC_OK;
-    const size_t Bz = (size_t)B, m = D->m, n = D->n;
-    DevTmp ds, de, dc, di, dq, du;
-    if ((rc = ds.alloc(Bz * m)) || (rc = de.alloc(Bz * n)) || (rc = dc.alloc(Bz * 4)) || (rc = di.alloc(Bz * 4)) || (rc = dq.alloc(Bz * 4)) || (rc = du.alloc(Bz)))
-        return rc;
-    QLDPC_HIP_TRY(hipMemcpy(ds.p, syndromes, Bz * m, hipMemcpyHostToDevice));
+    HostStage S;
+    const auto ds = S.in(syndromes, B, D->m);
+    const auto de = S.out(err, B, D->n);
+    const auto dc = S.out(conv, B);
+    const auto di = S.out(iters, B);
+    const auto dq = S.out(osd, B);
+    const auto du = S.out(unsat, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(D->mu);
-        rc = window_decode_launch(D, B, ds.as<int8_t>(), de.as<int8_t>(), dc.as<int32_t>(), di.as<int32_t>(), dq.as<int32_t>(), du.as<uint8_t>(), nullptr,
-                                  nullptr, nullptr);
-        if (rc == QLDPC_OK && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("window decode failed: %s", hipGetErrorString(hipGetLastError())); rc = QLDPC_ERR_HIP; }
+        rc = window_decode_launch(D, B, S[ds], S[de], S[dc], S[di], S[dq], S[du], nullptr, nullptr, nullptr);
     }
-    if (rc != QLDPC_OK) return rc;
-    if (n) QLDPC_HIP_TRY(hipMemcpy(err, de.p, Bz * n, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(conv, dc.p, Bz * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(iters, di.p, Bz * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(osd, dq.p, Bz * 4, hipMemcpyDeviceToHost));
-    QLDPC_HIP_TRY(hipMemcpy(unsat, du.p, Bz, hipMemcpyDeviceToHost));
-    return QLDPC_OK;
+    return rc != QLDPC_OK ? rc : S.finish("window decode", HostStage::kStream);
 }
