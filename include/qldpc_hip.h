@@ -776,6 +776,12 @@ void qldpc_comm_destroy(qldpc_comm *comm);
 /* Philox4x32-10 reference vector helper (host; lets tests pin the generator against the oracle) */
 void qldpc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* Diagnostic: the device allocations the library's own handles hold right now, process-wide and over all devices -- *buffers their number, *bytes
+ * their sum (either may be NULL).  Every handle's device memory is counted, staging of a host-pointer call in flight included; memory the caller
+ * allocated and the diagnostic build's process-lifetime timer buffer are not.  A handle's destroy function brings both numbers back to what they
+ * were before its create, which is what tests of ownership compare (a shared card's free-memory figure moves with other processes). */
+int qldpc_device_memory(int64_t *buffers, int64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,8 +180,45 @@ def set_option(name, value):
     check(lib().qldpc_set_option(name.encode(), int(value)))
 
 
-class Stream:
+class Owner:
+    """Base of the wrappers that own a C handle in `_h`: the `handle` property, an idempotent close() that calls the class's destroy function
+    (`_destroy`, by name) once, and __del__."""
+    _destroy = None
+    _h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _destroy_args(self, h):
+        return (h,)
+
+    def close(self):
+        h = self._h
+        if h is not None and h.value:
+            self._h = C.c_void_p()
+            getattr(lib(), self._destroy)(*self._destroy_args(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def device_memory():
+    """qldpc_device_memory -> (buffers, bytes): the device allocations the library holds right now (a diagnostic of its own handles' memory)."""
+    nb, by = C.c_int64(0), C.c_int64(0)
+    check(lib().qldpc_device_memory(C.byref(nb), C.byref(by)))
+    return int(nb.value), int(by.value)
+
+
+class Stream(Owner):
     """A HIP stream of `device` owned by this object (qldpc_stream_*); `.ptr` goes where the ABI takes a `stream`."""
+    _destroy = "qldpc_stream_destroy"
+
+    def _destroy_args(self, h):
+        return (self.device, h)
 
     def __init__(self, device=0):
         require_device()
@@ -195,17 +232,6 @@ class Stream:
 
     def synchronize(self):
         check(lib().qldpc_stream_sync(self.device, self._h))
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_stream_destroy(self.device, self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def require_device():
@@ -233,6 +259,14 @@ def u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def prior_of(prior, n, name="prior", owner="H"):
+    """The prior as contiguous f64[n]; ValueError unless it has one entry per column."""
+    prior = f64(prior).reshape(-1)
+    if prior.size != n:
+        raise ValueError(f"{name} has {prior.size} entries, {owner} has {n} columns")
+    return prior
+
+
 def alpha_args(alpha_mode, alpha):
     """Alpha-mode rules of the reference wrappers (src/decoding/sparse.py:18-29,36-39; dense.py:19-33)."""
     if alpha_mode is None:
@@ -255,8 +289,9 @@ def alpha_args(alpha_mode, alpha):
     return mode, float(alpha), np.zeros(1)
 
 
-class Graph:
+class Graph(Owner):
     """Owning wrapper of a qldpc_graph handle (Tanner graph of a parity-check matrix in canonical CSR)."""
+    _destroy = "qldpc_graph_destroy"
 
     def __init__(self, indptr, indices, n, device=0):
         self.indptr, self.indices = i32(indptr), i32(indices)
@@ -267,17 +302,6 @@ class Graph:
         check(lib().qldpc_graph_create(C.c_int(self.m), C.c_int(self.n), ptr(self.indptr, C.c_int32), ptr(self.indices, C.c_int32),
                                        C.c_int(device), C.byref(self._h)))
 
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                lib().qldpc_graph_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
 
 _graph_cache = OrderedDict()
@@ -324,9 +348,7 @@ def minsum_decode_batch(graph, syndromes, prior, max_iter, alpha_mode, alpha, da
     mode, aval, seq = alpha_args(alpha_mode, alpha)
     syndromes = i8(syndromes).reshape(-1, graph.m) if graph.m else np.zeros((np.asarray(syndromes).shape[0], 0), np.int8)
     B = syndromes.shape[0]
-    prior = f64(prior)
-    if prior.size != graph.n:
-        raise ValueError(f"initialBelief has {prior.size} entries, H has {graph.n} columns")
+    prior = prior_of(prior, graph.n, "initialBelief")
     err = np.zeros((B, graph.n), np.int8)
     llr = np.zeros((B, graph.n), np.float64) if want_llr else None
     conv = np.zeros(B, np.uint8)
@@ -344,9 +366,7 @@ def minsum_decode_path(graph, prior, max_iter, alpha_mode, alpha, damping=1.0, c
     prior=None asks for the device-pointer entry point, which does not know the prior.  Launches nothing."""
     mode, aval, seq = alpha_args(alpha_mode, alpha)
     if prior is not None:
-        prior = f64(prior)
-        if prior.size != graph.n:
-            raise ValueError(f"initialBelief has {prior.size} entries, H has {graph.n} columns")
+        prior = prior_of(prior, graph.n, "initialBelief")
     path, detail = C.c_int(-1), C.c_int(0)
     check(lib().qldpc_minsum_decode_path(graph.handle, ptr(prior, C.c_double) if prior is not None else None, C.c_int(int(max_iter)), C.c_int(mode),
                                          C.c_double(aval), ptr(seq, C.c_double), C.c_int(seq.size), C.c_double(float(damping)),
@@ -467,9 +487,7 @@ def relay_check_inputs(prior, tag):
 def relay_decode_batch(graph, syndromes, prior, seed, shot_begin=0, tag=0, **params):
     """qldpc_relay_decode_batch on host arrays -> (err int8[B, n], conv uint8[B], legs int32[B], iters int32[B], solutions int32[B])."""
     p = relay_params(params)
-    prior = f64(prior)
-    if prior.size != graph.n:
-        raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+    prior = prior_of(prior, graph.n)
     relay_check_inputs(prior, tag)
     syndromes = i8(syndromes).reshape(-1, graph.m)
     B = syndromes.shape[0]
@@ -516,9 +534,7 @@ def decim_params(params, with_clip=True):
 def decim_decode_batch(graph, syndromes, prior, **params):
     """qldpc_decim_decode_batch on host arrays -> (err int8[B, n], llr f64[B, n], conv uint8[B], iters int32[B], rounds int32[B], fixed int32[B])."""
     p = decim_params(params)
-    prior = f64(prior).reshape(-1)
-    if prior.size != graph.n:
-        raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+    prior = prior_of(prior, graph.n)
     if not np.all(np.isfinite(prior)):
         raise ValueError("guided decimation needs a finite prior")
     syndromes = i8(syndromes).reshape(-1, graph.m)
@@ -545,25 +561,20 @@ def check_window_args(layer_rows, window, commit, m=None):
     return layer_rows, window, commit
 
 
-class WindowDecoder:
+class WindowDecoder(Owner):
     """Owning wrapper of a qldpc_window_decoder (sliding-window min-sum + OSD-0 over the row layers of `graph`; semantics in include/qldpc_hip.h)."""
+    _destroy = "qldpc_window_decoder_destroy"
 
     def __init__(self, graph, layer_rows, window, commit, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, flags=0):
         layer_rows, window, commit = check_window_args(layer_rows, window, commit, graph.m)
         mode, aval, seq = alpha_args(alpha_mode, alpha)
-        prior = f64(prior).reshape(-1)
-        if prior.size != graph.n:
-            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        prior = prior_of(prior, graph.n)
         if not np.isfinite(prior).all():
             raise ValueError("sliding-window decoding needs a finite prior")
         self.graph = graph                     # keeps the full graph alive as long as the decoder
         self._h = C.c_void_p()
         check(lib().qldpc_window_decoder_create(graph.handle, layer_rows, window, commit, ptr(prior, C.c_double), int(max_iter), mode, aval,
                                                 ptr(seq, C.c_double), seq.size, float(clip_llr), int(flags), C.byref(self._h)))
-
-    @property
-    def handle(self):
-        return self._h
 
     def info(self):
         """{windows, graphs (distinct handles), max_rows, max_cols (of the largest window), wg2_windows (windows on the LDS-resident decoder)}"""
@@ -581,17 +592,6 @@ class WindowDecoder:
         check(lib().qldpc_window_decode_batch(self._h, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(err, C.c_int8), ptr(conv, C.c_int32),
                                               ptr(iters, C.c_int32), ptr(osd, C.c_int32), ptr(unsat, C.c_uint8)))
         return err, conv, iters, osd, unsat
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_window_decoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def check_layered_args(max_iter, clip_llr):
@@ -628,24 +628,19 @@ def graph_check_layers(graph):
     return lay[:graph.m], nl.value
 
 
-class LayeredDecoder:
+class LayeredDecoder(Owner):
     """Owning wrapper of a qldpc_layered_decoder (normalised min-sum with a layered schedule on `graph`; semantics in include/qldpc_hip.h)."""
+    _destroy = "qldpc_layered_decoder_destroy"
 
     def __init__(self, graph, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, layers=None, flags=0):
         max_iter, clip_llr = check_layered_args(max_iter, clip_llr)
         mode, aval, seq = alpha_args(alpha_mode, alpha)
-        prior = f64(prior).reshape(-1)
-        if prior.size != graph.n:
-            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        prior = prior_of(prior, graph.n)
         layers = check_row_layer(layers, graph.m)
         self.graph = graph                     # the decoder keeps a pointer to the graph handle
         self._h = C.c_void_p()
         check(lib().qldpc_layered_decoder_create(graph.handle, ptr(layers, C.c_int32) if layers is not None else None, ptr(prior, C.c_double), max_iter,
                                                  mode, aval, ptr(seq, C.c_double), seq.size, clip_llr, int(flags), C.byref(self._h)))
-
-    @property
-    def handle(self):
-        return self._h
 
     def info(self):
         """{layers, max_layer_rows, max_layer_edges, lds_bytes, block (threads per workgroup), v_global, lds_indices}"""
@@ -671,17 +666,6 @@ class LayeredDecoder:
                                                ptr(conv, C.c_uint8), ptr(iters, C.c_int32)))
         return err, conv, llr, iters
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_layered_decoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def check_minsum32_args(max_iter, clip_llr):
     """ValueError unless max_iter is an integer >= 1 and clip_llr is finite and > 0 once rounded to f32 -> (int, float)."""
@@ -695,23 +679,18 @@ def check_minsum32_args(max_iter, clip_llr):
     return int(max_iter), clip_llr
 
 
-class Minsum32Decoder:
+class Minsum32Decoder(Owner):
     """Owning wrapper of a qldpc_minsum32_decoder (single-precision flooding min-sum on `graph`; semantics in include/qldpc_hip.h)."""
+    _destroy = "qldpc_minsum32_decoder_destroy"
 
     def __init__(self, graph, prior, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, flags=0):
         max_iter, clip_llr = check_minsum32_args(max_iter, clip_llr)
         mode, aval, seq = alpha_args(alpha_mode, alpha)
-        prior = f64(prior).reshape(-1)
-        if prior.size != graph.n:
-            raise ValueError(f"prior has {prior.size} entries, H has {graph.n} columns")
+        prior = prior_of(prior, graph.n)
         self.graph = graph                     # the decoder keeps a pointer to the graph handle
         self._h = C.c_void_p()
         check(lib().qldpc_minsum32_decoder_create(graph.handle, ptr(prior, C.c_double), max_iter, mode, aval, ptr(seq, C.c_double), seq.size, clip_llr,
                                                   int(flags), C.byref(self._h)))
-
-    @property
-    def handle(self):
-        return self._h
 
     def info(self):
         """{lds_bytes, block (threads per workgroup), wg_per_cu (resident workgroups per CU, the runtime's occupancy query), clean}"""
@@ -729,17 +708,6 @@ class Minsum32Decoder:
                                                 ptr(conv, C.c_uint8), ptr(iters, C.c_int32)))
         return err, conv, llr, iters
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_minsum32_decoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def osd_timers(reset=True):
     """Phase counters of the OSD-0 kernels [0..15] and of the workgroup BP kernel [16..31] (diagnostic build only, see csrc/clocks.h) -> uint64[32]."""
@@ -748,9 +716,10 @@ def osd_timers(reset=True):
     return out
 
 
-class Comm:
+class Comm(Owner):
     """RCCL communicator of the tally all-reduce (qldpc_comm_*): `Comm.init_all(ndev)` for one process driving ndev GPUs,
     `Comm.init_rank(nranks, rank, id, device)` for one process per GPU (id = Comm.unique_id() of rank 0, handed over by the launcher)."""
+    _destroy = "qldpc_comm_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -786,17 +755,6 @@ class Comm:
         check(lib().qldpc_tally_allreduce(self._h, ptr(t, C.c_int64)))
         return t.reshape(np.shape(tallies))
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_comm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def cc_sample_decode_tally(graph, L, p, seed, shot_begin, count, max_iter=50, alpha=1.0, alpha_mode="dynamical", damping=1.0,
                            clip_llr=20.0, use_osd=True, flags=0):
@@ -810,8 +768,9 @@ def cc_sample_decode_tally(graph, L, p, seed, shot_begin, count, max_iter=50, al
     return tally
 
 
-class CodeCapacityPlan:
+class CodeCapacityPlan(Owner):
     """Asynchronous code-capacity Monte-Carlo plan (qldpc_cc_plan_*): device-resident sample -> decode -> tally."""
+    _destroy = "qldpc_cc_plan_destroy"
 
     def __init__(self, graph, L, p, max_iter=50, alpha=1.0, alpha_mode="dynamical", damping=1.0, clip_llr=20.0, use_osd=True,
                  flags=0, batch=1 << 18, min_launch=0):
@@ -849,17 +808,6 @@ class CodeCapacityPlan:
         mhz = C.c_double(0)
         check(lib().qldpc_cc_plan_clock(self._h, C.c_void_p(stream), C.byref(mhz)))
         return float(mhz.value)
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_cc_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _attr(src, name):
@@ -915,15 +863,14 @@ def circuit_fault_signatures(compiled, Lx, Lz, sector_is_x):
 STATS_CHECK_MESSAGES, STATS_POSTERIOR = 0, 1
 
 
-class MessageStats:
+class MessageStats(Owner):
     """Device-resident samples of an estimator trial loop (qldpc_msgstats_*): check messages after `iters` decoder iterations
     (alpha.py:119-137, 206-255) or the decoder's final posteriors (scopt.py:80-134), split by the true error bit."""
+    _destroy = "qldpc_msgstats_destroy"
 
     def __init__(self, graph, errors, prior, kind, iters, alpha_mode="dynamical", alpha=1.0, damping=1.0, clip_llr=20.0):
         errors = i8(errors).reshape(-1, graph.n)
-        prior = f64(prior)
-        if prior.size != graph.n:
-            raise ValueError(f"prior has {prior.size} entries, the graph has {graph.n} columns")
+        prior = prior_of(prior, graph.n, owner="the graph")
         mode, aval, seq = alpha_args(alpha_mode, alpha)
         rng, fin = np.zeros(2), np.zeros(2, np.int64)
         self._h = C.c_void_p()
@@ -941,17 +888,6 @@ class MessageStats:
         h0, h1 = np.zeros(bins, np.int64), np.zeros(bins, np.int64)
         check(lib().qldpc_msgstats_histogram(self._h, ptr(edges, C.c_double), C.c_int(bins), ptr(h0, C.c_int64), ptr(h1, C.c_int64)))
         return h0, h1
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_msgstats_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def pack_events(bits):
@@ -985,9 +921,10 @@ def check_fixed_weight(weight):
     return weight
 
 
-class CircuitPlan:
+class CircuitPlan(Owner):
     """Circuit-level Monte-Carlo plan (qldpc_circuit_plan_*): Philox fault sampling through precomputed fault signatures,
     decode of both sectors, OSD-0, logical comparison and tally, all on the device."""
+    _destroy = "qldpc_circuit_plan_destroy"
 
     def __init__(self, compiled, Lx, Lz, graph_z, graph_x, prior_z, prior_x, logmask_z, logmask_x, p, max_iter=50, alpha_z=1.0, alpha_x=1.0,
                  alpha_mode="dynamical", damping=1.0, clip_llr=20.0, use_osd=True, flags=0, batch=16384):
@@ -1148,17 +1085,6 @@ class CircuitPlan:
         check(lib().qldpc_circuit_plan_unpack_events(self._h, C.c_int64(count), ptr(events, C.c_uint8), C.c_int64(events.shape[1]), ptr(sp0, C.c_int8),
                                                      ptr(sp1, C.c_int8)))
         return sp0, sp1
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().qldpc_circuit_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def make_dem_desc(prob, sectors):

@@ -141,14 +141,6 @@ __global__ void collect_failed2_kernel(int64_t B, const uint8_t *__restrict__ co
 
 using namespace qldpc;
 
-// A DevBuf that the plan owns: released when the plan is deleted, so a buffer added below needs no line anywhere else.
-struct PlanBuf : DevBuf {
-    PlanBuf() = default;
-    PlanBuf(const PlanBuf &) = delete;
-    PlanBuf &operator=(const PlanBuf &) = delete;
-    ~PlanBuf() { release(); }
-};
-
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
 enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW };      // who fills the BP bracket and its follow-up
 enum class Osd { OSD0, CS };                                        // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
@@ -160,25 +152,26 @@ struct qldpc_circuit_plan {
         int nsyn = 0, layer_rows = 0;              // detectors (= rows of g); rows per syndrome cycle
         // on the host: the prior lets the decode dispatch pick the LDS-resident workgroup kernel (minsum_wg2.hip), the window decoder takes both at the switch
         std::vector<double> h_prior, h_alpha;
-        qldpc_window_decoder *win = nullptr;       // Path::WINDOW (window.hip)
-        qldpc_layered_decoder *lay = nullptr;      // Path::LAYERED (minsum_layered.hip)
-        qldpc_minsum32_decoder *f32 = nullptr;     // Path::F32 (minsum_f32.hip)
-        PlanBuf d_ptr, d_idx, d_log;               // fault signatures (SigTab)
-        PlanBuf d_alpha, d_prior, d_lm;
-        PlanBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
-        PlanBuf d_legs;                            // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
-        PlanBuf d_flips;                           // Osd::CS: workspace of the sweep
+        DevBuf d_ptr, d_idx, d_log;                // fault signatures (SigTab)
+        DevBuf d_alpha, d_prior, d_lm;
+        DevBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
+        DevBuf d_legs;                             // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
+        DevBuf d_flips;                            // Osd::CS: workspace of the sweep
         // decode of recorded events (events.hip): the record bit of every row (ev_tab, else the contiguous run at ev_base); the predictions of a batch
-        PlanBuf d_evtab, d_pred;
+        DevBuf d_evtab, d_pred;
         bool ev_tab = false;
         int ev_base = 0;
+        // the decoder objects of a path, below the buffers they write so that they go first (each waits for what it has in flight)
+        Handle<qldpc_window_decoder, qldpc_window_decoder_destroy> win;       // Path::WINDOW (window.hip)
+        Handle<qldpc_layered_decoder, qldpc_layered_decoder_destroy> lay;     // Path::LAYERED (minsum_layered.hip)
+        Handle<qldpc_minsum32_decoder, qldpc_minsum32_decoder_destroy> f32;   // Path::F32 (minsum_f32.hip)
     } sec[2];
     int device = 0, k = 0, n_locs = 0, max_iter = 0, use_osd = 0, flags = 0;
     int nsec = 2, ks[2] = {0, 0};                  // sectors in use (1: a one-sector detector error model, sec[1] stays empty); logicals per sector
     // dem: the sampler draws from a detector error model (dem.hip).  n_locs then counts its mechanisms, d_ptr / d_idx / d_log of a sector hold their
     // projection onto it, and d_thr their thresholds (uint32, zero-padded to a multiple of four).
     bool dem = false;
-    PlanBuf d_thr;
+    DevBuf d_thr;
     // the sampler axis (qldpc_circuit_plan_use_fixed_weight): -1 = the independent draws above, w >= 0 = exactly w faults per trial (fixed_weight.hip).
     // dem_odd: the first mechanism whose threshold differs from mechanism 0's (-1: none), which refuses the switch
     int fixed_weight = -1;
@@ -187,9 +180,9 @@ struct qldpc_circuit_plan {
     uint32_t thr = 0;
     int64_t batch = 0;
     bool nanfree = false;
-    PlanBuf d_loc_type, d_count, d_tally, d_outcome, d_clk;    // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
+    DevBuf d_loc_type, d_count, d_tally, d_outcome, d_clk;     // d_count: [0] Z failures, [4] X failures (int32, 16 bytes apart)
     int ev_bits = 0;                               // bits of an event record that rows may name; 0: the default layout (sector 0's rows, then sector 1's)
-    PlanBuf d_events, d_evflags;                   // qldpc_circuit_plan_decode_events: the records of a batch (staging), its flags
+    DevBuf d_events, d_evflags;                    // qldpc_circuit_plan_decode_events: the records of a batch (staging), its flags
     Path path = Path::FLOOD;
     Osd osd = Osd::OSD0;
     RelayParams rp{};                              // Path::RELAY (relay_bp.hip)
@@ -203,6 +196,11 @@ struct qldpc_circuit_plan {
     int64_t batches = 0;
     int32_t *fail_count(int sector) { return d_count.as<int32_t>() + 4 * sector; }
     bool osd_stage() const { return use_osd && path != Path::RELAY; }            // the judge then adds d_count to the OSD tally slots
+    ~qldpc_circuit_plan() {                        // the events; the sectors' decoder objects and every buffer then release themselves
+        (void)hipSetDevice(device);
+        for (auto &br : pending) { (void)hipEventDestroy(br.a); if (br.b) (void)hipEventDestroy(br.b); }
+        for (auto e : pool) (void)hipEventDestroy(e);
+    }
 };
 using Sector = qldpc_circuit_plan::Sector;
 static const int kPhaseBp[2] = {QLDPC_PHASE_BP_Z, QLDPC_PHASE_BP_X}, kPhaseOsd[2] = {QLDPC_PHASE_OSD_Z, QLDPC_PHASE_OSD_X};
@@ -244,14 +242,6 @@ static void drain_phases(qldpc_circuit_plan *P, bool wait) {
     }
     P->pending.resize(keep);
     (void)hipGetLastError();                               // hipEventQuery's hipErrorNotReady is not an error of the caller
-}
-
-template <class T>
-static int up(DevBuf &b, const std::vector<T> &v) {
-    int rc = b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (rc != QLDPC_OK) return rc;
-    if (!v.empty()) QLDPC_HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return QLDPC_OK;
 }
 
 // What the descriptor holds for one sector (0 = Z: the X checks measure it; 1 = X): the checks' measurements, checks, detectors, logicals.
@@ -382,16 +372,16 @@ static int plan_sector(qldpc_circuit_plan *P, int i, const SectorIn &in, int alp
     // (+-inf messages) still keep the NaN test of kernels.py:328 inside it
     P->nanfree = P->nanfree && inputs_clean(in.prior, (int)n, P->clip, S.h_alpha.data(), P->max_iter);
     const std::vector<uint64_t> lm(in.logmask, in.logmask + n);
-    if ((rc = up(S.d_ptr, sp)) || (rc = up(S.d_idx, si)) || (rc = up(S.d_log, sl)) || (rc = up(S.d_alpha, S.h_alpha)) || (rc = up(S.d_prior, S.h_prior)) ||
-        (rc = up(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
+    if ((rc = upload(S.d_ptr, sp)) || (rc = upload(S.d_idx, si)) || (rc = upload(S.d_log, sl)) || (rc = upload(S.d_alpha, S.h_alpha)) || (rc = upload(S.d_prior, S.h_prior)) ||
+        (rc = upload(S.d_lm, lm)) || (rc = S.d_syn.ensure(Bz * S.nsyn)) || (rc = S.d_true.ensure(Bz * 8)) || (rc = S.d_det.ensure(Bz * n)) ||
         (rc = S.d_llr.ensure(Bz * n * 8)) || (rc = S.d_conv.ensure(Bz)) || (rc = S.d_iter.ensure(Bz * 4)) || (rc = S.d_list.ensure(Bz * 4)))
         return rc;
     return QLDPC_OK;
 }
 
 // what a new plan holds once, whatever it samples: the arguments of both creation entry points, then (after the sectors) the buffers
-static qldpc_circuit_plan *plan_new(int device, int nsec, int n_locs, int max_iter, double damping, double clip_llr, int use_osd, int flags, int64_t batch) {
-    qldpc_circuit_plan *P = new qldpc_circuit_plan();
+static std::unique_ptr<qldpc_circuit_plan> plan_new(int device, int nsec, int n_locs, int max_iter, double damping, double clip_llr, int use_osd, int flags, int64_t batch) {
+    std::unique_ptr<qldpc_circuit_plan> P(new qldpc_circuit_plan());
     P->device = device; P->nsec = nsec; P->n_locs = n_locs;
     P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags; P->damping = damping; P->clip = clip_llr; P->batch = batch;
     P->nanfree = true;
@@ -426,17 +416,17 @@ QLDPC_EXPORT int qldpc_circuit_plan_create(const qldpc_circuit_desc *D, const ql
     const std::vector<uint8_t> loc_type(D->base_ops, D->base_ops + D->base_len);      // error location l = base op l
 
     const SectorIn in[2] = {{gz, prior_z, logmask_z, alpha_val_z, alpha_seq_z, alpha_len_z}, {gx, prior_x, logmask_x, alpha_val_x, alpha_seq_x, alpha_len_x}};
-    qldpc_circuit_plan *P = plan_new(gz->device, 2, (int)loc_type.size(), max_iter, damping, clip_llr, use_osd, flags, batch);
-    auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
+    std::unique_ptr<qldpc_circuit_plan> owner = plan_new(gz->device, 2, (int)loc_type.size(), max_iter, damping, clip_llr, use_osd, flags, batch);
+    qldpc_circuit_plan *const P = owner.get();
     P->k = P->ks[0] = P->ks[1] = D->k; P->p = p; P->thr = bernoulli_threshold(p);
     for (int i = 0; i < 2; i++) {
         std::vector<int32_t> sp;
         std::vector<uint16_t> si;
         std::vector<uint64_t> sl;
-        if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK || (rc = plan_sector(P, i, in[i], alpha_mode, sd[i].nchk, sp, si, sl)) != QLDPC_OK) return fail(rc);
+        if ((rc = build_signatures(D, i, sp, si, sl)) != QLDPC_OK || (rc = plan_sector(P, i, in[i], alpha_mode, sd[i].nchk, sp, si, sl)) != QLDPC_OK) return rc;
     }
-    if ((rc = up(P->d_loc_type, loc_type)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
-    *out = P;
+    if ((rc = upload(P->d_loc_type, loc_type)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return rc;
+    *out = owner.release();
     return QLDPC_OK;
 }
 
@@ -465,8 +455,8 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
     }
     QLDPC_USE_DEVICE(g0->device);
 
-    qldpc_circuit_plan *P = plan_new(g0->device, nsec, (int)D->n_mech, max_iter, damping, clip_llr, use_osd, flags, batch);
-    auto fail = [&](int code) { qldpc_circuit_plan_destroy(P); return code; };
+    std::unique_ptr<qldpc_circuit_plan> owner = plan_new(g0->device, nsec, (int)D->n_mech, max_iter, damping, clip_llr, use_osd, flags, batch);
+    qldpc_circuit_plan *const P = owner.get();
     P->dem = true; P->k = std::max(D->k[0], nsec == 2 ? D->k[1] : 0);
     const size_t nm = (size_t)D->n_mech;
     for (int i = 0; i < nsec; i++) {
@@ -474,15 +464,15 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
         const std::vector<int32_t> sp(D->det_ptr[i], D->det_ptr[i] + nm + 1);
         const std::vector<uint16_t> si(D->det_idx[i], D->det_idx[i] + sp[nm]);
         const std::vector<uint64_t> sl(D->logmask[i], D->logmask[i] + nm);
-        if ((rc = plan_sector(P, i, in[i], alpha_mode, D->layer_rows[i], sp, si, sl)) != QLDPC_OK) return fail(rc);
+        if ((rc = plan_sector(P, i, in[i], alpha_mode, D->layer_rows[i], sp, si, sl)) != QLDPC_OK) return rc;
     }
     std::vector<uint32_t> thr((nm + 3) / 4 * 4, 0u);                      // zero padding: a padded entry never fires
     for (size_t l = 0; l < nm; l++) {
         thr[l] = bernoulli_threshold(D->prob[l]);
         if (P->dem_odd < 0 && thr[l] != thr[0]) P->dem_odd = (int64_t)l;
     }
-    if ((rc = up(P->d_thr, thr)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return fail(rc);
-    *out = P;
+    if ((rc = upload(P->d_thr, thr)) != QLDPC_OK || (rc = plan_common(P)) != QLDPC_OK) return rc;
+    *out = owner.release();
     return QLDPC_OK;
 }
 
@@ -524,7 +514,7 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
     case Path::WINDOW: {  // the window loop in the two brackets: BP = gather + min-sum, OSD = collect + OSD-0 + commit, summed over the windows
         const WindowPlanSlots slots{S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), count};
         const std::function<int(int, bool)> mark = [&](int part, bool open) { return phase_mark(P, part ? ph_osd : ph_bp, s, open); };
-        return window_decoder_lock_and_launch(S.win, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), &slots, &mark, s);
+        return window_decoder_lock_and_launch(S.win.get(), B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), &slots, &mark, s);
     }
     case Path::RELAY: {   // Relay-BP in the BP phase's bracket; no OSD stage (its phase time stays 0)
         std::lock_guard<std::mutex> lk(g->mu);
@@ -534,10 +524,10 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
         break;
     }
     case Path::LAYERED:   // the layered schedule: same outputs, so the OSD stage below takes them unchanged
-        rc = layered_lock_and_launch(S.lay, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
+        rc = layered_lock_and_launch(S.lay.get(), B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
         break;
     case Path::F32:       // single precision: same outputs (the posteriors widened to f64)
-        rc = minsum32_lock_and_launch(S.f32, B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
+        rc = minsum32_lock_and_launch(S.f32.get(), B, S.d_syn.as<int8_t>(), S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), s);
         break;
     case Path::DECIM: {   // guided decimation: same outputs too; iter_bias -1 as for Relay-BP, the rounds go where its legs go
         std::lock_guard<std::mutex> lk(g->mu);
@@ -728,7 +718,7 @@ static int inputs_supported(const qldpc_circuit_plan *P, int params_rc, F graph_
 }
 
 // `bytes` in one buffer of every sector in use
-static int ensure_each(qldpc_circuit_plan *P, PlanBuf Sector::*buf, size_t bytes) {
+static int ensure_each(qldpc_circuit_plan *P, DevBuf Sector::*buf, size_t bytes) {
     QLDPC_USE_DEVICE(P->device);
     for (int i = 0; i < P->nsec; i++)
         if (const int rc = (P->sec[i].*buf).ensure(bytes); rc != QLDPC_OK) return rc;
@@ -737,13 +727,16 @@ static int ensure_each(qldpc_circuit_plan *P, PlanBuf Sector::*buf, size_t bytes
 
 // One handle per sector in use, all or none: create(S, i, &h) builds sector i's; if one fails, what was built is destroyed and the plan keeps what it
 // had.  Then every sector's `slot` takes its new handle and the one it held (if any) is destroyed.
-template <class H, class Create>
-static int build_handles(qldpc_circuit_plan *P, H *Sector::*slot, void (*destroy)(H *), Create create) {
+template <class Ptr, class Create>
+static int build_handles(qldpc_circuit_plan *P, Ptr Sector::*slot, Create create) {
     QLDPC_USE_DEVICE(P->device);
-    H *h[2] = {nullptr, nullptr};
-    for (int i = 0; i < P->nsec; i++)
-        if (const int rc = create(P->sec[i], i, &h[i]); rc != QLDPC_OK) { destroy(h[0]); return rc; }
-    for (int i = 0; i < P->nsec; i++) { destroy(P->sec[i].*slot); P->sec[i].*slot = h[i]; }
+    Ptr h[2];
+    for (int i = 0; i < P->nsec; i++) {
+        typename Ptr::pointer raw = nullptr;
+        if (const int rc = create(P->sec[i], i, &raw); rc != QLDPC_OK) return rc;
+        h[i].reset(raw);
+    }
+    for (int i = 0; i < P->nsec; i++) P->sec[i].*slot = std::move(h[i]);
     return QLDPC_OK;
 }
 
@@ -778,7 +771,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_window(qldpc_circuit_plan *P, int window
         QLDPC_REQUIRE(P->sec[i].layer_rows > 0 && P->sec[i].nsyn % P->sec[i].layer_rows == 0,
                       "sector %d of the detector error model has layer_rows = %d, which %s: sliding-window decoding needs the rows of a syndrome cycle", i,
                       P->sec[i].layer_rows, P->sec[i].layer_rows > 0 ? "does not divide its detectors" : "means no layers were given");
-    rc = build_handles(P, &Sector::win, qldpc_window_decoder_destroy, [&](const Sector &S, int, qldpc_window_decoder **out) {
+    rc = build_handles(P, &Sector::win, [&](const Sector &S, int, qldpc_window_decoder **out) {
         return window_decoder_create_tab(S.g, S.layer_rows, window, commit, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
     });
     if (rc == QLDPC_OK) P->path = Path::WINDOW;
@@ -789,7 +782,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *P, const int
     int rc = switch_allowed(P, Path::LAYERED);
     if (rc != QLDPC_OK) return rc;
     const int32_t *const row_layer[2] = {row_layer_z, row_layer_x};
-    rc = build_handles(P, &Sector::lay, qldpc_layered_decoder_destroy, [&](const Sector &S, int i, qldpc_layered_decoder **out) {
+    rc = build_handles(P, &Sector::lay, [&](const Sector &S, int i, qldpc_layered_decoder **out) {
         return layered_decoder_create_tab(S.g, row_layer[i], S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
     });
     if (rc == QLDPC_OK) P->path = Path::LAYERED;
@@ -811,7 +804,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double
 QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
     int rc = switch_allowed(P, Path::F32);
     if (rc != QLDPC_OK || P->path == Path::F32) return rc;                  // asked again: nothing to replace
-    rc = build_handles(P, &Sector::f32, qldpc_minsum32_decoder_destroy, [&](const Sector &S, int, qldpc_minsum32_decoder **out) {
+    rc = build_handles(P, &Sector::f32, [&](const Sector &S, int, qldpc_minsum32_decoder **out) {
         return minsum32_decoder_create_tab(S.g, S.h_prior.data(), P->max_iter, S.h_alpha, P->clip, P->flags & QLDPC_FLAG_PUBLIC_MASK, out);
     });
     if (rc == QLDPC_OK) P->path = Path::F32;
@@ -866,7 +859,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_set_event_layout(qldpc_circuit_plan *P, int3
     int rc = QLDPC_OK;
     QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a decode that is still enqueued reads the tables replaced here
     for (int i = 0; i < P->nsec; i++)
-        if (is_tab[i] && (rc = up(P->sec[i].d_evtab, std::vector<int32_t>(tab[i], tab[i] + P->sec[i].nsyn))) != QLDPC_OK) return rc;
+        if (is_tab[i] && (rc = upload(P->sec[i].d_evtab, std::vector<int32_t>(tab[i], tab[i] + P->sec[i].nsyn))) != QLDPC_OK) return rc;
     for (int i = 0; i < P->nsec; i++) { P->sec[i].ev_tab = is_tab[i]; P->sec[i].ev_base = base[i]; }
     P->ev_bits = n_bits;
     return QLDPC_OK;
@@ -971,11 +964,4 @@ QLDPC_EXPORT int qldpc_circuit_plan_unpack_events(qldpc_circuit_plan *P, int64_t
     return QLDPC_OK;
 }
 
-QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) {
-    if (!P) return;
-    (void)hipSetDevice(P->device);
-    for (Sector &S : P->sec) { qldpc_window_decoder_destroy(S.win); qldpc_layered_decoder_destroy(S.lay); qldpc_minsum32_decoder_destroy(S.f32); }
-    for (auto &br : P->pending) { (void)hipEventDestroy(br.a); if (br.b) (void)hipEventDestroy(br.b); }
-    for (auto e : P->pool) (void)hipEventDestroy(e);
-    delete P;                                      // every PlanBuf releases itself
-}
+QLDPC_EXPORT void qldpc_circuit_plan_destroy(qldpc_circuit_plan *P) { delete P; }

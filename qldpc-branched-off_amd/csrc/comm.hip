@@ -76,18 +76,18 @@ struct qldpc_comm {
     std::vector<int> devices;
     std::vector<ncclComm_t> comms;
     std::vector<hipStream_t> streams;
-    std::vector<int64_t *> bufs;          // device int64[QLDPC_TALLY_SLOTS] per local rank
+    std::vector<DevBuf> bufs;             // device int64[QLDPC_TALLY_SLOTS] per local rank
+    ~qldpc_comm();                        // per rank on its device: the stream waited for and destroyed, the buffer freed, the communicator destroyed
 };
 
 static int comm_alloc_local(qldpc_comm *c) {
     for (size_t i = 0; i < c->devices.size(); i++) {
         QLDPC_HIP_TRY(hipSetDevice(c->devices[i]));
         hipStream_t s = nullptr;
-        int64_t *b = nullptr;
         QLDPC_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         c->streams.push_back(s);
-        QLDPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b), QLDPC_TALLY_SLOTS * sizeof(int64_t)));
-        c->bufs.push_back(b);
+        c->bufs.emplace_back();
+        if (const int rc = c->bufs.back().ensure(QLDPC_TALLY_SLOTS * sizeof(int64_t)); rc != QLDPC_OK) return rc;
     }
     return QLDPC_OK;
 }
@@ -102,15 +102,16 @@ QLDPC_EXPORT int qldpc_comm_init_all(int ndev, const int *devices, qldpc_comm **
     QLDPC_REQUIRE(ndev <= count, "%d devices requested, %d visible", ndev, count);
     RcclApi *api = rccl();
     if (!api) return QLDPC_ERR_UNSUPPORTED;
-    qldpc_comm *c = new qldpc_comm();
+    std::unique_ptr<qldpc_comm> C(new qldpc_comm());
+    qldpc_comm *const c = C.get();
     c->nranks = ndev;
     for (int i = 0; i < ndev; i++) c->devices.push_back(devices ? devices[i] : i);
     c->comms.assign(ndev, nullptr);
     ncclResult_t r = api->CommInitAll(c->comms.data(), ndev, c->devices.data());
-    if (r != ncclSuccess) { set_error("ncclCommInitAll failed: %s", api->GetErrorString(r)); delete c; return QLDPC_ERR_HIP; }
-    int rc = comm_alloc_local(c);
-    if (rc != QLDPC_OK) { qldpc_comm_destroy(c); return rc; }
-    *out = c;
+    if (r != ncclSuccess) { set_error("ncclCommInitAll failed: %s", api->GetErrorString(r)); return QLDPC_ERR_HIP; }
+    const int rc = comm_alloc_local(c);
+    if (rc != QLDPC_OK) return rc;
+    *out = C.release();
     return QLDPC_OK;
 }
 
@@ -135,15 +136,16 @@ QLDPC_EXPORT int qldpc_comm_init_rank(int nranks, int rank, const uint8_t *id128
     if (!api) return QLDPC_ERR_UNSUPPORTED;
     ncclUniqueId id;
     std::memcpy(&id, id128, sizeof(id));
-    qldpc_comm *c = new qldpc_comm();
+    std::unique_ptr<qldpc_comm> C(new qldpc_comm());
+    qldpc_comm *const c = C.get();
     c->nranks = nranks;
     c->devices.push_back(device);
     c->comms.assign(1, nullptr);
     ncclResult_t r = api->CommInitRank(&c->comms[0], nranks, id, rank);
-    if (r != ncclSuccess) { set_error("ncclCommInitRank failed: %s", api->GetErrorString(r)); delete c; return QLDPC_ERR_HIP; }
-    int rc = comm_alloc_local(c);
-    if (rc != QLDPC_OK) { qldpc_comm_destroy(c); return rc; }
-    *out = c;
+    if (r != ncclSuccess) { set_error("ncclCommInitRank failed: %s", api->GetErrorString(r)); return QLDPC_ERR_HIP; }
+    const int rc = comm_alloc_local(c);
+    if (rc != QLDPC_OK) return rc;
+    *out = C.release();
     return QLDPC_OK;
 }
 
@@ -164,17 +166,17 @@ QLDPC_EXPORT int qldpc_tally_allreduce(qldpc_comm *c, int64_t *tallies) {
     const size_t bytes = QLDPC_TALLY_SLOTS * sizeof(int64_t);
     for (int i = 0; i < nl; i++) {
         QLDPC_HIP_TRY(hipSetDevice(c->devices[i]));
-        QLDPC_HIP_TRY(hipMemcpyAsync(c->bufs[i], tallies + (size_t)i * QLDPC_TALLY_SLOTS, bytes, hipMemcpyHostToDevice, c->streams[i]));
+        QLDPC_HIP_TRY(hipMemcpyAsync(c->bufs[i].p, tallies + (size_t)i * QLDPC_TALLY_SLOTS, bytes, hipMemcpyHostToDevice, c->streams[i]));
     }
     QLDPC_RCCL_TRY(api, api->GroupStart());
     for (int i = 0; i < nl; i++) {
-        ncclResult_t r = api->AllReduce(c->bufs[i], c->bufs[i], QLDPC_TALLY_SLOTS, ncclInt64, ncclSum, c->comms[i], c->streams[i]);
+        ncclResult_t r = api->AllReduce(c->bufs[i].p, c->bufs[i].p, QLDPC_TALLY_SLOTS, ncclInt64, ncclSum, c->comms[i], c->streams[i]);
         if (r != ncclSuccess) { (void)api->GroupEnd(); set_error("ncclAllReduce failed: %s", api->GetErrorString(r)); return QLDPC_ERR_HIP; }
     }
     QLDPC_RCCL_TRY(api, api->GroupEnd());
     for (int i = 0; i < nl; i++) {
         QLDPC_HIP_TRY(hipSetDevice(c->devices[i]));
-        QLDPC_HIP_TRY(hipMemcpyAsync(tallies + (size_t)i * QLDPC_TALLY_SLOTS, c->bufs[i], bytes, hipMemcpyDeviceToHost, c->streams[i]));
+        QLDPC_HIP_TRY(hipMemcpyAsync(tallies + (size_t)i * QLDPC_TALLY_SLOTS, c->bufs[i].p, bytes, hipMemcpyDeviceToHost, c->streams[i]));
         QLDPC_HIP_TRY(hipStreamSynchronize(c->streams[i]));
     }
     return QLDPC_OK;
@@ -205,17 +207,17 @@ QLDPC_EXPORT int qldpc_comm_group_end(void) {
     return QLDPC_OK;
 }
 
-QLDPC_EXPORT void qldpc_comm_destroy(qldpc_comm *c) {
-    if (!c) return;
+qldpc_comm::~qldpc_comm() {
     RcclApi *api = rccl();
     int prev = -1;
     (void)hipGetDevice(&prev);
-    for (size_t i = 0; i < c->devices.size(); i++) {
-        (void)hipSetDevice(c->devices[i]);
-        if (i < c->streams.size() && c->streams[i]) { (void)hipStreamSynchronize(c->streams[i]); (void)hipStreamDestroy(c->streams[i]); }
-        if (i < c->bufs.size() && c->bufs[i]) (void)hipFree(c->bufs[i]);
-        if (api && i < c->comms.size() && c->comms[i]) (void)api->CommDestroy(c->comms[i]);
+    for (size_t i = 0; i < devices.size(); i++) {
+        (void)hipSetDevice(devices[i]);
+        if (i < streams.size() && streams[i]) { (void)hipStreamSynchronize(streams[i]); (void)hipStreamDestroy(streams[i]); }
+        if (i < bufs.size()) bufs[i].release();
+        if (api && i < comms.size() && comms[i]) (void)api->CommDestroy(comms[i]);
     }
     if (prev >= 0) (void)hipSetDevice(prev);
-    delete c;
 }
+
+QLDPC_EXPORT void qldpc_comm_destroy(qldpc_comm *c) { delete c; }

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -66,14 +67,42 @@ struct DeviceScope {
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set it once per (device, kernel), thread-safe.
 int ensure_max_lds(int device, const void *func, int bytes);
 
-// Grow-only device buffer (never shrinks; freed with the owner).
+// Grow-only device buffer (never shrinks).  It OWNS its allocation: freed when the object that holds it is deleted, so a handle that gains a buffer
+// needs no line in its destroy function.  Move-only.  Every hipMalloc / hipFree of the library is in ensure() / release() (the process-lifetime
+// timer buffer of gf2.hip aside), which keep the count behind qldpc_device_memory.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    ~DevBuf() { release(); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
     int ensure(size_t bytes);
-    void release();
+    void release();                                  // idempotent
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+
+// Pinned host memory with the same rules (grow-only, owning, move-only): every hipHostMalloc / hipHostFree of the library.
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    ~PinnedBuf() { release(); }
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    PinnedBuf(PinnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    int ensure(size_t bytes);
+    void release();
+};
+
+// unique_ptr to a library handle that its public destroy function releases: Handle<qldpc_graph, qldpc_graph_destroy>
+template <auto Destroy> struct HandleDelete { template <class H> void operator()(H *h) const { Destroy(h); } };
+template <class H, auto Destroy> using Handle = std::unique_ptr<H, HandleDelete<Destroy>>;
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 
@@ -101,7 +130,6 @@ class HostStage {
     enum Wait { kCopies, kStream, kDevice };
     HostStage() = default;
     HostStage(DevBuf &slab, std::mutex &mu) : slab_(&slab), lock_(mu) {}
-    ~HostStage() { if (!slab_ && base_) (void)hipFree(base_); }
     HostStage(const HostStage &) = delete;
     HostStage &operator=(const HostStage &) = delete;
 
@@ -116,7 +144,7 @@ class HostStage {
     int stage();
     int finish(const char *what, Wait wait);        // a failed wait: "<what> failed: <hip error string>"
     // finish() for a latency-bound call: outputs of at most 1 MiB come back in ONE copy through the pinned buffer (grown here) and are scattered on the host
-    int finish_pinned(const char *what, void *&pin, size_t &pin_cap);
+    int finish_pinned(const char *what, PinnedBuf &pin);
     // one region into a host array, for an output that the call downloads only once it has looked at another (declared as scratch)
     template <class T> int fetch(Staged<T> h, T *host) const { return fetch_bytes(h.id, host); }
 
@@ -130,13 +158,10 @@ class HostStage {
     }
     StageLayout layout_;
     Copy copies_[StageLayout::kMaxRegions];
-    DevBuf *slab_ = nullptr;
+    DevBuf own_, *slab_ = nullptr;                   // the temporary allocation, or the caller's slab
     std::unique_lock<std::mutex> lock_;
     unsigned char *base_ = nullptr;
 };
-
-// The call checks shared by the decoder objects whose outputs are (err, llr, conv, iter): layered and f32.
-int decoder_check_call(const void *decoder, int64_t B, const void *synd, const void *err, const void *llr, const void *conv, const void *iter);
 
 // Compute units of a device (256 when the runtime does not say): what the persistent grids are sized by.
 int cu_count(int device);
@@ -148,10 +173,91 @@ struct StreamHandover {
     hipEvent_t event = nullptr;
     hipStream_t stream = nullptr;
     bool used = false;
+    StreamHandover() = default;
+    ~StreamHandover();
+    StreamHandover(const StreamHandover &) = delete;
+    StreamHandover &operator=(const StreamHandover &) = delete;
     int acquire(hipStream_t s);
     int release(hipStream_t s);
-    void destroy();
 };
+
+// The destructor's body of a handle that has a hand-over: select its device and, when the hand-over was used, wait for what is in flight.  Members are
+// destroyed after a destructor's body, so the buffers are freed only then.  (A base class's destructor runs AFTER the derived members are gone,
+// which is why the decoder objects below call this from their own destructor.)
+inline void quiesce(int device, const StreamHandover &hand) {
+    (void)hipSetDevice(device);
+    if (hand.used) (void)hipDeviceSynchronize();
+}
+
+// What the decoder objects with the outputs (err, llr, conv, iter) hold alike on the host: layered (minsum_layered.hip) and f32 (minsum_f32.hip).
+// A decoder adds its tables, a destructor that calls quiesce(device, hand), and
+//     int launch(int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s);      callers hold mu
+// which fills its kernel's argument struct, picks the instantiation and goes through decoder_launch.
+struct DecoderBase {
+    const qldpc_graph *g = nullptr;
+    int device = 0, m = 0, n = 0, max_iter = 0, flags = 0;
+    int block = 0, lds = 0, grid_cap = 0;
+    DevBuf d_prior, d_alpha, d_queue;
+    // the queue word (and a decoder's slabs) are handed from stream to stream like a graph handle's workspaces
+    std::mutex mu;
+    StreamHandover hand;
+};
+
+// Enqueues kern(A) for B shots on s: the queue word zeroed in stream order, min(B, grid_cap) workgroups of D.block threads and D.lds bytes.
+template <class Args>
+int decoder_launch(DecoderBase &D, void (*kern)(Args), int max_lds, const Args &A, int64_t B, hipStream_t s) {
+    int rc = D.hand.acquire(s);
+    if (rc != QLDPC_OK) return rc;
+    auto launch = [&]() -> int {
+        QLDPC_HIP_TRY(hipMemsetAsync(D.d_queue.p, 0, 16, s));
+        const int rcl = ensure_max_lds(D.device, reinterpret_cast<const void *>(kern), max_lds);
+        if (rcl != QLDPC_OK) return rcl;
+        const unsigned grid = (unsigned)std::min<int64_t>(B, D.grid_cap);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(D.block), (size_t)D.lds, s, A);
+        QLDPC_HIP_TRY(hipGetLastError());
+        return QLDPC_OK;
+    };
+    rc = launch();
+    const int rel = D.hand.release(s);              // always: a failing call may have enqueued work the next stream has to wait for
+    return rc != QLDPC_OK ? rc : rel;
+}
+
+template <class D>
+int decoder_lock_and_launch(D *dec, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(dec->mu);
+    return dec->launch(B, d_synd, d_err, d_llr, d_conv, d_iter, s);
+}
+
+// The call checks of the two entry points below.
+int decoder_check_call(const void *decoder, int64_t B, const void *synd, const void *err, const void *llr, const void *conv, const void *iter);
+
+// qldpc_*_decode_batch_dev of such a decoder: device pointers, enqueued on `stream`
+template <class D>
+int decoder_decode_dev(D *dec, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, void *stream) {
+    const int rc = decoder_check_call(dec, B, d_synd, d_err, d_llr, d_conv, d_iter);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(dec->device);
+    if (B == 0) return QLDPC_OK;
+    return decoder_lock_and_launch(dec, B, d_synd, d_err, d_llr, d_conv, d_iter, reinterpret_cast<hipStream_t>(stream));
+}
+
+// qldpc_*_decode_batch: host pointers, staged, decoded on the null stream and waited for ("<what> failed: ..." when the wait fails)
+template <class D>
+int decoder_decode_host(D *dec, const char *what, int64_t B, const int8_t *synd, int8_t *err, double *llr, uint8_t *conv, int32_t *iter) {
+    int rc = decoder_check_call(dec, B, synd, err, llr, conv, iter);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(dec->device);
+    if (B == 0) return QLDPC_OK;
+    HostStage S;
+    const auto ds = S.in(synd, B, dec->m);
+    const auto de = S.out(err, B, dec->n);
+    const auto dl = S.out(llr, B, dec->n);
+    const auto dc = S.out(conv, B);
+    const auto di = S.out(iter, B);
+    if ((rc = S.stage()) != QLDPC_OK) return rc;
+    rc = decoder_lock_and_launch(dec, B, S[ds], S[de], S[dl], S[dc], S[di], nullptr);
+    return rc != QLDPC_OK ? rc : S.finish(what, HostStage::kStream);
+}
 
 // clocks.h: what the shader-clock probe stamped
 double clock_probe_median(const unsigned long long *pairs, int slots);   // MHz; 0 when nothing was stamped
@@ -180,6 +286,16 @@ struct qldpc_graph {
     uint16_t *d_ell_col_s = nullptr; // [round_up(max_row_deg, 8)][m] indexed by row slot
     uint32_t *d_ell_var_s = nullptr; // [max_col_deg][n] indexed by column slot: (row slot << 8) | position-in-row, ascending ROW order
     int32_t *d_identity = nullptr;   // [max(m, n)] 0, 1, 2, ... (the natural-order "permutation")
+    // The pointers above and below (and d_col_rows) are VIEWS that the launchers read; the memory behind them is owned here, so a table added to the
+    // handle is freed with it.  own() uploads a host vector into a new owned buffer and sets the view (NULL when it fails).
+    mutable std::vector<qldpc::DevBuf> owned;
+    template <class T> int own(T **view, const std::vector<T> &v) const {
+        qldpc::DevBuf b;
+        const int rc = qldpc::upload(b, v);
+        *view = rc == QLDPC_OK ? b.as<T>() : nullptr;
+        if (rc == QLDPC_OK) owned.push_back(std::move(b));
+        return rc;
+    }
     int32_t *d_regown = nullptr;     // [m][16] edge-ownership records of the regular (6,3) kernel (regular_own.h), NULL where the graph has no assignment; built at creation
     // Device workspaces of the decode / OSD kernels.  `mu` guards the bookkeeping while launches are enqueued; the buffers themselves
     // are protected in STREAM order: every user calls ws_acquire(stream) before its launches and ws_release(stream) after them
@@ -196,11 +312,19 @@ struct qldpc_graph {
     mutable qldpc::DevBuf ws_io;
     // alpha tables already on the device (guarded by mu).  A table is uploaded once from a pinned host copy and never overwritten, so
     // the *_dev entry points stay pure enqueues (no synchronisation) however the alpha schedule changes between calls.
-    struct AlphaEntry { std::vector<double> host; double *pinned = nullptr; double *dev = nullptr; hipEvent_t ready = nullptr; hipStream_t stream = nullptr; };
+    struct AlphaEntry {                          // owns its pinned copy, its device copy and its event
+        std::vector<double> host;
+        qldpc::PinnedBuf pinned;
+        qldpc::DevBuf dev;
+        hipEvent_t ready = nullptr;
+        hipStream_t stream = nullptr;
+        AlphaEntry() = default;
+        AlphaEntry(AlphaEntry &&o) noexcept : host(std::move(o.host)), pinned(std::move(o.pinned)), dev(std::move(o.dev)), ready(o.ready), stream(o.stream) { o.ready = nullptr; }
+        ~AlphaEntry() { if (ready) (void)hipEventDestroy(ready); }
+    };
     mutable std::vector<AlphaEntry> alpha_cache;
     int alpha_table(const std::vector<double> &tab, hipStream_t stream, const double **d_out) const;   // callers hold mu
-    mutable void *pin = nullptr;     // pinned host staging for small results
-    mutable size_t pin_cap = 0;
+    mutable qldpc::PinnedBuf pin;    // pinned host staging for small results
     mutable int gf2_rank = -1;       // rank of H over GF(2), computed on first OSD use
     mutable int osd_path = -1, osd_detail = 0;   // what the last OSD-0 launch on this handle took (QLDPC_OSD_PATH_*, QLDPC_OSD_DETAIL_*; guarded by mu)
     mutable uint16_t *d_col_rows = nullptr;   // [n][max_col_deg] rows of every column (ascending, padded with m), built on first OSD use

@@ -207,5 +207,5 @@ QLDPC_EXPORT int qldpc_minsum_decode_batch(const qldpc_graph *g, int64_t B, cons
     rc = decode_dev_impl(g, B, S[ds], S[dp], max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, damping, clip_llr, flags, prior_finite, prior_le_clip,
                          S[de], S[dl], S[dc], S[di], nullptr, prior);
     if (rc != QLDPC_OK) return rc;
-    return out_llr ? S.finish_pinned("min-sum decode", g->pin, g->pin_cap) : S.finish("min-sum decode", HostStage::kCopies);
+    return out_llr ? S.finish_pinned("min-sum decode", g->pin) : S.finish("min-sum decode", HostStage::kCopies);
 }

@@ -1046,12 +1046,10 @@ __global__ __launch_bounds__(1024) void osd0_lds_kernel(OsdLdsArgs P) {
 int ensure_col_rows(const qldpc_graph *g) {
     if (g->d_col_rows) return QLDPC_OK;
     const int cdeg = std::max(g->max_col_deg, 1);
-    std::vector<uint16_t> cr((size_t)std::max(g->n, 1) * cdeg, (uint16_t)g->m);
+    std::vector<uint16_t> cr((size_t)std::max(g->n, 1) * cdeg + 8, (uint16_t)g->m);      // + 8: the 16 spare bytes behind the table
     for (int j = 0; j < g->n; j++)
         for (int k = g->colptr[j]; k < g->colptr[j + 1]; k++) cr[(size_t)j * cdeg + (k - g->colptr[j])] = (uint16_t)g->rowidx[k];
-    QLDPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g->d_col_rows), cr.size() * 2 + 16));
-    QLDPC_HIP_TRY(hipMemcpy(g->d_col_rows, cr.data(), cr.size() * 2, hipMemcpyHostToDevice));
-    return QLDPC_OK;
+    return g->own(&g->d_col_rows, cr);
 }
 
 // rank of H over GF(2) (host, once per graph): the sweep above can stop as soon as this many pivots exist
@@ -1167,6 +1165,8 @@ namespace qldpc {
 unsigned long long *osd_timer_buffer() {
 #ifdef QLDPC_OSD_TIMERS
     static std::mutex mu;
+    // process lifetime, deliberately raw and never freed: an owning static would call hipFree after the runtime has shut down.  The one allocation
+    // of the library outside DevBuf, and outside the count of qldpc_device_memory.
     static unsigned long long *d_buf[64] = {nullptr};
     std::lock_guard<std::mutex> lk(mu);
     int dev = 0;

@@ -5,6 +5,7 @@
 #include "regular_own.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 
 namespace qldpc {
@@ -71,9 +72,12 @@ double clock_probe_median(const unsigned long long *pairs, int slots) {
     return v[v.size() / 2];
 }
 
+// what qldpc_device_memory reports: the DevBufs that hold an allocation, and their bytes
+static std::atomic<int64_t> g_live_buffers{0}, g_live_bytes{0};
+
 int DevBuf::ensure(size_t bytes) {
     if (bytes <= cap && p) return QLDPC_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    release();
     if (bytes == 0) bytes = 256;
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
@@ -82,11 +86,28 @@ int DevBuf::ensure(size_t bytes) {
         return QLDPC_ERR_HIP;
     }
     cap = bytes;
+    g_live_buffers += 1; g_live_bytes += (int64_t)bytes;
     return QLDPC_OK;
 }
 
 void DevBuf::release() {
-    if (p) (void)hipFree(p);
+    if (!p) return;
+    (void)hipFree(p);
+    g_live_buffers -= 1; g_live_bytes -= (int64_t)cap;
+    p = nullptr;
+    cap = 0;
+}
+
+int PinnedBuf::ensure(size_t bytes) {
+    if (bytes <= cap && p) return QLDPC_OK;
+    release();
+    QLDPC_HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    cap = bytes;
+    return QLDPC_OK;
+}
+
+void PinnedBuf::release() {
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
 }
@@ -107,21 +128,16 @@ int StreamHandover::release(hipStream_t s) {
     stream = s; used = true;
     return QLDPC_OK;
 }
-void StreamHandover::destroy() {
+StreamHandover::~StreamHandover() {
     if (event) (void)hipEventDestroy(event);
-    event = nullptr;
 }
 
 int HostStage::stage() {
     QLDPC_REQUIRE(!layout_.overflow, "a buffer's byte count does not fit size_t, a dimension is negative or there are more than %d buffers", StageLayout::kMaxRegions);
-    if (slab_) {
-        const int rc = slab_->ensure(layout_.bytes());
-        if (rc != QLDPC_OK) return rc;
-        base_ = slab_->as<unsigned char>();
-    } else {
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&base_), layout_.bytes());
-        if (e != hipSuccess) { set_error("hipMalloc(%zu bytes) failed: %s", layout_.bytes(), hipGetErrorString(e)); base_ = nullptr; return QLDPC_ERR_HIP; }
-    }
+    DevBuf &b = slab_ ? *slab_ : own_;
+    const int rc = b.ensure(layout_.bytes());
+    if (rc != QLDPC_OK) return rc;
+    base_ = b.as<unsigned char>();
     for (int i = 0; i < layout_.count; i++) {
         const StageLayout::Region &r = layout_.regions[i];
         if (r.bytes == 0) continue;
@@ -149,7 +165,7 @@ int HostStage::fetch_bytes(int id, void *host) const {
     return QLDPC_OK;
 }
 
-int HostStage::finish_pinned(const char *what, void *&pin, size_t &pin_cap) {
+int HostStage::finish_pinned(const char *what, PinnedBuf &pin) {
     const size_t kPin = (size_t)1 << 20;
     size_t lo = layout_.total, hi = 0;
     for (int i = 0; i < layout_.count; i++) {
@@ -157,18 +173,13 @@ int HostStage::finish_pinned(const char *what, void *&pin, size_t &pin_cap) {
         if (copies_[i].out && r.bytes) { lo = std::min(lo, r.off); hi = std::max(hi, r.off + r.bytes); }
     }
     if (hi <= lo || hi - lo > kPin) return finish(what, kCopies);
-    if (pin_cap < kPin) {
-        if (pin) (void)hipHostFree(pin);
-        pin = nullptr; pin_cap = 0;
-        QLDPC_HIP_TRY(hipHostMalloc(&pin, kPin, hipHostMallocDefault));
-        pin_cap = kPin;
-    }
-    QLDPC_HIP_TRY(hipMemcpyAsync(pin, base_ + lo, hi - lo, hipMemcpyDeviceToHost, nullptr));
+    if (const int rc = pin.ensure(kPin); rc != QLDPC_OK) return rc;
+    QLDPC_HIP_TRY(hipMemcpyAsync(pin.p, base_ + lo, hi - lo, hipMemcpyDeviceToHost, nullptr));
     const hipError_t e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(e)); return QLDPC_ERR_HIP; }
     for (int i = 0; i < layout_.count; i++) {
         const StageLayout::Region &r = layout_.regions[i];
-        if (copies_[i].out && r.bytes) std::memcpy(copies_[i].out, static_cast<const unsigned char *>(pin) + (r.off - lo), r.bytes);
+        if (copies_[i].out && r.bytes) std::memcpy(copies_[i].out, static_cast<const unsigned char *>(pin.p) + (r.off - lo), r.bytes);
     }
     return QLDPC_OK;
 }
@@ -191,26 +202,25 @@ int qldpc_graph::alpha_table(const std::vector<double> &tab, hipStream_t stream,
     for (const AlphaEntry &e : alpha_cache)
         if (e.host == tab) {
             if (stream != e.stream) QLDPC_HIP_TRY(hipStreamWaitEvent(stream, e.ready, 0));   // uploaded on another stream: order behind it
-            *d_out = e.dev;
+            *d_out = e.dev.as<double>();
             return QLDPC_OK;
         }
     if (alpha_cache.size() >= 64) {            // a caller cycling through > 64 schedules: start over once everything in flight is done
         QLDPC_HIP_TRY(hipDeviceSynchronize());
-        for (AlphaEntry &e : alpha_cache) { if (e.dev) (void)hipFree(e.dev); if (e.pinned) (void)hipHostFree(e.pinned); if (e.ready) (void)hipEventDestroy(e.ready); }
         alpha_cache.clear();
     }
-    AlphaEntry e;
+    AlphaEntry e;                               // a failure below releases what it made
     e.host = tab;
     const size_t bytes = std::max<size_t>(tab.size(), 1) * sizeof(double);
-    QLDPC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e.pinned), bytes, hipHostMallocDefault));
-    std::memcpy(e.pinned, tab.data(), tab.size() * sizeof(double));
-    if (hipMalloc(reinterpret_cast<void **>(&e.dev), bytes) != hipSuccess) { (void)hipHostFree(e.pinned); set_error("hipMalloc failed for an alpha table"); return QLDPC_ERR_HIP; }
-    QLDPC_HIP_TRY(hipMemcpyAsync(e.dev, e.pinned, tab.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    int rc;
+    if ((rc = e.pinned.ensure(bytes)) != QLDPC_OK || (rc = e.dev.ensure(bytes)) != QLDPC_OK) return rc;
+    std::memcpy(e.pinned.p, tab.data(), tab.size() * sizeof(double));
+    QLDPC_HIP_TRY(hipMemcpyAsync(e.dev.p, e.pinned.p, tab.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     QLDPC_HIP_TRY(hipEventCreateWithFlags(&e.ready, hipEventDisableTiming));
     QLDPC_HIP_TRY(hipEventRecord(e.ready, stream));
     e.stream = stream;
-    alpha_cache.push_back(e);
-    *d_out = e.dev;
+    *d_out = e.dev.as<double>();
+    alpha_cache.push_back(std::move(e));
     return QLDPC_OK;
 }
 
@@ -226,11 +236,10 @@ QLDPC_EXPORT int qldpc_device_count(void) {
     return count;
 }
 
-template <class T>
-static int upload(T **dst, const std::vector<T> &src) {
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    QLDPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(dst), bytes));
-    if (!src.empty()) QLDPC_HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+// A diagnostic of the library's own device allocations (include/qldpc_hip.h).
+QLDPC_EXPORT int qldpc_device_memory(int64_t *buffers, int64_t *bytes) {
+    if (buffers) *buffers = g_live_buffers.load();
+    if (bytes) *bytes = g_live_bytes.load();
     return QLDPC_OK;
 }
 
@@ -251,7 +260,8 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
     int rc = use_device(device);
     if (rc != QLDPC_OK) return rc;
 
-    qldpc_graph *g = new qldpc_graph();
+    Handle<qldpc_graph, qldpc_graph_destroy> G(new qldpc_graph());      // (the deleter selects the device)
+    qldpc_graph *const g = G.get();
     g->m = m; g->n = n; g->nnz = nnz; g->device = device;
     g->indptr.assign(indptr, indptr + m + 1);
     g->indices.assign(indices, indices + nnz);
@@ -269,12 +279,12 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         }
     }
     for (int j = 0; j < n; j++) g->max_col_deg = std::max(g->max_col_deg, g->colptr[j + 1] - g->colptr[j]);
-    rc = upload(&g->d_indptr, g->indptr);
-    if (rc == QLDPC_OK) rc = upload(&g->d_indices, g->indices);
-    if (rc == QLDPC_OK) rc = upload(&g->d_colptr, g->colptr);
-    if (rc == QLDPC_OK) rc = upload(&g->d_rowidx, g->rowidx);
-    if (rc == QLDPC_OK) rc = upload(&g->d_csc2csr, g->csc2csr);
-    if (rc == QLDPC_OK) rc = upload(&g->d_csr2csc, g->csr2csc);
+    rc = g->own(&g->d_indptr, g->indptr);
+    if (rc == QLDPC_OK) rc = g->own(&g->d_indices, g->indices);
+    if (rc == QLDPC_OK) rc = g->own(&g->d_colptr, g->colptr);
+    if (rc == QLDPC_OK) rc = g->own(&g->d_rowidx, g->rowidx);
+    if (rc == QLDPC_OK) rc = g->own(&g->d_csc2csr, g->csc2csr);
+    if (rc == QLDPC_OK) rc = g->own(&g->d_csr2csc, g->csr2csc);
     if (rc == QLDPC_OK && n < 65535 && m < (1 << 24) && g->max_row_deg < 256) {
         std::vector<uint16_t> ec((size_t)round_up(std::max(g->max_row_deg, 1), 8) * std::max(m, 1), 0);   // slots padded to 8 rows, column 0
         std::vector<uint32_t> ev((size_t)std::max(g->max_col_deg, 1) * std::max(n, 1), 0xFFFFFFFFu);
@@ -285,8 +295,8 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
                 const int row = g->rowidx[k], pos = g->csc2csr[k] - indptr[row];
                 ev[(size_t)(k - g->colptr[j]) * n + j] = ((uint32_t)row << 8) | (uint32_t)pos;
             }
-        rc = upload(&g->d_ell_col, ec);
-        if (rc == QLDPC_OK) rc = upload(&g->d_ell_var, ev);
+        rc = g->own(&g->d_ell_col, ec);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_ell_var, ev);
         // degree-ordered views (stable sort, descending degree)
         std::vector<int32_t> ros(std::max(m, 1)), cos(std::max(n, 1)), slot_of_row(std::max(m, 1));
         for (int i = 0; i < m; i++) ros[i] = i;
@@ -313,46 +323,32 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         }
         std::vector<int32_t> ident(std::max(std::max(m, n), 1));
         for (size_t i = 0; i < ident.size(); i++) ident[i] = (int32_t)i;
-        if (rc == QLDPC_OK) rc = upload(&g->d_row_of_slot, ros);
-        if (rc == QLDPC_OK) rc = upload(&g->d_col_of_slot, cos);
-        if (rc == QLDPC_OK) rc = upload(&g->d_deg_of_rslot, drs);
-        if (rc == QLDPC_OK) rc = upload(&g->d_deg_of_cslot, dcs);
-        if (rc == QLDPC_OK) rc = upload(&g->d_deg_of_row, dr);
-        if (rc == QLDPC_OK) rc = upload(&g->d_deg_of_col, dc);
-        if (rc == QLDPC_OK) rc = upload(&g->d_ell_col_s, ecs);
-        if (rc == QLDPC_OK) rc = upload(&g->d_ell_var_s, evs);
-        if (rc == QLDPC_OK) rc = upload(&g->d_identity, ident);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_row_of_slot, ros);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_col_of_slot, cos);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_deg_of_rslot, drs);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_deg_of_cslot, dcs);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_deg_of_row, dr);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_deg_of_col, dc);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_ell_col_s, ecs);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_ell_var_s, evs);
+        if (rc == QLDPC_OK) rc = g->own(&g->d_identity, ident);
     }
     if (rc == QLDPC_OK && g->max_row_deg == kRegOwnCdeg && g->max_col_deg == kRegOwnVdeg && n == 2 * m && m <= 1024) {
         // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL).
         // Which valid assignment it is changes LDS bank conflicts only, never a result ("regular_own_search", options.hip).
         std::vector<int32_t> own;
-        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) rc = upload(&g->d_regown, own);
+        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) rc = g->own(&g->d_regown, own);
     }
-    if (rc != QLDPC_OK) { qldpc_graph_destroy(g); return rc; }
-    *out = g;
+    if (rc != QLDPC_OK) return rc;
+    *out = G.release();
     return QLDPC_OK;
 }
 
 QLDPC_EXPORT void qldpc_graph_destroy(qldpc_graph *g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    for (int32_t *p : {g->d_indptr, g->d_indices, g->d_colptr, g->d_rowidx, g->d_csc2csr, g->d_csr2csc})
-        if (p) (void)hipFree(p);
-    if (g->d_ell_col) (void)hipFree(g->d_ell_col);
-    if (g->d_ell_var) (void)hipFree(g->d_ell_var);
-    if (g->d_col_rows) (void)hipFree(g->d_col_rows);
-    if (g->d_regown) (void)hipFree(g->d_regown);
-    for (void *p : {(void *)g->d_row_of_slot, (void *)g->d_col_of_slot, (void *)g->d_deg_of_rslot, (void *)g->d_deg_of_cslot, (void *)g->d_deg_of_row,
-                    (void *)g->d_deg_of_col, (void *)g->d_ell_col_s, (void *)g->d_ell_var_s, (void *)g->d_identity})
-        if (p) (void)hipFree(p);
-    g->ws_prior.release();
-    g->ws_msg.release(); g->ws_qold.release(); g->ws_vals.release(); g->ws_misc.release(); g->ws_io.release(); g->ws_queue.release(); g->ws_squeue.release(); g->ws_list.release(); g->ws_redo.release(); g->ws_cs.release();
-    for (auto &e : g->alpha_cache) { if (e.dev) (void)hipFree(e.dev); if (e.pinned) (void)hipHostFree(e.pinned); if (e.ready) (void)hipEventDestroy(e.ready); }
     if (g->wg2_cache) qldpc::wg2_cache_free(g->wg2_cache);
-    g->ws_hand.destroy();
-    if (g->pin) (void)hipHostFree(g->pin);
-    delete g;
+    delete g;                                      // every buffer, alpha table and event of the handle releases itself
 }
 
 QLDPC_EXPORT int qldpc_graph_dims(const qldpc_graph *g, int *m, int *n, int *nnz) {

@@ -138,7 +138,7 @@ struct qldpc_cc_plan {
     // (a fan-out lane owns a private copy of the graph handle: the OSD-0 workspaces hang off the handle and are handed over between streams in
     // order, which would serialise the tails of concurrent batches)
     struct Lane { DevBuf err, synd, dec, llr, list, count, cold, cont; hipStream_t st = nullptr; hipEvent_t decoded = nullptr, tail = nullptr; bool tail_pending = false;
-                  qldpc_graph *g = nullptr; };
+                  Handle<qldpc_graph, qldpc_graph_destroy> g; };
     std::vector<Lane> lanes;              // lane 0 uses d_err, d_synd, ... above
     hipStream_t side = nullptr;
     hipEvent_t ev_in = nullptr;
@@ -156,7 +156,22 @@ struct qldpc_cc_plan {
     std::vector<hipEvent_t> pool;
     double ms_total = 0;
     int64_t launches = 0;
+    ~qldpc_cc_plan();                     // events and streams (the streams waited for); the members then free themselves
 };
+
+qldpc_cc_plan::~qldpc_cc_plan() {
+    (void)hipSetDevice(g->device);
+    for (auto &pr : pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+    for (auto &pr : pending_first) (void)hipEventDestroy(pr.second);
+    for (auto e : pool) (void)hipEventDestroy(e);
+    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    if (ev_in) (void)hipEventDestroy(ev_in);
+    for (auto &Ln : lanes) {
+        if (Ln.st) { (void)hipStreamSynchronize(Ln.st); (void)hipStreamDestroy(Ln.st); }
+        if (Ln.decoded) (void)hipEventDestroy(Ln.decoded);
+        if (Ln.tail) (void)hipEventDestroy(Ln.tail);
+    }
+}
 
 static hipEvent_t get_event(qldpc_cc_plan *P) {
     if (!P->pool.empty()) { hipEvent_t e = P->pool.back(); P->pool.pop_back(); return e; }
@@ -182,18 +197,17 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
     // `batch` is taken literally: a piece is three enqueues (decode, OSD-0, judge).  A caller that prefers fewer, larger launches to the memory bound
     // passes a granule for THIS plan (include/qldpc_hip.h); the tallies do not depend on the cut.
     if (batch < min_launch) batch = min_launch;
-    qldpc_cc_plan *P = new qldpc_cc_plan();
+    std::unique_ptr<qldpc_cc_plan> P(new qldpc_cc_plan());
     P->g = g; P->k = k; P->max_iter = max_iter; P->use_osd = use_osd; P->flags = flags;
     P->p = p; P->damping = damping; P->clip = clip_llr; P->batch = batch;
     P->thr = bernoulli_threshold(p);
-    if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, P->alpha)) != QLDPC_OK) { delete P; return rc; }
+    if ((rc = build_alpha_table(max_iter, alpha_mode, alpha_val, alpha_seq, alpha_len, P->alpha)) != QLDPC_OK) return rc;
     const size_t n = g->n, m = g->m;
     std::vector<double> prior(n ? n : 1, std::log((1.0 - p) / p));     // uniform prior log((1-p)/p), alpha.py:119-120
     std::vector<uint64_t> Lmask(n ? n : 1, 0);
     for (int r = 0; r < k; r++)
         for (size_t j = 0; j < n; j++)
             if (L[(size_t)r * n + j] & 1) Lmask[j] |= (uint64_t)1 << r;
-    auto fail = [&](int code) { qldpc_cc_plan_destroy(P); return code; };
     {
         const double pr = std::log((1.0 - p) / p);
         P->nanfree = inputs_clean(&pr, 1, clip_llr, P->alpha.data(), max_iter);
@@ -209,14 +223,14 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
         (rc = P->d_dec.ensure(batch * n)) || (rc = P->d_llr.ensure(batch * n * 8)) || (rc = P->d_conv.ensure(batch)) ||
         (rc = P->d_iter.ensure(batch * 4)) || (rc = P->d_tally.ensure(QLDPC_TALLY_SLOTS * 8)) ||
         (rc = P->d_list.ensure(batch * 4)) || (rc = P->d_count.ensure(16)))
-        return fail(rc);
-    if (zero_now(P->d_count.p, 16) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
+        return rc;
+    if (zero_now(P->d_count.p, 16) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
     if (hipMemcpy(P->d_alpha.p, P->alpha.data(), P->alpha.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(P->d_prior.p, prior.data(), prior.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(P->d_Lmask.p, Lmask.data(), Lmask.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
         zero_now(P->d_tally.p, QLDPC_TALLY_SLOTS * 8) != hipSuccess) {
         set_error("plan upload failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(QLDPC_ERR_HIP);
+        return QLDPC_ERR_HIP;
     }
     if (P->fused && !P->generic && !(flags & QLDPC_FLAG_FIXED_ITERS) && max_iter >= 1 && P->clean) {
         P->first_ok = mc_first_table(g, prior[0], P->alpha[0], clip_llr, max_iter, P->negbits) && (size_t)(g->m + g->n) * 64 <= 60 * 1024;
@@ -227,25 +241,25 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
                 lptr[r + 1] = (int32_t)lidx.size();
             }
             if ((rc = P->d_lptr.ensure(lptr.size() * 4)) || (rc = P->d_lidx.ensure(std::max<size_t>(lidx.size(), 1) * 4)) || (rc = P->d_cont.ensure(batch * 4)))
-                return fail(rc);
+                return rc;
             if (hipMemcpy(P->d_lptr.p, lptr.data(), lptr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
                 (!lidx.empty() && hipMemcpy(P->d_lidx.p, lidx.data(), lidx.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
                 set_error("plan upload failed: %s", hipGetErrorString(hipGetLastError()));
-                return fail(QLDPC_ERR_HIP);
+                return QLDPC_ERR_HIP;
             }
         }
     }
     if (P->fused) {
-        if ((rc = P->d_cold.ensure(mc_regular_cold_bytes())) != QLDPC_OK) return fail(rc);
+        if ((rc = P->d_cold.ensure(mc_regular_cold_bytes())) != QLDPC_OK) return rc;
         if (flags & QLDPC_FLAG_CLOCK_PROBE) {
             // two probe buffers: [0] the full decoder's workgroups, [1] the first-iteration kernel's
-            if ((rc = P->d_clk.ensure(4 * kClkSlots * 8)) != QLDPC_OK) return fail(rc);
-            if (zero_now(P->d_clk.p, 4 * kClkSlots * 8) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
+            if ((rc = P->d_clk.ensure(4 * kClkSlots * 8)) != QLDPC_OK) return rc;
+            if (zero_now(P->d_clk.p, 4 * kClkSlots * 8) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
         }
         if ((rc = mc_regular_fill_cold(P->d_cold.p, P->d_tally.as<unsigned long long>(), P->d_count.as<int32_t>(), P->d_list.as<int32_t>(),
                                        P->d_synd.as<int8_t>(), P->d_err.as<int8_t>(), P->d_dec.as<int8_t>(), P->d_llr.as<double>(),
                                        (flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr)) != QLDPC_OK)
-            return fail(rc);
+            return rc;
         // (fixed-work plans with large batches keep everything on the caller's stream: beside a 13 ms decode launch the 0.1 ms tail gains nothing, and
         // measured concurrently it slows the persistent decode kernel by 5 %, profiles/r03_experiments.txt)
         if (mc_tail_overlap_choice() >= 1 && (!(flags & QLDPC_FLAG_FIXED_ITERS) || batch <= kFanBatch)) {
@@ -263,12 +277,12 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
                 if ((rc = Ln.err.ensure(batch * n)) || (rc = Ln.synd.ensure(batch * m)) || (rc = Ln.dec.ensure(batch * n)) || (rc = Ln.llr.ensure(batch * n * 8)) ||
                     (rc = Ln.list.ensure(batch * 4)) || (rc = Ln.count.ensure(16)) || (rc = Ln.cold.ensure(mc_regular_cold_bytes())) ||
                     (P->first_ok && (rc = Ln.cont.ensure(batch * 4))))
-                    return fail(rc);
-                if (zero_now(Ln.count.p, 16) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
+                    return rc;
+                if (zero_now(Ln.count.p, 16) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
                 if ((rc = mc_regular_fill_cold(Ln.cold.p, P->d_tally.as<unsigned long long>(), Ln.count.as<int32_t>(), Ln.list.as<int32_t>(), Ln.synd.as<int8_t>(),
                                                Ln.err.as<int8_t>(), Ln.dec.as<int8_t>(), Ln.llr.as<double>(),
                                                (flags & QLDPC_FLAG_CLOCK_PROBE) ? P->d_clk.as<unsigned long long>() : nullptr)) != QLDPC_OK)
-                    return fail(rc);
+                    return rc;
             }
             for (int i = 0; i < nl && ok; i++) {
                 qldpc_cc_plan::Lane &Ln = P->lanes[i];
@@ -276,16 +290,18 @@ QLDPC_EXPORT int qldpc_cc_plan_create(const qldpc_graph *g, int k, const uint8_t
                 if (ok && P->fan) ok = hipStreamCreateWithFlags(&Ln.st, hipStreamNonBlocking) == hipSuccess;
                 // a lane owns a private copy of the graph handle (its OSD-0 workspaces are then used from the lane's stream alone: no hand-over events)
                 if (ok && P->fan && use_osd) {
-                    if (qldpc_graph_create(g->m, g->n, g->indptr.data(), g->indices.data(), g->device, &Ln.g) != QLDPC_OK) return fail(QLDPC_ERR_HIP);
+                    qldpc_graph *lg = nullptr;
+                    if (qldpc_graph_create(g->m, g->n, g->indptr.data(), g->indices.data(), g->device, &lg) != QLDPC_OK) return QLDPC_ERR_HIP;
+                    Ln.g.reset(lg);
                     Ln.g->ws_private = true;
                 }
             }
             if (ok && !P->fan && nl == 2) ok = hipStreamCreateWithFlags(&P->side, hipStreamNonBlocking) == hipSuccess;
             if (ok && P->fan) ok = hipEventCreateWithFlags(&P->ev_in, hipEventDisableTiming) == hipSuccess;
-            if (!ok) { set_error("stream / event creation failed: %s", hipGetErrorString(hipGetLastError())); return fail(QLDPC_ERR_HIP); }
+            if (!ok) { set_error("stream / event creation failed: %s", hipGetErrorString(hipGetLastError())); return QLDPC_ERR_HIP; }
         }
     }
-    *out = P;
+    *out = P.release();
     return QLDPC_OK;
 }
 
@@ -357,7 +373,7 @@ QLDPC_EXPORT int qldpc_cc_plan_run(qldpc_cc_plan *P, uint64_t seed, int64_t shot
                     QLDPC_HIP_TRY(hipEventRecord(Ln->decoded, s));
                     QLDPC_HIP_TRY(hipStreamWaitEvent(ts, Ln->decoded, 0));
                 }
-                const qldpc_graph *go = (Ln && Ln->g) ? Ln->g : g;
+                const qldpc_graph *go = (Ln && Ln->g) ? Ln->g.get() : g;
                 std::lock_guard<std::mutex> lk(go->mu);
                 // a lane's private handle: nobody else draws tickets from its OSD-0 queue, so the judge kernel (behind the OSD-0 launch on the same
                 // stream) zeroes it for the next piece and the launch skips its memset
@@ -479,26 +495,7 @@ QLDPC_EXPORT int qldpc_cc_plan_clock(qldpc_cc_plan *P, void *stream, double *mhz
     return QLDPC_OK;
 }
 
-QLDPC_EXPORT void qldpc_cc_plan_destroy(qldpc_cc_plan *P) {
-    if (!P) return;
-    (void)hipSetDevice(P->g->device);
-    for (auto &pr : P->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (auto &pr : P->pending_first) (void)hipEventDestroy(pr.second);
-    for (auto e : P->pool) (void)hipEventDestroy(e);
-    if (P->side) { (void)hipStreamSynchronize(P->side); (void)hipStreamDestroy(P->side); }
-    if (P->ev_in) (void)hipEventDestroy(P->ev_in);
-    for (auto &Ln : P->lanes) {
-        if (Ln.st) { (void)hipStreamSynchronize(Ln.st); (void)hipStreamDestroy(Ln.st); }
-        if (Ln.decoded) (void)hipEventDestroy(Ln.decoded);
-        if (Ln.tail) (void)hipEventDestroy(Ln.tail);
-        if (Ln.g) qldpc_graph_destroy(Ln.g);
-        for (DevBuf *b : {&Ln.err, &Ln.synd, &Ln.dec, &Ln.llr, &Ln.list, &Ln.count, &Ln.cold, &Ln.cont}) b->release();
-    }
-    for (DevBuf *b : {&P->d_alpha, &P->d_prior, &P->d_Lmask, &P->d_err, &P->d_synd, &P->d_dec, &P->d_llr, &P->d_conv, &P->d_iter,
-                      &P->d_tally, &P->d_list, &P->d_count, &P->d_sol, &P->d_cold, &P->d_clk, &P->d_lptr, &P->d_lidx, &P->d_cont})
-        b->release();
-    delete P;
-}
+QLDPC_EXPORT void qldpc_cc_plan_destroy(qldpc_cc_plan *P) { delete P; }
 
 QLDPC_EXPORT int qldpc_cc_sample_decode_tally(const qldpc_graph *g, int k, const uint8_t *L, double p, uint64_t seed,
                                               int64_t shot_begin, int64_t count, int max_iter, int alpha_mode, double alpha_val,

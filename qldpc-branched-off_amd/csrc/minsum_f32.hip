@@ -158,18 +158,27 @@ static F32Kernel f32_kernel(int block, bool clean) {
 
 using namespace qldpc;
 
-struct qldpc_minsum32_decoder {
-    const qldpc_graph *g = nullptr;
-    int device = 0, m = 0, n = 0, max_iter = 0, flags = 0;
+struct qldpc_minsum32_decoder : DecoderBase {
     float clip = 20.0f;
-    int block = 0, lds = 0, wg_per_cu = 0, grid_cap = 0;
+    int wg_per_cu = 0;
     bool clean = false;
     int offR = 0, offD = 0, offF = 0;
-    DevBuf d_prior, d_alpha, d_queue;
-    // the queue word is handed from stream to stream like a graph handle's workspaces (common.h)
-    std::mutex mu;
-    StreamHandover hand;
+    ~qldpc_minsum32_decoder() { quiesce(device, hand); }
+    int launch(int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s);
 };
+
+// Enqueues the decode of B shots on `s`.  Callers hold mu.
+int qldpc_minsum32_decoder::launch(int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s) {
+    F32Args A;
+    A.m = m; A.n = n; A.cdeg = g->max_col_deg;
+    A.row_of_slot = g->d_row_of_slot; A.col_of_slot = g->d_col_of_slot; A.degr = g->d_deg_of_rslot;
+    A.ell_col = g->d_ell_col_s; A.ell_var = g->d_ell_var_s;
+    A.B = B; A.synd = d_synd; A.prior_s = d_prior.as<float>(); A.alpha = d_alpha.as<float>(); A.clip = clip; A.max_iter = max_iter;
+    A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
+    A.offR = offR; A.offD = offD; A.offF = offF;
+    A.queue = d_queue.as<int>();
+    return decoder_launch(*this, f32_kernel(block, clean), kF32Lds, A, B, s);
+}
 
 namespace qldpc {
 
@@ -194,6 +203,7 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
         set_error("the f32 decoder supports row degree <= %d (this graph: %d)", kF32RowDeg, g->max_row_deg);
         return QLDPC_ERR_UNSUPPORTED;
     }
+    QLDPC_USE_DEVICE(g->device);                                    // ahead of D: a return deletes D on its device, then the caller's device comes back
     std::unique_ptr<qldpc_minsum32_decoder> D(new qldpc_minsum32_decoder());
     D->g = g; D->device = g->device; D->m = m; D->n = n; D->max_iter = max_iter; D->flags = flags & QLDPC_FLAG_PUBLIC_MASK; D->clip = clip32;
     // LDS layout: V | records | degree and syndrome bytes | flags
@@ -220,8 +230,6 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
     for (int k = 0; k < max_iter && clean; k++) clean = alpha32[k] > 0.0f && alpha32[k] <= 1024.0f;
     for (int c = 0; c < n && clean; c++) clean = std::fabs(prior_s[c]) <= 0x1p100f;
     D->clean = clean;
-    QLDPC_USE_DEVICE(g->device);
-    auto fail = [&](int code) { qldpc_minsum32_decoder_destroy(D.release()); return code; };
     // ---- workgroup size.  One workgroup of a CU: all 1024 threads; else the size whose passes have work for every thread (a row and eight columns),
     // and the host asks the runtime whether as many workgroups as LDS allows (two are enough) are resident with it; if not, the next smaller size.
     const int by_lds = kF32Lds / D->lds, work = std::max(m, n / 8);
@@ -230,52 +238,22 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
     int rc;
     for (;; block >>= 1) {
         const void *kern = reinterpret_cast<const void *>(f32_kernel(block, clean));
-        if ((rc = ensure_max_lds(g->device, kern, kF32Lds)) != QLDPC_OK) return fail(rc);
+        if ((rc = ensure_max_lds(g->device, kern, kF32Lds)) != QLDPC_OK) return rc;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, block, (size_t)D->lds) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
         D->block = block; D->wg_per_cu = nb;
         if (fb || block == 256 || nb >= std::min(by_lds, 2)) break;
     }
-    if (D->wg_per_cu < 1) { set_error("the f32 decoder's kernel is not launchable with %d threads and %d bytes of LDS", D->block, D->lds); return fail(QLDPC_ERR_HIP); }
+    if (D->wg_per_cu < 1) { set_error("the f32 decoder's kernel is not launchable with %d threads and %d bytes of LDS", D->block, D->lds); return QLDPC_ERR_HIP; }
     D->grid_cap = cu_count(g->device) * D->wg_per_cu;
-    if ((rc = upload(D->d_prior, prior_s)) || (rc = upload(D->d_alpha, alpha32)) || (rc = D->d_queue.ensure(16))) return fail(rc);
+    if ((rc = upload(D->d_prior, prior_s)) || (rc = upload(D->d_alpha, alpha32)) || (rc = D->d_queue.ensure(16))) return rc;
     *out = D.release();
     return QLDPC_OK;
 }
 
-// Enqueues the decode of B shots on `s`.  Callers hold D->mu.
-static int minsum32_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
-                           hipStream_t s) {
-    int rc = D->hand.acquire(s);
-    if (rc != QLDPC_OK) return rc;
-    const qldpc_graph *g = D->g;
-    F32Args A;
-    A.m = D->m; A.n = D->n; A.cdeg = g->max_col_deg;
-    A.row_of_slot = g->d_row_of_slot; A.col_of_slot = g->d_col_of_slot; A.degr = g->d_deg_of_rslot;
-    A.ell_col = g->d_ell_col_s; A.ell_var = g->d_ell_var_s;
-    A.B = B; A.synd = d_synd; A.prior_s = D->d_prior.as<float>(); A.alpha = D->d_alpha.as<float>(); A.clip = D->clip; A.max_iter = D->max_iter;
-    A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
-    A.offR = D->offR; A.offD = D->offD; A.offF = D->offF;
-    A.queue = D->d_queue.as<int>();
-    auto launch = [&]() -> int {
-        QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
-        const F32Kernel kern = f32_kernel(D->block, D->clean);
-        const int rcl = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kF32Lds);
-        if (rcl != QLDPC_OK) return rcl;
-        const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
-        QLDPC_HIP_TRY(hipGetLastError());
-        return QLDPC_OK;
-    };
-    rc = launch();
-    const int rel = D->hand.release(s);             // always: a failing call may have enqueued work the next stream has to wait for
-    return rc != QLDPC_OK ? rc : rel;
-}
-
 int minsum32_lock_and_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                              hipStream_t s) {
-    std::lock_guard<std::mutex> lk(D->mu);
-    return minsum32_launch(D, B, d_synd, d_err, d_llr, d_conv, d_iter, s);
+    return decoder_lock_and_launch(D, B, d_synd, d_err, d_llr, d_conv, d_iter, s);
 }
 
 }  // namespace qldpc
@@ -291,14 +269,7 @@ QLDPC_EXPORT int qldpc_minsum32_decoder_create(const qldpc_graph *g, const doubl
     return minsum32_decoder_create_tab(g, prior, max_iter, tab, clip_llr, flags, out);
 }
 
-QLDPC_EXPORT void qldpc_minsum32_decoder_destroy(qldpc_minsum32_decoder *D) {
-    if (!D) return;
-    (void)hipSetDevice(D->device);
-    if (D->hand.used) (void)hipDeviceSynchronize();
-    D->hand.destroy();
-    for (DevBuf *b : {&D->d_prior, &D->d_alpha, &D->d_queue}) b->release();
-    delete D;
-}
+QLDPC_EXPORT void qldpc_minsum32_decoder_destroy(qldpc_minsum32_decoder *D) { delete D; }
 
 QLDPC_EXPORT int qldpc_minsum32_decoder_info(const qldpc_minsum32_decoder *D, int *lds_bytes, int *threads, int *wg_per_cu, int *form) {
     QLDPC_REQUIRE(D != nullptr, "decoder is NULL");
@@ -311,29 +282,10 @@ QLDPC_EXPORT int qldpc_minsum32_decoder_info(const qldpc_minsum32_decoder *D, in
 
 QLDPC_EXPORT int qldpc_minsum32_decode_batch_dev(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
                                                  uint8_t *d_conv, int32_t *d_iter, void *stream) {
-    int rc = decoder_check_call(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter);
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_USE_DEVICE(D->device);
-    if (B == 0) return QLDPC_OK;
-    return minsum32_lock_and_launch(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter, reinterpret_cast<hipStream_t>(stream));
+    return decoder_decode_dev(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter, stream);
 }
 
 QLDPC_EXPORT int qldpc_minsum32_decode_batch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
                                              int32_t *iter) {
-    int rc = decoder_check_call(D, B, syndromes, err, llr, conv, iter);
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_USE_DEVICE(D->device);
-    if (B == 0) return QLDPC_OK;
-    HostStage S;
-    const auto ds = S.in(syndromes, B, D->m);
-    const auto de = S.out(err, B, D->n);
-    const auto dl = S.out(llr, B, D->n);
-    const auto dc = S.out(conv, B);
-    const auto di = S.out(iter, B);
-    if ((rc = S.stage()) != QLDPC_OK) return rc;
-    {
-        std::lock_guard<std::mutex> lk(D->mu);
-        rc = minsum32_launch(D, B, S[ds], S[de], S[dl], S[dc], S[di], nullptr);
-    }
-    return rc != QLDPC_OK ? rc : S.finish("f32 decode", HostStage::kStream);
+    return decoder_decode_host(D, "f32 decode", B, syndromes, err, llr, conv, iter);
 }

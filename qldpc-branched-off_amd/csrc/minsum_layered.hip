@@ -187,19 +187,32 @@ static int greedy_layers(const qldpc_graph *g, std::vector<int32_t> &layer) {
 
 using namespace qldpc;
 
-struct qldpc_layered_decoder {
-    const qldpc_graph *g = nullptr;
-    int device = 0, m = 0, n = 0, nnz = 0, max_iter = 0, flags = 0;
+struct qldpc_layered_decoder : DecoderBase {      // (the VG slab is handed from stream to stream with the queue word)
+    int nnz = 0;
     double clip = 20;
-    int nlayers = 0, nslots = 0, max_rows = 0, max_edges = 0, block = 0, lds = 0, grid_cap = 0;
+    int nlayers = 0, nslots = 0, max_rows = 0, max_edges = 0;
     bool vg = false, idxl = false;
     int offP = 0, offI = 0, offE = 0, offL = 0, offS = 0, offX = 0, offF = 0;
     std::vector<int32_t> row_layer;
-    DevBuf d_prior, d_alpha, d_layer, d_slot_row, d_estart, d_idx16, d_idx32, d_queue, d_vglobal;
-    // the queue word and the VG slab are handed from stream to stream like a graph handle's workspaces (common.h)
-    std::mutex mu;
-    StreamHandover hand;
+    DevBuf d_layer, d_slot_row, d_estart, d_idx16, d_idx32, d_vglobal;
+    ~qldpc_layered_decoder() { quiesce(device, hand); }
+    int launch(int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s);
 };
+
+// Enqueues the decode of B shots on `s`.  Callers hold mu.
+int qldpc_layered_decoder::launch(int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter, hipStream_t s) {
+    LayeredArgs A;
+    A.m = m; A.n = n; A.nslots = nslots; A.nlayers = nlayers; A.nnz = nnz;
+    A.layer = d_layer.as<uint32_t>(); A.slot_row = d_slot_row.as<int32_t>(); A.estart = d_estart.as<uint32_t>();
+    A.idx16 = d_idx16.as<uint16_t>(); A.idx32 = d_idx32.as<int32_t>();
+    A.B = B; A.synd = d_synd; A.prior = d_prior.as<double>(); A.alpha = d_alpha.as<double>(); A.max_iter = max_iter; A.clip = clip;
+    A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
+    A.offP = offP; A.offI = offI; A.offE = offE; A.offL = offL; A.offS = offS; A.offX = offX; A.offF = offF;
+    A.vglobal = d_vglobal.as<double>(); A.queue = d_queue.as<int>();
+    void (*kern)(LayeredArgs) = vg ? (idxl ? minsum_layered_kernel<true, true> : minsum_layered_kernel<true, false>)
+                                   : (idxl ? minsum_layered_kernel<false, true> : minsum_layered_kernel<false, false>);
+    return decoder_launch(*this, kern, kLayeredLds, A, B, s);
+}
 
 namespace qldpc {
 
@@ -216,7 +229,9 @@ int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, c
     const int m = g->m, n = g->n;
     const int fb = flags & (QLDPC_FLAG_LAYERED_BLOCK_256 | QLDPC_FLAG_LAYERED_BLOCK_512 | QLDPC_FLAG_LAYERED_BLOCK_1024);
     QLDPC_REQUIRE((fb & (fb - 1)) == 0, "more than one QLDPC_FLAG_LAYERED_BLOCK_* flag");
+    QLDPC_USE_DEVICE(g->device);                                    // ahead of D: a return deletes D on its device, then the caller's device comes back
     std::unique_ptr<qldpc_layered_decoder> D(new qldpc_layered_decoder());
+    D->device = g->device;
     // ---- layers: the caller's (validated) or the greedy colouring, then compressed to 0 .. nlayers - 1 in ascending order
     if (row_layer) {
         for (int i = 0; i < m; i++) QLDPC_REQUIRE(row_layer[i] >= 0, "row_layer[%d] = %d is negative", i, row_layer[i]);
@@ -304,53 +319,21 @@ int layered_decoder_create_tab(const qldpc_graph *g, const int32_t *row_layer, c
         return QLDPC_ERR_UNSUPPORTED;
     }
     D->lds = (int)bytes;
-    QLDPC_USE_DEVICE(g->device);
-    auto fail = [&](int code) { qldpc_layered_decoder_destroy(D.release()); return code; };
     D->grid_cap = cu_count(g->device) * (int)std::max<int64_t>(1, std::min<int64_t>(kLayeredLds / D->lds, 2048 / D->block));
     int rc;
-    if (D->idxl) { idx16.assign(idx32.begin(), idx32.end()); if ((rc = upload(D->d_idx16, idx16)) != QLDPC_OK) return fail(rc); }
+    if (D->idxl) { idx16.assign(idx32.begin(), idx32.end()); if ((rc = upload(D->d_idx16, idx16)) != QLDPC_OK) return rc; }
     const std::vector<double> pv(prior, prior + n), av(tab.begin(), tab.begin() + max_iter);
     if ((rc = upload(D->d_prior, pv)) || (rc = upload(D->d_alpha, av)) || (rc = upload(D->d_layer, layer)) || (rc = upload(D->d_slot_row, slot_row)) ||
         (rc = upload(D->d_estart, estart)) || (rc = upload(D->d_idx32, idx32)) || (rc = D->d_queue.ensure(16)) ||
         (D->vg && (rc = D->d_vglobal.ensure((size_t)D->grid_cap * n * 8))))
-        return fail(rc);
+        return rc;
     *out = D.release();
     return QLDPC_OK;
 }
 
-// Enqueues the decode of B shots on `s`.  Callers hold D->mu.
-static int layered_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
-                          hipStream_t s) {
-    int rc = D->hand.acquire(s);
-    if (rc != QLDPC_OK) return rc;
-    LayeredArgs A;
-    A.m = D->m; A.n = D->n; A.nslots = D->nslots; A.nlayers = D->nlayers; A.nnz = D->nnz;
-    A.layer = D->d_layer.as<uint32_t>(); A.slot_row = D->d_slot_row.as<int32_t>(); A.estart = D->d_estart.as<uint32_t>();
-    A.idx16 = D->d_idx16.as<uint16_t>(); A.idx32 = D->d_idx32.as<int32_t>();
-    A.B = B; A.synd = d_synd; A.prior = D->d_prior.as<double>(); A.alpha = D->d_alpha.as<double>(); A.max_iter = D->max_iter; A.clip = D->clip;
-    A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
-    A.offP = D->offP; A.offI = D->offI; A.offE = D->offE; A.offL = D->offL; A.offS = D->offS; A.offX = D->offX; A.offF = D->offF;
-    A.vglobal = D->d_vglobal.as<double>(); A.queue = D->d_queue.as<int>();
-    auto launch = [&]() -> int {
-        QLDPC_HIP_TRY(hipMemsetAsync(D->d_queue.p, 0, 16, s));
-        void (*kern)(LayeredArgs) = D->vg ? (D->idxl ? minsum_layered_kernel<true, true> : minsum_layered_kernel<true, false>)
-                                          : (D->idxl ? minsum_layered_kernel<false, true> : minsum_layered_kernel<false, false>);
-        const int rcl = ensure_max_lds(D->device, reinterpret_cast<const void *>(kern), kLayeredLds);
-        if (rcl != QLDPC_OK) return rcl;
-        const unsigned grid = (unsigned)std::min<int64_t>(B, D->grid_cap);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(D->block), (size_t)D->lds, s, A);
-        QLDPC_HIP_TRY(hipGetLastError());
-        return QLDPC_OK;
-    };
-    rc = launch();
-    const int rel = D->hand.release(s);             // always: a failing call may have enqueued work the next stream has to wait for
-    return rc != QLDPC_OK ? rc : rel;
-}
-
 int layered_lock_and_launch(qldpc_layered_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                             hipStream_t s) {
-    std::lock_guard<std::mutex> lk(D->mu);
-    return layered_launch(D, B, d_synd, d_err, d_llr, d_conv, d_iter, s);
+    return decoder_lock_and_launch(D, B, d_synd, d_err, d_llr, d_conv, d_iter, s);
 }
 
 }  // namespace qldpc
@@ -376,14 +359,7 @@ QLDPC_EXPORT int qldpc_layered_decoder_create(const qldpc_graph *g, const int32_
     return layered_decoder_create_tab(g, row_layer, prior, max_iter, tab, clip_llr, flags, out);
 }
 
-QLDPC_EXPORT void qldpc_layered_decoder_destroy(qldpc_layered_decoder *D) {
-    if (!D) return;
-    (void)hipSetDevice(D->device);
-    if (D->hand.used) (void)hipDeviceSynchronize();
-    D->hand.destroy();
-    for (DevBuf *b : {&D->d_prior, &D->d_alpha, &D->d_layer, &D->d_slot_row, &D->d_estart, &D->d_idx16, &D->d_idx32, &D->d_queue, &D->d_vglobal}) b->release();
-    delete D;
-}
+QLDPC_EXPORT void qldpc_layered_decoder_destroy(qldpc_layered_decoder *D) { delete D; }
 
 QLDPC_EXPORT int qldpc_layered_decoder_info(const qldpc_layered_decoder *D, int *layers, int *max_layer_rows, int *max_layer_edges, int *lds_bytes,
                                             int *form) {
@@ -404,29 +380,10 @@ QLDPC_EXPORT int qldpc_layered_decoder_layers(const qldpc_layered_decoder *D, in
 
 QLDPC_EXPORT int qldpc_layered_decode_batch_dev(qldpc_layered_decoder *D, int64_t B, const int8_t *d_syndromes, int8_t *d_err, double *d_llr,
                                                 uint8_t *d_conv, int32_t *d_iter, void *stream) {
-    int rc = decoder_check_call(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter);
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_USE_DEVICE(D->device);
-    if (B == 0) return QLDPC_OK;
-    return layered_lock_and_launch(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter, reinterpret_cast<hipStream_t>(stream));
+    return decoder_decode_dev(D, B, d_syndromes, d_err, d_llr, d_conv, d_iter, stream);
 }
 
 QLDPC_EXPORT int qldpc_layered_decode_batch(qldpc_layered_decoder *D, int64_t B, const int8_t *syndromes, int8_t *err, double *llr, uint8_t *conv,
                                             int32_t *iter) {
-    int rc = decoder_check_call(D, B, syndromes, err, llr, conv, iter);
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_USE_DEVICE(D->device);
-    if (B == 0) return QLDPC_OK;
-    HostStage S;
-    const auto ds = S.in(syndromes, B, D->m);
-    const auto de = S.out(err, B, D->n);
-    const auto dl = S.out(llr, B, D->n);
-    const auto dc = S.out(conv, B);
-    const auto di = S.out(iter, B);
-    if ((rc = S.stage()) != QLDPC_OK) return rc;
-    {
-        std::lock_guard<std::mutex> lk(D->mu);
-        rc = layered_launch(D, B, S[ds], S[de], S[dl], S[dc], S[di], nullptr);
-    }
-    return rc != QLDPC_OK ? rc : S.finish("layered decode", HostStage::kStream);
+    return decoder_decode_host(D, "layered decode", B, syndromes, err, llr, conv, iter);
 }

@@ -62,7 +62,8 @@ QLDPC_EXPORT int qldpc_set_option(const char *name, int value) {
     return QLDPC_ERR_INVALID;
 }
 
-// Streams for hosts that do not bring their own runtime (run_simulation(num_workers = N): one plan and one stream per worker).
+// Streams for hosts that do not bring their own runtime (run_simulation(num_workers = N): one plan and one stream per worker).  They stay raw: the caller
+// owns them and says when they end (qldpc_stream_destroy); the library keeps no stream of its own that would have to outlive the runtime's shutdown.
 QLDPC_EXPORT int qldpc_stream_create(int device, void **stream) {
     QLDPC_REQUIRE(stream != nullptr, "stream is NULL");
     QLDPC_USE_DEVICE(device);

@@ -316,15 +316,10 @@ struct qldpc_msgstats {
     int L = 0;                       // samples per trial: nnz (check messages) or n (posteriors)
     bool by_edge = false;
     DevBuf d_samples, d_err;
+    ~qldpc_msgstats() { (void)hipSetDevice(g->device); }
 };
 
-QLDPC_EXPORT void qldpc_msgstats_destroy(qldpc_msgstats *S) {
-    if (!S) return;
-    (void)hipSetDevice(S->g->device);
-    S->d_samples.release();
-    S->d_err.release();
-    delete S;
-}
+QLDPC_EXPORT void qldpc_msgstats_destroy(qldpc_msgstats *S) { delete S; }
 
 QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const int8_t *errors, const double *prior, int kind, int iters,
                                        int alpha_mode, double alpha_val, const double *alpha_seq, int alpha_len, double damping,
@@ -344,9 +339,8 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
     std::vector<double> tab;
     if (by_edge && (rc = build_alpha_table(iters, alpha_mode, alpha_val, alpha_seq, alpha_len, tab)) != QLDPC_OK) return rc;
 
-    qldpc_msgstats *S = new qldpc_msgstats;
+    std::unique_ptr<qldpc_msgstats> S(new qldpc_msgstats);
     S->g = g; S->B = B; S->L = (int)L; S->by_edge = by_edge;
-    auto fail = [&](int code) { qldpc_msgstats_destroy(S); return code; };
     // trials are independent: process them in chunks so the [trial][edge] temporaries stay below ~6 GB
     const size_t per_trial = by_edge ? (nnz * 16 + n * 8 + m * 9 + 2) : (m + n + 5);
     int64_t chunk = (int64_t)(((size_t)6 << 30) / (per_trial ? per_trial : 1));
@@ -363,23 +357,23 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
     const auto d_hard = T.scratch<int8_t>(cp, n);
     const auto d_conv = T.scratch<uint8_t>(cp);
     const auto d_iter = T.scratch<int32_t>(cp);
-    if ((rc = S->d_samples.ensure((size_t)B * L * 8 + 16)) || (rc = S->d_err.ensure((size_t)B * n + 16)) || (rc = T.stage())) return fail(rc);
+    if ((rc = S->d_samples.ensure((size_t)B * L * 8 + 16)) || (rc = S->d_err.ensure((size_t)B * n + 16)) || (rc = T.stage())) return rc;
     const hipError_t he = B * n ? hipMemcpy(S->d_err.p, errors, (size_t)B * n, hipMemcpyHostToDevice) : hipSuccess;
-    if (he != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(he)); return fail(QLDPC_ERR_HIP); }
+    if (he != hipSuccess) { set_error("upload failed: %s", hipGetErrorString(he)); return QLDPC_ERR_HIP; }
     for (int64_t off = 0; off < B; off += chunk) {
         const int64_t Bc = std::min<int64_t>(chunk, B - off);
         const int8_t *err_c = S->d_err.as<int8_t>() + off * n;
         double *smp_c = S->d_samples.as<double>() + off * L;
-        if ((rc = gf2_spmv_launch(g, Bc, err_c, T[d_synd], nullptr)) != QLDPC_OK) return fail(rc);      // alpha.py:121 / scopt.py:82
+        if ((rc = gf2_spmv_launch(g, Bc, err_c, T[d_synd], nullptr)) != QLDPC_OK) return rc;      // alpha.py:121 / scopt.py:82
         if (by_edge) {
             size_t tot = Bc * nnz; if (Bc * m > tot) tot = Bc * m; if ((size_t)Bc > tot) tot = Bc;
             hipLaunchKernelGGL(bp_init_kernel, dim3(blocks(tot)), dim3(256), 0, nullptr, Bc, (int)m, (int)n, (int)nnz, g->d_indices,
                                T[d_prior], T[d_synd], T[d_Q], T[d_ss], T[d_done],
                                T[d_unsat]);                                                           // alpha.py:122-124
             if (nnz && hipMemcpyAsync(T[d_Qold], T[d_Q], Bc * nnz * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) {
-                set_error("device copy failed"); return fail(QLDPC_ERR_HIP);
+                set_error("device copy failed"); return QLDPC_ERR_HIP;
             }
-            if (hipMemsetAsync(smp_c, 0, Bc * nnz * 8 + (nnz ? 0 : 8), nullptr) != hipSuccess) { set_error("memset failed"); return fail(QLDPC_ERR_HIP); }
+            if (hipMemsetAsync(smp_c, 0, Bc * nnz * 8 + (nnz ? 0 : 8), nullptr) != hipSuccess) { set_error("memset failed"); return QLDPC_ERR_HIP; }
             for (int k = 0; k <= iters; k++) {
                 const double a = (k < iters) ? tab[k] : 1.0;                                                     // alpha.py:214-218, 247-249
                 if (Bc * m > 0)
@@ -393,26 +387,26 @@ QLDPC_EXPORT int qldpc_msgstats_create(const qldpc_graph *g, int64_t B, const in
                     hipLaunchKernelGGL(stats_q_update_kernel, dim3(blocks(Bc * nnz)), dim3(256), 0, nullptr, Bc, (int)n, (int)nnz, g->d_indices,
                                        T[d_val], smp_c, damping, clip_llr, T[d_Q], T[d_Qold]);
             }
-            if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed"); return fail(QLDPC_ERR_HIP); }
+            if (hipGetLastError() != hipSuccess) { set_error("kernel launch failed"); return QLDPC_ERR_HIP; }
         } else {
             rc = qldpc_minsum_decode_batch_dev(g, Bc, T[d_synd], T[d_prior], iters, alpha_mode, alpha_val, alpha_seq,
                                                alpha_len, damping, clip_llr, 0, T[d_hard], smp_c, T[d_conv],
                                                T[d_iter], nullptr);                                   // scopt.py:88-131
-            if (rc != QLDPC_OK) return fail(rc);
+            if (rc != QLDPC_OK) return rc;
         }
-        if (hipDeviceSynchronize() != hipSuccess) { set_error("device synchronisation failed"); return fail(QLDPC_ERR_HIP); }
+        if (hipDeviceSynchronize() != hipSuccess) { set_error("device synchronisation failed"); return QLDPC_ERR_HIP; }
     }
     if (B * (int64_t)L > 0) {
         const unsigned grid = (unsigned)std::min<int64_t>(4096, (B * (int64_t)L + 255) / 256);
         hipLaunchKernelGGL(stats_range_kernel, dim3(grid), dim3(256), 0, nullptr, B, (int)L, (int)n, by_edge ? g->d_indices : (const int32_t *)nullptr,
                            S->d_samples.as<double>(), S->d_err.as<int8_t>(), T[d_red]);
     }
-    if ((rc = T.finish("range read-back", HostStage::kCopies)) != QLDPC_OK) return fail(rc);
+    if ((rc = T.finish("range read-back", HostStage::kCopies)) != QLDPC_OK) return rc;
     finite[0] = (int64_t)red[2]; finite[1] = (int64_t)red[3];
     const bool any = (red[2] | red[3]) != 0;
     range[0] = any ? key_f64(red[0]) : 0.0;
     range[1] = any ? key_f64(red[1]) : 0.0;
-    *out = S;
+    *out = S.release();
     return QLDPC_OK;
 }
 

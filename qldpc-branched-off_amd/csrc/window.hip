@@ -117,7 +117,7 @@ struct qldpc_window_decoder {
     double clip = 20;
     std::vector<double> alpha;                       // alpha_k, k < max_iter
     struct Shared {                                  // one per distinct (CSR, prior slice)
-        qldpc_graph *g = nullptr;
+        Handle<qldpc_graph, qldpc_graph_destroy> g;
         std::vector<int32_t> indptr, indices;
         std::vector<double> prior;
         DevBuf d_prior;
@@ -135,6 +135,7 @@ struct qldpc_window_decoder {
     std::mutex mu, mu_io;
     DevBuf run, wsyn, werr, wllr, wconv, witer, list, count, acc;
     StreamHandover hand;
+    ~qldpc_window_decoder() { quiesce(device, hand); }
 };
 
 namespace qldpc {
@@ -161,7 +162,6 @@ int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, 
     }
     QLDPC_USE_DEVICE(g->device);
     std::unique_ptr<qldpc_window_decoder> D(new qldpc_window_decoder());
-    auto fail = [&](int code) { qldpc_window_decoder_destroy(D.release()); return code; };
     D->full = g; D->device = g->device; D->m = m; D->n = n; D->layer_rows = lr; D->layers = Lyr; D->window = window; D->commit = commit;
     D->max_iter = max_iter; D->flags = flags & QLDPC_FLAG_PUBLIC_MASK; D->clip = clip_llr; D->alpha = tab;
     int rc;
@@ -183,13 +183,13 @@ int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, 
             cptr.push_back((int32_t)crow.size());
         }
         S->wn = (int)colmap.size(); S->ncommit = (int)ccol.size();
-        if (S->wn == 0) { set_error("the window at layer %d has no columns", la); return fail(QLDPC_ERR_UNSUPPORTED); }
+        if (S->wn == 0) { set_error("the window at layer %d has no columns", la); return QLDPC_ERR_UNSUPPORTED; }
         S->c_row0 = S->row0;
         S->c_nrows = last ? m - S->row0 : (std::min(la + commit + 1, Lyr) - la) * lr;
         S->c_nfinal = last ? S->c_nrows : commit * lr;
         for (int32_t r : crow)
-            if (r < S->c_row0 || r >= S->c_row0 + S->c_nrows) { set_error("internal: a committed column leaves its rows"); return fail(QLDPC_ERR_INVALID); }
-        if (S->c_nrows > (1 << 19)) { set_error("a commit touches %d rows: more than the LDS bit set holds", S->c_nrows); return fail(QLDPC_ERR_UNSUPPORTED); }
+            if (r < S->c_row0 || r >= S->c_row0 + S->c_nrows) { set_error("internal: a committed column leaves its rows"); return QLDPC_ERR_INVALID; }
+        if (S->c_nrows > (1 << 19)) { set_error("a commit touches %d rows: more than the LDS bit set holds", S->c_nrows); return QLDPC_ERR_UNSUPPORTED; }
         // the window graph: the covered rows restricted to the window's columns (entries of columns committed earlier are already in the running syndrome)
         std::vector<int32_t> ip(1, 0), ix;
         for (int i = S->row0; i < S->row0 + S->wm; i++) {
@@ -205,35 +205,31 @@ int window_decoder_create_tab(const qldpc_graph *g, int layer_rows, int window, 
                 found = (int)k;
         if (found < 0) {
             std::unique_ptr<qldpc_window_decoder::Shared> H(new qldpc_window_decoder::Shared());
-            if ((rc = qldpc_graph_create(S->wm, S->wn, ip.data(), ix.data(), g->device, &H->g)) != QLDPC_OK) return fail(rc);
+            qldpc_graph *wg = nullptr;
+            if ((rc = qldpc_graph_create(S->wm, S->wn, ip.data(), ix.data(), g->device, &wg)) != QLDPC_OK) return rc;
+            H->g.reset(wg);
             found = (int)D->shared.size();
             D->shared.push_back(std::move(H));
             qldpc_window_decoder::Shared &R = *D->shared.back();
             R.indptr = std::move(ip); R.indices = std::move(ix); R.prior = std::move(pw);
-            if ((rc = R.d_prior.ensure(R.prior.size() * 8)) != QLDPC_OK) return fail(rc);
-            if (hipMemcpy(R.d_prior.p, R.prior.data(), R.prior.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { set_error("prior upload failed"); return fail(QLDPC_ERR_HIP); }
+            if ((rc = upload(R.d_prior, R.prior)) != QLDPC_OK) return rc;
             R.nanfree = inputs_clean(R.prior.data(), S->wn, clip_llr, tab.data(), max_iter);
             // which decoder form the window takes; this also builds the LDS-resident form's tables now, so that decode calls only enqueue
             DecodePath P;
             {
                 std::lock_guard<std::mutex> lk(R.g->mu);
-                rc = select_decode_path(R.g, max_iter, 1.0, clip_llr, D->flags | QLDPC_FLAG_INTERNAL_PRIOR_FINITE, R.nanfree, R.prior.data(), P);
+                rc = select_decode_path(R.g.get(), max_iter, 1.0, clip_llr, D->flags | QLDPC_FLAG_INTERNAL_PRIOR_FINITE, R.nanfree, R.prior.data(), P);
             }
-            if (rc != QLDPC_OK) return fail(rc);
+            if (rc != QLDPC_OK) return rc;
             R.path = P.path;
         }
         S->shared = found;
-        auto upl = [&](DevBuf &b, const std::vector<int32_t> &v) {
-            int r = b.ensure(std::max<size_t>(v.size(), 1) * 4);
-            if (r == QLDPC_OK && !v.empty() && hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("table upload failed"); r = QLDPC_ERR_HIP; }
-            return r;
-        };
-        if ((rc = upl(S->d_colmap, colmap)) || (rc = upl(S->d_ccol, ccol)) || (rc = upl(S->d_cptr, cptr)) || (rc = upl(S->d_crow, crow))) return fail(rc);
+        if ((rc = upload(S->d_colmap, colmap)) || (rc = upload(S->d_ccol, ccol)) || (rc = upload(S->d_cptr, cptr)) || (rc = upload(S->d_crow, crow))) return rc;
         D->max_wm = std::max(D->max_wm, S->wm); D->max_wn = std::max(D->max_wn, S->wn);
         D->stages.push_back(std::move(S));
         if (last) break;
     }
-    if ((rc = D->count.ensure(64)) != QLDPC_OK) return fail(rc);
+    if ((rc = D->count.ensure(64)) != QLDPC_OK) return rc;
     *out = D.release();
     return QLDPC_OK;
 }
@@ -260,7 +256,7 @@ static int window_stages_launch(qldpc_window_decoder *D, int64_t B, const int8_t
             std::lock_guard<std::mutex> lk(R.g->mu);
             const double *d_alpha = nullptr;
             if ((rc = R.g->alpha_table(D->alpha, s, &d_alpha)) != QLDPC_OK) return rc;
-            rc = minsum_decode_dispatch(R.g, B, D->wsyn.as<int8_t>(), R.d_prior.as<double>(), D->max_iter, d_alpha, 1.0, D->clip,
+            rc = minsum_decode_dispatch(R.g.get(), B, D->wsyn.as<int8_t>(), R.d_prior.as<double>(), D->max_iter, d_alpha, 1.0, D->clip,
                                         D->flags | QLDPC_FLAG_INTERNAL_PRIOR_FINITE, R.nanfree, D->werr.as<int8_t>(), D->wllr.as<double>(),
                                         D->wconv.as<uint8_t>(), D->witer.as<int32_t>(), s, R.prior.data());
         }
@@ -270,7 +266,7 @@ static int window_stages_launch(qldpc_window_decoder *D, int64_t B, const int8_t
         QLDPC_HIP_TRY(hipGetLastError());
         {
             std::lock_guard<std::mutex> lk(R.g->mu);
-            rc = osd0_listed_launch(R.g, D->list.as<int32_t>(), count, B, D->wsyn.as<int8_t>(), D->wllr.as<double>(), D->werr.as<int8_t>(), nullptr,
+            rc = osd0_listed_launch(R.g.get(), D->list.as<int32_t>(), count, B, D->wsyn.as<int8_t>(), D->wllr.as<double>(), D->werr.as<int8_t>(), nullptr,
                                     D->werr.as<int8_t>(), D->flags, s);
         }
         if (rc != QLDPC_OK) return rc;
@@ -323,16 +319,7 @@ QLDPC_EXPORT int qldpc_window_decoder_create(const qldpc_graph *g, int layer_row
     return window_decoder_create_tab(g, layer_rows, window, commit, prior, max_iter, tab, clip_llr, flags, out);
 }
 
-QLDPC_EXPORT void qldpc_window_decoder_destroy(qldpc_window_decoder *D) {
-    if (!D) return;
-    (void)hipSetDevice(D->device);
-    if (D->hand.used) (void)hipDeviceSynchronize();
-    D->hand.destroy();
-    for (auto &S : D->stages) { S->d_colmap.release(); S->d_ccol.release(); S->d_cptr.release(); S->d_crow.release(); }
-    for (auto &R : D->shared) { R->d_prior.release(); qldpc_graph_destroy(R->g); }
-    for (DevBuf *b : {&D->run, &D->wsyn, &D->werr, &D->wllr, &D->wconv, &D->witer, &D->list, &D->count, &D->acc}) b->release();
-    delete D;
-}
+QLDPC_EXPORT void qldpc_window_decoder_destroy(qldpc_window_decoder *D) { delete D; }
 
 QLDPC_EXPORT int qldpc_window_decoder_info(const qldpc_window_decoder *D, int *windows, int *graphs, int *max_rows, int *max_cols, int *wg2_windows) {
     QLDPC_REQUIRE(D != nullptr, "decoder is NULL");
