@@ -15,8 +15,8 @@
 //   * clean undamped inputs (CLIPMIN = NANFREE && !DAMP; "clean", inputs_clean() in decode_api.hip: every prior finite and not
 //     -0.0, clip finite > 0, every alpha finite > 0) build the CDEG message words of a check with neither a compare nor a select,
 //     from the UNCLIPPED t_k = V[col_k] - Rprev_k.  Why each word equals the reference's, bit for bit:
-//       signs      A posterior is never -0.0: it is 0.0 + R + ... + R + prior (kernels.py:279,316,320), a sum that starts at +0.0
-//                  stays +0.0 or nonzero under round-to-nearest (x + y is -0.0 only for x = y = -0.0), and the prior is not -0.0.
+//       signs      A posterior is never -0.0: it is (a sum of messages) + prior (kernels.py:279,316,320), x + y is -0.0 only for
+//                  x = y = -0.0 under round-to-nearest, and the prior is not -0.0 (with or without the leading 0.0 of "zero" below).
 //                  a - b is -0.0 only for a = -0.0, b = +0.0, so no t_k is -0.0 either, and none is NaN (all operands finite:
 //                  |R| <= max(|prior|, clip)).  Hence x < 0 <=> the sign bit of x's high word, for posteriors and for t_k:
 //                  the parity of the hard decisions is the sign bit of the XOR of the posteriors' high words, and the sign of
@@ -40,6 +40,13 @@
 //       rounding   The word is sign | (alpha * mag_k): one v_mul_f64 of the same two operands the reference multiplies
 //                  (mag_k is its min1 or min2 after the clip), and (alpha * sign) * mag == sign * (alpha * mag) exactly for
 //                  sign = +-1.  The sign bit goes in with v_bfi_b32; alpha * mag_k >= 0 has a clear sign bit to replace.
+//       zero       The reference's variable sum is (((0.0 + a) + b) + c) + prior (kernels.py:279,316,320); the clean forms compute ((a + b) + c) + prior.
+//                  0.0 + a differs from a only for a = -0.0, so the two running sums differ only while every addend so far is -0.0, and
+//                  then as +0.0 against -0.0: once a nonzero message arrives both are that message's sum, exactly.  If all VDEG messages
+//                  are -0.0 the sums are +0.0 and -0.0, and the prior closes the gap: (+-0.0) + x = x for x != 0, (+-0.0) + (+0.0) = +0.0.
+//                  A prior of -0.0 would not: (+0.0) + (-0.0) = +0.0 but (-0.0) + (-0.0) = -0.0, a posterior the sign argument above
+//                  excludes.  Clean inputs have no such prior; the damped and the NaN-tolerant forms accept one and keep the add.
+//                  The same covers OWN with the own message first in check order: it adds o1 + own where the reference adds own + o1.
 //     Per check and iteration: CDEG v_sub, 3 * CDEG - 4 v_min_f64 (two of them the seeds), CDEG v_mul_f64, 2 * CDEG + 1 v_xor,
 //     CDEG v_bfi.  The suffix chain is built first, the prefix chain runs forward and each message leaves as soon as its two
 //     inputs exist, so t_k dies edge by edge.
@@ -47,8 +54,9 @@
 //     its OWN check, edges 0 and 1 of the reordered row (the check update does not depend on edge order: min and XOR are exact and commutative and no
 //     selector exists).  Their two messages never leave Rprev, their posteriors are gathered from registers, the row holds the other four words, and
 //     the variable sum takes its two other messages from LDS in ascending check order with the own one selected into its place: the reference's
-//     ((0 + a) + b) + c word for word.  Per thread and pass 8 words gathered and 6 stored instead of 12 and 8, for eight v_cndmask_b32 -- the LDS pipe,
-//     not VALU issue, bounds the loop (profiles/r20_own_edges.txt).  qldpc_set_option("regular_own_edges", 0) takes the body without ownership.
+//     ((0 + a) + b) + c, whose posterior word (a + b) + c gives as well ("zero" above).  Per thread and pass 8 words gathered and 6 stored instead of
+//     12 and 8, for eight v_cndmask_b32 -- the LDS pipe, not VALU issue, bounds the loop (profiles/r20_own_edges.txt).
+//     qldpc_set_option("regular_own_edges", 0) takes the body without ownership.
 // MC = true fuses the sampler (Philox4x32-10 stream of mc_common.h), the GF(2) syndrome (a6), the decode, the logical
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
@@ -136,6 +144,8 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     // a check and two columns; a team without a shot (b >= nshots) works on its own slot, which nobody else touches, and the lanes of the block that
     // belong to no team work on the dummy region Dl: a row of RST doubles, two posteriors, one parity word.  Nothing they compute is ever read.
     constexpr bool ALL = CLIPMIN;
+    // ZEROFREE: the variable sum starts at its first message instead of at 0.0 + that message (header comment, "zero"): clean inputs only
+    constexpr bool ZEROFREE = CLIPMIN;
     static_assert(!OWN || (CLIPMIN && CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg), "edge ownership: the clean (6,3) form");
     constexpr int NOWN = OWN ? kRegOwnOwned : 0;                                   // edges of a row that are not stored
     double *Dl = reinterpret_cast<double *>(lds + A.offD);
@@ -383,10 +393,11 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                         double s = 0.0;                                                        // kernels.py:279
                         if (OWN) {
                             const double o1 = Rl[voff[v][0]], o2 = Rl[voff[v][1]], own = Rprev[v];
-                            s += o1; s += vlast[v] ? o2 : own; s += vlast[v] ? own : o2;       // ascending check order (regular_own.h)
+                            s = ZEROFREE ? o1 : s + o1;                                        // clean forms start at the first message (header comment, "zero")
+                            s += vlast[v] ? o2 : own; s += vlast[v] ? own : o2;                // ascending check order (regular_own.h)
                         } else {
 #pragma unroll
-                            for (int d = 0; d < VDEG; d++) s += Rl[voff[v][d]];                // kernels.py:316, ascending check order
+                            for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? Rl[voff[v][0]] : s + Rl[voff[v][d]];   // kernels.py:316, ascending check order
                         }
                         const double xv = s + vprior[v];                                       // kernels.py:320
                         Vl[vj[v]] = xv;
@@ -402,6 +413,10 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             // update -- without its control: no unsat word, no freeze test, no `done`, no first-iteration case (it >= 2 here).  The parities are kept
             // alive by one OR per pass and one store per shot into the dummy region.
             unsigned parity = 0u;
+            // alpha_it travels in scalar registers: the pass's own alpha was loaded during the pass before it (the first one comes from the staged table),
+            // so no pass reads Al from LDS; the table A.alpha is never written by a kernel, hence the constant address space
+            const __attribute__((address_space(4))) double *alpha_tab = (const __attribute__((address_space(4))) double *)A.alpha;
+            double alpha_it = (it < max_iter) ? Al[it] : 0.0;
             for (; it < max_iter; it++) {
                 double x[CDEG];
                 unsigned ph = synw;
@@ -410,7 +425,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
                 for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(x[k]);               // kernels.py:349,356
                 parity |= ph;
-                clean_messages<CDEG, NOWN>(x, Rprev, true, Al[it], clip, synw, Rl + roff);
+                clean_messages<CDEG, NOWN>(x, Rprev, true, alpha_it, clip, synw, Rl + roff);
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(1);                                                     // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
                 double r[2][VDEG];
@@ -427,11 +442,13 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
                     double s = 0.0;                                                                // kernels.py:279
 #pragma unroll
-                    for (int d = 0; d < VDEG; d++) s += r[v][d];                                   // kernels.py:316, ascending check order
+                    for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? r[v][0] : s + r[v][d];   // kernels.py:316, ascending check order; no leading 0.0 + (header comment, "zero")
                     Vown[v] = s + vprior[v];                                                       // kernels.py:320
                     Vl[vj[v]] = Vown[v];
                 }
                 __builtin_amdgcn_s_setprio(0);
+                // the next pass's alpha, clamped (the table has max_iter entries): a uniform address, and the barrier below waits for LDS anyway
+                alpha_it = alpha_tab[it + 1 < max_iter ? it + 1 : max_iter - 1];
                 __syncthreads();
             }
             if (it == max_iter) {                                                                  // the syndrome test of values_{max_iter-1}
