@@ -427,6 +427,8 @@ QLDPC_EXPORT int qldpc_msgstats_histogram(qldpc_msgstats *S, const double *edges
         int64_t grid = std::min<int64_t>(4096, (total + 255) / 256);
         while (total / grid >= ((int64_t)1 << 31)) grid *= 2;
         const size_t lds = (size_t)(bins + 1) * 8 + (size_t)2 * bins * 4;
+        constexpr int lds_max = (kStatsMaxBins + 1) * 8 + 2 * kStatsMaxBins * 4;             // 65 544 bytes at 4096 bins: above 64 KB
+        if (lds > 48 * 1024 && (rc = ensure_max_lds(S->g->device, reinterpret_cast<const void *>(stats_hist_kernel), lds_max)) != QLDPC_OK) return rc;
         hipLaunchKernelGGL(stats_hist_kernel, dim3((unsigned)grid), dim3(256), lds, nullptr, S->B, S->L, S->g->n,
                            S->by_edge ? S->g->d_indices : (const int32_t *)nullptr, S->d_samples.as<double>(), S->d_err.as<int8_t>(),
                            T[d_edges], bins, T[d_hist]);
