@@ -283,7 +283,8 @@ int qldpc_gf2_spmv_batch(const qldpc_graph *g, int64_t B, const int8_t *vectors,
 int qldpc_gf2_spmv_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_vectors, int8_t *d_out, void *stream);
 
 /* a7: gf2_elimination (kernels.py:5-34): Gauss-Jordan on B byte matrices A[B][m][n] (0/1), b[B][m], in place.
- * pivot_rows/pivot_cols: int64[B][min(m,n)], num_pivots int32[B]. */
+ * pivot_rows/pivot_cols: int64[B][min(m,n)], num_pivots int32[B].  One workgroup per matrix with 5 m + 8 nwords + 40 bytes of LDS scratch:
+ * QLDPC_ERR_UNSUPPORTED above 150 KiB (m > 30710 at one row word), for this entry point and the packed one. */
 int qldpc_gf2_eliminate(int64_t B, int m, int n, uint8_t *A, uint8_t *b, int64_t *pivot_rows, int64_t *pivot_cols,
                         int32_t *num_pivots);
 /* a8: gf2_elimination_packed_core (kernels.py:48-96) on rows packed little-endian into uint64 words

@@ -250,6 +250,18 @@ def gf2_elimination_packed(A, b):
     return P, b, pr[:k].copy(), pc[:k].copy()
 
 
+def gf2_elimination_packed_words(P, b, n):
+    """The packed elimination on rows the caller packed: P uint64 [m, nwords] with nwords * 64 >= n (bits beyond column n allowed) -> as above."""
+    P = np.ascontiguousarray(P, dtype=np.uint64).copy()
+    m, nwords = P.shape
+    assert nwords * 64 >= n
+    b = _u8(b).copy()
+    pr = np.zeros(min(m, n) + 1, np.int64)
+    pc = np.zeros(min(m, n) + 1, np.int64)
+    k = lib().orc_gf2_elimination_packed(C.c_int(m), C.c_int(n), C.c_int(nwords), _p(P, C.c_uint64), _p(b, C.c_uint8), _p(pr, C.c_int64), _p(pc, C.c_int64))
+    return P, b, pr[:k].copy(), pc[:k].copy()
+
+
 def argsort_abs(llr):
     llr = _f64(llr)
     o = np.zeros(llr.size, np.int32)

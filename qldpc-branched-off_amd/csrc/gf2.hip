@@ -442,7 +442,7 @@ QLDPC_EXPORT int qldpc_gf2_eliminate_packed(int64_t B, int m, int n, int nwords,
     QLDPC_REQUIRE(A && b && pivot_rows && pivot_cols, "NULL buffer");
     const int maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
-    QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
+    if (lds > (size_t)kOsdElimMax) { set_error("GF(2) elimination: matrix too large for the LDS scratch (m=%d nwords=%d)", m, nwords); return QLDPC_ERR_UNSUPPORTED; }
     HostStage S;
     const auto dA = S.inout(A, A, B, m, nwords);
     const auto db = S.inout(b, b, B, m);
@@ -469,7 +469,7 @@ QLDPC_EXPORT int qldpc_gf2_eliminate(int64_t B, int m, int n, uint8_t *A, uint8_
     QLDPC_REQUIRE(A && b && pivot_rows && pivot_cols, "NULL buffer");
     const int nwords = ((n + 7) / 8 + 7) / 8, maxp = m < n ? m : n;
     const size_t lds = elim_lds_bytes(m, nwords);
-    QLDPC_REQUIRE(lds <= (size_t)kOsdElimMax, "matrix too large for the LDS scratch");
+    if (lds > (size_t)kOsdElimMax) { set_error("GF(2) elimination: matrix too large for the LDS scratch (m=%d nwords=%d)", m, nwords); return QLDPC_ERR_UNSUPPORTED; }
     HostStage S;
     const auto dA8 = S.inout(A, A, B, m, n);
     const auto dA = S.scratch<uint64_t>(B, m, nwords);
@@ -495,6 +495,12 @@ QLDPC_EXPORT int qldpc_osd0_batch(const qldpc_graph *g, int64_t B, const int8_t 
     QLDPC_USE_DEVICE(g->device);
     if (B == 0 || g->n == 0) return QLDPC_OK;
     QLDPC_REQUIRE(llr && hard && solution && (syndromes || g->m == 0), "NULL buffer");
+    if (g->m == 0) {      // no rows: no pivot, e_correction = 0 (osd.py:19-25); no kernel runs on an empty matrix, so the answer is written here
+        if (solution != hard) std::memmove(solution, hard, (size_t)B * g->n);
+        std::lock_guard<std::mutex> lk(g->mu);
+        g->osd_path = QLDPC_OSD_PATH_NONE; g->osd_detail = 0;
+        return QLDPC_OK;
+    }
     HostStage S;
     const auto ds = S.in(syndromes, B, g->m);
     const auto dl = S.in(llr, B, g->n);

@@ -183,7 +183,8 @@ TABLE = {
     "ident192": ("ident", 192, 592, None, "GJ", False, 192, "full row rank at m % 64 == 0 (non-W16)"),
     "empty130x20": ("empty", 130, 20, None, "GJ", False, 0, "rank 0: no sweep at all"),
     "halfdup256": ("halfdup", 256, 600, None, "GJ", False, 128, "half the rows duplicated: rank about m / 2, m % 64 == 0"),
-    # beyond everything
+    # the global kernel's own edge, then beyond everything
+    "m30710": ("plain", 30710, 64, None, "GLOBAL", False, 64, "largest scratch the literal elimination accepts"),
     "refused": ("plain", 30720, 64, None, "NONE", False, 64, "elim_lds_bytes > 150 KiB: QLDPC_ERR_UNSUPPORTED, no kernel"),
 }
 # the families whose label depends on a flag somewhere (every kind of boundary, both sides): run again under FLAG_SETS
