@@ -46,6 +46,7 @@
  *        additive, same version: qldpc_minsum_decode_path names the resident kernel's instantiation, QLDPC_DETAIL_RES_CDEG8 and QLDPC_DETAIL_RES_CPT2
  *        additive, same version (the suites pin 101): fixed-weight fault sampling on a circuit plan, qldpc_circuit_plan_use_fixed_weight,
  *        QLDPC_FIXED_WEIGHT_MAX and QLDPC_FIXED_WEIGHT_MAX_LOCS
+ *        additive, same version: BP+LSD, qldpc_lsd_batch[_dev], qldpc_circuit_plan_use_lsd and qldpc_circuit_plan_lsd_counts
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -354,6 +355,34 @@ int qldpc_osdcs_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, 
 int qldpc_osdcs_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
                           const double *d_weights, int order, const int32_t *d_select, const int32_t *d_select_count,
                           int8_t *d_solution, int32_t *d_flips, void *stream);
+/* BP+LSD: localized statistics decoding (Hillmann et al. 2024) as a post-processor of the OSD hand-over, batched over B shots of one graph.  New
+ * here (the reference has no counterpart).  It grows clusters around the unsatisfied checks and solves each on its own small system, so what it
+ * needs of a workgroup is set by the cap max_rows and not by m.  Per shot the inputs are syndromes int8[m], llr f64[n] and hard int8[n]; the
+ * parameters are bits_per_step (1..64) and max_rows (1..1024).  The key of a column is key(j) = (|llr_j| with NaN as +inf, j), compared
+ * lexicographically: qldpc_osd0_batch's order with ordering = NULL.
+ *   0. b = s + H hard (mod 2).  b = 0: the solution is hard, flag 0, no rounds.
+ *   1. State: A, an ordered list of added columns, empty at first; R, the set of cluster rows, {r : b_r = 1} at first.  The clusters are the
+ *      connected components of the bipartite graph on (R, A) with H's edges; each seed row is alone at first.  Every row of an added column is
+ *      in R, so a cluster K is VALID iff b restricted to K lies in the span of the columns of A inside K.
+ *   2. Round t = 1, 2, ..., on the state at the start of the round: for every invalid cluster K, cand(K) = {j not in A : column j has a row in
+ *      K}.  An empty cand(K) ends the shot with flag 2 (the residual is outside the reachable column space).  Otherwise K picks its
+ *      min(bits_per_step, |cand(K)|) smallest keys, and N_t is the union of the picks.  If |R u rows(N_t)| > max_rows the shot ends with flag 1
+ *      (capped).  Else N_t is appended to A in ascending key order, R takes its rows, and clusters and validity are evaluated again.  The loop
+ *      stops when every cluster is valid.
+ *   3. Pivots are the columns of A independent of the ones before them in A; c is the unique vector on the pivots with H c = b; the solution is
+ *      hard ^ c.  info int32[B][4] = {flag, rounds, |R|, |A|}, the last three 0 when the flag is not 0.
+ *   4. Shots with flag 1 or 2 get exactly qldpc_osd0_batch's answer (the OSD-0 kernels run on them behind the cluster kernel).
+ * The outcome is a function of sets and of the (round, key) order only: no thread or lane order enters it (tests/lsd_model.py is the model).
+ * With bits_per_step = 1 a flag-0 answer was qldpc_osd0_batch's on every recorded circ144 case; larger steps take fewer rounds and may differ.
+ * QLDPC_ERR_INVALID for parameters outside their ranges; QLDPC_ERR_UNSUPPORTED for n >= 65535, m > 65535, or a layout at max_rows beyond
+ * 160 KiB of LDS (csrc/lsd_plan.h).  solution int8[B][n]. */
+int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
+                    int max_rows, int8_t *solution, int32_t *info);
+/* same on device pointers; only enqueues on `stream`.  d_select / d_select_count as in qldpc_osd0_batch_dev: shots not listed keep whatever
+ * d_solution and d_info hold.  d_solution may alias d_hard. */
+int qldpc_lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard, int bits_per_step,
+                        int max_rows, const int32_t *d_select, const int32_t *d_select_count, int8_t *d_solution, int32_t *d_info,
+                        void *stream);
 
 /* Sliding-window decoding over the row layers of a space-time decoding matrix: min-sum + OSD-0 on W layers at a time, the first C layers
  * of every window committed.  New here (the reference decodes the whole matrix).  The window graphs do not grow with the number of layers,
@@ -620,6 +649,16 @@ int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *plan, double alpha, double 
  * Relay-BP (and qldpc_circuit_plan_use_relay after this call returns QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is
  * outside the range of qldpc_osdcs_batch. */
 int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *plan, int order);
+/* Switches the plan's OSD stage to BP+LSD (qldpc_lsd_batch with these parameters): the same unconverged trials, the same phase brackets, the
+ * same tally slots.  It goes with flooding, the layered schedule, guided decimation and f32 in either order, and may be called again with new
+ * parameters.  QLDPC_ERR_INVALID on a plan created with use_osd = 0, switched to Relay-BP, to windows or to OSD-CS (and
+ * qldpc_circuit_plan_use_relay / _use_window / _use_osd_cs after this call return QLDPC_ERR_INVALID), or for parameters outside their ranges;
+ * QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_lsd_batch refuses at this max_rows. */
+int qldpc_circuit_plan_use_lsd(qldpc_circuit_plan *plan, int bits_per_step, int max_rows);
+/* The shots the plan's LSD stage has ended with flag 0 / 1 / 2 since the last clear: counts int64[2][3], counts[sector][flag] (sector 1 stays 0 on
+ * a one-sector plan; all 0 on a plan that was never switched).  The cluster kernel accumulates them on the device; the three of a sector add up to
+ * the sector's OSD tally slot over the same batches.  Synchronises `stream`. */
+int qldpc_circuit_plan_lsd_counts(qldpc_circuit_plan *plan, void *stream, int clear, int64_t *counts);
 /* Switches the BP + OSD-0 stage of both sectors to sliding-window decoding (one-way): a qldpc_window_decoder per sector with the plan's
  * prior, alpha schedule, max_iter and clip_llr, layer_rows = the sector's number of checks (num_x_checks for sector Z, num_z_checks for
  * sector X: one layer per syndrome cycle).  Sampler, judge and tally are unchanged; bp_conv_* counts the trials in which every window

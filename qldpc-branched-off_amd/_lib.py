@@ -434,6 +434,42 @@ def osdcs_batch(graph, syndromes, llr, hard, weights, order):
     return sol, flips
 
 
+LSD_MAX_BITS, LSD_MAX_ROWS = 64, 1024
+LSD_DEFAULTS = {"bits_per_step": 1, "max_rows": 512}
+
+
+def lsd_params(params=None):
+    """The argument rule of BP+LSD, before any device call: None or a dict with bits_per_step (1..LSD_MAX_BITS) and / or max_rows (1..LSD_MAX_ROWS) ->
+    the complete dict of ints (LSD_DEFAULTS where a key is missing)."""
+    p = dict(LSD_DEFAULTS)
+    extra = set(params or {}) - set(p)
+    if extra:
+        raise ValueError(f"unknown LSD parameter(s) {sorted(extra)} (expected {sorted(p)})")
+    for k, v in (params or {}).items():
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"LSD {k} must be an integer, got {v!r}")
+        p[k] = int(v)
+    if not 1 <= p["bits_per_step"] <= LSD_MAX_BITS:
+        raise ValueError(f"LSD bits_per_step must be in 1..{LSD_MAX_BITS}, got {p['bits_per_step']}")
+    if not 1 <= p["max_rows"] <= LSD_MAX_ROWS:
+        raise ValueError(f"LSD max_rows must be in 1..{LSD_MAX_ROWS}, got {p['max_rows']}")
+    return p
+
+
+def lsd_batch(graph, syndromes, llr, hard, bits_per_step=1, max_rows=512):
+    """qldpc_lsd_batch on host arrays: BP+LSD, cluster-local post-processing of the OSD hand-over (semantics in include/qldpc_hip.h)
+    -> (solution int8[B, n], info int32[B, 4] = flag, rounds, cluster rows, added columns; flag 1 capped / 2 no candidates: OSD-0's answer)."""
+    p = lsd_params({"bits_per_step": bits_per_step, "max_rows": max_rows})
+    syndromes = i8(syndromes).reshape(-1, graph.m) if graph.m else np.zeros((np.asarray(hard).reshape(-1, graph.n).shape[0], 0), np.int8)
+    B = syndromes.shape[0]
+    llr, hard = f64(llr).reshape(B, graph.n), i8(hard).reshape(B, graph.n)
+    sol = np.zeros((B, graph.n), np.int8)
+    info = np.zeros((B, 4), np.int32)
+    check(lib().qldpc_lsd_batch(graph.handle, B, ptr(syndromes, C.c_int8), ptr(llr, C.c_double), ptr(hard, C.c_int8), p["bits_per_step"], p["max_rows"],
+                                ptr(sol, C.c_int8), ptr(info, C.c_int32)))
+    return sol, info
+
+
 def gf2_spmv_batch(graph, vectors):
     """s = H e over GF(2) for B vectors (qldpc_gf2_spmv_batch, kernels.py:222-231): int8[B, n] -> int8[B, m]."""
     vectors = i8(vectors).reshape(-1, graph.n)
@@ -961,6 +997,20 @@ class CircuitPlan(Owner):
             raise ValueError(f"OSD-CS order must be in 0..{OSDCS_MAX_ORDER}, got {order}")
         check(lib().qldpc_circuit_plan_use_osd_cs(self._h, order))
         self.osd_cs_order = order
+
+    def use_lsd(self, bits_per_step=1, max_rows=512):
+        """Run BP+LSD in the OSD stage from now on (qldpc_circuit_plan_use_lsd; again with new parameters is allowed).  Goes with flooding, the layered
+        schedule, guided decimation and f32; not with Relay-BP, windows or OSD-CS."""
+        p = lsd_params({"bits_per_step": bits_per_step, "max_rows": max_rows})
+        check(lib().qldpc_circuit_plan_use_lsd(self._h, p["bits_per_step"], p["max_rows"]))
+        self.lsd = p
+
+    def lsd_counts(self, stream=0, clear=False):
+        """int64[2, 3]: the shots per sector that the LSD stage ended with flag 0 (solved in clusters) / 1 (capped) / 2 (no candidates) since the last
+        clear (qldpc_circuit_plan_lsd_counts); a row adds up to the sector's OSD tally slot over the same batches."""
+        counts = np.zeros((2, 3), np.int64)
+        check(lib().qldpc_circuit_plan_lsd_counts(self._h, C.c_void_p(stream), C.c_int(int(clear)), ptr(counts, C.c_int64)))
+        return counts
 
     def use_window(self, window, commit):
         """Decode both sectors window by window from now on: `window` syndrome cycles at a time, the first `commit` of them committed

@@ -143,7 +143,7 @@ using namespace qldpc;
 
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
 enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW };      // who fills the BP bracket and its follow-up
-enum class Osd { OSD0, CS };                                        // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
+enum class Osd { OSD0, CS, LSD };                                     // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
 
 struct qldpc_circuit_plan {
     // Everything that exists once per sector: sec[0] = Z, sec[1] = X.  A batch decodes Z, then X, on the caller's stream.
@@ -157,6 +157,7 @@ struct qldpc_circuit_plan {
         DevBuf d_syn, d_true, d_det, d_llr, d_conv, d_iter, d_list;
         DevBuf d_legs;                             // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
         DevBuf d_flips;                            // Osd::CS: workspace of the sweep
+        DevBuf d_lsd_info;                         // Osd::LSD: info of the batch in flight
         // decode of recorded events (events.hip): the record bit of every row (ev_tab, else the contiguous run at ev_base); the predictions of a batch
         DevBuf d_evtab, d_pred;
         bool ev_tab = false;
@@ -188,6 +189,8 @@ struct qldpc_circuit_plan {
     RelayParams rp{};                              // Path::RELAY (relay_bp.hip)
     DecimParams dp{};                              // Path::DECIM (decimation.hip)
     int cs_order = 0;                              // Osd::CS (osd_cs.hip)
+    int lsd_bits = 0, lsd_rows = 0;                // Osd::LSD (lsd.hip)
+    DevBuf d_lsd_counts;                           // ... uint64[2][3]: shots per sector that ended with flag 0 / 1 / 2 (the kernel accumulates)
     // hipEvent brackets of the phases of every batch not yet read by qldpc_circuit_plan_phase_times
     struct Bracket { int phase; hipEvent_t a, b; };
     std::vector<Bracket> pending;
@@ -556,6 +559,9 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
         if (P->osd == Osd::CS)
             rc = osdcs_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(),
                                      S.d_prior.as<double>(), P->cs_order, S.d_det.as<int8_t>(), S.d_flips.as<int32_t>(), s);
+        else if (P->osd == Osd::LSD)
+            rc = lsd_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), P->lsd_bits,
+                                   P->lsd_rows, S.d_det.as<int8_t>(), S.d_lsd_info.as<int32_t>(), P->d_lsd_counts.as<unsigned long long>() + 3 * sector, s);
         else
             rc = osd0_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), nullptr,
                                     S.d_det.as<int8_t>(), P->flags, s);
@@ -686,20 +692,23 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 //   Path: who fills the BP bracket and its follow-up -- flooding min-sum (as created), the layered schedule, guided decimation, single precision (f32),
 //     Relay-BP or sliding windows.  A plan leaves flooding at most once.  Asking again for the path it is on brings new arguments (Relay-BP, layered,
 //     decimation), changes nothing (f32) or is refused (windows).
-//   OSD stage: OSD-0 (as created; none with use_osd = 0) or OSD-CS.  OSD-CS needs use_osd, goes with flooding, layered, decimation and f32 whichever came
-//     first, and may be asked for again with a new order.  It goes with neither Relay-BP nor windows, whichever came first.
+//   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation and f32
+//     whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
+//     refuse each other in either order.
 //   Windows need use_osd as well; Relay-BP, layered, decimation and f32 do not.  Windows, layered, decimation and f32 need damping = 1.
 // Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation: finite priors and a supported graph).
-// `to`: the path asked for; Path::FLOOD stands for the one request on the other axis, OSD-CS (no call asks for flooding).
+// `to`: the path asked for; Path::FLOOD stands for a request on the other axis, for the OSD stage `stage` (no call asks for flooding).
 // QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
-static int switch_allowed(const qldpc_circuit_plan *P, Path to) {
+static int switch_allowed(const qldpc_circuit_plan *P, Path to, Osd stage = Osd::CS) {
     static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding"};
-    static const char osd_cs_name[] = "BP + OSD-CS";
+    static const char *const osd_name[] = {"BP + OSD-0", "BP + OSD-CS", "BP + LSD"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    const bool cs = to == Path::FLOOD;
+    const bool cs = to == Path::FLOOD;                                   // a request on the OSD axis: `stage` says for which of the two
+    const bool switched = P->osd != Osd::OSD0, other = cs && switched && P->osd != stage;      // OSD-CS and LSD refuse each other
     const auto without_cs = [](Path p) { return p == Path::RELAY || p == Path::WINDOW; };
-    const char *now = P->path == Path::FLOOD && P->osd == Osd::CS ? osd_cs_name : path_name[(int)P->path], *asked = cs ? osd_cs_name : path_name[(int)to];
-    const bool follows = cs ? !without_cs(P->path) : P->path == Path::FLOOD ? !(P->osd == Osd::CS && without_cs(to)) : (P->path == to && to != Path::WINDOW);
+    const char *now = other || (P->path == Path::FLOOD && switched) ? osd_name[(int)P->osd] : path_name[(int)P->path];
+    const char *asked = cs ? osd_name[(int)stage] : path_name[(int)to];
+    const bool follows = cs ? !without_cs(P->path) && !other : P->path == Path::FLOOD ? !(switched && without_cs(to)) : (P->path == to && to != Path::WINDOW);
     QLDPC_REQUIRE(follows, "the plan was switched to %s: %s cannot follow", now, asked);
     QLDPC_REQUIRE(P->use_osd || !(cs || to == Path::WINDOW), "the plan was created with use_osd = 0: %s needs its OSD stage", asked);
     QLDPC_REQUIRE(P->damping == 1.0 || cs || to == Path::RELAY, "%s needs damping = 1 (the plan has %g)", asked, P->damping);
@@ -761,6 +770,33 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *P, int order)
         return rc;
     P->cs_order = order;
     P->osd = Osd::CS;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_lsd(qldpc_circuit_plan *P, int bits_per_step, int max_rows) {
+    int rc = switch_allowed(P, Path::FLOOD, Osd::LSD);
+    if (rc != QLDPC_OK || (rc = lsd_check_params(bits_per_step, max_rows)) != QLDPC_OK) return rc;
+    for (int i = 0; i < P->nsec; i++)
+        if ((rc = lsd_graph_supported(P->sec[i].g, max_rows)) != QLDPC_OK) return rc;
+    if ((rc = ensure_each(P, &Sector::d_lsd_info, (size_t)P->batch * 16)) != QLDPC_OK) return rc;
+    if (!P->d_lsd_counts.p) {                                            // (asked again: the counts go on)
+        QLDPC_USE_DEVICE(P->device);
+        if ((rc = P->d_lsd_counts.ensure(6 * 8)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(zero_now(P->d_lsd_counts.p, 6 * 8));
+    }
+    P->lsd_bits = bits_per_step; P->lsd_rows = max_rows;
+    P->osd = Osd::LSD;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_lsd_counts(qldpc_circuit_plan *P, void *stream, int clear, int64_t *counts) {
+    QLDPC_REQUIRE(P != nullptr && counts != nullptr, "NULL argument");
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    for (int i = 0; i < 6; i++) counts[i] = 0;
+    if (!P->d_lsd_counts.p) return QLDPC_OK;
+    QLDPC_HIP_TRY(hipMemcpy(counts, P->d_lsd_counts.p, 6 * 8, hipMemcpyDeviceToHost));
+    if (clear) QLDPC_HIP_TRY(zero_now(P->d_lsd_counts.p, 6 * 8));
     return QLDPC_OK;
 }
 

@@ -25,7 +25,7 @@ Differences that are deliberate and documented:
 The extensions below choose what a worker's plan decodes with, on the plan's two axes.  The path: at most one of
 ``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``precision="f32"`` leaves flooding min-sum, and none of them
 goes with the reference's OSD-w pass (``osd_order > 0`` with ``decoder="bp_osd"``).  The OSD stage: ``decoder="bp_osd_cs"`` puts OSD-CS in the place
-of OSD-0; it goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
+of OSD-0 and ``decoder="bp_lsd"`` puts BP+LSD there; each goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
 
 ``decoder="relay_bp"`` (an extension; ``"bp_osd"`` is the default) decodes both sectors with Relay-BP (``decoding/relay.py``) instead of
 min-sum + OSD-0, with ``relay_params`` over ``_lib.RELAY_DEFAULTS``.  Relay-BP uses its own constant alpha, so the alpha / beta estimators do not run,
@@ -37,6 +37,11 @@ plan's OSD stage, with the plan's priors as the weights.  Here ``osd_order`` is 
 reliable non-pivot columns), not the reference's OSD-w order.  The alpha / SCOPT estimators run as for ``"bp_osd"``; ``relay_params`` raises
 ValueError.  OSD-CS returns OSD-0's answer wherever the syndrome is not reproducible, so no OSD-w pass follows.  The result also holds
 ``decoder`` and ``osd_order``.
+
+``decoder="bp_lsd"`` (an extension) runs BP+LSD (``decoding/lsd.py``: cluster-local post-processing, Hillmann et al. 2024) in the plan's OSD stage,
+with ``lsd={"bits_per_step": 1, "max_rows": 512}`` (either key may be left out).  Its rules are those of ``"bp_osd_cs"``, and ``osd_order`` must be 0.
+A trial whose clusters would pass ``max_rows`` rows, or whose residual no column reaches, gets OSD-0's answer.  The result also holds ``decoder``,
+``lsd`` (the parameters used) and ``lsd_counts`` (int64[2, 3]: trials per sector that ended solved in clusters / capped / without candidates).
 
 ``window=(W, C)`` (an extension; ``decoder="bp_osd"`` with ``osd_order=0`` only) decodes both sectors with the
 sliding-window decoder (``decoding/window.py``): W syndrome cycles at a time, the first C of them committed, min-sum + OSD-0 per window.  The
@@ -93,20 +98,29 @@ def _estimation_trials(requested, n_cols, error_rate):
 
 
 def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
-                     maxIter, num_workers):
+                     maxIter, num_workers, lsd=None):
     """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision), shared by run_simulation and run_dem_simulation:
     raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered", "decimation", "f32", "relay" or
-    "window": who decodes the BP stage) and ``osd_cs`` (OSD-CS instead of OSD-0 in the OSD stage) -- with the normalised parameters of that path
-    (``layers``, ``decimation``, ``relay_params``, ``window``; None where the path is another)."""
+    "window": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
+    parameters, else None) -- with the normalised parameters of that path (``layers``, ``decimation``, ``relay_params``, ``window``; None where the path
+    is another)."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
         raise ValueError(f"Unsupported precision: {precision!r} (expected 'f64' or 'f32')")
     if schedule not in ("flooding", "layered"):
         raise ValueError(f"Unsupported schedule: {schedule!r} (expected 'flooding' or 'layered')")
-    if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs"):
-        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp' or 'bp_osd_cs')")
+    if decoder not in ("bp_osd", "relay_bp", "bp_osd_cs", "bp_lsd"):
+        raise ValueError(f"Unsupported decoder: {decoder!r} (expected 'bp_osd', 'relay_bp', 'bp_osd_cs' or 'bp_lsd')")
     osd_cs = decoder == "bp_osd_cs"
+    if lsd is not None and decoder != "bp_lsd":
+        raise ValueError("lsd is for decoder='bp_lsd'")
+    if decoder == "bp_lsd":
+        if osd_order != 0:
+            raise ValueError(f"decoder='bp_lsd' goes with osd_order=0 (got {osd_order}): LSD takes the place of the OSD stage")
+        if lsd is not None and not isinstance(lsd, dict):
+            raise ValueError("lsd must be a dict with bits_per_step and / or max_rows (or None)")
+        lsd = _lib.lsd_params(lsd)
     # the path: at most one argument leaves flooding min-sum (the plan's own rule, qldpc_circuit_plan_use_*) ...
     asked = [(path, text) for path, text, given in (("f32", "precision='f32'", precision == "f32"), ("decimation", "decimation=...", decimation is not None),
                                                      ("layered", "schedule='layered'", schedule == "layered"),
@@ -152,7 +166,7 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         if not isinstance(layers, (tuple, list)) or len(layers) != 2:
             raise ValueError("layers must be a pair (row_layer_z, row_layer_x); either may be None")
     elif path == "window":
-        if osd_cs:
+        if osd_cs or lsd is not None:
             raise ValueError("window=(W, C) goes with decoder='bp_osd' and osd_order=0 only")
         if not isinstance(window, (tuple, list)) or len(window) != 2:
             raise ValueError("window must be a pair (W, C)")
@@ -168,7 +182,7 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         relay_params = _lib.relay_params(relay_params, with_clip=False)
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
-    return SimpleNamespace(path=path, osd_cs=osd_cs, layers=layers, decimation=decimation, relay_params=relay_params, window=window)
+    return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window)
 
 
 def _worker_devices(num_workers, devices, device):
@@ -199,7 +213,7 @@ def _worker_devices(num_workers, devices, device):
 
 def _plan_switch(rules, csr, osd_order):
     """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
-    dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` in the OSD stage when the rules ask for it, then moves the BP stage to
+    dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` or LSD in the OSD stage when the rules ask for it, then moves the BP stage to
     rules.path.  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
     layers = None
     if rules.path == "layered":
@@ -211,6 +225,8 @@ def _plan_switch(rules, csr, osd_order):
     def switch(plan):
         if rules.osd_cs:
             plan.use_osd_cs(int(osd_order))
+        if rules.lsd is not None:
+            plan.use_lsd(**rules.lsd)
         to_path(plan)
 
     return switch, layers
@@ -359,6 +375,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         extra["phase_ms_per_batch"] = {k: v / max(nbat, 1) for k, v in ph.items()}
     except _lib.QldpcError:
         pass
+    if rules.lsd is not None:                                                    # flag 0 / 1 / 2 per sector over this process's plans (whole rounds, like the tally)
+        extra["lsd_counts"] = np.sum([w.plan.lsd_counts(w.stream.ptr) for w in workers], axis=0)
     for w in workers:
         w.close()
     if stop_on_errors:
@@ -369,6 +387,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     result.update(extra)
     if rules.osd_cs:
         result.update(decoder=decoder, osd_order=int(osd_order))
+    if rules.lsd is not None:
+        result.update(decoder=decoder, lsd=dict(rules.lsd))
     per_trial = [float(total[T[slot]]) / max(int(total[T["trials"]]), 1) for slot in ("legs_z", "legs_x")]      # Relay-BP: legs; decimation: rounds
     if rules.path == "relay":
         result.update(decoder=decoder, relay_params=dict(rules.relay_params), mean_legs_z=per_trial[0], mean_legs_x=per_trial[1])
@@ -415,9 +435,9 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", **bb_params):
+                   layers=None, decimation=None, precision="f64", lsd=None, **bb_params):
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
-                             use_dynamic_alpha, scopt, maxIter, num_workers)
+                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd)
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:

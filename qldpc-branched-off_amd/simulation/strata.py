@@ -233,7 +233,7 @@ def _sweep(plan, stream, n_locs, weights, cap, target_failures, batch, base_seed
 def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=None, trials_per_weight=4096, target_failures=None,
                       max_trials_per_weight=None, coverage=1e-9, num_cycles=12, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding",
                       layers=None, decimation=None, precision="f64", relay_params=None, precomputed_matrices=None, device=None, base_seed=0, batch=16384,
-                      flags=0, **bb_params):
+                      flags=0, lsd=None, **bb_params):
     """One sweep over the number of faults on the circuit plan of ``run_simulation`` -> WeightStrata.
 
     The circuit and decoder arguments are ``run_simulation``'s, under the same rules (``engine._extension_rules``: ValueError before any device call).
@@ -246,7 +246,7 @@ def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=No
     Per weight: ``trials_per_weight`` trials; with ``target_failures``, batches of ``batch`` until that many failures or ``max_trials_per_weight``
     (default ``trials_per_weight``) trials -- whole batches, all counted.
     One plan on a single ``device`` serves the whole sweep; weight w uses the global trial range starting at ``w << 40``."""
-    rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, None, None, True, False, maxIter, None)
+    rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, None, None, True, False, maxIter, None, lsd=lsd)
     if decoder == "bp_osd" and osd_order > 0:
         raise ValueError(f"osd_order={osd_order} with decoder='bp_osd' asks for the OSD-w pass, which runs outside the plan; use decoder='bp_osd_cs' "
                          "(osd_order is then the combination-sweep order)")
@@ -269,12 +269,12 @@ def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=No
 
 def run_dem_weight_strata(dem, weights=None, p_range=None, trials_per_weight=4096, target_failures=None, max_trials_per_weight=None, coverage=1e-9,
                           maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding", layers=None, decimation=None, precision="f64",
-                          relay_params=None, alpha_mode=None, alvarado_alpha=None, device=None, base_seed=0, batch=16384, flags=0):
+                          relay_params=None, alpha_mode=None, alvarado_alpha=None, device=None, base_seed=0, batch=16384, flags=0, lsd=None):
     """``run_weight_strata`` for a DetectorErrorModel whose mechanisms all have ONE probability (N = its mechanisms); the arguments and rules are
     ``run_dem_simulation``'s.  The decoder view -- and with it the priors -- is the model's own, held fixed across the sweep.  A model with two
     different probabilities raises ValueError before any device call."""
     rules, alpha_mode, alphas = dem_mod._dem_rules("run_dem_weight_strata", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window,
-                                                   schedule, layers, decimation, precision)
+                                                   schedule, layers, decimation, precision, lsd=lsd)
     thr = np.floor(dem.prob * 4294967296.0)
     odd = np.flatnonzero(thr != thr[0]) if thr.size else np.zeros(0, np.int64)
     if odd.size:
