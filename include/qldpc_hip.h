@@ -149,6 +149,9 @@ int qldpc_device_count(void);
  *                         variable thread of two of its own columns (csrc/regular_own.h), 0 = the body without ownership on every graph
  *   "regular_own_search"  read by qldpc_graph_create: 1 (default) = of the valid assignments of those columns the one whose gathers the LDS bank model of
  *                         csrc/regular_own.h prices lowest, 0 = the first matching found
+ *   "regular_place"       read at a fixed-work launch of that form: 1 (default) = every thread takes the LDS addresses of its posteriors and messages from the placement of
+ *                         csrc/regular_place.h (edge colouring: the gathers and the message stores free of bank conflicts), built at the handle's first
+ *                         launch with a workgroup shape; 0 = the linear layout, through the same kernel
  *   "regular_kernel", "wave_cpl", "wave_rst", "wave_grid"  experiments build only: the wave-private decoder (csrc/minsum_wave.hip); the
  *                         product library accepts 0 and answers anything else with QLDPC_ERR_UNSUPPORTED */
 int qldpc_set_option(const char *name, int value);

@@ -297,6 +297,14 @@ struct qldpc_graph {
         return rc;
     }
     int32_t *d_regown = nullptr;     // [m][16] edge-ownership records of the regular (6,3) kernel (regular_own.h), NULL where the graph has no assignment; built at creation
+    // LDS place tables of that kernel (regular_place.h), one per workgroup shape: built and uploaded at the first launch with the shape and kept for the
+    // handle's life (minsum_regular.hip: regular_place_table).  A shape is (S, block): "mc_list_shots" and a long iteration table change S on the same
+    // graph.  placed = 0: today's linear addresses as a table, which also depend on where the dummy region lies (offD).  dev.p == NULL: placement
+    // declined the shape.  Guarded by mu_place, which is held for the build and the upload only.
+    std::vector<int32_t> regown;     // the host copy of d_regown the tables are built from
+    struct PlaceEntry { int S = 0, block = 0, placed = 0, offD = 0; qldpc::DevBuf dev; };
+    mutable std::mutex mu_place;
+    mutable std::vector<PlaceEntry> place_cache;
     // Device workspaces of the decode / OSD kernels.  `mu` guards the bookkeeping while launches are enqueued; the buffers themselves
     // are protected in STREAM order: every user calls ws_acquire(stream) before its launches and ws_release(stream) after them
     // (StreamHandover above).

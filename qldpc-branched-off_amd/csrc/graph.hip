@@ -337,7 +337,7 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL).
         // Which valid assignment it is changes LDS bank conflicts only, never a result ("regular_own_search", options.hip).
         std::vector<int32_t> own;
-        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) rc = g->own(&g->d_regown, own);
+        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) { rc = g->own(&g->d_regown, own); g->regown = std::move(own); }
     }
     if (rc != QLDPC_OK) return rc;
     *out = G.release();

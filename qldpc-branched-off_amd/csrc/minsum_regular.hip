@@ -57,6 +57,14 @@
 //     ((0 + a) + b) + c, whose posterior word (a + b) + c gives as well ("zero" above).  Per thread and pass 8 words gathered and 6 stored instead of
 //     12 and 8, for eight v_cndmask_b32 -- the LDS pipe, not VALU issue, bounds the loop (profiles/r20_own_edges.txt).
 //     qldpc_set_option("regular_own_edges", 0) takes the body without ownership.
+//   * the fixed-work ownership form (PLACE) takes WHERE in LDS its posteriors and messages live from a per-thread record (regular_place.h), built per
+//     (S, block) on the host by edge colouring and loaded once into 14 address registers: the four posterior gathers, the four message gathers and the
+//     four message stores of every wave are free of bank conflicts, the two posterior stores nearly so.  The row leaves as four independent
+//     ds_write_b64.  The kernel's edges 2 .. 5 are "whatever posterior gather k reads": the table may order a check's four stored edges as it likes,
+//     because Rprev[k] and the message store of edge k follow the gather and the check update is order-free (above).  The readers of a thread's own
+//     posterior (prologue store, final syndrome test, logical comparison, export, out_llr) use the record's store places.  No address is packed: the
+//     bare loop keeps one basic block, 64 VGPRs and no scratch access with 14 address registers.  qldpc_set_option("regular_place", 0) launches the
+//     same kernel with the linear addresses as a table.  The early-exit form keeps the slot-relative addresses (see PLACE below).
 // MC = true fuses the sampler (Philox4x32-10 stream of mc_common.h), the GF(2) syndrome (a6), the decode, the logical
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
@@ -68,6 +76,7 @@
 #include "minsum_f64.h"
 #include "regular_plan.h"
 #include "regular_own.h"
+#include "regular_place.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -78,6 +87,7 @@ struct RegArgs {
     int m, n, max_iter, fixed, S, TS;
     const int32_t *indptr, *indices, *colptr, *rowidx, *csc2csr;
     const int32_t *own;             // ownership records of the (6,3) clean form (regular_own.h), NULL = the body without ownership
+    const int32_t *place;           // with `own`, fixed work: the LDS places of every thread of the workgroup, [block] records (regular_place.h)
     int64_t B;
     const double *prior, *alpha;
     double damping, clip;
@@ -95,9 +105,11 @@ struct RegArgs {
 
 // The compare-free message words of one check (header comment): x holds the gathered posteriors and becomes the unclipped t_k = x_k - Rprev_k
 // (`later`: iteration 0 reads priors, nothing to subtract), the clip sits in the two chain seeds (cmin), the words go to Rprev and to the check's row.
-// SKIP: the first SKIP edges are the thread's own columns (regular_own.h); their words stay in Rprev only, edge k >= SKIP goes to row[k - SKIP].
+// SKIP: the first SKIP edges are the thread's own columns (regular_own.h); their words stay in Rprev only, edge k >= SKIP goes to row[k - SKIP], or, with a
+// place table `at` (regular_place.h), to row[at[k - SKIP]]: CDEG - SKIP independent stores.
 template <int CDEG, int SKIP = 0>
-__device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev)[CDEG], bool later, double alpha, double cmin, unsigned synw, double *row) {
+__device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev)[CDEG], bool later, double alpha, double cmin, unsigned synw, double *row,
+                                               const int *at = nullptr) {
     unsigned spw = synw;                                                       // sign of the whole row in bit 31
 #pragma unroll
     for (int k = 0; k < CDEG; k++) {
@@ -118,7 +130,7 @@ __device__ __forceinline__ void clean_messages(double (&x)[CDEG], double (&Rprev
         const unsigned hi = ((unsigned)__double2hiint(prod) & 0x7fffffffu) | (sgn & 0x80000000u);
         const double msg = __hiloint2double((int)hi, __double2loint(prod));
         Rprev[k] = msg;
-        if (k >= SKIP) row[k - SKIP] = msg;
+        if (k >= SKIP) row[at ? at[k - SKIP] : k - SKIP] = msg;
     }
 }
 
@@ -148,6 +160,10 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     constexpr bool ZEROFREE = CLIPMIN;
     static_assert(!OWN || (CLIPMIN && CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg), "edge ownership: the clean (6,3) form");
     constexpr int NOWN = OWN ? kRegOwnOwned : 0;                                   // edges of a row that are not stored
+    // PLACE: the fixed-work ownership form takes every LDS address of its posteriors and messages from a per-thread place record (regular_place.h).  The
+    // early-exit form keeps the slot-relative addresses: its iteration loop is the one with the freeze bookkeeping, three more address registers took its
+    // spills from 16 to 25 VGPRs, and the launch on listed shots under reference semantics, a few iterations per workgroup, ran 27 % longer (profiles/r24_place.txt)
+    constexpr bool PLACE = OWN && FIXED;
     double *Dl = reinterpret_cast<double *>(lds + A.offD);
     double *Rl = (ALL && !in_team) ? Dl : reinterpret_cast<double *>(lds) + (size_t)sl * m * RST;
     double *Vl = (ALL && !in_team) ? Dl + RST : reinterpret_cast<double *>(lds + A.offV) + (size_t)sl * n;
@@ -211,6 +227,32 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 
     auto vcol = [&](int v) { return OWN ? ecol(v) : vj[v]; };             // OWN: the owned columns are edges 0 and 1 of the reordered row
 
+    // PLACE: every LDS address of the posteriors and the messages comes from the thread's place record (regular_place.h), in doubles from the start of the
+    // workgroup's LDS and loaded once; the slot-relative Rl / Vl / roff / coff / voff / vj and the redirection of the lanes of no team to Dl are not used by
+    // this form (a lane of no team has places of its own in the record, or the dummy region's where the table holds the linear layout).  The kernel's
+    // edges 2 .. 5 are whatever the four posterior gathers read: the same order in Rprev and in the message stores, any order for the check update.
+    double *Lb = reinterpret_cast<double *>(lds);
+    int pgat[CDEG], mgat[4], msto[4];       // pgat[k]: the posterior of edge k (k < NOWN: where the thread stores its own), mgat[2 v + d]: the two other messages of owned column v, msto[k - NOWN]: the row word of edge k
+#pragma unroll
+    for (int k = 0; k < CDEG; k++) pgat[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { mgat[k] = 0; msto[k] = 0; }
+    if (PLACE) {
+        static_assert(kRegPlaceWords == 16, "a record is four 16-byte loads");
+        const int4 *rec4 = reinterpret_cast<const int4 *>(A.place) + (size_t)threadIdx.x * 4;
+        const int4 r0 = rec4[0], r1 = rec4[1], r2 = rec4[2], r3 = rec4[3];
+        const int pr[kRegPlaceWords] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y, r3.z, r3.w};
+#pragma unroll
+        for (int k = 0; k < CDEG; k++) pgat[k] = (k < NOWN) ? pr[kRegPlacePostStore + k] : pr[kRegPlacePostGather + k - NOWN];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { mgat[k] = pr[kRegPlaceMsgGather + k]; msto[k] = pr[kRegPlaceMsgStore + k]; }
+    }
+    auto Vof = [&](int k) -> double & { return PLACE ? Lb[pgat[k]] : Vl[coff[k]]; };                   // the posterior of the row's k-th column
+    auto Vmine = [&](int v) -> double & { return PLACE ? Lb[pgat[v]] : Vl[vj[v]]; };                   // the v-th posterior the thread writes
+    auto Rin = [&](int v, int d) -> double & { return PLACE ? Lb[mgat[2 * v + d]] : Rl[voff[v][d]]; }; // the d-th message into it (OWN: d < 2, the other two)
+    double *const rowp = PLACE ? Lb : Rl + roff;                                                     // the row words: rowp[k - NOWN], PLACE: rowp[msto[k - NOWN]]
+    const int *const rowat = PLACE ? msto : nullptr;
+
     // a shot list (the shots the bit-sliced first iteration, mc_first.hip, did not finish) replaces the contiguous range
     const int64_t nshots = (MC && A.shot_list) ? (int64_t)*A.shot_count : A.B;
     for (int64_t base = (int64_t)blockIdx.x * S; base < nshots; base += (int64_t)gridDim.x * S) {
@@ -248,7 +290,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
         for (int k = 0; k < CDEG; k++) { Rprev[k] = 0.0; Qold[k] = 0.0; }
 #pragma unroll
-        for (int v = 0; v < 2; v++) if (ALL || has_var[v]) Vl[vj[v]] = vprior[v];      // Q_{-1} = prior[col] (kernels.py:263-265)
+        for (int v = 0; v < 2; v++) if (ALL || has_var[v]) Vmine(v) = vprior[v];      // Q_{-1} = prior[col] (kernels.py:263-265)
         double Vown[2] = {vprior[0], vprior[1]};                                        // OWN: what this thread last wrote to Vl[vj[v]]; the check phase gathers it from here (re-reading it from LDS measured 9 % slower)
         if (in_team && member == 0) { unsat[0] = 0; unsat[1] = 0; }
         if (threadIdx.x == 0) { const int64_t left = nshots - base; active[0] = (int)(left < S ? left : S); }
@@ -265,7 +307,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 if (CLIPMIN) {                                        // clean inputs: a posterior is never -0.0 (header comment), so x < 0 <=> its sign bit: one XOR per edge
                     unsigned ph = synw;
 #pragma unroll
-                    for (int k = 0; k < CDEG; k++) { x[k] = (OWN && k < NOWN) ? Vown[k] : Vl[coff[k]]; ph ^= (unsigned)__double2hiint(x[k]); }
+                    for (int k = 0; k < CDEG; k++) { x[k] = (OWN && k < NOWN) ? Vown[k] : Vof(k); ph ^= (unsigned)__double2hiint(x[k]); }
                     par = (int)ph < 0;                                                            // kernels.py:349,356
                 } else {
 #pragma unroll
@@ -294,12 +336,12 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     const double mag = Al[0] * fabs(p0);
                     const double msg = sneg ? -mag : mag;
 #pragma unroll
-                    for (int k = 0; k < CDEG; k++) { Rprev[k] = msg; if (k >= NOWN) Rl[roff + k - NOWN] = msg; }
+                    for (int k = 0; k < CDEG; k++) { Rprev[k] = msg; if (k >= NOWN) rowp[PLACE ? msto[k - NOWN] : k - NOWN] = msg; }
                 }
             } else if (in_check && !skip_msg) {
                 if (CLIPMIN && it < max_iter) {
                     // compare-free form (header comment); iteration 0 reads priors: no clip (kernels.py:263-265)
-                    clean_messages<CDEG, NOWN>(x, Rprev, it > 0, Al[it], (it > 0) ? clip : INFINITY, synw, Rl + roff);
+                    clean_messages<CDEG, NOWN>(x, Rprev, it > 0, Al[it], (it > 0) ? clip : INFINITY, synw, rowp, rowat);
                 } else if (it < max_iter) {
                     const double alpha = Al[it];
                     if (it > 0) {
@@ -363,7 +405,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                             unsigned long long lm = 0ull;
 #pragma unroll
                             for (int v = 0; v < 2; v++)
-                                if (has_var[v] && ((Eb[vcol(v)] ^ ((it >= 1 && Vl[vj[v]] < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[vcol(v)];   // V still holds values_{it-1}
+                                if (has_var[v] && ((Eb[vcol(v)] ^ ((it >= 1 && Vmine(v) < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[vcol(v)];   // V still holds values_{it-1}
                             if (lm) atomicXor(lacc, lm);
                         } else if (member == 0) {
                             active[1] = 1;
@@ -373,7 +415,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
                         for (int v = 0; v < 2; v++)
                             if (has_var[v]) {
-                                const double xo = (it >= 1) ? Vl[vj[v]] : 0.0;        // V still holds values_{it-1}
+                                const double xo = (it >= 1) ? Vmine(v) : 0.0;        // V still holds values_{it-1}
                                 A.out_llr[b * n + vcol(v)] = xo;
                                 A.out_err[b * n + vcol(v)] = (xo < 0.0) ? 1 : 0;               // kernels.py:349
                             }
@@ -392,7 +434,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     if (ALL || has_var[v]) {
                         double s = 0.0;                                                        // kernels.py:279
                         if (OWN) {
-                            const double o1 = Rl[voff[v][0]], o2 = Rl[voff[v][1]], own = Rprev[v];
+                            const double o1 = Rin(v, 0), o2 = Rin(v, 1), own = Rprev[v];
                             s = ZEROFREE ? o1 : s + o1;                                        // clean forms start at the first message (header comment, "zero")
                             s += vlast[v] ? o2 : own; s += vlast[v] ? own : o2;                // ascending check order (regular_own.h)
                         } else {
@@ -400,7 +442,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                             for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? Rl[voff[v][0]] : s + Rl[voff[v][d]];   // kernels.py:316, ascending check order
                         }
                         const double xv = s + vprior[v];                                       // kernels.py:320
-                        Vl[vj[v]] = xv;
+                        Vmine(v) = xv;
                         Vown[v] = xv;
                     }
             }
@@ -421,18 +463,18 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 double x[CDEG];
                 unsigned ph = synw;
 #pragma unroll
-                for (int k = 0; k < CDEG; k++) x[k] = (OWN && k < NOWN) ? Vown[k] : Vl[coff[k]];
+                for (int k = 0; k < CDEG; k++) x[k] = (OWN && k < NOWN) ? Vown[k] : Vof(k);
 #pragma unroll
                 for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(x[k]);               // kernels.py:349,356
                 parity |= ph;
-                clean_messages<CDEG, NOWN>(x, Rprev, true, alpha_it, clip, synw, Rl + roff);
+                clean_messages<CDEG, NOWN>(x, Rprev, true, alpha_it, clip, synw, rowp, rowat);
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(1);                                                     // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
                 double r[2][VDEG];
 #pragma unroll
                 for (int v = 0; v < 2; v++)
 #pragma unroll
-                    for (int d = 0; d < VDEG - (OWN ? 1 : 0); d++) r[v][d] = Rl[voff[v][d]];
+                    for (int d = 0; d < VDEG - (OWN ? 1 : 0); d++) r[v][d] = Rin(v, d);
 #pragma unroll
                 for (int v = 0; v < 2; v++) {
                     if (OWN) {                                                                     // r[v] = the three messages in ascending check order (regular_own.h)
@@ -444,7 +486,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
                     for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? r[v][0] : s + r[v][d];   // kernels.py:316, ascending check order; no leading 0.0 + (header comment, "zero")
                     Vown[v] = s + vprior[v];                                                       // kernels.py:320
-                    Vl[vj[v]] = Vown[v];
+                    Vmine(v) = Vown[v];
                 }
                 __builtin_amdgcn_s_setprio(0);
                 // the next pass's alpha, clamped (the table has max_iter entries): a uniform address, and the barrier below waits for LDS anyway
@@ -454,7 +496,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             if (it == max_iter) {                                                                  // the syndrome test of values_{max_iter-1}
                 unsigned ph = synw;
 #pragma unroll
-                for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(Vl[coff[k]]);
+                for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(Vof(k));
                 parity |= ph;
             }
             reinterpret_cast<unsigned *>(Dl + RST + 2)[0] = parity;
@@ -476,7 +518,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
 #pragma unroll
                     for (int v = 0; v < 2; v++)
                         if (has_var[v]) {
-                            const double xo = (max_iter >= 1) ? Vl[vj[v]] : 0.0;
+                            const double xo = (max_iter >= 1) ? Vmine(v) : 0.0;
                             C.f_llr[(int64_t)f * n + vcol(v)] = xo;
                             C.f_hard[(int64_t)f * n + vcol(v)] = (xo < 0.0) ? 1 : 0;
                             C.f_err[(int64_t)f * n + vcol(v)] = (int8_t)Eb[vcol(v)];
@@ -574,7 +616,7 @@ static int launch_reg2(const RegArgs &A, bool damp, bool nanfree, unsigned grid,
         hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, true, false, false, FIXED>), dim3(grid), dim3(block), lds, stream, A);
     } else if (nanfree && A.clip > 0.0) {             // the clean form folds the clip into its two chain seeds: exact for clip > 0 only (inputs_clean() has checked it; kept next to the launch)
         if constexpr (CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg) {
-            if (A.own) {
+            if (A.own && (A.place || !FIXED)) {          // the fixed-work form reads its place table (regular_place_table), the early-exit form has none
                 hipLaunchKernelGGL((minsum_regular_kernel<CDEG, VDEG, false, true, MC, FIXED, true>), dim3(grid), dim3(block), lds, stream, A);
                 QLDPC_HIP_TRY(hipGetLastError());
                 return QLDPC_OK;
@@ -612,6 +654,46 @@ static void fill_common(const qldpc_graph *g, const RegPlan &P, RegArgs &A, int6
     A.offV = P.offV; A.offE = P.offE; A.offL = P.offL; A.offI = P.offI; A.offA = P.offA; A.offT = P.offT; A.offD = P.offD;
 }
 
+static std::atomic<int> g_place{1};       // qldpc_set_option("regular_place"): 1 = the ownership form takes its LDS addresses from the placement of regular_place.h, 0 = today's linear ones
+void regular_set_place(int v) { g_place = v; }
+
+// The place table of the ownership form for this launch's workgroup shape, from the handle's cache (common.h); built and uploaded (a blocking copy) the
+// first time the handle meets the shape.  The placement where the option asks for it and the header has one, else the linear layout as a table: the
+// same kernel either way.
+static int regular_place_table(const qldpc_graph *g, const RegPlan &P, const int32_t **out) {
+    *out = nullptr;
+    if (g->regown.size() != (size_t)g->m * kRegOwnWords) { set_error("regular min-sum: the graph handle has no ownership table"); return QLDPC_ERR_INVALID; }
+    const int rst = regular_row_stride(kRegOwnCdeg);
+    std::lock_guard<std::mutex> lk(g->mu_place);
+    auto find = [&](int placed, int offD) -> const qldpc_graph::PlaceEntry * {
+        for (const auto &e : g->place_cache) if (e.S == P.S && e.block == (int)P.block && e.placed == placed && e.offD == offD) return &e;
+        return nullptr;
+    };
+    auto add = [&](int placed, int offD, const std::vector<int32_t> &rec) -> int {
+        qldpc_graph::PlaceEntry e;
+        e.S = P.S; e.block = (int)P.block; e.placed = placed; e.offD = offD;
+        if (!rec.empty()) { const int rc = upload(e.dev, rec); if (rc != QLDPC_OK) return rc; }
+        g->place_cache.push_back(std::move(e));
+        return QLDPC_OK;
+    };
+    std::vector<int32_t> rec;
+    if (g_place.load()) {
+        if (!find(1, 0)) {
+            regular_place_build(g->m, g->regown.data(), P, rst, rec);          // "none" leaves rec empty: the entry records that, so the build is not repeated
+            const int rc = add(1, 0, rec);
+            if (rc != QLDPC_OK) return rc;
+        }
+        if (const auto *e = find(1, 0); e && e->dev.p) { *out = e->dev.as<int32_t>(); return QLDPC_OK; }
+    }
+    if (!find(0, P.offD)) {
+        regular_place_linear(g->m, g->regown.data(), P, rst, rec);
+        const int rc = add(0, P.offD, rec);
+        if (rc != QLDPC_OK) return rc;
+    }
+    *out = find(0, P.offD)->dev.as<int32_t>();
+    return QLDPC_OK;
+}
+
 static unsigned persistent_grid(int64_t B, int S) {
     const int64_t groups = (B + S - 1) / S;
     const int64_t cap = 256 * 12;
@@ -625,6 +707,7 @@ int minsum_regular_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd,
     if (!plan_regular(g, max_iter, P)) { set_error("graph is not regular (6,3)/(4,2)/(8,4)"); return QLDPC_ERR_UNSUPPORTED; }
     RegArgs A;
     fill_common(g, P, A, B, d_prior, max_iter, d_alpha, damping, clip, flags);
+    if (A.own && A.fixed && damping == 1.0 && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place); if (rc != QLDPC_OK) return rc; }      // the launches that take the ownership form (launch_reg2)
     A.synd = d_synd; A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
     return dispatch_reg<false>(P, A, damping != 1.0, nanfree, persistent_grid(B, P.S), stream);
 }
@@ -638,6 +721,7 @@ int mc_regular_launch(const qldpc_graph *g, int64_t B, const double *d_prior, in
     if (!plan_regular(g, max_iter, P, d_shot_list ? g_list_shots : 0)) { set_error("graph is not regular (6,3)/(4,2)/(8,4)"); return QLDPC_ERR_UNSUPPORTED; }
     RegArgs A;
     fill_common(g, P, A, B, d_prior, max_iter, d_alpha, 1.0, clip, flags);
+    if (A.own && A.fixed && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place); if (rc != QLDPC_OK) return rc; }
     A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.thr = thr; A.use_osd = use_osd; A.shot_begin = shot_begin;
     A.Lmask = d_Lmask; A.cold = reinterpret_cast<const RegCold *>(d_cold);
     A.shot_list = d_shot_list; A.shot_count = d_shot_count;

@@ -286,7 +286,7 @@ def analyse(src, pattern, loop_pick=None):
 # bookkeeping has more instructions and runs a pass or two), "whole" = the whole kernel body (kernels whose time is spread over many loops), the files whose text fixes the instruction stream: the .hip file and every device header it reaches through #include "..." -- csrc/launchers.h,
 # csrc/common.h and include/qldpc_hip.h hold nothing a kernel reads and are in no list.  osd_plan.h is host planning code, listed because the
 # OSD kernels name its block and chunk constants.
-_REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h", "regular_own.h"]      # regular_own.h: host code, listed for the record layout the kernel indexes with
+_REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h", "regular_own.h", "regular_place.h"]      # regular_own.h, regular_place.h: host code, listed for the record layouts the kernel indexes with
 RECORDED = {
     # the seventh argument: OWN, two edges of each check inside its thread (the form bench.py's bb144 graph takes by default)
     "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true, true>", "straight", _REGULAR),
