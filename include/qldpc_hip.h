@@ -47,6 +47,8 @@
  *        additive, same version (the suites pin 101): fixed-weight fault sampling on a circuit plan, qldpc_circuit_plan_use_fixed_weight,
  *        QLDPC_FIXED_WEIGHT_MAX and QLDPC_FIXED_WEIGHT_MAX_LOCS
  *        additive, same version: BP+LSD, qldpc_lsd_batch[_dev], qldpc_circuit_plan_use_lsd and qldpc_circuit_plan_lsd_counts
+ *        additive, same version: min-sum with a per-shot prior and correlated two-sector decoding, qldpc_shotprior_decode_batch[_dev] and
+ *        qldpc_circuit_plan_use_correlated
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -280,6 +282,40 @@ int qldpc_decim_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *synd
 int qldpc_decim_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_prior, double alpha,
                                  double clip_llr, int t_round, int max_rounds, int per_round, double fix_llr, int8_t *d_err, double *d_llr,
                                  uint8_t *d_conv, int32_t *d_iters, int32_t *d_rounds, int32_t *d_fixed, void *stream);
+
+/* Min-sum with a prior that differs per shot, and the reweighting step of correlated two-sector decoding.  New here: the reference has no
+ * counterpart.  Soft measurement information, heralded erasures and any re-weighting scheme enter through `prior`; the link tables let the
+ * correction of ANOTHER decoding problem (src_err: sector 0 of a circuit plan) raise the probability of columns of this one.
+ * Per-shot prior.  For shot b and column j of a graph with n columns:
+ *     P[b][j] = min( prior[b * prior_stride + j],
+ *                    min{ link_llr[l] : link_ptr[j] <= l < link_ptr[j + 1], src_err[b * n_src + link_src[l]] == 1 } )
+ *   prior_stride is 0 (one prior[n] for every shot) or n (prior[B][n]).  src_err is int8[B][n_src]; link_ptr int32[n + 1] with link_ptr[0] = 0,
+ *   monotone; link_src int32[link_ptr[n]], 0 <= link_src < n_src, strictly ascending inside a column's run; link_llr f64[link_ptr[n]].  src_err and
+ *   the three tables are all NULL (then P is the prior as given and n_src is not used) or all given.  Every prior and link_llr value must be
+ *   finite, of any sign: the host-pointer entry checks it, for the _dev entry it is a precondition (as the table rules are).  A minimum of finite
+ *   doubles involves no rounding and no order, so the result does not depend on the order in which a run is walked.
+ * Decode.  Shot b is decoded exactly as one round of qldpc_decim_decode_batch with nothing frozen: V = P[b], then one leg of max_iter iterations
+ *   with bias_j = P[b][j], the constant alpha and the messages clipped to +-clip_llr (steps 1 and 2 there: same operations, same order).  With
+ *   prior_stride = 0 and no tables the outputs equal qldpc_decim_decode_batch(max_rounds = 0, t_round = max_iter) word for word.
+ * Outputs per shot: err int8[n] = V < 0; llr f64[n] = V (may be NULL); conv; iters (the iteration at which V reproduced the syndrome, else
+ *   max_iter); prior_out f64[n] = the P[b] the shot was decoded with (may be NULL).
+ * Arguments: alpha, clip_llr finite and > 0; max_iter >= 1; B = 0 is a no-op.  QLDPC_ERR_INVALID for these, a prior_stride other than 0 or n, a
+ *   value that is not finite or a table that breaks a rule above (the error text names the offending index); nothing is written then.
+ * QLDPC_ERR_UNSUPPORTED, before any launch, for a graph without slot tables (n >= 65535 or a row degree >= 256), with a row degree above 56, or
+ *   whose check state does not fit in 160 KB of LDS: 24 bytes per check and 16 bytes of flags.  On top, with link tables, 8 bytes per column keep V
+ *   in LDS and 8 more keep P there (mode 1); when both do not fit P lives in a per-workgroup slab in global memory (mode 2), and when V alone does
+ *   not fit either, both do (mode 3).  Without tables there is no P to keep: the bias reads the prior where it is.  Results never depend on the mode,
+ *   on batch splits, the grid or the order of the shots. */
+int qldpc_shotprior_decode_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *prior, int64_t prior_stride,
+                                 int32_t n_src, const int8_t *src_err, const int32_t *link_ptr, const int32_t *link_src,
+                                 const double *link_llr, double alpha, double clip_llr, int max_iter, int8_t *err, double *llr,
+                                 uint8_t *conv, int32_t *iters, double *prior_out);
+/* same on device pointers (d_llr / d_prior_out may be NULL); only enqueues on `stream`.  Preconditions: finite d_prior and d_link_llr, tables that
+ * keep the rules above. */
+int qldpc_shotprior_decode_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_prior, int64_t prior_stride,
+                                     int32_t n_src, const int8_t *d_src_err, const int32_t *d_link_ptr, const int32_t *d_link_src,
+                                     const double *d_link_llr, double alpha, double clip_llr, int max_iter, int8_t *d_err, double *d_llr,
+                                     uint8_t *d_conv, int32_t *d_iters, double *d_prior_out, void *stream);
 
 /* a6: GF(2) syndrome SpMV  s = H e (kernels.py:222-231, 352-359; H_csr.dot(e)%2 in alpha.py:128): vectors[B][n] -> out[B][m] */
 int qldpc_gf2_spmv_batch(const qldpc_graph *g, int64_t B, const int8_t *vectors, int8_t *out);
@@ -686,6 +722,19 @@ int qldpc_circuit_plan_use_layered(qldpc_circuit_plan *plan, const int32_t *row_
  * Relay-BP or to windows or whose BP stage runs the layered schedule (and qldpc_circuit_plan_use_relay / _use_window / _use_layered after this
  * call return QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_decim_decode_batch refuses. */
 int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *plan, double alpha, int t_round, int max_rounds, int per_round, double fix_llr);
+/* Switches the BP launch of both sectors to two-pass correlated decoding (qldpc_shotprior_decode_batch's kernel) with the constant `alpha` and the
+ * plan's max_iter and clip_llr (its alpha table is NOT used).  Sector 0 is decoded with its own prior and no tables.  Sector 1 is then decoded with
+ * prior = base_x (f64[n_x]; NULL: the plan's sector-1 prior) at stride 0, src_err = sector 0's correction as its OSD stage left it, and the link
+ * tables given here: link_ptr int32[n_x + 1] (NULL with n_links = 0: no links, the same kernel with nothing to raise), link_src int32[n_links]
+ * naming sector-0 columns, link_llr f64[n_links], under the rules of qldpc_shotprior_decode_batch.  Only the launch inside the BP bracket changes:
+ * sampler, unconverged list, the OSD-0 / OSD-CS / LSD stage, judge and tally slots are untouched (QLDPC_TALLY_LEGS_* stay 0), recorded events
+ * (qldpc_circuit_plan_decode_events) decode the same way, and qldpc_circuit_plan_use_osd_cs / _use_lsd may come before or after.  OSD-CS scores its
+ * candidates with the plan's sector prior, not the per-shot one.  A second call replaces the arguments.  QLDPC_ERR_INVALID for a one-sector plan,
+ * arguments or tables qldpc_shotprior_decode_batch refuses, priors that are not finite, damping != 1, or a plan switched to another path (and every
+ * other path switch after this call returns QLDPC_ERR_INVALID); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_shotprior_decode_batch
+ * refuses. */
+int qldpc_circuit_plan_use_correlated(qldpc_circuit_plan *plan, double alpha, const double *base_x, int64_t n_links, const int32_t *link_ptr,
+                                      const int32_t *link_src, const double *link_llr);
 /* Switches the BP launch of both sectors to the single-precision decoder (one-way): a qldpc_minsum32_decoder per sector with the plan's prior, alpha
  * table, max_iter (>= 1) and clip_llr.  Only the launch inside the BP bracket changes: it writes the plan's hard decisions, posteriors (f64, the f32
  * values widened), converged flags and iteration counts, so sampler, unconverged list, the OSD-0 / OSD-CS stage, judge and tally slots are untouched,

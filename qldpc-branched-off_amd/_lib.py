@@ -585,6 +585,69 @@ def decim_decode_batch(graph, syndromes, prior, **params):
     return err, llr, conv, iters, rounds, fixed
 
 
+def shotprior_params(alpha=1.0, clip_llr=20.0, max_iter=50):
+    """The scalar arguments of qldpc_shotprior_decode_batch, validated: ValueError for a value it rejects -> (alpha, clip_llr, max_iter)."""
+    alpha, clip_llr = float(alpha), float(clip_llr)
+    for name, v in (("alpha", alpha), ("clip_llr", clip_llr)):
+        if not np.isfinite(v) or v <= 0:
+            raise ValueError(f"{name} must be finite and > 0")
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError("max_iter must be an integer >= 1")
+    return alpha, clip_llr, int(max_iter)
+
+
+def link_tables(links, n):
+    """links: None, or an object with ptr / src / llr (simulation.correlated.CorrelationLinks), or a (ptr, src, llr) triple -> contiguous
+    (ptr int32[n + 1], src int32[>= 1], llr f64[>= 1], number of links); None gives empty runs.  The rules themselves are checked by the library."""
+    if links is None:
+        return np.zeros(n + 1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.float64), 0
+    lp, ls, ll = (links.ptr, links.src, links.llr) if hasattr(links, "ptr") else links
+    lp, ls, ll = i32(lp).ravel(), i32(ls).ravel(), f64(ll).ravel()
+    if lp.size != n + 1:
+        raise ValueError(f"link ptr has {lp.size} entries, the graph has {n} columns (n + 1 expected)")
+    if ls.size != ll.size:
+        raise ValueError(f"link src has {ls.size} entries, link llr {ll.size}")
+    if ls.size < int(lp[-1]) or int(lp[-1]) < 0:
+        raise ValueError(f"link ptr ends at {int(lp[-1])}, the tables hold {ls.size} links")
+    nl = int(lp[-1])
+    if ls.size == 0:
+        ls, ll = np.zeros(1, np.int32), np.zeros(1, np.float64)
+    return lp, ls, ll, nl
+
+
+def shotprior_decode_batch(graph, syndromes, priors, alpha=1.0, clip_llr=20.0, max_iter=50, links=None, src_err=None, want_prior=False):
+    """qldpc_shotprior_decode_batch on host arrays: min-sum with the prior priors[n] (every shot) or priors[B, n] (per shot), lowered per shot by the
+    `links` (link_tables) whose source fired in src_err int8[B, n_src] -> (err int8[B, n], llr f64[B, n], conv uint8[B], iters int32[B]) and, with
+    want_prior, the per-shot prior f64[B, n] the shots were decoded with as a fifth entry."""
+    alpha, clip_llr, max_iter = shotprior_params(alpha, clip_llr, max_iter)
+    syndromes = i8(syndromes).reshape(-1, graph.m)
+    B, n = syndromes.shape[0], graph.n
+    priors = f64(priors)
+    if priors.shape not in ((n,), (B, n)):
+        raise ValueError(f"priors must have shape ({n},) or ({B}, {n}), got {priors.shape}")
+    stride = n if priors.ndim == 2 else 0
+    if (links is None) != (src_err is None):
+        raise ValueError("links and src_err go together")
+    if links is not None:
+        src_err = i8(src_err)
+        if src_err.ndim != 2 or src_err.shape[0] != B:
+            raise ValueError(f"src_err must be int8[{B}, n_src], got shape {src_err.shape}")
+        n_src = src_err.shape[1]
+        lp, ls, ll, _ = link_tables(links, n)
+        if src_err.size == 0:
+            src_err = np.zeros(1, np.int8)
+        tabs = (C.c_int32(n_src), ptr(src_err, C.c_int8), ptr(lp, C.c_int32), ptr(ls, C.c_int32), ptr(ll, C.c_double))
+    else:
+        tabs = (C.c_int32(0), None, None, None, None)
+    err, llr = np.zeros((B, n), np.int8), np.zeros((B, n), np.float64)
+    conv, iters = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+    pout = np.zeros((B, n), np.float64) if want_prior else None
+    check(lib().qldpc_shotprior_decode_batch(graph.handle, C.c_int64(B), ptr(syndromes, C.c_int8), ptr(priors, C.c_double), C.c_int64(stride), *tabs,
+                                             alpha, clip_llr, max_iter, ptr(err, C.c_int8), ptr(llr, C.c_double), ptr(conv, C.c_uint8),
+                                             ptr(iters, C.c_int32), ptr(pout, C.c_double) if want_prior else None))
+    return (err, llr, conv, iters, pout) if want_prior else (err, llr, conv, iters)
+
+
 def check_window_args(layer_rows, window, commit, m=None):
     """ValueError unless window >= 1, 1 <= commit <= window and layer_rows >= 1 (dividing m when m is given) -> the three as ints."""
     for name, v in (("layer_rows", layer_rows), ("window", window), ("commit", commit)):
@@ -1043,6 +1106,23 @@ class CircuitPlan(Owner):
         p = decim_params(params, with_clip=False)
         check(lib().qldpc_circuit_plan_use_decimation(self._h, p["alpha"], p["t_round"], p["max_rounds"], p["per_round"], p["fix_llr"]))
         self.decimation = p
+
+    def use_correlated(self, alpha=1.0, links=None, base=None):
+        """Decode the two sectors in two passes from now on (qldpc_circuit_plan_use_correlated): sector 0 as constant-alpha min-sum with its own
+        prior, then sector 1 with a per-shot prior -- `base` (f64[n_x]; None: the plan's sector-1 prior) lowered to a link's llr wherever the link's
+        sector-0 column is in sector 0's correction.  links: a simulation.correlated.CorrelationLinks or (ptr, src, llr); None = no links (the same
+        kernel with nothing to raise).  The plan's max_iter and clip_llr apply, its alpha table does not.  Goes with OSD-0, OSD-CS and LSD; with no
+        other path; needs two sectors.  Again with new arguments is allowed."""
+        alpha = shotprior_params(alpha)[0]
+        n_x = self.graph_x.n if self.graph_x is not None else 0                  # (a one-sector DemPlan: the library refuses it)
+        lp, ls, ll, nl = link_tables(links, n_x)
+        if base is not None:
+            base = f64(base).ravel()
+            if base.size != n_x:
+                raise ValueError(f"base has {base.size} entries, sector 1 has {n_x} columns")
+        check(lib().qldpc_circuit_plan_use_correlated(self._h, alpha, ptr(base, C.c_double) if base is not None else None, C.c_int64(nl),
+                                                      ptr(lp, C.c_int32), ptr(ls, C.c_int32), ptr(ll, C.c_double)))
+        self.correlated = {"alpha": alpha, "links": nl, "base": base is not None}
 
     def use_fixed_weight(self, weight):
         """Draw exactly `weight` faulty locations (mechanisms of a DemPlan) per trial from now on, uniformly among the subsets of that size

@@ -142,7 +142,7 @@ __global__ void collect_failed2_kernel(int64_t B, const uint8_t *__restrict__ co
 using namespace qldpc;
 
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
-enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW };      // who fills the BP bracket and its follow-up
+enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED };      // who fills the BP bracket and its follow-up
 enum class Osd { OSD0, CS, LSD };                                     // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
 
 struct qldpc_circuit_plan {
@@ -188,6 +188,10 @@ struct qldpc_circuit_plan {
     Osd osd = Osd::OSD0;
     RelayParams rp{};                              // Path::RELAY (relay_bp.hip)
     DecimParams dp{};                              // Path::DECIM (decimation.hip)
+    // Path::CORRELATED (shot_prior.hip): constant alpha; the links sector-0 column -> sector-1 column; base_x in place of sector 1's prior (corr_base)
+    double corr_alpha = 1.0;
+    bool corr_base = false;
+    DevBuf d_cl_ptr, d_cl_src, d_cl_llr, d_cl_base;
     int cs_order = 0;                              // Osd::CS (osd_cs.hip)
     int lsd_bits = 0, lsd_rows = 0;                // Osd::LSD (lsd.hip)
     DevBuf d_lsd_counts;                           // ... uint64[2][3]: shots per sector that ended with flag 0 / 1 / 2 (the kernel accumulates)
@@ -538,6 +542,16 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
                                  S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), S.d_legs.as<int32_t>(), nullptr, s);
         break;
     }
+    case Path::CORRELATED: {   // the per-shot-prior kernel: sector 0 as it is; sector 1 with the links, read against sector 0's correction as its OSD stage left it
+        const Sector &Z = P->sec[0];
+        const ShotLinks none{0, nullptr, nullptr, nullptr, nullptr};
+        const ShotLinks links{Z.g->n, Z.d_det.as<int8_t>(), P->d_cl_ptr.as<int32_t>(), P->d_cl_src.as<int32_t>(), P->d_cl_llr.as<double>()};
+        const double *prior = sector == 1 && P->corr_base ? P->d_cl_base.as<double>() : S.d_prior.as<double>();
+        std::lock_guard<std::mutex> lk(g->mu);
+        rc = shotprior_decode_launch(g, B, S.d_syn.as<int8_t>(), prior, 0, sector == 1 ? links : none, P->corr_alpha, P->clip, P->max_iter, -1,
+                                     S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), nullptr, s);
+        break;
+    }
     case Path::FLOOD: {
         std::lock_guard<std::mutex> lk(g->mu);
         g->clk_probe = (clk && sector == 0) ? clk : nullptr;                  // sector Z carries the probe (one writer per buffer)
@@ -690,17 +704,19 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 
 // The switch rules, once.  A plan decodes on two axes, and qldpc_circuit_plan_use_* moves it along one of them:
 //   Path: who fills the BP bracket and its follow-up -- flooding min-sum (as created), the layered schedule, guided decimation, single precision (f32),
-//     Relay-BP or sliding windows.  A plan leaves flooding at most once.  Asking again for the path it is on brings new arguments (Relay-BP, layered,
-//     decimation), changes nothing (f32) or is refused (windows).
-//   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation and f32
-//     whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
+//     Relay-BP, sliding windows or correlated two-sector decoding.  A plan leaves flooding at most once.  Asking again for the path it is on brings
+//     new arguments (Relay-BP, layered, decimation, correlated), changes nothing (f32) or is refused (windows).
+//   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation, f32 and
+//     correlated whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
 //     refuse each other in either order.
-//   Windows need use_osd as well; Relay-BP, layered, decimation and f32 do not.  Windows, layered, decimation and f32 need damping = 1.
-// Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation: finite priors and a supported graph).
+//   Windows need use_osd as well; Relay-BP, layered, decimation, f32 and correlated do not.  Windows, layered, decimation, f32 and correlated need
+//   damping = 1.
+// Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation, correlated: finite priors and a supported graph;
+// correlated: two sectors).
 // `to`: the path asked for; Path::FLOOD stands for a request on the other axis, for the OSD stage `stage` (no call asks for flooding).
 // QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
 static int switch_allowed(const qldpc_circuit_plan *P, Path to, Osd stage = Osd::CS) {
-    static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding"};
+    static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding", "correlated decoding"};
     static const char *const osd_name[] = {"BP + OSD-0", "BP + OSD-CS", "BP + LSD"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     const bool cs = to == Path::FLOOD;                                   // a request on the OSD axis: `stage` says for which of the two
@@ -834,6 +850,35 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_decimation(qldpc_circuit_plan *P, double
         return rc;
     P->dp = dp;
     P->path = Path::DECIM;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_correlated(qldpc_circuit_plan *P, double alpha, const double *base_x, int64_t n_links, const int32_t *link_ptr,
+                                                   const int32_t *link_src, const double *link_llr) {
+    int rc = switch_allowed(P, Path::CORRELATED);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(P->nsec == 2, "correlated decoding needs a plan with two sectors (this detector error model has one)");
+    const int n0 = P->sec[0].g->n, n1 = P->sec[1].g->n;
+    QLDPC_REQUIRE(n_links >= 0, "n_links = %lld is negative", (long long)n_links);
+    QLDPC_REQUIRE(link_ptr != nullptr || n_links == 0, "link_ptr is NULL but n_links = %lld", (long long)n_links);
+    std::vector<int32_t> ptr((size_t)n1 + 1, 0);                          // no tables: every run is empty
+    if (link_ptr) ptr.assign(link_ptr, link_ptr + n1 + 1);
+    QLDPC_REQUIRE(ptr[n1] == n_links, "link_ptr[%d] = %d, not n_links = %lld", n1, ptr[n1], (long long)n_links);
+    if ((rc = shotprior_check_links(n1, n0, ptr.data(), link_src, link_llr)) != QLDPC_OK) return rc;
+    for (int j = 0; base_x && j < n1; j++) QLDPC_REQUIRE(std::isfinite(base_x[j]), "base_x[%d] is not finite", j);
+    if ((rc = inputs_supported(P, shotprior_check_params(alpha, P->clip, P->max_iter),
+                               [](const qldpc_graph *g) { return shotprior_mode(g) ? QLDPC_OK : shotprior_unsupported(g); })) != QLDPC_OK)
+        return rc;
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a decode that is still enqueued reads the tables replaced here
+    const std::vector<int32_t> src(link_src, link_src + n_links);
+    const std::vector<double> llr(link_llr, link_llr + n_links), base(base_x, base_x + (base_x ? n1 : 0));
+    DevBuf d_ptr, d_src, d_llr, d_base;                                  // all four or none: a failed upload leaves the plan's tables as they were
+    if ((rc = upload(d_ptr, ptr)) || (rc = upload(d_src, src)) || (rc = upload(d_llr, llr)) || (rc = upload(d_base, base))) return rc;
+    P->d_cl_ptr = std::move(d_ptr); P->d_cl_src = std::move(d_src); P->d_cl_llr = std::move(d_llr); P->d_cl_base = std::move(d_base);
+    P->corr_alpha = alpha;
+    P->corr_base = base_x != nullptr;
+    P->path = Path::CORRELATED;
     return QLDPC_OK;
 }
 

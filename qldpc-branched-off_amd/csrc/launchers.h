@@ -120,6 +120,18 @@ int decim_unsupported(const qldpc_graph *g);     // sets the error text, returns
 // callers hold g->mu.  iter_bias is added to every iteration count written to d_iters; d_llr / d_rounds / d_fixed may be NULL
 int decim_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, const DecimParams &P, int iter_bias, int8_t *d_err,
                         double *d_llr, uint8_t *d_conv, int32_t *d_iters, int32_t *d_rounds, int32_t *d_fixed, hipStream_t stream);
+// Min-sum with a per-shot prior (shot_prior.hip): P[b][j] = min(prior[b * stride + j], the link_llr of column j's links whose source fired in src_err[b]),
+// then one leg of constant-alpha min-sum with that prior.  ShotLinks: device pointers, ptr == NULL means no tables (the other three are then NULL as well).
+struct ShotLinks { int n_src; const int8_t *src_err; const int32_t *ptr, *src; const double *llr; };
+int shotprior_check_params(double alpha, double clip_llr, int max_iter);
+// host tables of n columns: ptr[0] = 0 and monotone, 0 <= src < n_src strictly ascending inside a column's run, every llr finite (the text names the index)
+int shotprior_check_links(int n, int n_src, const int32_t *link_ptr, const int32_t *link_src, const double *link_llr);
+int shotprior_mode(const qldpc_graph *g);        // 0: not supported; where V / P live with link tables: 1 LDS / LDS, 2 LDS / global, 3 global / global
+int shotprior_unsupported(const qldpc_graph *g); // sets the error text, returns QLDPC_ERR_UNSUPPORTED
+// callers hold g->mu.  stride: 0 or n.  iter_bias is added to every iteration count written to d_iters; d_llr / d_prior_out may be NULL
+int shotprior_decode_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int64_t stride, const ShotLinks &K, double alpha,
+                            double clip, int max_iter, int iter_bias, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iters, double *d_prior_out,
+                            hipStream_t stream);
 // h_prior: the same prior on the host when the caller has it (a circuit plan, the host-pointer entry point), else NULL
 int minsum_decode_dispatch(const qldpc_graph *g, int64_t B, const int8_t *d_synd, const double *d_prior, int max_iter,
                            const double *d_alpha, double damping, double clip, int flags, bool nanfree, int8_t *d_err, double *d_llr,

@@ -278,13 +278,18 @@ class DetectorErrorModel:
                             alphas=alphas, alpha_mode=alpha_mode, batch=batch, flags=flags, use_osd=use_osd, **kw)
 
 
-def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers, decimation, precision, num_workers=None, lsd=None):
+def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers, decimation, precision, num_workers=None, lsd=None, correlated=None):
     """The argument rules run_dem_simulation and DemDecoder share, raised as ValueError before any device call -> (rules of engine._extension_rules,
     alpha_mode, (alpha of sector 0, alpha of sector 1))."""
     if not isinstance(dem, DetectorErrorModel):
         raise ValueError("dem must be a DetectorErrorModel (from_decoding_matrices, from_text, from_columns)")
     rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, True, False,
-                                    maxIter, num_workers, lsd=lsd)
+                                    maxIter, num_workers, lsd=lsd, correlated=correlated)
+    if rules.path == "correlated":
+        if dem.n_sectors != 2:
+            raise ValueError(f"{who}: correlated=... needs a detector error model with two sectors (this one has {dem.n_sectors})")
+        from .correlated import links_from_dem
+        rules.links = links_from_dem(dem, rules.correlated["mode"], rules.correlated["floor"])
     if decoder == "bp_osd" and osd_order > 0:
         raise ValueError(f"{who}: osd_order={osd_order} with decoder='bp_osd' asks for the OSD-w pass, which is not available on detector error "
                          "models; use decoder='bp_osd_cs' (osd_order is then the combination-sweep order)")
@@ -315,16 +320,17 @@ def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder
 
 def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode=None, alvarado_alpha=None, base_seed=None, target_logical_errors=None,
                        max_trials=None, batch=16384, device=None, devices=None, num_workers=None, flags=0, decoder="bp_osd", relay_params=None, window=None,
-                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None):
+                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None, correlated=None):
     """``run_simulation`` for a DetectorErrorModel: the same result keys, in-order early stop (``target_logical_errors``), ``num_workers`` / ``devices`` and
-    extensions (``decoder`` with ``lsd`` for ``"bp_lsd"``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``) under the same argument rules; sector 0 fills the ``z``
+    extensions (``decoder`` with ``lsd`` for ``"bp_lsd"``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``, ``correlated`` with the links of
+    ``correlated.links_from_dem``) under the same argument rules; sector 0 fills the ``z``
     keys, sector 1 the ``x`` keys (0 for a one-sector model).  ``window=(W, C)`` needs the model's ``layer_rows``.
 
     Out of scope (ValueError before any device call): the alpha / SCOPT estimators, which draw errors at one error rate -- use ``alpha_mode="dynamical"``
     (the default) or ``"alvarado"`` with an explicit ``alvarado_alpha`` (a number or a pair) -- and ``osd_order > 0`` with ``decoder="bp_osd"`` (the
     reference's OSD-w pass; ``decoder="bp_osd_cs"`` is the higher-order OSD of the fused pipeline)."""
     rules, alpha_mode, alphas = _dem_rules("run_dem_simulation", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers,
-                                           decimation, precision, num_workers, lsd=lsd)
+                                           decimation, precision, num_workers, lsd=lsd, correlated=correlated)
     rank, world, devices = engine._worker_devices(num_workers, devices, device)
     if base_seed is None:
         base_seed = int(np.random.randint(0, 2 ** 31))
@@ -385,9 +391,9 @@ class DemDecoder:
     (record, seed, shot index) and depends neither on ``batch`` nor on how the shots are split over calls."""
 
     def __init__(self, dem, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding", layers=None, decimation=None, precision="f64",
-                 relay_params=None, alpha_mode=None, alvarado_alpha=None, batch=16384, device=None, seed=0, flags=0, lsd=None):
+                 relay_params=None, alpha_mode=None, alvarado_alpha=None, batch=16384, device=None, seed=0, flags=0, lsd=None, correlated=None):
         self._rules, self._alpha_mode, self._alphas = _dem_rules("DemDecoder", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window,
-                                                                 schedule, layers, decimation, precision, lsd=lsd)
+                                                                 schedule, layers, decimation, precision, lsd=lsd, correlated=correlated)
         if int(batch) < 1:
             raise ValueError("batch must be >= 1")
         self.dem, self.seed, self.batch, self.device = dem, int(seed), int(batch), device

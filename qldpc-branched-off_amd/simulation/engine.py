@@ -23,7 +23,7 @@ Differences that are deliberate and documented:
   * ``target_logical_errors`` stops at the exact trial the reference would (in-order prefix cut over per-trial verdicts).
 
 The extensions below choose what a worker's plan decodes with, on the plan's two axes.  The path: at most one of
-``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...`` and ``precision="f32"`` leaves flooding min-sum, and none of them
+``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...``, ``precision="f32"`` and ``correlated=...`` leaves flooding min-sum, and none of them
 goes with the reference's OSD-w pass (``osd_order > 0`` with ``decoder="bp_osd"``).  The OSD stage: ``decoder="bp_osd_cs"`` puts OSD-CS in the place
 of OSD-0 and ``decoder="bp_lsd"`` puts BP+LSD there; each goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
 
@@ -66,6 +66,13 @@ changes; OSD-0 (``decoder="bp_osd"``, ``osd_order=0``) or OSD-CS (``decoder="bp_
 f64: the alpha they return is rounded to f32 like any other.  Results differ from ``"f64"`` in some trials (rounding, amplified by the iteration);
 compare logical error rates, not trials.  The result holds ``precision``.
 
+``correlated={"alpha": 1.0, "mode": "raise"}`` (an extension; None is today's behaviour; either key, and ``floor``, may be left out) decodes the two
+sectors in two passes (``simulation/correlated.py``): sector Z as constant-alpha min-sum, then sector X with a per-shot prior in which every column that
+shares a fault with a column of sector Z's correction is raised to its conditional probability.  The links come from ``links_from_circuit`` at
+``error_rate``.  OSD-0, OSD-CS (which still scores with the shared prior) or LSD follows on the unconverged trials as before.  Its alpha is the constant of
+the dict, so every argument that selects or estimates another alpha raises ValueError, as for ``decimation``.  The result also holds ``correlated`` and
+``correlated_links``.
+
 ``simulation/dem.py`` (``run_dem_simulation``: the same pipeline fed by a detector error model instead of a bivariate-bicycle circuit) shares the
 argument rules of the extensions (``_extension_rules``), the choice of devices (``_worker_devices``) and the Worker, round loop, early stop,
 all-reduce and result assembly (``_run_trials``) with ``run_simulation``; the two differ in how a worker's plan is created.
@@ -98,12 +105,12 @@ def _estimation_trials(requested, n_cols, error_rate):
 
 
 def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
-                     maxIter, num_workers, lsd=None):
-    """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision), shared by run_simulation and run_dem_simulation:
-    raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered", "decimation", "f32", "relay" or
-    "window": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
-    parameters, else None) -- with the normalised parameters of that path (``layers``, ``decimation``, ``relay_params``, ``window``; None where the path
-    is another)."""
+                     maxIter, num_workers, lsd=None, correlated=None):
+    """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision, correlated), shared by run_simulation and
+    run_dem_simulation: raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered",
+    "decimation", "f32", "relay", "window" or "correlated": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
+    parameters, else None) -- with the normalised parameters of that path (``layers``, ``decimation``, ``relay_params``, ``window``, ``correlated``; None
+    where the path is another)."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
@@ -124,12 +131,13 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
     # the path: at most one argument leaves flooding min-sum (the plan's own rule, qldpc_circuit_plan_use_*) ...
     asked = [(path, text) for path, text, given in (("f32", "precision='f32'", precision == "f32"), ("decimation", "decimation=...", decimation is not None),
                                                      ("layered", "schedule='layered'", schedule == "layered"),
-                                                     ("window", f"window={window!r}", window is not None), ("relay", "decoder='relay_bp'", decoder == "relay_bp"))
+                                                     ("window", f"window={window!r}", window is not None), ("relay", "decoder='relay_bp'", decoder == "relay_bp"),
+                                                     ("correlated", "correlated=...", correlated is not None))
              if given]
     if len(asked) > 1:
         (_, one), (_, other) = asked[:2]
         raise ValueError(f"{one} does not go with {other}: {one} goes with none of the others of decoder='relay_bp', window=(W, C), schedule='layered', "
-                         "decimation=... and precision='f32' (each decodes the BP stage its own way)")
+                         "decimation=..., precision='f32' and correlated=... (each decodes the BP stage its own way)")
     path, text = asked[0] if asked else ("flooding", None)
     # ... and none of them goes with the OSD-w pass, which decodes again with flooding min-sum in f64
     if path != "flooding" and decoder == "bp_osd" and osd_order > 0:
@@ -154,6 +162,20 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         if "clip_llr" in decimation:
             raise ValueError("decimation: the circuit plan's clip_llr is fixed (20)")
         decimation = _lib.decim_params(decimation, with_clip=False)
+    elif path == "correlated":
+        if not isinstance(correlated, dict):
+            raise ValueError("correlated must be a dict with alpha, mode and / or floor (or None)")
+        bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None),
+                                        ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
+        if bad:
+            raise ValueError(f"correlated=... does not use {', '.join(bad)}: its alpha is the constant correlated['alpha']")
+        unknown = set(correlated) - {"alpha", "mode", "floor"}
+        if unknown:
+            raise ValueError(f"unknown correlated parameter(s): {sorted(unknown)}")
+        from .correlated import check_mode
+        correlated = {"alpha": _lib.shotprior_params(correlated.get("alpha", 1.0), 20.0, maxIter)[0], "mode": correlated.get("mode", "raise"),
+                      "floor": correlated.get("floor")}
+        check_mode(correlated["mode"], correlated["floor"])
     elif path == "layered":
         mode = alpha_mode if alpha_mode is not None else ("dynamical" if use_dynamic_alpha else "alvarado")
         if mode == "alvarado-autoregressive" or (mode == "alvarado" and alvarado_alpha is None):
@@ -182,7 +204,8 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         relay_params = _lib.relay_params(relay_params, with_clip=False)
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
-    return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window)
+    return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window, correlated=correlated,
+                           links=None)
 
 
 def _worker_devices(num_workers, devices, device):
@@ -214,13 +237,14 @@ def _worker_devices(num_workers, devices, device):
 def _plan_switch(rules, csr, osd_order):
     """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
     dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` or LSD in the OSD stage when the rules ask for it, then moves the BP stage to
-    rules.path.  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
+    rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
     layers = None
     if rules.path == "layered":
         layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
     to_path = {"flooding": lambda plan: None, "relay": lambda plan: plan.use_relay(**rules.relay_params), "window": lambda plan: plan.use_window(*rules.window),
                "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
-               "f32": lambda plan: plan.use_f32()}[rules.path]
+               "f32": lambda plan: plan.use_f32(),
+               "correlated": lambda plan: plan.use_correlated(rules.correlated["alpha"], rules.links, None if rules.links is None else rules.links.base)}[rules.path]
 
     def switch(plan):
         if rules.osd_cs:
@@ -398,6 +422,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         result.update(schedule=schedule, layers_z=layer_count(csr[0], layers[0]), layers_x=layer_count(csr[1], layers[1]) if len(csr) > 1 else 0)
     elif rules.path == "decimation":
         result.update(decimation=dict(rules.decimation), mean_rounds_z=per_trial[0], mean_rounds_x=per_trial[1])
+    elif rules.path == "correlated":
+        result.update(correlated=dict(rules.correlated), correlated_links=0 if rules.links is None else rules.links.n_links)
     result["precision"] = precision
     result["tally"] = total
     return result
@@ -428,16 +454,16 @@ def _circuit_problem(Hx, Hz, Lx, Lz, error_rate, num_cycles, precomputed_matrice
         return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
                                 alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
 
-    return SimpleNamespace(compiled=compiled, graphs=graphs, llrs=(llrs_z, llrs_x), masks=masks, k=k, make_plan=make_plan)
+    return SimpleNamespace(compiled=compiled, matrices=m, graphs=graphs, llrs=(llrs_z, llrs_x), masks=masks, k=k, make_plan=make_plan)
 
 
 def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, maxIter=50, osd_order=0, use_dynamic_alpha=True,
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", lsd=None, **bb_params):
+                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, **bb_params):
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
-                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd)
+                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated)
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:
@@ -453,6 +479,9 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
 
     prob = _circuit_problem(Hx, Hz, Lx, Lz, error_rate, num_cycles, precomputed_matrices, device, bb_params)
     graphs, masks, k, (llrs_z, llrs_x) = prob.graphs, prob.masks, prob.k, prob.llrs
+    if rules.path == "correlated":
+        from .correlated import links_from_circuit
+        rules.links = links_from_circuit(prob.compiled, Lx, Lz, prob.matrices, error_rate, rules.correlated["mode"], rules.correlated["floor"])
 
     # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
     # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
