@@ -49,6 +49,8 @@
  *        additive, same version: BP+LSD, qldpc_lsd_batch[_dev], qldpc_circuit_plan_use_lsd and qldpc_circuit_plan_lsd_counts
  *        additive, same version: min-sum with a per-shot prior and correlated two-sector decoding, qldpc_shotprior_decode_batch[_dev] and
  *        qldpc_circuit_plan_use_correlated
+ *        additive, same version: heralded-erasure noise and erasure-aware decoding on a circuit plan, qldpc_erasure_priors[_dev],
+ *        qldpc_circuit_plan_use_erasure_noise, _use_erasure_aware and _sample_erasures, QLDPC_ERASURE_H_INF
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -809,6 +811,71 @@ int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *dem, const qldpc_graph *
 #define QLDPC_FIXED_WEIGHT_MAX 4096
 #define QLDPC_FIXED_WEIGHT_MAX_LOCS 524288
 int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *plan, int weight);
+
+/* ---- heralded-erasure noise and erasure-aware decoding.  New here: the reference has no counterpart.  Circuit plans only. -------------------------
+ * A second noise process beside the plan's Pauli faults: a location is ERASED with the rate of its class, the hardware reports which ones were (the
+ * herald record), and an erased location is fully depolarised.  A decoder that reads the heralds treats such a location as a coin flip.
+ *
+ * Erasure draws, a pure function of (seed, global trial index g = trial_begin + t): rate[ty] in [0, 1) per location class, ty one of the six op
+ * codes 1..6 of a base circuit (CNOT, PrepX, PrepZ, MeasX, MeasZ, IDLE; rate[0] is not read); ethr[ty] = floor(rate[ty] * 2^32) (uint32; a rate of
+ * 0 never fires).  Location l is erased iff word (l & 3) of Philox4x32-10(counter = (lo32(g), hi32(g), l >> 2, 5), key = (lo32(seed), hi32(seed))) is
+ * below ethr[type(l)].  Counter word 3 is the domain: 5 and 6 are new (0 = the code-capacity samplers, 1 and 2 = the circuit sampler, 3 = the DEM
+ * sampler, 4 = the fixed-weight sampler, 0x52...... = Relay-BP).
+ * Pauli of an erased location: r = word 0 of Philox4x32-10(counter = (lo32(g), hi32(g), l, 6), same key).  Its component mask (bit 0 = X on slot 0,
+ * bit 1 = X on slot 1, bit 2 = Z on slot 0, bit 3 = Z on slot 1; slot 0 = the gate's first qubit, slot 1 = a CNOT's target) is
+ *     CNOT            r & 15                    the sixteen two-qubit Paulis, identity included
+ *     IDLE            {0, 1, 5, 4}[r & 3]       I, X, Y, Z
+ *     MeasX / PrepX   (r & 1) ? 4 : 0
+ *     MeasZ / PrepZ   (r & 1) ? 1 : 0
+ * and the fault signatures of its components are XORed into the sectors' syndromes and true logical flips exactly as an ordinary fault's are.  All
+ * moduli are powers of two: no bias.  The ordinary faults (domains 1 and 2) are drawn as without erasures, in addition: a uniform Pauli composed
+ * with anything is uniform, so this is the same physical channel, and with every rate 0 the syndromes and truths are the plain sampler's bit for bit.
+ * Herald record: uint32[B][ceil(n_locs / 32)], bit (l & 31) of word (l >> 5) set iff location l is erased.
+ *
+ * Decoder tables, per sector (simulation/erasure.py builds them on the host), for a sector with n columns:
+ *   loc_ptr int32[n_locs + 1], loc_col int32[loc_ptr[n_locs]] (columns, strictly ascending inside a location's run), loc_h uint8[loc_ptr[n_locs]]:
+ *     what an erasure of location l does to the columns -- h = QLDPC_ERASURE_H_INF: the column flips with probability 1/2 given the herald;
+ *     h = 1: with probability 1/4 (1 - 2q = 2^-1; one of the three projections of an erased CNOT).
+ *   lut_ptr int32[n + 1], lut f64[lut_ptr[n]]: column j has c_j + 1 entries, c_j = the number of its h = 1 contributions (at most 65535);
+ *     lut[lut_ptr[j]] is the column's prior without heralds, entry H >= 1 the prior LLR of (1 - (1 - 2 p_j) 2^-H) / 2.  Every entry is finite.
+ * Per-shot prior: H = the sum of h over column j's contributions whose location is erased in shot b;
+ *     prior[b][j] = 0.0 if one of them is QLDPC_ERASURE_H_INF, else lut[lut_ptr[j] + H].
+ *   H is an integer sum: the value does not depend on the order in which the locations are met, and the device takes no logarithm.  A shot without
+ *   heralds gets lut[lut_ptr[j]] bit for bit. */
+#define QLDPC_ERASURE_H_INF 255
+/* The prior kernel alone: heralds erased uint32[B][ceil(n_locs / 32)] (bits at or above n_locs are ignored) and one sector's tables -> prior f64[B][n].
+ * Host pointers, staged on the calling thread's current device.  QLDPC_ERR_INVALID for a table that breaks a rule above (the error text names the
+ * offending index); QLDPC_ERR_UNSUPPORTED when a 16-bit counter and a bit per column do not fit in 160 KB of LDS (n above about 77 000). */
+int qldpc_erasure_priors(int64_t B, int32_t n_locs, const uint32_t *erased, const int32_t *loc_ptr, const int32_t *loc_col, const uint8_t *loc_h,
+                         int32_t n, const int32_t *lut_ptr, const double *lut, double *prior);
+/* same on device pointers of the current device; only enqueues on `stream`.  Precondition: tables that keep the rules above (a column outside
+ * 0 .. n - 1 is skipped and H is held inside the column's run, so nothing outside the arrays is addressed either way). */
+int qldpc_erasure_priors_dev(int64_t B, int32_t n_locs, const uint32_t *d_erased, const int32_t *d_loc_ptr, const int32_t *d_loc_col,
+                             const uint8_t *d_loc_h, int32_t n, const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, void *stream);
+/* The sampler axis of a plan (beside qldpc_circuit_plan_use_fixed_weight): from now on the plan's sampler draws the erasures above at rate[op code]
+ * on top of its ordinary faults; rate == NULL switches them off again.  Two-way, any number of times; not a decode switch, so it goes with every
+ * path and OSD stage in either call order.  _run, _run_outcomes, _sample and _sample_erasures honour it; a plan that is not on the erasure-aware
+ * path decodes the syndromes as it always does (it does not read the heralds).  QLDPC_ERR_INVALID: a rate outside [0, 1) or NaN (the text names the
+ * class), a plan created from a detector error model, or a plan with a fixed weight in force -- and qldpc_circuit_plan_use_fixed_weight(w >= 0)
+ * returns QLDPC_ERR_INVALID while erasure noise is on.  QLDPC_ERR_UNSUPPORTED: one bit per location does not fit in LDS.  A refused call leaves the
+ * plan as it was. */
+int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *plan, const double rate[7]);
+/* A decode path, "erasure-aware decoding": the BP launch of both sectors becomes qldpc_shotprior_decode_batch's kernel with the constant `alpha`, the
+ * plan's max_iter and clip_llr, no link tables, and prior[batch][n] (stride n) computed per batch from the sampler's herald record and the sector's
+ * tables given here (host pointers, copied; the rules above, and lut[lut_ptr[j]] must equal the plan's prior of column j bit for bit).  While erasure
+ * noise is off -- and for recorded events, which carry no heralds -- every herald is zero and the path decodes with the plan's prior (stride 0): the
+ * same answers as qldpc_circuit_plan_use_correlated with no links.  The rules of that path apply: damping = 1, OSD-0, OSD-CS or LSD may follow in
+ * either call order, no other path, a second call replaces the arguments; OSD-CS scores its candidates with the plan's sector prior, not the
+ * per-shot one.  QLDPC_ERR_INVALID for these, for a plan created from a detector error model, for arguments qldpc_shotprior_decode_batch refuses and
+ * for tables that break a rule (the text names the sector and the index); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one
+ * qldpc_shotprior_decode_batch or qldpc_erasure_priors refuses.  A refused call leaves the plan as it was. */
+int qldpc_circuit_plan_use_erasure_aware(qldpc_circuit_plan *plan, double alpha, const int32_t *loc_ptr_z, const int32_t *loc_col_z,
+                                         const uint8_t *loc_h_z, const int32_t *lut_ptr_z, const double *lut_z, const int32_t *loc_ptr_x,
+                                         const int32_t *loc_col_x, const uint8_t *loc_h_x, const int32_t *lut_ptr_x, const double *lut_x);
+/* qldpc_circuit_plan_sample plus erased uint32[count][ceil(n_locs / 32)] (all zero while erasure noise is off) and, where prior_z / prior_x are
+ * not NULL (both or neither; needs the erasure-aware path), the per-shot priors f64[count][n_z] / f64[count][n_x] the plan would decode with. */
+int qldpc_circuit_plan_sample_erasures(qldpc_circuit_plan *plan, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z,
+                                       int8_t *true_z, int8_t *sparse_x, int8_t *true_x, uint32_t *erased, double *prior_z, double *prior_x);
 
 /* ---- recorded detection events in place of the sampler: events -> decode -> OSD -> predict.  New here: the reference has no counterpart. ---------
  * The second front door of a circuit plan, for plans of qldpc_circuit_plan_create and _create_dem alike: the syndromes come from the caller's records

@@ -648,6 +648,50 @@ def shotprior_decode_batch(graph, syndromes, priors, alpha=1.0, clip_llr=20.0, m
     return (err, llr, conv, iters, pout) if want_prior else (err, llr, conv, iters)
 
 
+def erasure_table_args(tables, n=None, n_locs=None):
+    """One sector's erasure tables -- an object with loc_ptr / loc_col / loc_h / lut_ptr / lut (simulation.erasure.ErasureTables) or that 5-tuple ->
+    contiguous (loc_ptr int32, loc_col int32[>= 1], loc_h uint8[>= 1], lut_ptr int32, lut f64[>= 1]).  The shapes are checked here (the library reads
+    n_locs + 1, loc_ptr[n_locs], n + 1 and lut_ptr[n] entries), the rules themselves by the library."""
+    t = tables
+    lp, lc, lh, up, lu = (t.loc_ptr, t.loc_col, t.loc_h, t.lut_ptr, t.lut) if hasattr(t, "loc_ptr") else t
+    lp, lc, lh, up, lu = i32(lp).ravel(), i32(lc).ravel(), u8(lh).ravel(), i32(up).ravel(), f64(lu).ravel()
+    if lp.size < 1 or (n_locs is not None and lp.size != n_locs + 1):
+        raise ValueError(f"erasure tables: loc_ptr has {lp.size} entries" + (f", the plan has {n_locs} locations (n_locs + 1 expected)" if n_locs is not None else ""))
+    if up.size < 2 or (n is not None and up.size != n + 1):
+        raise ValueError(f"erasure tables: lut_ptr has {up.size} entries" + (f", the sector has {n} columns (n + 1 expected)" if n is not None else ""))
+    if lc.size != lh.size or lc.size < max(int(lp[-1]), 0):
+        raise ValueError(f"erasure tables: loc_ptr ends at {int(lp[-1])}, loc_col holds {lc.size} entries and loc_h {lh.size}")
+    if lu.size < max(int(up[-1]), 0):
+        raise ValueError(f"erasure tables: lut_ptr ends at {int(up[-1])}, lut holds {lu.size} entries")
+    if lc.size == 0:
+        lc, lh = np.zeros(1, np.int32), np.ones(1, np.uint8)
+    if lu.size == 0:
+        lu = np.zeros(1, np.float64)
+    return lp, lc, lh, up, lu
+
+
+def _erasure_table_ptrs(t):
+    return ptr(t[0], C.c_int32), ptr(t[1], C.c_int32), ptr(t[2], C.c_uint8), ptr(t[3], C.c_int32), ptr(t[4], C.c_double)
+
+
+def erasure_priors(erased, tables):
+    """qldpc_erasure_priors on host arrays: the herald record erased uint32[B, ceil(n_locs / 32)] and one sector's tables (erasure_table_args) ->
+    the per-shot prior f64[B, n]."""
+    lp, lc, lh, up, lu = t = erasure_table_args(tables)
+    n_locs, n = lp.size - 1, up.size - 1
+    erased = np.ascontiguousarray(erased, np.uint32)
+    nw = (n_locs + 31) // 32
+    if erased.ndim != 2 or erased.shape[1] != nw:
+        raise ValueError(f"erased must be uint32[B, {nw}] for {n_locs} locations, got shape {erased.shape}")
+    B = erased.shape[0]
+    prior = np.zeros((B, n), np.float64)
+    if erased.size == 0:
+        erased = np.zeros(1, np.uint32)
+    p = _erasure_table_ptrs(t)
+    check(lib().qldpc_erasure_priors(C.c_int64(B), C.c_int32(n_locs), ptr(erased, C.c_uint32), *p[:3], C.c_int32(n), *p[3:], ptr(prior, C.c_double)))
+    return prior
+
+
 def check_window_args(layer_rows, window, commit, m=None):
     """ValueError unless window >= 1, 1 <= commit <= window and layer_rows >= 1 (dividing m when m is given) -> the three as ints."""
     for name, v in (("layer_rows", layer_rows), ("window", window), ("commit", commit)):
@@ -1036,6 +1080,7 @@ class CircuitPlan(Owner):
         self.k, self.nsx, self.nsz = d.k, int(keep["x_syn_ptrs"][-1]), int(keep["z_syn_ptrs"][-1])
         self.n_locs = int(d.base_len)                       # fault locations: what use_fixed_weight counts
         self.fixed_weight = None                            # the sampler axis: None = the independent draws, else the weight in force
+        self.erasure_rates = None                           # ... and None = no erasure noise, else the rates in force (f64[7] by op code)
         self.graph_z, self.graph_x = graph_z, graph_x
         self.flags = flags
         self._h = C.c_void_p()
@@ -1131,6 +1176,45 @@ class CircuitPlan(Owner):
         weight = check_fixed_weight(weight)
         check(lib().qldpc_circuit_plan_use_fixed_weight(self._h, C.c_int(weight)))
         self.fixed_weight = None if weight < 0 else weight
+
+    def use_erasure_noise(self, rates):
+        """Draw heralded erasures on top of the plan's ordinary faults from now on (qldpc_circuit_plan_use_erasure_noise): `rates` is a number (every
+        location class) or a dict keyed by the gate names CNOT, PrepX, PrepZ, MeasX, MeasZ, IDLE; None: off again.  The sampler axis, beside
+        use_fixed_weight (the two refuse each other): two-way, and it goes with every other use_* in either order.  Circuit plans only."""
+        if rates is None:
+            check(lib().qldpc_circuit_plan_use_erasure_noise(self._h, None))
+            self.erasure_rates = None
+            return
+        from .simulation.erasure import erasure_rates
+        r = erasure_rates(rates)
+        check(lib().qldpc_circuit_plan_use_erasure_noise(self._h, ptr(r, C.c_double)))
+        self.erasure_rates = r
+
+    def use_erasure_aware(self, alpha=1.0, tables=None):
+        """Decode both sectors with the heralds from now on (qldpc_circuit_plan_use_erasure_aware): constant-alpha min-sum whose prior is computed
+        per shot from the sampler's herald record.  tables: (sector Z, sector X), each a simulation.erasure.ErasureTables or its 5-tuple -- what
+        erasure_tables_from_circuit returns.  The plan's max_iter and clip_llr apply, its alpha table does not.  Goes with OSD-0, OSD-CS (which still
+        scores with the shared prior) and LSD; with no other path; circuit plans only.  Again with new arguments is allowed."""
+        alpha = shotprior_params(alpha)[0]
+        if tables is None or len(tables) != 2:
+            raise ValueError("use_erasure_aware needs the tables of both sectors (simulation.erasure.erasure_tables_from_circuit)")
+        ns = [g.n if g is not None else None for g in (self.graph_z, self.graph_x)]
+        keep = [erasure_table_args(t, n, self.n_locs) for t, n in zip(tables, ns)]
+        check(lib().qldpc_circuit_plan_use_erasure_aware(self._h, alpha, *_erasure_table_ptrs(keep[0]), *_erasure_table_ptrs(keep[1])))
+        self.erasure_aware = {"alpha": alpha}
+
+    def sample_erasures(self, seed, trial_begin, count, want_priors=False):
+        """sample() plus the herald record -> (sparse_z, true_z, sparse_x, true_x, erased uint32[count, ceil(n_locs / 32)]) and, with want_priors (the
+        erasure-aware path), the per-shot priors f64[count, n_z], f64[count, n_x] the plan decodes those trials with (qldpc_circuit_plan_sample_erasures)."""
+        spz, spx = np.zeros((count, self.nsx), np.int8), np.zeros((count, self.nsz), np.int8)
+        tz, tx = np.zeros((count, self.k), np.int8), np.zeros((count, self.k), np.int8)
+        erased = np.zeros((count, (self.n_locs + 31) // 32), np.uint32)
+        pz = np.zeros((count, self.graph_z.n), np.float64) if want_priors else None
+        px = np.zeros((count, self.graph_x.n), np.float64) if want_priors else None
+        check(lib().qldpc_circuit_plan_sample_erasures(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), ptr(spz, C.c_int8),
+                                                       ptr(tz, C.c_int8), ptr(spx, C.c_int8), ptr(tx, C.c_int8), ptr(erased, C.c_uint32),
+                                                       ptr(pz, C.c_double) if want_priors else None, ptr(px, C.c_double) if want_priors else None))
+        return (spz, tz, spx, tx, erased, pz, px) if want_priors else (spz, tz, spx, tx, erased)
 
     def run(self, seed, trial_begin, count, stream=0):
         check(lib().qldpc_circuit_plan_run(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream)))
@@ -1252,6 +1336,7 @@ class DemPlan(CircuitPlan):
         self.n_sectors, self.k, self.ks, self.nsx, self.nsz = nsec, max(ks), (ks[0], ks[1]), nd[0], nd[1]
         self.n_locs = int(d.n_mech)
         self.fixed_weight = None
+        self.erasure_rates = None
         self.graph_z, self.graph_x = g[0], g[1]
         self.flags = flags
         opt = lambda a, t: ptr(a, t) if a is not None else None

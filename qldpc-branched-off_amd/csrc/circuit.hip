@@ -142,7 +142,7 @@ __global__ void collect_failed2_kernel(int64_t B, const uint8_t *__restrict__ co
 using namespace qldpc;
 
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
-enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED };      // who fills the BP bracket and its follow-up
+enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED, ERASURE };      // who fills the BP bracket and its follow-up
 enum class Osd { OSD0, CS, LSD };                                     // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
 
 struct qldpc_circuit_plan {
@@ -160,6 +160,8 @@ struct qldpc_circuit_plan {
         DevBuf d_lsd_info;                         // Osd::LSD: info of the batch in flight
         // decode of recorded events (events.hip): the record bit of every row (ev_tab, else the contiguous run at ev_base); the predictions of a batch
         DevBuf d_evtab, d_pred;
+        // Path::ERASURE (erasure.hip): the sector's tables location -> (column, h) and column -> lut run; the per-shot prior f64[batch][n] of a batch
+        DevBuf d_er_ptr, d_er_col, d_er_h, d_er_lutptr, d_er_lut, d_eprior;
         bool ev_tab = false;
         int ev_base = 0;
         // the decoder objects of a path, below the buffers they write so that they go first (each waits for what it has in flight)
@@ -177,6 +179,12 @@ struct qldpc_circuit_plan {
     // dem_odd: the first mechanism whose threshold differs from mechanism 0's (-1: none), which refuses the switch
     int fixed_weight = -1;
     int64_t dem_odd = -1;
+    // ... and qldpc_circuit_plan_use_erasure_noise: heralded erasures on top of the independent draws (erasure.hip); ethr: the threshold per op code;
+    // d_erased: the herald record uint32[batch][ceil(n_locs / 32)] of a batch.  Erasure noise and a fixed weight refuse each other.
+    bool erasure = false;
+    uint32_t ethr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf d_erased;
+    double era_alpha = 1.0;                        // Path::ERASURE: constant alpha
     double p = 0, damping = 1, clip = 20;
     uint32_t thr = 0;
     int64_t batch = 0;
@@ -498,6 +506,10 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
                                  zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
     }
     const auto sig = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
+    if (P->erasure)
+        return erasure_sample_launch(P->device, B, begin, seed, P->thr, P->ethr, P->n_locs, P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn,
+                                     Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
+                                     P->d_erased.as<uint32_t>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
     const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
     const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
     const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
@@ -508,8 +520,16 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
     return QLDPC_OK;
 }
 
-// enqueues the decode of sector `sector` (0 = Z, 1 = X) of a batch on s, inside that sector's phase brackets
-static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s, uint64_t seed, int64_t trial_begin) {
+// Path::ERASURE: the per-shot prior of sector `sector` from the herald record of the batch in d_erased
+static int launch_erasure_prior(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s) {
+    const Sector &S = P->sec[sector];
+    return erasure_prior_launch(P->device, B, P->n_locs, P->d_erased.as<uint32_t>(), S.d_er_ptr.as<int32_t>(), S.d_er_col.as<int32_t>(), S.d_er_h.as<uint8_t>(),
+                                S.g->n, S.d_er_lutptr.as<int32_t>(), S.d_er_lut.as<double>(), S.d_eprior.as<double>(), s);
+}
+
+// enqueues the decode of sector `sector` (0 = Z, 1 = X) of a batch on s, inside that sector's phase brackets.  heralds: the batch came from the
+// erasure sampler and d_eprior holds its per-shot priors (Path::ERASURE reads them; without, it decodes with the plan's prior)
+static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s, uint64_t seed, int64_t trial_begin, bool heralds = false) {
     Sector &S = P->sec[sector];
     const qldpc_graph *g = S.g;
     int rc = QLDPC_OK;
@@ -550,6 +570,14 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
         std::lock_guard<std::mutex> lk(g->mu);
         rc = shotprior_decode_launch(g, B, S.d_syn.as<int8_t>(), prior, 0, sector == 1 ? links : none, P->corr_alpha, P->clip, P->max_iter, -1,
                                      S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), nullptr, s);
+        break;
+    }
+    case Path::ERASURE: {      // the per-shot-prior kernel with no links: prior[B][n] of the batch's heralds, or the plan's prior where there are none
+        const ShotLinks none{0, nullptr, nullptr, nullptr, nullptr};
+        std::lock_guard<std::mutex> lk(g->mu);
+        rc = shotprior_decode_launch(g, B, S.d_syn.as<int8_t>(), heralds ? S.d_eprior.as<double>() : S.d_prior.as<double>(), heralds ? g->n : 0, none,
+                                     P->era_alpha, P->clip, P->max_iter, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(),
+                                     S.d_iter.as<int32_t>(), nullptr, s);
         break;
     }
     case Path::FLOOD: {
@@ -607,9 +635,12 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         if (P->pending.size() > 256) drain_phases(P, false);         // a caller that never reads phase times: recycle finished brackets (bounded event count)
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, s, true)) != QLDPC_OK) return rc;
+        const bool heralds = P->erasure && P->path == Path::ERASURE;       // (the prior kernels count as sampling: they turn the draws into the decoder's input)
+        for (int sector = 0; heralds && sector < P->nsec; sector++)
+            if ((rc = launch_erasure_prior(P, sector, B, s)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
         for (int sector = 0; sector < P->nsec; sector++)
-            if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off)) != QLDPC_OK) return rc;
+            if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off, heralds)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, true)) != QLDPC_OK) return rc;
         hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
                            outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
@@ -704,19 +735,20 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 
 // The switch rules, once.  A plan decodes on two axes, and qldpc_circuit_plan_use_* moves it along one of them:
 //   Path: who fills the BP bracket and its follow-up -- flooding min-sum (as created), the layered schedule, guided decimation, single precision (f32),
-//     Relay-BP, sliding windows or correlated two-sector decoding.  A plan leaves flooding at most once.  Asking again for the path it is on brings
-//     new arguments (Relay-BP, layered, decimation, correlated), changes nothing (f32) or is refused (windows).
-//   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation, f32 and
-//     correlated whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
+//     Relay-BP, sliding windows, correlated two-sector decoding or erasure-aware decoding.  A plan leaves flooding at most once.  Asking again for the
+//     path it is on brings new arguments (Relay-BP, layered, decimation, correlated, erasure-aware), changes nothing (f32) or is refused (windows).
+//   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation, f32,
+//     correlated and erasure-aware whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
 //     refuse each other in either order.
-//   Windows need use_osd as well; Relay-BP, layered, decimation, f32 and correlated do not.  Windows, layered, decimation, f32 and correlated need
-//   damping = 1.
+//   Windows need use_osd as well; Relay-BP, layered, decimation, f32, correlated and erasure-aware do not.  Windows, layered, decimation, f32,
+//   correlated and erasure-aware need damping = 1.
 // Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation, correlated: finite priors and a supported graph;
-// correlated: two sectors).
+// correlated: two sectors; erasure-aware: what correlated's kernel needs, and a circuit plan).
 // `to`: the path asked for; Path::FLOOD stands for a request on the other axis, for the OSD stage `stage` (no call asks for flooding).
 // QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
 static int switch_allowed(const qldpc_circuit_plan *P, Path to, Osd stage = Osd::CS) {
-    static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding", "correlated decoding"};
+    static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding", "correlated decoding",
+                                             "erasure-aware decoding"};
     static const char *const osd_name[] = {"BP + OSD-0", "BP + OSD-CS", "BP + LSD"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     const bool cs = to == Path::FLOOD;                                   // a request on the OSD axis: `stage` says for which of the two
@@ -899,9 +931,111 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *P, int 
     if (weight == -1) { P->fixed_weight = -1; return QLDPC_OK; }
     const int rc = fixed_weight_check(P->n_locs, weight);
     if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a fixed weight counts the faults of the independent draws alone (switch erasure noise off first)");
     QLDPC_REQUIRE(!P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
                   "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
     P->fixed_weight = weight;
+    return QLDPC_OK;
+}
+
+// The sampler axis again: heralded erasures on top of the independent draws (erasure.hip).  rate[op code], NULL = off.
+QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *P, const double rate[7]) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    if (rate == nullptr) { P->erasure = false; return QLDPC_OK; }
+    QLDPC_REQUIRE(!P->dem, "erasure noise needs a circuit plan: a detector error model has no gate locations to erase");
+    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: erasure noise goes with the independent draws (switch the fixed weight off first)",
+                  P->fixed_weight);
+    uint32_t thr[8];
+    int rc = erasure_rates_check(rate, thr);
+    if (rc != QLDPC_OK || (rc = erasure_sample_supported(P->sec[0].nsyn, P->sec[1].nsyn, P->n_locs)) != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_erased.ensure((size_t)P->batch * ((size_t)(P->n_locs + 31) / 32) * 4 + 4)) != QLDPC_OK) return rc;
+    std::copy(thr, thr + 8, P->ethr);
+    P->erasure = true;
+    return QLDPC_OK;
+}
+
+// One sector's tables of qldpc_circuit_plan_use_erasure_aware (host pointers).
+struct ErasureTabIn { const int32_t *loc_ptr, *loc_col; const uint8_t *loc_h; const int32_t *lut_ptr; const double *lut; };
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_aware(qldpc_circuit_plan *P, double alpha, const int32_t *loc_ptr_z, const int32_t *loc_col_z,
+                                                      const uint8_t *loc_h_z, const int32_t *lut_ptr_z, const double *lut_z, const int32_t *loc_ptr_x,
+                                                      const int32_t *loc_col_x, const uint8_t *loc_h_x, const int32_t *lut_ptr_x, const double *lut_x) {
+    int rc = switch_allowed(P, Path::ERASURE);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(!P->dem, "erasure-aware decoding needs a circuit plan: a detector error model has no gate locations to herald");
+    const ErasureTabIn in[2] = {{loc_ptr_z, loc_col_z, loc_h_z, lut_ptr_z, lut_z}, {loc_ptr_x, loc_col_x, loc_h_x, lut_ptr_x, lut_x}};
+    for (int i = 0; i < 2; i++) {
+        const Sector &S = P->sec[i];
+        QLDPC_REQUIRE(in[i].loc_ptr && in[i].lut_ptr && in[i].lut, "sector %c: loc_ptr, lut_ptr or lut is NULL", "ZX"[i]);
+        if ((rc = erasure_check_tables(P->n_locs, in[i].loc_ptr, in[i].loc_col, in[i].loc_h, S.g->n, in[i].lut_ptr, in[i].lut)) != QLDPC_OK) return rc;
+        for (int j = 0; j < S.g->n; j++)      // entry 0 of a column's run is the plan's own prior, verbatim: a shot without heralds decodes as the plan does
+            QLDPC_REQUIRE(std::memcmp(&in[i].lut[in[i].lut_ptr[j]], &S.h_prior[j], 8) == 0, "sector %c: lut[lut_ptr[%d]] = %.17g is not the plan's prior %.17g of column %d",
+                          "ZX"[i], j, in[i].lut[in[i].lut_ptr[j]], S.h_prior[j], j);
+        if ((rc = erasure_prior_supported(S.g->n)) != QLDPC_OK) return rc;
+    }
+    if ((rc = inputs_supported(P, shotprior_check_params(alpha, P->clip, P->max_iter),
+                               [](const qldpc_graph *g) { return shotprior_mode(g) ? QLDPC_OK : shotprior_unsupported(g); })) != QLDPC_OK)
+        return rc;
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a decode that is still enqueued reads the tables replaced here
+    DevBuf nb[2][5];                                                     // all or none: a failed upload leaves the plan's tables as they were
+    for (int i = 0; i < 2; i++) {
+        const size_t ne = (size_t)in[i].loc_ptr[P->n_locs], n = (size_t)P->sec[i].g->n;
+        if ((rc = upload(nb[i][0], std::vector<int32_t>(in[i].loc_ptr, in[i].loc_ptr + P->n_locs + 1))) ||
+            (rc = upload(nb[i][1], std::vector<int32_t>(in[i].loc_col, in[i].loc_col + ne))) ||
+            (rc = upload(nb[i][2], std::vector<uint8_t>(in[i].loc_h, in[i].loc_h + ne))) ||
+            (rc = upload(nb[i][3], std::vector<int32_t>(in[i].lut_ptr, in[i].lut_ptr + n + 1))) ||
+            (rc = upload(nb[i][4], std::vector<double>(in[i].lut, in[i].lut + in[i].lut_ptr[n]))))
+            return rc;
+    }
+    for (int i = 0; i < 2; i++)
+        if ((rc = P->sec[i].d_eprior.ensure((size_t)P->batch * (size_t)P->sec[i].g->n * 8)) != QLDPC_OK) return rc;
+    if ((rc = P->d_erased.ensure((size_t)P->batch * ((size_t)(P->n_locs + 31) / 32) * 4 + 4)) != QLDPC_OK) return rc;
+    for (int i = 0; i < 2; i++) {
+        Sector &S = P->sec[i];
+        S.d_er_ptr = std::move(nb[i][0]); S.d_er_col = std::move(nb[i][1]); S.d_er_h = std::move(nb[i][2]);
+        S.d_er_lutptr = std::move(nb[i][3]); S.d_er_lut = std::move(nb[i][4]);
+    }
+    P->era_alpha = alpha;
+    P->path = Path::ERASURE;
+    return QLDPC_OK;
+}
+
+// qldpc_circuit_plan_sample plus the herald record and, where asked for, the per-shot priors of both sectors (host pointers)
+QLDPC_EXPORT int qldpc_circuit_plan_sample_erasures(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z,
+                                                    int8_t *true_z, int8_t *sparse_x, int8_t *true_x, uint32_t *erased, double *prior_z, double *prior_x) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(!P->dem, "sample_erasures needs a circuit plan: a detector error model has no gate locations to erase");
+    QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
+    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x && erased), "NULL output");
+    QLDPC_REQUIRE((prior_z == nullptr) == (prior_x == nullptr), "prior_z and prior_x are both NULL or both given");
+    QLDPC_REQUIRE(!prior_z || P->path == Path::ERASURE, "the per-shot priors need the tables of qldpc_circuit_plan_use_erasure_aware");
+    QLDPC_USE_DEVICE(P->device);
+    int rc;
+    const size_t nw = (size_t)(P->n_locs + 31) / 32;
+    if ((rc = P->d_erased.ensure((size_t)P->batch * nw * 4 + 4)) != QLDPC_OK) return rc;
+    int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
+    double *const prior[2] = {prior_z, prior_x};
+    std::vector<unsigned long long> t;
+    for (int64_t off = 0; off < count; off += P->batch) {
+        const int64_t B = std::min<int64_t>(P->batch, count - off);
+        if (!P->erasure) QLDPC_HIP_TRY(hipMemsetAsync(P->d_erased.p, 0, (size_t)B * nw * 4, nullptr));      // the switch is off: no location is erased
+        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
+        for (int i = 0; prior_z && i < 2; i++)
+            if ((rc = launch_erasure_prior(P, i, B, nullptr)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(hipDeviceSynchronize());
+        t.resize(B);
+        if (nw) QLDPC_HIP_TRY(hipMemcpy(erased + off * nw, P->d_erased.p, (size_t)B * nw * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 2; i++) {
+            const Sector &S = P->sec[i];
+            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
+            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+            for (int64_t b = 0; b < B; b++)
+                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
+            if (prior[i]) QLDPC_HIP_TRY(hipMemcpy(prior[i] + off * S.g->n, S.d_eprior.p, (size_t)B * S.g->n * 8, hipMemcpyDeviceToHost));
+        }
+    }
     return QLDPC_OK;
 }
 

@@ -196,6 +196,19 @@ int fixed_weight_check(int64_t n_locs, int weight);
 int fixed_weight_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, int weight, int n_locs, bool dem, const uint8_t *d_loc_type,
                                const SigTab &T0, const SigTab &T1, int n0, int n1, bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0,
                                unsigned long long *d_true1, int32_t *d_fail_counts, hipStream_t s);
+// Heralded-erasure noise of a circuit plan (erasure.hip).  sample: circuit_sample_kernel's draws at threshold thr plus the erasures at ethr[op code]
+// (erasure_rates_check turns rate[7] into them: QLDPC_ERR_INVALID naming the class), the herald record uint32[B][ceil(n_locs / 32)] written to d_erased.
+// prior: heralds and the tables of one sector (device pointers) -> d_prior f64[B][n].  check_tables: the table rules of qldpc_erasure_priors on host
+// arrays, QLDPC_ERR_INVALID with the text naming the offending index.  *_supported: QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the text set (LDS).
+int erasure_rates_check(const double *rate, uint32_t thr[8]);
+int erasure_sample_supported(int nsx, int nsz, int64_t n_locs);
+int erasure_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const uint32_t ethr[8], int n_locs,
+                          const uint8_t *d_loc_type, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
+                          unsigned long long *d_true_z, unsigned long long *d_true_x, uint32_t *d_erased, int32_t *d_fail_counts, hipStream_t s);
+int erasure_check_tables(int n_locs, const int32_t *loc_ptr, const int32_t *loc_col, const uint8_t *loc_h, int n, const int32_t *lut_ptr, const double *lut);
+int erasure_prior_supported(int n);
+int erasure_prior_launch(int device, int64_t B, int n_locs, const uint32_t *d_erased, const int32_t *d_loc_ptr, const int32_t *d_loc_col,
+                         const uint8_t *d_loc_h, int n, const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, hipStream_t s);
 // Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
 // only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
 // predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does

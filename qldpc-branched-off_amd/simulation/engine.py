@@ -23,7 +23,7 @@ Differences that are deliberate and documented:
   * ``target_logical_errors`` stops at the exact trial the reference would (in-order prefix cut over per-trial verdicts).
 
 The extensions below choose what a worker's plan decodes with, on the plan's two axes.  The path: at most one of
-``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...``, ``precision="f32"`` and ``correlated=...`` leaves flooding min-sum, and none of them
+``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...``, ``precision="f32"``, ``correlated=...`` and ``erasure={..., "aware": True}`` leaves flooding min-sum, and none of them
 goes with the reference's OSD-w pass (``osd_order > 0`` with ``decoder="bp_osd"``).  The OSD stage: ``decoder="bp_osd_cs"`` puts OSD-CS in the place
 of OSD-0 and ``decoder="bp_lsd"`` puts BP+LSD there; each goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
 
@@ -73,6 +73,14 @@ shares a fault with a column of sector Z's correction is raised to its condition
 the dict, so every argument that selects or estimates another alpha raises ValueError, as for ``decimation``.  The result also holds ``correlated`` and
 ``correlated_links``.
 
+``erasure={"rates": ..., "aware": True, "alpha": 1.0}`` (an extension; None is today's behaviour; ``aware`` defaults to True and ``alpha`` to 1.0) adds
+heralded-erasure noise to the sampler (``simulation/erasure.py``, ``CircuitPlan.use_erasure_noise``): ``rates`` is a number (every location class) or a
+dict keyed by the gate names CNOT, PrepX, PrepZ, MeasX, MeasZ, IDLE.  With ``aware=True`` both sectors are decoded with a per-shot prior built from the
+heralds (``CircuitPlan.use_erasure_aware``, the tables of ``erasure_tables_from_circuit``): a decode path, so it goes with none of the others, its alpha
+is the constant of the dict as for ``correlated``, and OSD-0, OSD-CS (which still scores with the shared prior) or LSD follows as before.  With
+``aware=False`` only the sampler changes -- the sampler axis -- and every path and decoder goes with it: the decoder does not see the heralds.  The result
+also holds ``erasure`` (rates as f64[7] by op code, aware, alpha).  Circuit plans only: ``run_weight_strata`` and ``run_dem_simulation`` raise ValueError.
+
 ``simulation/dem.py`` (``run_dem_simulation``: the same pipeline fed by a detector error model instead of a bivariate-bicycle circuit) shares the
 argument rules of the extensions (``_extension_rules``), the choice of devices (``_worker_devices``) and the Worker, round loop, early stop,
 all-reduce and result assembly (``_run_trials``) with ``run_simulation``; the two differ in how a worker's plan is created.
@@ -105,12 +113,12 @@ def _estimation_trials(requested, n_cols, error_rate):
 
 
 def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
-                     maxIter, num_workers, lsd=None, correlated=None):
+                     maxIter, num_workers, lsd=None, correlated=None, erasure=None):
     """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision, correlated), shared by run_simulation and
     run_dem_simulation: raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered",
-    "decimation", "f32", "relay", "window" or "correlated": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
+    "decimation", "f32", "relay", "window", "correlated" or "erasure": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
     parameters, else None) -- with the normalised parameters of that path (``layers``, ``decimation``, ``relay_params``, ``window``, ``correlated``; None
-    where the path is another)."""
+    where the path is another) and ``erasure`` (the sampler axis: rates f64[7], aware, alpha; None without erasure noise)."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
@@ -128,16 +136,29 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         if lsd is not None and not isinstance(lsd, dict):
             raise ValueError("lsd must be a dict with bits_per_step and / or max_rows (or None)")
         lsd = _lib.lsd_params(lsd)
+    if erasure is not None:
+        if not isinstance(erasure, dict) or "rates" not in erasure:
+            raise ValueError("erasure must be a dict with rates and, optionally, aware and alpha (or None)")
+        unknown = set(erasure) - {"rates", "aware", "alpha"}
+        if unknown:
+            raise ValueError(f"unknown erasure parameter(s): {sorted(unknown)}")
+        if not isinstance(erasure.get("aware", True), (bool, np.bool_)):
+            raise ValueError("erasure['aware'] must be True or False")
+        from .erasure import erasure_rates
+        erasure = {"rates": erasure_rates(erasure["rates"]), "aware": bool(erasure.get("aware", True)),
+                   "alpha": _lib.shotprior_params(erasure.get("alpha", 1.0), 20.0, maxIter)[0]}
+    aware = erasure is not None and erasure["aware"]
     # the path: at most one argument leaves flooding min-sum (the plan's own rule, qldpc_circuit_plan_use_*) ...
     asked = [(path, text) for path, text, given in (("f32", "precision='f32'", precision == "f32"), ("decimation", "decimation=...", decimation is not None),
                                                      ("layered", "schedule='layered'", schedule == "layered"),
                                                      ("window", f"window={window!r}", window is not None), ("relay", "decoder='relay_bp'", decoder == "relay_bp"),
-                                                     ("correlated", "correlated=...", correlated is not None))
+                                                     ("correlated", "correlated=...", correlated is not None),
+                                                     ("erasure", "erasure={..., 'aware': True}", aware))
              if given]
     if len(asked) > 1:
         (_, one), (_, other) = asked[:2]
         raise ValueError(f"{one} does not go with {other}: {one} goes with none of the others of decoder='relay_bp', window=(W, C), schedule='layered', "
-                         "decimation=..., precision='f32' and correlated=... (each decodes the BP stage its own way)")
+                         "decimation=..., precision='f32', correlated=... and erasure={..., 'aware': True} (each decodes the BP stage its own way)")
     path, text = asked[0] if asked else ("flooding", None)
     # ... and none of them goes with the OSD-w pass, which decodes again with flooding min-sum in f64
     if path != "flooding" and decoder == "bp_osd" and osd_order > 0:
@@ -176,6 +197,11 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         correlated = {"alpha": _lib.shotprior_params(correlated.get("alpha", 1.0), 20.0, maxIter)[0], "mode": correlated.get("mode", "raise"),
                       "floor": correlated.get("floor")}
         check_mode(correlated["mode"], correlated["floor"])
+    elif path == "erasure":
+        bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None),
+                                        ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
+        if bad:
+            raise ValueError(f"erasure={{..., 'aware': True}} does not use {', '.join(bad)}: its alpha is the constant erasure['alpha']")
     elif path == "layered":
         mode = alpha_mode if alpha_mode is not None else ("dynamical" if use_dynamic_alpha else "alvarado")
         if mode == "alvarado-autoregressive" or (mode == "alvarado" and alvarado_alpha is None):
@@ -205,7 +231,7 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
     return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window, correlated=correlated,
-                           links=None)
+                           links=None, erasure=erasure, erasure_tables=None)
 
 
 def _worker_devices(num_workers, devices, device):
@@ -237,14 +263,16 @@ def _worker_devices(num_workers, devices, device):
 def _plan_switch(rules, csr, osd_order):
     """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
     dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` or LSD in the OSD stage when the rules ask for it, then moves the BP stage to
-    rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
+    rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links; erasure: with rules.erasure_tables), then
+    switches erasure noise on where rules.erasure asks for it (the sampler axis: last, since it goes with whatever the plan decodes with).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
     layers = None
     if rules.path == "layered":
         layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
     to_path = {"flooding": lambda plan: None, "relay": lambda plan: plan.use_relay(**rules.relay_params), "window": lambda plan: plan.use_window(*rules.window),
                "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
                "f32": lambda plan: plan.use_f32(),
-               "correlated": lambda plan: plan.use_correlated(rules.correlated["alpha"], rules.links, None if rules.links is None else rules.links.base)}[rules.path]
+               "correlated": lambda plan: plan.use_correlated(rules.correlated["alpha"], rules.links, None if rules.links is None else rules.links.base),
+               "erasure": lambda plan: plan.use_erasure_aware(rules.erasure["alpha"], rules.erasure_tables)}[rules.path]
 
     def switch(plan):
         if rules.osd_cs:
@@ -252,6 +280,9 @@ def _plan_switch(rules, csr, osd_order):
         if rules.lsd is not None:
             plan.use_lsd(**rules.lsd)
         to_path(plan)
+        if rules.erasure is not None:                                            # the sampler axis: goes with whatever the plan decodes with
+            from .erasure import GATES                                           # (in op-code order: rates[1..6])
+            plan.use_erasure_noise({g: rules.erasure["rates"][i + 1] for i, g in enumerate(GATES)})
 
     return switch, layers
 
@@ -424,6 +455,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         result.update(decimation=dict(rules.decimation), mean_rounds_z=per_trial[0], mean_rounds_x=per_trial[1])
     elif rules.path == "correlated":
         result.update(correlated=dict(rules.correlated), correlated_links=0 if rules.links is None else rules.links.n_links)
+    if rules.erasure is not None:
+        result.update(erasure=dict(rules.erasure))
     result["precision"] = precision
     result["tally"] = total
     return result
@@ -461,9 +494,9 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, **bb_params):
+                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, **bb_params):
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
-                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated)
+                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated, erasure=erasure)
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:
@@ -482,6 +515,9 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if rules.path == "correlated":
         from .correlated import links_from_circuit
         rules.links = links_from_circuit(prob.compiled, Lx, Lz, prob.matrices, error_rate, rules.correlated["mode"], rules.correlated["floor"])
+    if rules.path == "erasure":
+        from .erasure import erasure_tables_from_circuit
+        rules.erasure_tables = erasure_tables_from_circuit(prob.compiled, Lx, Lz, prob.matrices)
 
     # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
     # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
