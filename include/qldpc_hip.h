@@ -156,6 +156,9 @@ int qldpc_device_count(void);
  *   "regular_place"       read at a fixed-work launch of that form: 1 (default) = every thread takes the LDS addresses of its posteriors and messages from the placement of
  *                         csrc/regular_place.h (edge colouring: the gathers and the message stores free of bank conflicts), built at the handle's first
  *                         launch with a workgroup shape; 0 = the linear layout, through the same kernel
+ *   "regular_wave_classes" read with "regular_place" 1: 1 (default) = that table is built from the assignment that owns the fewest `last` edges and deals the
+ *                         threads of a workgroup so that whole waves share one class of them; such a wave runs the fixed-work loop without selects.
+ *                         0 = the assignment of "regular_own_search" in thread order, every wave on the loop with selects.  No output word depends on it
  *   "regular_kernel", "wave_cpl", "wave_rst", "wave_grid"  experiments build only: the wave-private decoder (csrc/minsum_wave.hip); the
  *                         product library accepts 0 and answers anything else with QLDPC_ERR_UNSUPPORTED */
 int qldpc_set_option(const char *name, int value);

@@ -177,7 +177,7 @@ def device_count():
 def set_option(name, value):
     """Process-wide kernel-selection switch (include/qldpc_hip.h: qldpc_set_option); results never depend on it.
     Most are read at a launch or at plan creation; "regular_own_search" is read when a Graph is created, so set it before the handle is made;
-    "regular_place" (next to "regular_own_edges") is read at every fixed-work launch of the regular min-sum kernel's ownership form."""
+    "regular_place" and "regular_wave_classes" (next to "regular_own_edges") are read at every fixed-work launch of the regular min-sum kernel's ownership form."""
     check(lib().qldpc_set_option(name.encode(), int(value)))
 
 

@@ -299,9 +299,14 @@ struct qldpc_graph {
     int32_t *d_regown = nullptr;     // [m][16] edge-ownership records of the regular (6,3) kernel (regular_own.h), NULL where the graph has no assignment; built at creation
     // LDS place tables of that kernel (regular_place.h), one per workgroup shape: built and uploaded at the first launch with the shape and kept for the
     // handle's life (minsum_regular.hip: regular_place_table).  A shape is (S, block): "mc_list_shots" and a long iteration table change S on the same
-    // graph.  placed = 0: today's linear addresses as a table, which also depend on where the dummy region lies (offD).  dev.p == NULL: placement
+    // graph.  placed = 0: today's linear addresses as a table, which also depend on where the dummy region lies (offD); 1: the placement of d_regown in
+    // the identity thread order; 2: the placement of d_regown_minlast under the thread order of regular_place_order.  dev.p == NULL: placement
     // declined the shape.  Guarded by mu_place, which is held for the build and the upload only.
     std::vector<int32_t> regown;     // the host copy of d_regown the tables are built from
+    // The min-last assignment (regular_own.h: the perfect assignment that owns the fewest `last` edges), for place tables with class-uniform waves: the
+    // launches that read such a table read this ownership table with it; every other launch reads d_regown.  Built at creation next to d_regown.
+    int32_t *d_regown_minlast = nullptr;
+    std::vector<int32_t> regown_minlast;
     struct PlaceEntry { int S = 0, block = 0, placed = 0, offD = 0; qldpc::DevBuf dev; };
     mutable std::mutex mu_place;
     mutable std::vector<PlaceEntry> place_cache;

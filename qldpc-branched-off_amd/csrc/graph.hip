@@ -337,7 +337,12 @@ QLDPC_EXPORT int qldpc_graph_create(int m, int n, const int32_t *indptr, const i
         // the regular (6,3) kernel's edge ownership: once per handle, here, where nothing is in flight and no lock is needed ("none" leaves the pointer NULL).
         // Which valid assignment it is changes LDS bank conflicts only, never a result ("regular_own_search", options.hip).
         std::vector<int32_t> own;
-        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) { rc = g->own(&g->d_regown, own); g->regown = std::move(own); }
+        if (regular_own_assign(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), own, regular_own_search_choice())) {
+            rc = g->own(&g->d_regown, own); g->regown = std::move(own);
+            // the assignment of the class-uniform waves (regular_place.h); it exists wherever the one above does
+            std::vector<int32_t> minlast;
+            if (rc == QLDPC_OK && regular_own_assign_minlast(m, n, indptr, indices, regular_row_stride(kRegOwnCdeg), minlast)) { rc = g->own(&g->d_regown_minlast, minlast); g->regown_minlast = std::move(minlast); }
+        }
     }
     if (rc != QLDPC_OK) return rc;
     *out = G.release();

@@ -53,6 +53,7 @@ void mc_first_set_bits(int bits);
 void regular_set_list_shots(int s);
 void regular_set_own_edges(int v);
 void regular_set_place(int v);           // minsum_regular.hip: qldpc_set_option("regular_place")
+void regular_set_wave_classes(int v);    // minsum_regular.hip: qldpc_set_option("regular_wave_classes")
 int regular_own_search_choice();         // options.hip: qldpc_set_option("regular_own_search"), read by qldpc_graph_create
 void mc_set_big_lanes(int n);
 int mc_tail_overlap_choice();  // qldpc_set_option("mc_tail_overlap"): 1 = OSD-0 + judge of a batch on a side stream beside the next batch's decode (default)

@@ -65,6 +65,19 @@
 //     posterior (prologue store, final syndrome test, logical comparison, export, out_llr) use the record's store places.  No address is packed: the
 //     bare loop keeps one basic block, 64 VGPRs and no scratch access with 14 address registers.  qldpc_set_option("regular_place", 0) launches the
 //     same kernel with the linear addresses as a table.  The early-exit form keeps the slot-relative addresses (see PLACE below).
+//   * class-uniform waves (PLACE; qldpc_set_option("regular_wave_classes", 0) turns them off).  The eight v_cndmask_b32 of the ownership form exist only because
+//     `last` differs from lane to lane.  A placed table is therefore built from the assignment that owns the FEWEST last edges (regular_own.h: min-cost
+//     flow) and deals the (slot, check) items of a workgroup to its threads so that whole waves hold checks that own no last edge (regular_place.h); the
+//     record names the thread's (slot, member) and its wave's class, and in the bare passes such a wave takes, by one scalar branch, the arm that adds
+//     (o1 + own) + o2 without a select.  Why no output word moves:
+//       assignment   every perfect assignment gives the reference's words (regular_own.h, header: the sum is the ascending-order sum whichever of
+//                    the column's three checks owns it);
+//       thread order threads exchange data only through LDS addresses taken from the table, which is built for the order; the leaders of a team are
+//                    `member == 0` by value, `threadIdx.x == 0` and `threadIdx.x < S` only pick one thread or S threads of the block for block-wide
+//                    words, a lane of no team has slot S (in_team false) as before, and the tally's and the logical mask's atomics commute;
+//       the arm      a wave takes it only if the table labels it "none", and the label is computed from the same `last` bits the selects read.
+//     Four copies of the loop (or of the pass inside one loop) were built first and dropped: the register allocator reloads 8 to 15 loop invariants from
+//     scratch inside three of four sequential loops, and four passes inside one loop cost five scalar branches per pass (profiles/r27_wave_classes.txt).
 // MC = true fuses the sampler (Philox4x32-10 stream of mc_common.h), the GF(2) syndrome (a6), the decode, the logical
 // comparison L (e xor e_hat) (engine.py:99-100) and the tally (engine.py:450-457) into the same launch: errors and
 // syndromes live in LDS, the posterior in registers; only shots BP fails on are written out (for the OSD-0 stage).
@@ -148,22 +161,31 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
     constexpr int RST = (CDEG % 2 == 0) ? CDEG + 1 : CDEG;
     const int m = A.m, n = A.n, S = A.S, TS = A.TS, max_iter = A.max_iter;
     const int nq = (n + 3) >> 2;
-    const int slot = threadIdx.x / TS, member = threadIdx.x - slot * TS;
+    constexpr bool CLIPMIN = NANFREE && !DAMP;      // compare-free message words with the clip in the two chain seeds (header comment); needs clip > 0, which NANFREE includes
+    static_assert(!OWN || (CLIPMIN && CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg), "edge ownership: the clean (6,3) form");
+    // PLACE: the fixed-work ownership form takes every LDS address of its posteriors and messages from a per-thread place record (regular_place.h).  The
+    // early-exit form keeps the slot-relative addresses: its iteration loop is the one with the freeze bookkeeping, three more address registers took its
+    // spills from 16 to 25 VGPRs, and the launch on listed shots under reference semantics, a few iterations per workgroup, ran 27 % longer (profiles/r24_place.txt)
+    constexpr bool PLACE = OWN && FIXED;
+    // Which (slot, member) a thread is: thread / TS and the remainder, except where a PLACE record names them (word [15], regular_place.h: the threads of a
+    // workgroup dealt so that whole waves hold checks of one class of the ownership table).  The order is unobservable: threads exchange data through the
+    // table's LDS addresses only, the leaders of a team are `member == 0` by value, a lane of no team has slot S, and the tally's atomics commute.
+    int slot = threadIdx.x / TS, member = threadIdx.x - slot * TS;
+    int wave_class = kRegWaveMixed;                                                  // PLACE: wave-uniform, in a scalar register
+    if (PLACE) {
+        const int w = A.place[(size_t)threadIdx.x * kRegPlaceWords + kRegPlaceOrder];
+        if (w & kRegPlaceOrdered) { slot = (w >> 12) & 0xfff; member = w & 0xfff; }
+        wave_class = __builtin_amdgcn_readfirstlane((w >> 24) & 3);
+    }
     const bool in_team = slot < S;
     const int sl = in_team ? slot : 0;
-    constexpr bool CLIPMIN = NANFREE && !DAMP;      // compare-free message words with the clip in the two chain seeds (header comment); needs clip > 0, which NANFREE includes
     // ALL: the iteration body of the clean form runs with every lane enabled.  plan_regular takes n == 2 m only, so TS == m and every lane of a team owns
     // a check and two columns; a team without a shot (b >= nshots) works on its own slot, which nobody else touches, and the lanes of the block that
     // belong to no team work on the dummy region Dl: a row of RST doubles, two posteriors, one parity word.  Nothing they compute is ever read.
     constexpr bool ALL = CLIPMIN;
     // ZEROFREE: the variable sum starts at its first message instead of at 0.0 + that message (header comment, "zero"): clean inputs only
     constexpr bool ZEROFREE = CLIPMIN;
-    static_assert(!OWN || (CLIPMIN && CDEG == kRegOwnCdeg && VDEG == kRegOwnVdeg), "edge ownership: the clean (6,3) form");
     constexpr int NOWN = OWN ? kRegOwnOwned : 0;                                   // edges of a row that are not stored
-    // PLACE: the fixed-work ownership form takes every LDS address of its posteriors and messages from a per-thread place record (regular_place.h).  The
-    // early-exit form keeps the slot-relative addresses: its iteration loop is the one with the freeze bookkeeping, three more address registers took its
-    // spills from 16 to 25 VGPRs, and the launch on listed shots under reference semantics, a few iterations per workgroup, ran 27 % longer (profiles/r24_place.txt)
-    constexpr bool PLACE = OWN && FIXED;
     double *Dl = reinterpret_cast<double *>(lds + A.offD);
     double *Rl = (ALL && !in_team) ? Dl : reinterpret_cast<double *>(lds) + (size_t)sl * m * RST;
     double *Vl = (ALL && !in_team) ? Dl + RST : reinterpret_cast<double *>(lds + A.offV) + (size_t)sl * n;
@@ -459,6 +481,51 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             // so no pass reads Al from LDS; the table A.alpha is never written by a kernel, hence the constant address space
             const __attribute__((address_space(4))) double *alpha_tab = (const __attribute__((address_space(4))) double *)A.alpha;
             double alpha_it = (it < max_iter) ? Al[it] : 0.0;
+            // PLACE: the variable sums of a pass come in two forms, picked per WAVE by one scalar branch (wave_class is wave-uniform, regular_place.h).  A
+            // wave whose team lanes all own no `last` edge adds (o1 + own) + o2 for both columns without a select; every other wave keeps the two selects per
+            // column (a wave of "one" or "both" could have an arm of its own, but they are rare -- none, one and none of eight waves on bb144, bb72 and
+            // bb288 -- and every further copy of the pass, as a loop or as an arm, cost more than it saved: profiles/r27_wave_classes.txt).  Both arms sit
+            // between the same two barriers, so the waves of a workgroup meet at every barrier whichever arm they take.  The empty asm keeps the arm from
+            // being folded back into selects on the class.
+            if constexpr (PLACE) {
+                for (; it < max_iter; it++) {
+                    double x[CDEG];
+                    unsigned ph = synw;
+#pragma unroll
+                    for (int k = 0; k < CDEG; k++) x[k] = (k < NOWN) ? Vown[k] : Vof(k);
+#pragma unroll
+                    for (int k = 0; k < CDEG; k++) ph ^= (unsigned)__double2hiint(x[k]);           // kernels.py:349,356
+                    parity |= ph;
+                    clean_messages<CDEG, NOWN>(x, Rprev, true, alpha_it, clip, synw, rowp, rowat);
+                    __syncthreads();
+                    __builtin_amdgcn_s_setprio(1);                                                 // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
+                    double o[2][2], s[2];                                                          // o[v] = the two other messages of owned column v in ascending check order (regular_own.h)
+#pragma unroll
+                    for (int v = 0; v < 2; v++)
+#pragma unroll
+                        for (int d = 0; d < 2; d++) o[v][d] = Rin(v, d);
+                    if (__builtin_expect(wave_class == kRegWaveNone, 1)) {
+                        asm volatile("");
+#pragma unroll
+                        for (int v = 0; v < 2; v++) s[v] = (o[v][0] + Rprev[v]) + o[v][1];         // kernels.py:316 with the own message second or first ("zero")
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < 2; v++) s[v] = (o[v][0] + (vlast[v] ? o[v][1] : Rprev[v])) + (vlast[v] ? Rprev[v] : o[v][1]);
+                    }
+#pragma unroll
+                    for (int v = 0; v < 2; v++) {
+                        // kernels.py:320.  A Monte-Carlo plan's prior is uniform (the closed form of iteration 0 above rests on it), so there the addend is the
+                        // scalar prior0: four VGPRs less across the loop.  A lane of no team adds prior0 where vprior holds 0.0; nothing reads its sum.
+                        Vown[v] = s[v] + (MC ? prior0 : vprior[v]);
+                        Vmine(v) = Vown[v];
+                    }
+                    __builtin_amdgcn_s_setprio(0);
+                    // the next pass's alpha, clamped (the table has max_iter entries): a uniform address, and the barrier below waits for LDS anyway
+                    alpha_it = alpha_tab[it + 1 < max_iter ? it + 1 : max_iter - 1];
+                    __syncthreads();
+                }
+            } else {
+            // the forms without a place table: the pass as it stands in the source since profiles/r18_bare_loop.txt, so that their code objects do not move
             for (; it < max_iter; it++) {
                 double x[CDEG];
                 unsigned ph = synw;
@@ -469,7 +536,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                 parity |= ph;
                 clean_messages<CDEG, NOWN>(x, Rprev, true, alpha_it, clip, synw, rowp, rowat);
                 __syncthreads();
-                __builtin_amdgcn_s_setprio(1);                                                     // the short LDS-only phase that releases the barrier goes first (measured: profiles/r18_bare_loop.txt)
+                __builtin_amdgcn_s_setprio(1);
                 double r[2][VDEG];
 #pragma unroll
                 for (int v = 0; v < 2; v++)
@@ -477,21 +544,21 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     for (int d = 0; d < VDEG - (OWN ? 1 : 0); d++) r[v][d] = Rin(v, d);
 #pragma unroll
                 for (int v = 0; v < 2; v++) {
-                    if (OWN) {                                                                     // r[v] = the three messages in ascending check order (regular_own.h)
+                    if (OWN) {
                         const double o2 = r[v][1], own = Rprev[v];
                         r[v][1] = vlast[v] ? o2 : own;
                         r[v][2] = vlast[v] ? own : o2;
                     }
                     double s = 0.0;                                                                // kernels.py:279
 #pragma unroll
-                    for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? r[v][0] : s + r[v][d];   // kernels.py:316, ascending check order; no leading 0.0 + (header comment, "zero")
+                    for (int d = 0; d < VDEG; d++) s = (ZEROFREE && d == 0) ? r[v][0] : s + r[v][d];   // kernels.py:316
                     Vown[v] = s + vprior[v];                                                       // kernels.py:320
                     Vmine(v) = Vown[v];
                 }
                 __builtin_amdgcn_s_setprio(0);
-                // the next pass's alpha, clamped (the table has max_iter entries): a uniform address, and the barrier below waits for LDS anyway
                 alpha_it = alpha_tab[it + 1 < max_iter ? it + 1 : max_iter - 1];
                 __syncthreads();
+            }
             }
             if (it == max_iter) {                                                                  // the syndrome test of values_{max_iter-1}
                 unsigned ph = synw;
@@ -656,15 +723,20 @@ static void fill_common(const qldpc_graph *g, const RegPlan &P, RegArgs &A, int6
 
 static std::atomic<int> g_place{1};       // qldpc_set_option("regular_place"): 1 = the ownership form takes its LDS addresses from the placement of regular_place.h, 0 = today's linear ones
 void regular_set_place(int v) { g_place = v; }
+static std::atomic<int> g_wave_classes{1};   // qldpc_set_option("regular_wave_classes"): 1 = a placed table is built from the min-last assignment under the thread order of regular_place_order
+void regular_set_wave_classes(int v) { g_wave_classes = v; }
 
 // The place table of the ownership form for this launch's workgroup shape, from the handle's cache (common.h); built and uploaded (a blocking copy) the
 // first time the handle meets the shape.  The placement where the option asks for it and the header has one, else the linear layout as a table: the
-// same kernel either way.
-static int regular_place_table(const qldpc_graph *g, const RegPlan &P, const int32_t **out) {
+// same kernel either way.  *own: the ownership table the place table was built from, which the launch must read with it -- the min-last assignment for a
+// table with class-uniform waves ("regular_wave_classes" 1 and a placement), the bank-model assignment for every other.
+static int regular_place_table(const qldpc_graph *g, const RegPlan &P, const int32_t **out, const int32_t **own) {
     *out = nullptr;
+    *own = g->d_regown;
     if (g->regown.size() != (size_t)g->m * kRegOwnWords) { set_error("regular min-sum: the graph handle has no ownership table"); return QLDPC_ERR_INVALID; }
     const int rst = regular_row_stride(kRegOwnCdeg);
     std::lock_guard<std::mutex> lk(g->mu_place);
+    // placed: 0 the linear layout, 1 the placement in the identity order, 2 the placement of the min-last table under a thread order
     auto find = [&](int placed, int offD) -> const qldpc_graph::PlaceEntry * {
         for (const auto &e : g->place_cache) if (e.S == P.S && e.block == (int)P.block && e.placed == placed && e.offD == offD) return &e;
         return nullptr;
@@ -678,8 +750,18 @@ static int regular_place_table(const qldpc_graph *g, const RegPlan &P, const int
     };
     std::vector<int32_t> rec;
     if (g_place.load()) {
+        if (g_wave_classes.load() && g->d_regown_minlast && g->regown_minlast.size() == g->regown.size()) {
+            if (!find(2, 0)) {
+                RegPlaceOrder order;                                              // "none" leaves rec empty: the entry records that, so the build is not repeated
+                if (regular_place_order(g->m, g->regown_minlast.data(), P, order)) regular_place_build(g->m, g->regown_minlast.data(), P, rst, rec, kRegPlaceOrderedMoves, &order);
+                const int rc = add(2, 0, rec);
+                if (rc != QLDPC_OK) return rc;
+            }
+            if (const auto *e = find(2, 0); e && e->dev.p) { *out = e->dev.as<int32_t>(); *own = g->d_regown_minlast; return QLDPC_OK; }
+        }
         if (!find(1, 0)) {
-            regular_place_build(g->m, g->regown.data(), P, rst, rec);          // "none" leaves rec empty: the entry records that, so the build is not repeated
+            rec.clear();
+            regular_place_build(g->m, g->regown.data(), P, rst, rec);
             const int rc = add(1, 0, rec);
             if (rc != QLDPC_OK) return rc;
         }
@@ -707,7 +789,7 @@ int minsum_regular_launch(const qldpc_graph *g, int64_t B, const int8_t *d_synd,
     if (!plan_regular(g, max_iter, P)) { set_error("graph is not regular (6,3)/(4,2)/(8,4)"); return QLDPC_ERR_UNSUPPORTED; }
     RegArgs A;
     fill_common(g, P, A, B, d_prior, max_iter, d_alpha, damping, clip, flags);
-    if (A.own && A.fixed && damping == 1.0 && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place); if (rc != QLDPC_OK) return rc; }      // the launches that take the ownership form (launch_reg2)
+    if (A.own && A.fixed && damping == 1.0 && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place, &A.own); if (rc != QLDPC_OK) return rc; }      // the launches that take the ownership form (launch_reg2)
     A.synd = d_synd; A.out_err = d_err; A.out_llr = d_llr; A.out_conv = d_conv; A.out_iter = d_iter;
     return dispatch_reg<false>(P, A, damping != 1.0, nanfree, persistent_grid(B, P.S), stream);
 }
@@ -721,7 +803,7 @@ int mc_regular_launch(const qldpc_graph *g, int64_t B, const double *d_prior, in
     if (!plan_regular(g, max_iter, P, d_shot_list ? g_list_shots : 0)) { set_error("graph is not regular (6,3)/(4,2)/(8,4)"); return QLDPC_ERR_UNSUPPORTED; }
     RegArgs A;
     fill_common(g, P, A, B, d_prior, max_iter, d_alpha, 1.0, clip, flags);
-    if (A.own && A.fixed && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place); if (rc != QLDPC_OK) return rc; }
+    if (A.own && A.fixed && nanfree && clip > 0.0) { const int rc = regular_place_table(g, P, &A.place, &A.own); if (rc != QLDPC_OK) return rc; }
     A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32); A.thr = thr; A.use_osd = use_osd; A.shot_begin = shot_begin;
     A.Lmask = d_Lmask; A.cold = reinterpret_cast<const RegCold *>(d_cold);
     A.shot_list = d_shot_list; A.shot_count = d_shot_count;

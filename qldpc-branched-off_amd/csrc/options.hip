@@ -31,6 +31,9 @@ extern std::atomic<int> g_opt_wave_cpl, g_opt_wave_rst, g_opt_wave_grid;      //
 //                         check is the variable thread of two of its own columns, 0 = the body without ownership on every graph
 //   "regular_place"       read at a fixed-work launch of that form: 1 (default) = the LDS addresses of posteriors and messages come from the placement of regular_place.h (edge
 //                         colouring per workgroup shape, built at the handle's first launch with the shape), 0 = today's linear addresses through the same kernel
+//   "regular_wave_classes" read with "regular_place" 1: 1 (default) = the placed table is built from the min-last assignment (regular_own.h) under a thread order that
+//                         gives whole waves one class of `last` bits (regular_place.h), and such a wave runs a copy of the fixed-work loop without selects; 0 = the
+//                         bank-model assignment in the identity order, every wave on the loop with selects.  "regular_place" 0 implies 0
 //   "regular_own_search"  read when a graph handle is created: 1 (default) = of the valid ownership assignments the one the LDS bank model prices lowest
 //                         (regular_own.h: translation-invariant candidates, else a polished matching), 0 = the first matching found
 // experiments build only (libqldpc_hip_experiments.so):
@@ -47,6 +50,7 @@ QLDPC_EXPORT int qldpc_set_option(const char *name, int value) {
     if (!std::strcmp(name, "regular_own_search")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_own_search: 0 or 1"); qldpc::g_opt_own_search = value; return QLDPC_OK; }
     if (!std::strcmp(name, "regular_own_edges")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_own_edges: 0 or 1"); qldpc::regular_set_own_edges(value); return QLDPC_OK; }
     if (!std::strcmp(name, "regular_place")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_place: 0 or 1"); qldpc::regular_set_place(value); return QLDPC_OK; }
+    if (!std::strcmp(name, "regular_wave_classes")) { QLDPC_REQUIRE(value == 0 || value == 1, "regular_wave_classes: 0 or 1"); qldpc::regular_set_wave_classes(value); return QLDPC_OK; }
     const bool wave_opt =!std::strcmp(name, "regular_kernel") || !std::strcmp(name, "wave_cpl") || !std::strcmp(name, "wave_rst") || !std::strcmp(name, "wave_grid");
 #ifdef QLDPC_EXPERIMENTS
     if (!std::strcmp(name, "regular_kernel")) { QLDPC_REQUIRE(value >= 0 && value <= 2, "regular_kernel: 0, 1 or 2"); qldpc::g_opt_kernel = value; return QLDPC_OK; }

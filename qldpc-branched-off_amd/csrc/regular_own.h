@@ -31,6 +31,14 @@
 //       s_B" is a perfect assignment for each of the 3 x 3 pairs, and under it every gather address is a torus shift of the lane index;
 //   (c) on graphs without (b): (a) polished by rotations of ownership along random alternating cycles, a fixed number of evaluations.
 // The result is a function of the CSR alone: integer arithmetic, a PRNG of this header with a constant seed, no clock.
+//
+// A SECOND assignment, regular_own_assign_minlast, serves the fixed-work form on a placed table (regular_place.h).  There every gather address comes from an
+// edge colouring that is conflict-free for any assignment, so the choice is free again and goes to the other cost an assignment has: the two selects per
+// owned column that put the own message into its place, needed only where `last` differs between the lanes of a wave.  It owns the fewest last edges a
+// perfect assignment can (min-cost flow, cost 1 per owned last edge: 7 / 11 / 22 / 9 / 9 on the Hx matrices of bb72 / bb144 / bb288 / bb90 / bb108), and a
+// check that owns exactly one holds it as column v = 1, so a check is of one of three classes: none, one, both (word [14] = 0, 2, 3).  The graph handle
+// keeps both tables; the assignment above stays, byte for byte, for every launch that reads no placed table (early exit, the linear layout as a table,
+// qldpc_set_option "regular_wave_classes" 0).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -160,7 +168,8 @@ inline bool regular_own_kuhn(const RegOwnGraph &G, std::vector<int> &owner) {
 }
 
 // The records of an assignment.  False (tab empty) unless it is perfect: every column owned by one of its own checks, every check owning two.
-inline bool regular_own_records(const RegOwnGraph &G, const std::vector<int> &owner, std::vector<int32_t> &tab) {
+// last_second: a check that owns exactly one `last` column holds it as its column v = 1 instead of the two in ascending order (the min-last table below).
+inline bool regular_own_records(const RegOwnGraph &G, const std::vector<int> &owner, std::vector<int32_t> &tab, bool last_second = false) {
     const int m = G.m, n = G.n, rst = G.rst;
     const int32_t *indptr = G.indptr, *indices = G.indices;
     tab.clear();
@@ -175,6 +184,11 @@ inline bool regular_own_records(const RegOwnGraph &G, const std::vector<int> &ow
         if (h[0] < 0) h[0] = j; else if (h[1] < 0) h[1] = j; else return false;
     }
     for (int i = 0; i < m; i++) if (held[(size_t)i * kRegOwnOwned] < 0 || held[(size_t)i * kRegOwnOwned + 1] < 0) return false;
+    if (last_second)
+        for (int i = 0; i < m; i++) {
+            int *h = &held[(size_t)i * kRegOwnOwned];
+            if (G.rows_of(h[0])[kRegOwnVdeg - 1] == i && G.rows_of(h[1])[kRegOwnVdeg - 1] != i) std::swap(h[0], h[1]);
+        }
     // columns and slots first, the offsets need every row's slots
     tab.assign((size_t)m * kRegOwnWords, 0);
     for (int i = 0; i < m; i++) {
@@ -317,6 +331,82 @@ inline bool regular_own_polish(const RegOwnGraph &G, const RegPlan &P, std::vect
     }
     owner = best;
     return best_cost < cost0;
+}
+
+// The min-last assignment, for the fixed-work form on a place table (regular_place.h), where bank conflicts no longer depend on who owns what: the
+// perfect assignment that owns the FEWEST `last` edges (the owning check is the highest of the column's three).  A thread whose two `last` bits are
+// clear adds (o1 + own) + o2 for both columns without a select, and regular_place.h deals such threads into waves of their own.  Min-cost flow by
+// successive shortest augmenting paths: columns in ascending order, each along the cheapest alternating path to a check with a free place, cost 1 per
+// owned last edge, Dijkstra on reduced costs over the n + m nodes (a binary heap of (distance, node), so ties go to the lowest node index), potentials kept across augmentations.
+// Integer arithmetic only: a function of the CSR alone.
+inline bool regular_own_minlast(const RegOwnGraph &G, std::vector<int> &owner) {
+    const int m = G.m, n = G.n, N = n + m, INF = 1 << 29;
+    owner.assign(n, -1);
+    std::vector<int> held((size_t)m * kRegOwnOwned, -1), pot(N, 0), dist(N), from(N);
+    std::vector<char> fin(N);
+    std::vector<std::pair<int, int>> heap;
+    auto push = [&](int d, int x) { heap.emplace_back(d, x); std::push_heap(heap.begin(), heap.end(), std::greater<std::pair<int, int>>()); };
+    auto cost = [&](int j, int i) { return G.rows_of(j)[kRegOwnVdeg - 1] == i ? 1 : 0; };
+    for (int j0 = 0; j0 < n; j0++) {
+        std::fill(dist.begin(), dist.end(), INF); std::fill(fin.begin(), fin.end(), 0); std::fill(from.begin(), from.end(), -1);
+        dist[j0] = 0;
+        int target = -1;
+        heap.clear();
+        heap.emplace_back(0, j0);
+        while (!heap.empty()) {
+            std::pop_heap(heap.begin(), heap.end(), std::greater<std::pair<int, int>>());       // the smallest (distance, node)
+            const int du = heap.back().first, u = heap.back().second;
+            heap.pop_back();
+            if (fin[u] || du != dist[u]) continue;
+            fin[u] = 1;
+            if (u < n) {                                                             // a column: to each of its checks that does not hold it
+                for (int d = 0; d < kRegOwnVdeg; d++) {
+                    const int i = G.rows_of(u)[d];
+                    if (owner[u] == i || fin[n + i]) continue;
+                    const int w = dist[u] + cost(u, i) + pot[u] - pot[n + i];
+                    if (w < dist[n + i]) { dist[n + i] = w; from[n + i] = u; push(w, n + i); }
+                }
+            } else {                                                                 // a check: done if it has a free place, else back along a column it holds
+                const int i = u - n, *h = &held[(size_t)i * kRegOwnOwned];
+                if (h[0] < 0 || h[1] < 0) { target = u; break; }
+                for (int t = 0; t < kRegOwnOwned; t++) {
+                    const int j = h[t];
+                    if (fin[j]) continue;
+                    const int w = dist[u] - cost(j, i) + pot[u] - pot[j];
+                    if (w < dist[j]) { dist[j] = w; from[j] = u; push(w, j); }
+                }
+            }
+        }
+        if (target < 0) return false;
+        for (int x = 0; x < N; x++) pot[x] += std::min(dist[x], dist[target]);
+        for (int i = target - n;;) {                                                 // along the path backwards: column j moves to check i
+            const int j = from[n + i], prev = owner[j];
+            int *h = &held[(size_t)i * kRegOwnOwned];
+            h[h[0] < 0 ? 0 : 1] = j;
+            owner[j] = i;
+            if (prev < 0) break;                                                     // j0
+            int *hp = &held[(size_t)prev * kRegOwnOwned];
+            hp[hp[0] == j ? 0 : 1] = -1;
+            i = prev;
+        }
+    }
+    return true;
+}
+
+// Owned last edges of a table, and the class of check i under it: 0 none, 1 one (its column v = 1), 2 both.
+inline int regular_own_class(const int32_t *tab, int i) {
+    const int l = tab[(size_t)i * kRegOwnWords + kRegOwnLast] & 3;
+    return l == 0 ? 0 : l == 3 ? 2 : 1;
+}
+
+// The table of the min-last assignment in canonical order (a check owning exactly one last edge has it as column v = 1, so word [14] is 0, 2 or 3).
+// Returns false and leaves tab empty exactly where regular_own_assign does.
+inline bool regular_own_assign_minlast(int m, int n, const int32_t *indptr, const int32_t *indices, int rst, std::vector<int32_t> &tab) {
+    tab.clear();
+    RegOwnGraph G;
+    std::vector<int> owner;
+    if (!regular_own_graph(m, n, indptr, indices, rst, G) || !regular_own_minlast(G, owner) || !regular_own_records(G, owner, tab, true)) { tab.clear(); return false; }
+    return true;
 }
 
 // CSR of m checks over n columns.  Returns false ("none": the launch takes the body without ownership) unless the graph is (6,3)-regular with

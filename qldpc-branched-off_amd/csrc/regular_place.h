@@ -32,7 +32,12 @@
 //   [8,9]     where the thread stores the posteriors of its owned columns 0 and 1
 //   [10..13]  where it stores the messages of the kernel's edges 2 .. 5
 //   [14]      nibble k: the edge of the ownership record (2 .. 5, CSR order) that the kernel's edge 2 + k is; 0 for a lane of no team
-//   [15]      0
+//   [15]      0 in the identity order (thread t = slot * TS + member, the lanes of no team last).  Under a thread order (regular_place_order, below): bit 30,
+//             the class of the thread's wave in bits 24 .. 25 (kRegWave*), its slot in bits 12 .. 23, its member in bits 0 .. 11
+// Thread order.  Nothing requires thread t to be (t / TS, t % TS): every address is in the record, and slot and member are only values.  So the S * m
+// (slot, check) items are dealt to the threads by the class of the check under the min-last ownership table (regular_own.h): whole waves of checks that own
+// no last edge run the bare passes without selects (minsum_regular.hip).  The colourings below take an item's lane groups from the thread it is dealt to,
+// so they are as exact under an order as without one; regular_place_cost prices records in thread order and needs no change.
 // The table is a function of (ownership table, S, block) alone: integer arithmetic, a PRNG of this header with a constant seed, a fixed number of moves.
 #pragma once
 #include <algorithm>
@@ -51,6 +56,9 @@ static const int kRegPlaceStored = kRegOwnCdeg - kRegOwnOwned;      // 4
 // Kempe moves tried per table.  On the Hx matrices of bb72 / bb144 / bb288 the cycles above 6 per store instruction are 0 to 1 per workgroup from 4000
 // moves on and neither figure moves between 8000 and 20000 (profiles/r24_place.txt); a move prices 2 * block items, 8000 of them take about 15 ms.
 static const int kRegPlaceKempeMoves = 8000;
+// Under a thread order (regular_place_order) the items a 16-lane group stores no longer sit next to each other in the graph and the walk needs more: 24000
+// moves, thread swaps inside a 32-lane group among them, and up to four walks (regular_place_build; profiles/r27_wave_classes.txt has what each bought).
+static const int kRegPlaceOrderedMoves = 24000, kRegPlaceSwapEvery = 4, kRegPlaceOrderedStarts = 4, kRegPlaceRestartBelow = 4;
 #ifndef QLDPC_PLACE_THRESHOLD
 #define QLDPC_PLACE_THRESHOLD 4
 #endif
@@ -172,15 +180,79 @@ struct RegPlaceColouring {
     }
 };
 
-// The placement of one workgroup: P.block records (header comment) from the ownership table of regular_own_assign.  False ("none", rec empty) where the
-// arrays do not fit in [0, offV + S * n * 8), or the table is not one of m checks that own two columns each.
-inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int rst, std::vector<int32_t> &rec, int moves = kRegPlaceKempeMoves) {
+// ---- the thread order: which thread of the block is (slot, check), and the class of every wave
+// Word [15] of a record built with an order: bit 30 set, the wave's class in bits 24 .. 25, the thread's slot in bits 12 .. 23 and its member (= check) in
+// bits 0 .. 11; a lane of no team has slot = S.  Word [15] == 0 is the identity order, thread t = slot * TS + member, every wave mixed.
+enum { kRegWaveMixed = 0, kRegWaveNone = 1, kRegWaveOne = 2, kRegWaveBoth = 3 };
+static const int kRegPlaceOrder = 15, kRegPlaceOrdered = 1 << 30;
+inline int32_t regular_place_pack(int wave_class, int slot, int member) { return kRegPlaceOrdered | (wave_class << 24) | (slot << 12) | member; }
+inline int regular_place_wave_class(int32_t w) { return (w >> 24) & 3; }
+inline int regular_place_slot(int32_t w) { return (w >> 12) & 0xfff; }
+inline int regular_place_member(int32_t w) { return w & 0xfff; }
+
+struct RegPlaceOrder {
+    std::vector<int> thread_of;      // [S * m]: the thread of item slot * m + check
+    std::vector<int> spare;          // the block - S * m threads of no team, ascending
+    std::vector<int> wave_class;     // [block / 64]: kRegWave*
+};
+
+// Deals the S * m (slot, check) items of a workgroup to its threads so that as many waves as possible hold checks of ONE class of the ownership table
+// (regular_own_class: none, one or both of the thread's owned columns `last`): such a wave runs a copy of the fixed-work loop without selects
+// (minsum_regular.hip).  A lane of no team computes nothing that is read, so it completes any wave.  Per class, in the order none, one, both: its full
+// waves of 64 items (slot-major, checks ascending).  Then the classes' remainders, the one that needs the fewest spare lanes first, each as a wave of its
+// own while the spare lanes last.  What is left shares the mixed waves at the end of the block.  Integer arithmetic, a function of (table, S, block).
+inline bool regular_place_order(int m, const int32_t *own, const RegPlan &P, RegPlaceOrder &O) {
+    const int S = P.S, block = (int)P.block, team = S * m;
+    O.thread_of.clear(); O.spare.clear(); O.wave_class.clear();
+    if (m <= 0 || S <= 0 || P.TS != m || block % 64 || block < team || m > 0xfff || S >= 0xfff) return false;
+    std::vector<int> items[3];
+    for (int s = 0; s < S; s++) for (int i = 0; i < m; i++) items[regular_own_class(own, i)].push_back(s * m + i);
+    O.thread_of.assign(team, -1);
+    int t = 0, spare = block - team;
+    size_t at[3] = {0, 0, 0};
+    const int cls_of[3] = {kRegWaveNone, kRegWaveOne, kRegWaveBoth};
+    auto put = [&](int c, int count) { for (int x = 0; x < count; x++) O.thread_of[items[c][at[c]++]] = t++; };
+    auto idle = [&](int count) { for (int x = 0; x < count; x++) O.spare.push_back(t++); };
+    for (int c = 0; c < 3; c++)
+        for (; items[c].size() - at[c] >= 64;) { put(c, 64); O.wave_class.push_back(cls_of[c]); }
+    for (bool more = true; more;) {
+        int pick = -1;
+        for (int c = 0; c < 3; c++) {
+            const int left = (int)(items[c].size() - at[c]);
+            if (left > 0 && 64 - left <= spare && (pick < 0 || left > (int)(items[pick].size() - at[pick]))) pick = c;
+        }
+        more = pick >= 0;
+        if (more) { const int left = (int)(items[pick].size() - at[pick]); put(pick, left); idle(64 - left); spare -= 64 - left; O.wave_class.push_back(cls_of[pick]); }
+    }
+    for (int c = 0; c < 3; c++) put(c, (int)(items[c].size() - at[c]));
+    idle(spare);
+    if (t != block) return false;
+    while ((int)O.wave_class.size() < block / 64) O.wave_class.push_back(kRegWaveMixed);
+    // a "mixed" wave that happens to hold one class only (with or without spare lanes) is labelled by it
+    std::vector<int> seen(block / 64, 0);
+    for (int s = 0; s < S; s++) for (int i = 0; i < m; i++) seen[O.thread_of[s * m + i] / 64] |= 1 << regular_own_class(own, i);
+    for (int w = 0; w < block / 64; w++)
+        if (O.wave_class[w] == kRegWaveMixed && (seen[w] == 1 || seen[w] == 2 || seen[w] == 4)) O.wave_class[w] = cls_of[seen[w] == 1 ? 0 : seen[w] == 2 ? 1 : 2];
+    return true;
+}
+
+// The placement of one workgroup: P.block records (header comment) from an ownership table (regular_own_assign, or regular_own_assign_minlast with an
+// order).  False ("none", rec empty) where the arrays do not fit in [0, offV + S * n * 8), or the table is not one of m checks that own two columns each.
+// order: the thread of every (slot, check) (regular_place_order); NULL = thread slot * m + check, the lanes of no team last, word [15] = 0.  The lane
+// groups of the bank model are consecutive THREADS either way (32 for a gather, 16 for a store): an item's groups are those of the thread it is dealt to.
+inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int rst, std::vector<int32_t> &rec, int moves = kRegPlaceKempeMoves,
+                                RegPlaceOrder *order = nullptr) {
     rec.clear();
     const int n = 2 * m, S = P.S, block = (int)P.block;
     if (m <= 0 || S <= 0 || P.TS != m || block % 64 || block < S * m || rst < kRegPlaceStored) return false;
+    if (order && ((int)order->thread_of.size() != S * m || (int)order->spare.size() != block - S * m || (int)order->wave_class.size() != block / 64)) return false;
     const int nwin = block / 32, n16 = block / 16, msg_words = 4 * block, post_base = msg_words, post_words = 2 * block;
     if ((long long)(msg_words + post_words) * 8 > (long long)P.offV + (long long)S * n * 8) return false;        // the fit: both arrays inside R and V
-    auto lane = [&](int s, int i) { return s * m + i; };
+    RegPlaceOrder ord;                                                                                             // the order as the swaps below leave it
+    if (order) ord = *order;
+    auto lane = [&](int s, int i) { return order ? ord.thread_of[(size_t)s * m + i] : s * m + i; };
+    auto spare_lane = [&](int d) { return order ? ord.spare[d] : S * m + d; };                                     // the d-th lane of no team
+    const int nspare = block - S * m;
 
     // ---- the two readers of every posterior item g = owner + m * v, and an Euler orientation of the reader multigraph
     std::vector<int> rd_check((size_t)n * 2, -1), rd_edge((size_t)n * 2, -1);
@@ -222,9 +294,12 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
 
     rec.assign((size_t)block * kRegPlaceWords, 0);
     auto word = [&](int t, int w) -> int32_t & { return rec[(size_t)t * kRegPlaceWords + w]; };
-    for (int s = 0; s < S; s++)
-        for (int i = 0; i < m; i++)
-            for (int q = 0; q < kRegPlaceStored; q++) word(lane(s, i), kRegPlaceEdges) |= (kRegOwnOwned + q) << (4 * pos[(size_t)i * kRegPlaceStored + q]);
+    auto edges_word = [&]() {
+        for (int s = 0; s < S; s++)
+            for (int i = 0; i < m; i++)
+                for (int q = 0; q < kRegPlaceStored; q++) word(lane(s, i), kRegPlaceEdges) |= (kRegOwnOwned + q) << (4 * pos[(size_t)i * kRegPlaceStored + q]);
+    };
+    if (!order) edges_word();                                                            // under an order: once the swaps below have settled who sits where
 
     // ---- posteriors: 32 colours, then Kempe moves for the two stores
     {
@@ -237,8 +312,8 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
                 items.push_back({lane(s, u), pos[(size_t)u * kRegPlaceStored + rd_edge[(size_t)g * 2 + at]], lane(s, w),
                                  pos[(size_t)w * kRegPlaceStored + rd_edge[(size_t)g * 2 + 1 - at]] - 2, lane(s, g % m), g / m});
             }
-        for (int t = S * m; t < block; t++)
-            for (int v = 0; v < kRegOwnOwned; v++) items.push_back({t, v, t, v, t, v});      // a lane of no team: gathers 0 and 2 read its item 0, 1 and 3 its item 1
+        for (int d = 0; d < nspare; d++)
+            for (int v = 0, t = spare_lane(d); v < kRegOwnOwned; v++) items.push_back({t, v, t, v, t, v});      // a lane of no team: gathers 0 and 2 read its item 0, 1 and 3 its item 1
         for (const Item &it : items) K.edges.emplace_back(it.tail_k * nwin + it.tail_lane / 32, it.head_k * nwin + it.head_lane / 32);
         if (!K.colour(2 * nwin, 2 * nwin, 32)) { rec.clear(); return false; }
         const int ni = (int)items.size();
@@ -262,12 +337,54 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
         };
         // threshold accepting, as regular_own_polish: a move may raise the score by a bound that falls linearly to zero (greedy acceptance stalls within
         // 2000 moves); the best state seen is kept
+        // Under an order every kRegPlaceSwapEvery-th move is a SWAP instead.  A ds_read_b64 serves 32-lane groups and a ds_write_b64 16-lane groups, and who
+        // sits on which thread of a wave is free: two threads in different halves of one 32-lane group change places.  Every gather keeps its group, so the
+        // colouring stays proper as it is; only the four posterior items the two threads store move to the other store group.  A swap is kept if the score
+        // does not rise.  And the walk is run again from the Koenig colouring with another seed, up to kRegPlaceOrderedStarts times, while the best state
+        // has 1 .. kRegPlaceRestartBelow cycles above 6 left: the walks end within a few cycles of each other, and on the BB matrices one of the first
+        // four ends at none (profiles/r27_wave_classes.txt).  The identity order takes its one walk without swaps, as it always did.
+        std::vector<int> at_pos(order ? block : 0), who(order ? block : 0), stores(order ? (size_t)block * 2 : 0, -1);      // at_pos[thread as dealt] = where it sits now; who = the inverse
+        for (int t = 0; t < (int)at_pos.size(); t++) at_pos[t] = who[t] = t;
+        if (order) for (int e = 0; e < ni; e++) stores[(size_t)items[e].store_lane * 2 + items[e].v] = e;
+        auto move_thread = [&](int t, int to) {
+            for (int v = 0; v < 2; v++) {
+                const int e = stores[(size_t)t * 2 + v];
+                if (e < 0) continue;
+                cnt[(size_t)grp[e] * 16 + (K.col[e] & 15)]--;
+                grp[e] = items[e].v * n16 + to / 16;
+                cnt[(size_t)grp[e] * 16 + (K.col[e] & 15)]++;
+            }
+            at_pos[t] = to; who[to] = t;
+        };
         long long cur = score(), best = cur;
         RegPlaceColouring best_K = K;
+        std::vector<int> best_at = at_pos;
+        const RegPlaceColouring K0 = K;
+        const std::vector<int> cnt0 = cnt, grp0 = grp;
+        const int starts = order ? kRegPlaceOrderedStarts : 1;
+        for (int st = 0; st < starts; st++) {
+        if (st) {
+            if (best < 100000 || best > 100000LL * kRegPlaceRestartBelow + 99999) break;
+            K = K0; cnt = cnt0; grp = grp0; cur = score();
+            for (int t = 0; t < block; t++) at_pos[t] = who[t] = t;
+            std::fill(mark.begin(), mark.end(), -1);
+            state = 0x9e3779b97f4a7c15ull * (uint64_t)(2 * st + 1);
+        }
         for (int mv = 0; mv < moves; mv++) {
             bad.clear();
             for (int e = 0; e < ni; e++) if (cnt[(size_t)grp[e] * 16 + (K.col[e] & 15)] > 1) bad.push_back(e);
             if (bad.empty()) break;
+            if (order && mv % kRegPlaceSwapEvery == kRegPlaceSwapEvery - 1) {
+                const int e = bad[rnd((uint32_t)bad.size())], ta = items[e].store_lane, pa = at_pos[ta];
+                const int pb = (pa & ~31) | ((pa & 16) ^ 16) | (int)rnd(16), tb = who[pb];
+                move_thread(ta, pb); move_thread(tb, pa);
+                const long long now = score();
+                if (now <= cur) {
+                    cur = now;
+                    if (cur < best) { best = cur; best_K = K; best_at = at_pos; }
+                } else { move_thread(ta, pa); move_thread(tb, pb); }
+                continue;
+            }
             const int e = bad[rnd((uint32_t)bad.size())], a = K.col[e];
             int free_c[32], nfree = 0;
             for (int c = 0; c < 32; c++) if (c != a && cnt[(size_t)grp[e] * 16 + (c & 15)] == 0) free_c[nfree++] = c;
@@ -277,11 +394,20 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
             const long long now = score();
             if (now <= cur + (long long)kRegPlaceThreshold * (moves - mv) / moves) {
                 cur = now;
-                if (cur < best) { best = cur; best_K = K; }
+                if (cur < best) { best = cur; best_K = K; best_at = at_pos; }
             } else { recount(comp, -1); K.flip(comp, a, b); recount(comp, +1); }
         }
-        if (best < cur) K = best_K;
+        }
+        if (best < cur || starts > 1) { K = best_K; at_pos = best_at; }
         if (!K.proper()) { rec.clear(); return false; }
+        if (order) {
+            // the threads as the swaps of the walk left them; the message colouring below is built on the result
+            for (Item &it : items) { it.tail_lane = at_pos[it.tail_lane]; it.head_lane = at_pos[it.head_lane]; it.store_lane = at_pos[it.store_lane]; }
+            for (int &t : ord.thread_of) t = at_pos[t];
+            for (int &t : ord.spare) t = at_pos[t];
+            std::sort(ord.spare.begin(), ord.spare.end());
+            edges_word();
+        }
         std::vector<int> rank(32, 0);
         for (int e = 0; e < ni; e++) {
             const int c = K.col[e], a = post_base + 32 * rank[c]++ + c;
@@ -305,8 +431,8 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
                     if (off < 0 || r >= m || q >= kRegPlaceStored) { rec.clear(); return false; }
                     items.push_back({lane(s, i), vd, lane(s, r), pos[(size_t)r * kRegPlaceStored + q]});
                 }
-        for (int t = S * m; t < block; t++)
-            for (int k = 0; k < 4; k++) items.push_back({t, k, t, k});
+        for (int d = 0; d < nspare; d++)
+            for (int k = 0, t = spare_lane(d); k < 4; k++) items.push_back({t, k, t, k});
         for (const Item &it : items) K.edges.emplace_back(it.stream * n16 + it.read_lane / 16, it.t * n16 + it.store_lane / 16);
         if (!K.colour(4 * n16, 4 * n16, 16) || !K.proper()) { rec.clear(); return false; }
         std::vector<int> rank(32, 0);
@@ -317,6 +443,12 @@ inline bool regular_place_build(int m, const int32_t *own, const RegPlan &P, int
             word(it.read_lane, kRegPlaceMsgGather + it.stream) = a;
             word(it.store_lane, kRegPlaceMsgStore + it.t) = a;
         }
+    }
+    if (order) {
+        for (int s = 0; s < S; s++)
+            for (int i = 0; i < m; i++) { const int t = lane(s, i); word(t, kRegPlaceOrder) = regular_place_pack(ord.wave_class[t / 64], s, i); }
+        for (int d = 0; d < nspare; d++) { const int t = spare_lane(d); word(t, kRegPlaceOrder) = regular_place_pack(ord.wave_class[t / 64], S, 0); }
+        *order = ord;                                                                   // the caller's order names the threads as the records do
     }
     return true;
 }

@@ -227,6 +227,43 @@ def cfg_loops(ins, labels, branches):
     return out
 
 
+def loop_paths(ins, labels, branches, idx, limit=16):
+    """The simple paths once round a loop (header back to header) as lists of instruction indices, for a loop of a few blocks: the fixed-work regular
+    kernel's steady-state loop is no longer one block -- a scalar branch picks one of two forms of the variable sums per wave -- and what a wave issues
+    per pass is one path, not the loop's text.  [] where the loop has more than `limit` paths."""
+    inside = set(idx)
+    br = dict(branches)
+    starts = sorted({idx[0]} | {labels[l] for l in labels if labels[l] in inside} | {i + 1 for i in br if i in inside and i + 1 in inside})
+    end_of = {st: (starts[k + 1] if k + 1 < len(starts) else idx[-1] + 1) - 1 for k, st in enumerate(starts)}
+    for st in starts:                                     # a block ends where the loop's instruction indices stop being contiguous, too
+        e = st
+        while e + 1 in inside and e + 1 <= end_of[st]:
+            e += 1
+        end_of[st] = e
+
+    def succ(st):
+        en, out = end_of[st], []
+        if en in br and br[en] in labels:
+            out.append(labels[br[en]])
+        if not ins[en][1].startswith(("s_branch", "s_endpgm", "s_setpc")):
+            out.append(en + 1)
+        return out
+    head, paths, stack = idx[0], [], [(idx[0], [])]
+    while stack:
+        st, seen = stack.pop()
+        if st not in end_of or st in seen:
+            continue
+        seen = seen + [st]
+        for nx in succ(st):
+            if nx == head:
+                paths.append([i for b in seen for i in range(b, end_of[b] + 1)])
+            elif nx in inside:
+                stack.append((nx, seen))
+        if len(paths) > limit:
+            return []
+    return paths
+
+
 def mix_idx(ins, idx):
     cnt = {}
     for i in idx:
@@ -273,7 +310,13 @@ def analyse(src, pattern, loop_pick=None):
                              "valu": sum(k for cl, k in c.items() if cl.startswith("valu")),
                              "scratch": sum(1 for o in ops if o.startswith("scratch_")),
                              "xlane": sum(1 for o in ops if o.startswith(("v_readlane", "v_writelane"))),
-                             "ops": {o: ops.count(o) for o in sorted(set(ops))}})
+                             "ops": {o: ops.count(o) for o in sorted(set(ops))},
+                             "paths": [{"instructions": len(p), "mix": mix_idx(ins, p), "issue_cycles": weighted(mix_idx(ins, p)),
+                                        "valu": sum(k for cl, k in mix_idx(ins, p).items() if cl.startswith("valu")),
+                                        "selects": sum(1 for i in p if ins[i][1].startswith("v_cndmask")),
+                                        "lds": sum(1 for i in p if ins[i][1].startswith("ds_")),
+                                        "branches": sum(1 for i in p if ins[i][1].startswith(("s_cbranch", "s_branch")))}
+                                       for p in (loop_paths(ins, labels, branches, idx) if len(body) <= 12 else [])]})
     if res["loops"]:
         inner = [l for l in res["loops"] if l["innermost"]]
         res["steady_state"] = res["loops"][loop_pick] if loop_pick is not None else max(inner, key=lambda l: l["valu"])
@@ -289,7 +332,10 @@ def analyse(src, pattern, loop_pick=None):
 _REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", "minsum_f64.h", "regular_own.h", "regular_place.h"]      # regular_own.h, regular_place.h: host code, listed for the record layouts the kernel indexes with
 RECORDED = {
     # the seventh argument: OWN, two edges of each check inside its thread (the form bench.py's bb144 graph takes by default)
-    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true, true>", "straight", _REGULAR),
+    # "bare": the loop that holds s_setprio -- the passes a workgroup runs once its shots are frozen.  Under a place table a wave takes one of two paths
+    # through it per pass, by its class (csrc/regular_place.h); the entry holds the mix of the path WITHOUT selects, which seven of the eight waves of a bb144
+    # workgroup take, and lists every path under "paths"
+    "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true, true>", "bare", _REGULAR),
     "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "clocks.h", "mc_common.h"]),
     "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<true>", "whole", ["minsum_wg2.hip", "clocks.h", "minsum_f64.h"]),      # <true>: the shipped circ144 matrices have degree-1 checks
     "circ144_osd": ("osd_gj.hip", "osd0_gj_kernel<true>", "whole", ["osd_gj.hip", "osd_gj.h", "osd_common.h", "clocks.h", "osd_plan.h"]),
@@ -312,7 +358,21 @@ def record(path):
         r = analyse(src, pat)
         if which == "straight":
             r["steady_state"] = max((l for l in r["loops"] if l["innermost"] and l["blocks"] == 1), key=lambda l: l["valu"])
-        if which == "whole" or "steady_state" not in r:
+        paths = None
+        if which == "bare":
+            bare = [l for l in r["loops"] if l["innermost"] and "s_setprio" in l["ops"] and l["paths"]]
+            if len(bare) != 1:
+                sys.exit(f"{key}: {len(bare)} innermost loops hold s_setprio and have enumerable paths, expected the one bare loop")
+            # the compiler keeps the arm without selects behind a flag that is constant on that route, so of the static paths two cannot be taken: the one
+            # that skips both arms and the one that runs both.  A wave runs exactly one arm: the longest path without selects, or the shortest with them.
+            plain = max((p for p in bare[0]["paths"] if not p["selects"]), key=lambda p: p["valu"])
+            picked = min((p for p in bare[0]["paths"] if p["selects"]), key=lambda p: p["valu"])
+            r["steady_state"], paths = bare[0], [dict(plain, arm="no last edge in the wave: no select"), dict(picked, arm="any other wave: two selects per owned column")]
+        if paths:
+            m = paths[0]["mix"]
+            scope = (f"steady-state loop [{r['steady_state']['first']}..{r['steady_state']['last']}], {r['steady_state']['blocks']} blocks (static): the path of a "
+                     f"wave whose checks own no last edge ({paths[0]['selects']} selects; 7 of the 8 waves of a bb144 workgroup); the other path is under 'paths'")
+        elif which == "whole" or "steady_state" not in r:
             m, scope = r["whole"], "whole kernel (static)"
         else:
             m, scope = r["steady_state"]["mix"], f"steady-state loop [{r['steady_state']['first']}..{r['steady_state']['last']}] (static)"
@@ -321,6 +381,9 @@ def record(path):
         out["entries"][key] = {"kernel": r["kernel"], "scope": scope, "mix": m, "valu_instructions": valu, "valu_issue_cycles": cyc,
                                "cycles_per_valu_instruction": round(cyc / max(valu, 1), 4), "code_object": r["meta"],
                                "sources": files, "source_digest": digest(files)}
+        if paths:
+            out["entries"][key]["paths"] = paths
+            out["entries"][key]["scratch_in_loop"] = r["steady_state"]["scratch"]
         print(f"{key:22s} {r['kernel'][:60]:60s} {scope:46s} VALU {valu:5d}  issue cycles {cyc:6d}  -> {cyc / max(valu, 1):.3f} cycles per instruction; {r['meta']}")
     with open(path, "w") as fh:
         json.dump(out, fh, indent=1)
@@ -348,6 +411,8 @@ def main():
         star = "*" if l is r.get("steady_state") else " "
         print(f" {star}loop {i} [{l['first']}..{l['last']}, {l['blocks']} blocks, {l['instructions']} instructions] {'innermost' if l['innermost'] else 'outer    '} "
               f"scratch ops {l['scratch']}, lane moves {l['xlane']}: {describe(l['mix'])}")
+        for k, pth in enumerate(l["paths"] if len(l["paths"]) > 1 else []):
+            print(f"      path {k}: {pth['instructions']} instructions, VALU {pth['valu']} (issue cycles {pth['issue_cycles']}), selects {pth['selects']}, LDS {pth['lds']}, branches {pth['branches']}")
     if a.ops and r.get("steady_state"):
         print("  steady-state loop, instructions by mnemonic:")
         for o, k in sorted(r["steady_state"]["ops"].items(), key=lambda kv: -kv[1]):
