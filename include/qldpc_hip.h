@@ -51,6 +51,7 @@
  *        qldpc_circuit_plan_use_correlated
  *        additive, same version: heralded-erasure noise and erasure-aware decoding on a circuit plan, qldpc_erasure_priors[_dev],
  *        qldpc_circuit_plan_use_erasure_noise, _use_erasure_aware and _sample_erasures, QLDPC_ERASURE_H_INF
+ *        additive, same version: per-class, biased Pauli noise on a circuit plan, qldpc_noise_model and qldpc_circuit_plan_use_noise_model
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -879,6 +880,42 @@ int qldpc_circuit_plan_use_erasure_aware(qldpc_circuit_plan *plan, double alpha,
  * not NULL (both or neither; needs the erasure-aware path), the per-shot priors f64[count][n_z] / f64[count][n_x] the plan would decode with. */
 int qldpc_circuit_plan_sample_erasures(qldpc_circuit_plan *plan, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z,
                                        int8_t *true_z, int8_t *sparse_x, int8_t *true_x, uint32_t *erased, double *prior_z, double *prior_x);
+
+/* ---- per-class, biased Pauli noise.  New here: the reference has one rate p and uniform Paulis.  Circuit plans only. ------------------------------
+ * The plan's own sampler fires every location at the plan's p and draws an IDLE's Pauli as r % 3 and a CNOT's as r % 15.  A noise model gives every
+ * location class a rate of its own and, optionally, the Paulis of a faulty IDLE and of a faulty CNOT weights of their own (measurement five times as
+ * noisy as a gate, Z-biased idles, ...).  The decoder's priors are the caller's: simulation/noise_model.py computes the matched ones on the host.
+ *
+ * Which locations fire, a pure function of (seed, global trial index g = trial_begin + t): rate[ty] in [0, 1) per location class, ty one of the six
+ * op codes 1..6 of a base circuit (CNOT, PrepX, PrepZ, MeasX, MeasZ, IDLE; rate[0] is not read); thr[ty] = floor(rate[ty] * 2^32) (uint32; a rate of
+ * 0 never fires).  Location l is faulty iff word (l & 3) of Philox4x32-10(counter = (lo32(g), hi32(g), l >> 2, 1), key = (lo32(seed), hi32(seed))) is
+ * below thr[type(l)]: the words and the domain of the plain sampler, only the threshold depends on the class.
+ * Which Pauli a faulty location takes: a measurement or preparation keeps its one component.  IDLE and CNOT read r = word 0 of
+ * Philox4x32-10(counter = (lo32(g), hi32(g), l, 2), same key), as the plain sampler does, and pick index i of their component table (IDLE: X, Y, Z;
+ * CNOT: the fifteen two-qubit Paulis in the order of noise/kernels.py:283-343; both are the plain sampler's tables):
+ *     weights NULL        i = r % K                                   (K = 3 or 15: the plain sampler's choice)
+ *     weights w[K]        i = #{ j < K - 1 : r >= cut[j] },           cut[j] = (uint64) floor(ldexp(S_j / S_{K-1}, 32)),
+ *                         S_j = w_0 + ... + w_j, the running f64 sum in index order.
+ *   The compare is a 64-bit one: cut[j] may be 2^32 (then no r reaches it).  Index i is drawn for cut[i-1] <= r < cut[i] (cut[-1] = 0, cut[K-1] = 2^32):
+ *   a weight of 0 gives an empty interval, so that Pauli is never drawn -- a zero last weight included -- and every probability is within 2^-32 of
+ *   w_i / S_{K-1}.  The host computes the cuts; the kernel takes them, and the seven thresholds, by value.
+ * With every rate equal to the plan's p and both weight tables NULL the samples are the plain sampler's bit for bit. */
+typedef struct {
+    double rate[7];        /* per op code 1..6 of a base circuit (CNOT, PrepX, PrepZ, MeasX, MeasZ, IDLE); rate[0] is not read */
+    const double *idle_w;  /* [3]  weights of X, Y, Z on a faulty IDLE (order of c_idle_comp), or NULL = r % 3 */
+    const double *cnot_w;  /* [15] weights of the fifteen Paulis of a faulty CNOT (order of c_cnot_comp = noise/kernels.py:283-343), or NULL = r % 15 */
+} qldpc_noise_model;
+/* The sampler axis of a plan (beside qldpc_circuit_plan_use_fixed_weight and _use_erasure_noise): from now on the plan's sampler draws its Pauli
+ * faults by `model` (copied); model == NULL switches back to the plan's own p and uniform Paulis.  Two-way, any number of times; not a decode switch,
+ * so it goes with every path and OSD stage in either call order.  _run, _run_outcomes, _sample and _sample_erasures honour it (the herald record of
+ * _sample_erasures stays all zero); _decode_events* and _unpack_events do not sample and are untouched.  A plan that is never switched, or is
+ * switched off again, enqueues exactly what it enqueued before.
+ * QLDPC_ERR_INVALID: a rate outside [0, 1) or NaN (the text names the class); a weight that is negative or not finite, or a weight table whose sum is
+ * 0 (the text names the table and the index); a plan created from a detector error model; a plan with a fixed weight in force (that law needs one p);
+ * a plan with erasure noise on -- and qldpc_circuit_plan_use_fixed_weight(w >= 0) and qldpc_circuit_plan_use_erasure_noise(non-NULL) return
+ * QLDPC_ERR_INVALID while a model is on.  Composing a noise model with heralded erasures is deliberately out of scope: the erasure sampler draws its
+ * ordinary faults at one p.  A refused call leaves the plan as it was. */
+int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *plan, const qldpc_noise_model *model);
 
 /* ---- recorded detection events in place of the sampler: events -> decode -> OSD -> predict.  New here: the reference has no counterpart. ---------
  * The second front door of a circuit plan, for plans of qldpc_circuit_plan_create and _create_dem alike: the syndromes come from the caller's records

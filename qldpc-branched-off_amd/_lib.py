@@ -65,6 +65,11 @@ class CircuitDesc(C.Structure):
                 ("data_qubit_indices", C.POINTER(C.c_int32)), ("Lx", C.POINTER(C.c_uint8)), ("Lz", C.POINTER(C.c_uint8))]
 
 
+class NoiseModelStruct(C.Structure):
+    """qldpc_noise_model (include/qldpc_hip.h); simulation.noise_model.NoiseModel.as_struct fills it."""
+    _fields_ = [("rate", C.c_double * 7), ("idle_w", C.POINTER(C.c_double)), ("cnot_w", C.POINTER(C.c_double))]
+
+
 class DemDesc(C.Structure):
     """qldpc_dem_desc (include/qldpc_hip.h)."""
     _fields_ = [("n_mech", C.c_int64), ("prob", C.POINTER(C.c_double)), ("n_sectors", C.c_int32), ("k", C.c_int32 * 2), ("n_det", C.c_int32 * 2),
@@ -93,6 +98,8 @@ def _ctype_of(decl):
         t = CircuitDesc
     elif base == "qldpc_dem_desc":
         t = DemDesc
+    elif base == "qldpc_noise_model":
+        t = NoiseModelStruct
     elif base in ("void", "char") or base.startswith("qldpc_"):
         t = None                       # opaque: void*
     else:
@@ -1081,6 +1088,7 @@ class CircuitPlan(Owner):
         self.n_locs = int(d.base_len)                       # fault locations: what use_fixed_weight counts
         self.fixed_weight = None                            # the sampler axis: None = the independent draws, else the weight in force
         self.erasure_rates = None                           # ... and None = no erasure noise, else the rates in force (f64[7] by op code)
+        self.noise_model = None                             # ... and None = the plan's own p and uniform Paulis, else the NoiseModel in force
         self.graph_z, self.graph_x = graph_z, graph_x
         self.flags = flags
         self._h = C.c_void_p()
@@ -1189,6 +1197,24 @@ class CircuitPlan(Owner):
         r = erasure_rates(rates)
         check(lib().qldpc_circuit_plan_use_erasure_noise(self._h, ptr(r, C.c_double)))
         self.erasure_rates = r
+
+    def use_noise_model(self, model):
+        """Draw the plan's Pauli faults by `model` from now on (qldpc_circuit_plan_use_noise_model): a simulation.noise_model.NoiseModel -- a rate per
+        location class and, optionally, weights for the Paulis of a faulty IDLE and of a faulty CNOT; None: back to the plan's own p and uniform
+        Paulis.  The sampler axis, beside use_fixed_weight and use_erasure_noise (a model refuses both, and they refuse it): two-way, and it goes
+        with every other use_* in either order.  The plan's priors stay what it was created with (NoiseModel.prior_llrs gives the matched ones).
+        Circuit plans only."""
+        if model is None:
+            check(lib().qldpc_circuit_plan_use_noise_model(self._h, None))
+            self.noise_model = None
+            return
+        from .simulation.noise_model import NoiseModel
+        if not isinstance(model, NoiseModel):
+            raise ValueError(f"use_noise_model takes a simulation.noise_model.NoiseModel (or None), got {model!r}")
+        s, keep = model.as_struct()
+        check(lib().qldpc_circuit_plan_use_noise_model(self._h, C.byref(s)))
+        del keep                                            # (the library copied what it needs)
+        self.noise_model = model
 
     def use_erasure_aware(self, alpha=1.0, tables=None):
         """Decode both sectors with the heralds from now on (qldpc_circuit_plan_use_erasure_aware): constant-alpha min-sum whose prior is computed
@@ -1337,6 +1363,7 @@ class DemPlan(CircuitPlan):
         self.n_locs = int(d.n_mech)
         self.fixed_weight = None
         self.erasure_rates = None
+        self.noise_model = None
         self.graph_z, self.graph_x = g[0], g[1]
         self.flags = flags
         opt = lambda a, t: ptr(a, t) if a is not None else None

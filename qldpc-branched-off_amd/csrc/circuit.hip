@@ -209,6 +209,11 @@ struct qldpc_circuit_plan {
     std::vector<hipEvent_t> pool;
     double phase_ms[QLDPC_CIRCUIT_PHASES] = {0, 0, 0, 0, 0, 0};
     int64_t batches = 0;
+    // the sampler axis a third time, qldpc_circuit_plan_use_noise_model: a threshold per location class and weighted Paulis in place of thr and r % K (noise_model.hip); nm: the
+    // checked model; d_loc_cls: the op codes of d_loc_type, four to a word (uploaded at the first switch).  A model refuses a fixed weight and erasure noise.
+    bool noise_model = false;
+    NoiseModelHost nm{};
+    DevBuf d_loc_cls;
     int32_t *fail_count(int sector) { return d_count.as<int32_t>() + 4 * sector; }
     bool osd_stage() const { return use_osd && path != Path::RELAY; }            // the judge then adds d_count to the OSD tally slots
     ~qldpc_circuit_plan() {                        // the events; the sectors' decoder objects and every buffer then release themselves
@@ -510,6 +515,10 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
         return erasure_sample_launch(P->device, B, begin, seed, P->thr, P->ethr, P->n_locs, P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn,
                                      Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
                                      P->d_erased.as<uint32_t>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
+    if (P->noise_model)
+        return noise_model_sample_launch(B, begin, seed, P->nm, P->n_locs, P->d_loc_cls.as<uint32_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(),
+                                         X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
+                                         zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
     const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
     const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
     const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
@@ -932,6 +941,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *P, int 
     const int rc = fixed_weight_check(P->n_locs, weight);
     if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a fixed weight counts the faults of the independent draws alone (switch erasure noise off first)");
+    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the fixed-weight law needs one p for every location (switch the noise model off first)");
     QLDPC_REQUIRE(!P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
                   "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
     P->fixed_weight = weight;
@@ -945,6 +955,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *P, con
     QLDPC_REQUIRE(!P->dem, "erasure noise needs a circuit plan: a detector error model has no gate locations to erase");
     QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: erasure noise goes with the independent draws (switch the fixed weight off first)",
                   P->fixed_weight);
+    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the erasure sampler draws its ordinary faults at one p (switch the noise model off first)");
     uint32_t thr[8];
     int rc = erasure_rates_check(rate, thr);
     if (rc != QLDPC_OK || (rc = erasure_sample_supported(P->sec[0].nsyn, P->sec[1].nsyn, P->n_locs)) != QLDPC_OK) return rc;
@@ -952,6 +963,30 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *P, con
     if ((rc = P->d_erased.ensure((size_t)P->batch * ((size_t)(P->n_locs + 31) / 32) * 4 + 4)) != QLDPC_OK) return rc;
     std::copy(thr, thr + 8, P->ethr);
     P->erasure = true;
+    return QLDPC_OK;
+}
+
+// The sampler axis a third time: a rate per location class and weighted Paulis in place of the plan's p and r % K (noise_model.hip).  NULL = off.
+QLDPC_EXPORT int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *P, const qldpc_noise_model *model) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    if (model == nullptr) { P->noise_model = false; return QLDPC_OK; }
+    QLDPC_REQUIRE(!P->dem, "a noise model needs a circuit plan: a detector error model has no gate locations (give its mechanisms their probabilities)");
+    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: that law needs one p for every location (switch the fixed weight off first)",
+                  P->fixed_weight);
+    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a noise model does not compose with heralded erasures (switch erasure noise off first)");
+    NoiseModelHost nm;
+    int rc = noise_model_check(model, &nm);
+    if (rc != QLDPC_OK) return rc;
+    if (!P->d_loc_cls.p) {                                               // the first switch: pack the classes the plan already holds on the device
+        QLDPC_USE_DEVICE(P->device);
+        std::vector<uint8_t> loc_type((size_t)P->n_locs);
+        if (P->n_locs) QLDPC_HIP_TRY(hipMemcpy(loc_type.data(), P->d_loc_type.p, loc_type.size(), hipMemcpyDeviceToHost));
+        DevBuf cls;
+        if ((rc = upload(cls, noise_model_pack_classes(loc_type))) != QLDPC_OK) return rc;
+        P->d_loc_cls = std::move(cls);
+    }
+    P->nm = nm;
+    P->noise_model = true;
     return QLDPC_OK;
 }
 

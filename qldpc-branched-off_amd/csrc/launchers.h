@@ -210,6 +210,17 @@ int erasure_check_tables(int n_locs, const int32_t *loc_ptr, const int32_t *loc_
 int erasure_prior_supported(int n);
 int erasure_prior_launch(int device, int64_t B, int n_locs, const uint32_t *d_erased, const int32_t *d_loc_ptr, const int32_t *d_loc_col,
                          const uint8_t *d_loc_h, int n, const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, hipStream_t s);
+// Per-class, biased Pauli noise of a circuit plan (noise_model.hip).  NoiseModelHost: what a checked qldpc_noise_model becomes on the host -- the
+// threshold per op code, whether a weight table was given and its cuts (uint64: a cut may be 2^32).  check: the rules of
+// qldpc_circuit_plan_use_noise_model on the model alone, QLDPC_ERR_INVALID with the text naming the class or the index.  pack_classes: the op codes
+// of the four locations of Philox block b as the four bytes of word b (zero padding: class 0 has threshold 0).  sample: circuit_sample_kernel with a
+// threshold per class and the cut-based Pauli choice; d_loc_cls is pack_classes' array on the device, the other arguments as in erasure_sample_launch.
+struct NoiseModelHost { uint32_t thr[8]; bool idle_weighted, cnot_weighted; uint64_t idle_cut[2], cnot_cut[14]; };
+int noise_model_check(const qldpc_noise_model *M, NoiseModelHost *out);
+std::vector<uint32_t> noise_model_pack_classes(const std::vector<uint8_t> &loc_type);
+int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, const NoiseModelHost &M, int n_locs, const uint32_t *d_loc_cls,
+                              const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
+                              unsigned long long *d_true_z, unsigned long long *d_true_x, int32_t *d_fail_counts, hipStream_t s);
 // Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
 // only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
 // predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does

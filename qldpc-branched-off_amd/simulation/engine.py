@@ -81,6 +81,16 @@ is the constant of the dict as for ``correlated``, and OSD-0, OSD-CS (which stil
 ``aware=False`` only the sampler changes -- the sampler axis -- and every path and decoder goes with it: the decoder does not see the heralds.  The result
 also holds ``erasure`` (rates as f64[7] by op code, aware, alpha).  Circuit plans only: ``run_weight_strata`` and ``run_dem_simulation`` raise ValueError.
 
+``noise_model=NoiseModel(...)`` (an extension; None is today's behaviour) replaces the sampler's one rate and uniform Paulis by a rate per location class
+and, optionally, weighted Paulis on faulty IDLEs and CNOTs (``simulation/noise_model.py``, ``CircuitPlan.use_noise_model``): the sampler axis, so every
+path and decoder goes with it.  The decoding matrices are built or loaded at ``error_rate`` as without it -- their columns do not depend on the rates
+-- and with ``matched_priors=True`` (the default) both sectors' priors come from the model (``NoiseModel.prior_llrs``); ``matched_priors=False`` keeps the
+uniform priors of ``error_rate``: the mismatched-decoder study.  ``correlated=...`` and ``erasure=...`` raise ValueError beside it (link masses and erasure
+look-up tables under a model do not exist yet), and so does ``run_weight_strata``.  The result also holds ``noise_model`` and ``matched_priors``.
+The alpha / SCOPT estimators (``alpha_mode="alvarado"`` without ``alvarado_alpha``, ``"alvarado-autoregressive"``, ``scopt=True``) are NOT taught the model:
+they still draw their error patterns at the single ``error_rate`` while reading the priors the plan gets, so beside a model their factors belong to a
+noise that is neither the model's nor the priors'.  Only the dynamical alpha (the default) or a given ``alvarado_alpha`` is meaningful beside a model.
+
 ``simulation/dem.py`` (``run_dem_simulation``: the same pipeline fed by a detector error model instead of a bivariate-bicycle circuit) shares the
 argument rules of the extensions (``_extension_rules``), the choice of devices (``_worker_devices``) and the Worker, round loop, early stop,
 all-reduce and result assembly (``_run_trials``) with ``run_simulation``; the two differ in how a worker's plan is created.
@@ -231,7 +241,22 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
     return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window, correlated=correlated,
-                           links=None, erasure=erasure, erasure_tables=None)
+                           links=None, erasure=erasure, erasure_tables=None, noise_model=None, matched_priors=True)
+
+
+def _noise_model_rules(who, noise_model, matched_priors, correlated=None, erasure=None):
+    """The argument rules of ``noise_model=`` / ``matched_priors=``: raises ValueError before any device call."""
+    if noise_model is None:
+        return
+    from .noise_model import NoiseModel
+    if not isinstance(noise_model, NoiseModel):
+        raise ValueError(f"{who}: noise_model must be a simulation.noise_model.NoiseModel (or None), got {noise_model!r}")
+    if not isinstance(matched_priors, (bool, np.bool_)):
+        raise ValueError(f"{who}: matched_priors must be True or False")
+    if correlated is not None:
+        raise ValueError(f"{who}: noise_model=... does not go with correlated=... (the link masses are computed for one rate and uniform Paulis)")
+    if erasure is not None:
+        raise ValueError(f"{who}: noise_model=... does not go with erasure=... (the erasure sampler draws its ordinary faults at one rate)")
 
 
 def _worker_devices(num_workers, devices, device):
@@ -283,6 +308,8 @@ def _plan_switch(rules, csr, osd_order):
         if rules.erasure is not None:                                            # the sampler axis: goes with whatever the plan decodes with
             from .erasure import GATES                                           # (in op-code order: rates[1..6])
             plan.use_erasure_noise({g: rules.erasure["rates"][i + 1] for i, g in enumerate(GATES)})
+        if rules.noise_model is not None:                                        # the sampler axis again
+            plan.use_noise_model(rules.noise_model)
 
     return switch, layers
 
@@ -457,6 +484,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         result.update(correlated=dict(rules.correlated), correlated_links=0 if rules.links is None else rules.links.n_links)
     if rules.erasure is not None:
         result.update(erasure=dict(rules.erasure))
+    if rules.noise_model is not None:
+        result.update(noise_model=rules.noise_model, matched_priors=bool(rules.matched_priors))
     result["precision"] = precision
     result["tally"] = total
     return result
@@ -483,8 +512,9 @@ def _circuit_problem(Hx, Hz, Lx, Lz, error_rate, num_cycles, precomputed_matrice
             flr = int(m[f"first_logical_row{s}"])
             masks.append(_lib.logical_column_masks(np.asarray(m[f"H{s}_full"])[flr:flr + k], shape[1]))    # engine.py:412-413
 
-    def make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags):
-        return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], llrs_z, llrs_x, masks[0], masks[1], error_rate, max_iter=maxIter,
+    def make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags, llrs=None):
+        pz, px = (llrs_z, llrs_x) if llrs is None else llrs                      # llrs: other priors for the same columns (a noise model's matched ones)
+        return _lib.CircuitPlan(compiled, Lx, Lz, own_graphs[0], own_graphs[1], pz, px, masks[0], masks[1], error_rate, max_iter=maxIter,
                                 alpha_z=alpha_z, alpha_x=alpha_x, alpha_mode=alpha_mode, use_osd=True, batch=batch, flags=flags)    # flags: QLDPC_FLAG_* kernel variants (extension)
 
     return SimpleNamespace(compiled=compiled, matrices=m, graphs=graphs, llrs=(llrs_z, llrs_x), masks=masks, k=k, make_plan=make_plan)
@@ -494,7 +524,8 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, **bb_params):
+                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, noise_model=None, matched_priors=True, **bb_params):
+    _noise_model_rules("run_simulation", noise_model, matched_priors, correlated, erasure)
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
                              use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated, erasure=erasure)
     rank, world, devices = _worker_devices(num_workers, devices, device)
@@ -518,6 +549,11 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
     if rules.path == "erasure":
         from .erasure import erasure_tables_from_circuit
         rules.erasure_tables = erasure_tables_from_circuit(prob.compiled, Lx, Lz, prob.matrices)
+    own_llrs = None
+    if noise_model is not None:
+        rules.noise_model, rules.matched_priors = noise_model, bool(matched_priors)
+        if matched_priors:                                                       # the same columns, the model's probabilities
+            own_llrs = llrs_z, llrs_x = noise_model.prior_llrs(prob.compiled, Lx, Lz, prob.matrices)
 
     # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
     # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.
@@ -554,7 +590,7 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         extra.update(beta_z=betas[0][0], beta_x=betas[1][0], beta_r2_z=betas[0][1], beta_r2_x=betas[1][1])   # engine.py:482-486
 
     def make_plan(own_graphs, dev):
-        return prob.make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags)
+        return prob.make_plan(own_graphs, maxIter, alpha_z, alpha_x, alpha_mode, batch, flags, llrs=own_llrs)
 
     return _run_trials(make_plan, graphs, (llrs_z, llrs_x), masks, (alpha_z, alpha_x), (k, k), rules, rank, world, devices, base_seed, num_trials, max_trials,
                        target_logical_errors, maxIter, osd_order, alpha_mode, batch, decoder, schedule, precision, extra)

@@ -235,10 +235,15 @@ def _refuse_erasure(who, erasure):
         raise ValueError(f"{who}: erasure=... does not go with fixed-weight sampling (a weight stratum counts the faults of the independent draws alone)")
 
 
+def _refuse_noise_model(who, noise_model):
+    if noise_model is not None:
+        raise ValueError(f"{who}: noise_model=... does not go with fixed-weight sampling (the weight strata reweight one rate p for every location)")
+
+
 def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=None, trials_per_weight=4096, target_failures=None,
                       max_trials_per_weight=None, coverage=1e-9, num_cycles=12, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding",
                       layers=None, decimation=None, precision="f64", relay_params=None, precomputed_matrices=None, device=None, base_seed=0, batch=16384,
-                      flags=0, lsd=None, erasure=None, **bb_params):
+                      flags=0, lsd=None, erasure=None, noise_model=None, **bb_params):
     """One sweep over the number of faults on the circuit plan of ``run_simulation`` -> WeightStrata.
 
     The circuit and decoder arguments are ``run_simulation``'s, under the same rules (``engine._extension_rules``: ValueError before any device call).
@@ -251,8 +256,10 @@ def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=No
     Per weight: ``trials_per_weight`` trials; with ``target_failures``, batches of ``batch`` until that many failures or ``max_trials_per_weight``
     (default ``trials_per_weight``) trials -- whole batches, all counted.
     One plan on a single ``device`` serves the whole sweep; weight w uses the global trial range starting at ``w << 40``.
-    ``erasure=...`` raises ValueError: a weight counts the faults of the independent draws alone, and the plan refuses erasure noise beside it."""
+    ``erasure=...`` raises ValueError: a weight counts the faults of the independent draws alone, and the plan refuses erasure noise beside it.
+    ``noise_model=...`` raises ValueError too: LER(p) is rebuilt from the strata with one rate p for every location, and the plan refuses a model beside a weight."""
     _refuse_erasure("run_weight_strata", erasure)
+    _refuse_noise_model("run_weight_strata", noise_model)
     rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, None, None, True, False, maxIter, None, lsd=lsd)
     if decoder == "bp_osd" and osd_order > 0:
         raise ValueError(f"osd_order={osd_order} with decoder='bp_osd' asks for the OSD-w pass, which runs outside the plan; use decoder='bp_osd_cs' "
