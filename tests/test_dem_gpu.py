@@ -91,7 +91,7 @@ def assert_tally(L, got, want, slots=None):
 def test_t1_sampler_is_the_model(L, DEM, seed):
     dem, graphs = model(L, DEM, "tiny")
     begin, count = (1 << 32) - 100, 4096                       # crosses the 32-bit counter word
-    plan = dem.plan(graphs, batch=1024)                        # four batches; grid-stride inside each
+    plan = dem.plan(graphs, batch=1024)                        # four batches of 1024 workgroups, a trial each (a second trial per workgroup: test_dem_shapes_gpu.py, stride)
     got = plan.sample(seed, begin, count)
     plan.close()
     want = DM.sample(dem, seed, begin, count)
