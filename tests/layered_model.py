@@ -74,6 +74,16 @@ class LayeredModel:
             np.add.at(out, (slice(None), self.row_of_edge), e[:, self.indices].astype(np.int64))
         return (out & 1).astype(np.int8)
 
+    @staticmethod
+    def two_minima(ab):
+        """ab [B, rows, maxdeg], +inf beyond a row's degree -> (position of the minimum, the minimum, the minimum of the other positions).  A method
+        of its own so that a test can put another rule in its place (a subclass) and see what its inputs can tell apart."""
+        pos = np.argmin(ab, axis=2)                                               # the first position of the minimum
+        min1 = np.take_along_axis(ab, pos[..., None], axis=2)[..., 0]
+        rest = ab.copy()
+        np.put_along_axis(rest, pos[..., None], np.inf, axis=2)
+        return pos, min1, rest.min(axis=2)                                        # degree 1: +inf
+
     def decode(self, syndromes, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0):
         """-> (err int8[B, n], conv uint8[B], llr f64[B, n], final_iter int32[B])"""
         synd = (np.asarray(syndromes, np.int8).reshape(-1, self.m) & 1)
@@ -96,11 +106,7 @@ class LayeredModel:
                     Q = np.where(Q > clip_llr, clip_llr, np.where(Q < -clip_llr, -clip_llr, Q))
                     sg = np.where(mask, np.where(Q >= 0, 1.0, -1.0), 1.0)
                     ab = np.where(mask, np.abs(Q), np.inf)
-                    pos = np.argmin(ab, axis=2)                                   # the first position of the minimum
-                    min1 = np.take_along_axis(ab, pos[..., None], axis=2)[..., 0]
-                    rest = ab.copy()
-                    np.put_along_axis(rest, pos[..., None], np.inf, axis=2)
-                    min2 = rest.min(axis=2)                                       # degree 1: +inf
+                    pos, min1, min2 = self.two_minima(ab)
                     sign_prod = ss[act][:, rows] * np.prod(sg, axis=2)
                     mag = np.where(np.arange(ab.shape[2])[None, None, :] == pos[..., None], min2[..., None], min1[..., None])
                     Rn = a * (sign_prod[..., None] * sg) * mag

@@ -13,6 +13,7 @@ import torch  # noqa: F401  (first: the HIP runtime torch loads is the one libql
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import graph_shapes as GS  # noqa: E402
 import layered_model as LM  # noqa: E402
+import layered_shapes as LSH  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup, sampled  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +48,12 @@ def check(L, g, prior, synd, what, layers=None, max_iter=50, alpha_mode="dynamic
     model = LM.LayeredModel(g.indptr, g.indices, g.n, prior, row_layer=layers)
     assert np.array_equal(used, model.row_layer) and info["layers"] == len(model.stages), what
     assert info["max_layer_rows"] == max(model.layer_sizes()) and info["max_layer_edges"] == max(int(st[3].sum()) for st in model.stages), what
-    assert 0 < info["lds_bytes"] <= 160 * 1024 and info["block"] in (256, 512, 1024), (what, info)
+    ns, nl = sum(model.layer_sizes()), len(model.stages)                    # the exact layout of the form that runs, and that form is the rule's
+    assert info["lds_bytes"] == LSH.lds_bytes(g.n, ns, nl, len(g.indices), info["v_global"], info["lds_indices"]) <= LSH.LDS_BYTES, (what, info)
+    assert LSH.FORMS[2 * info["v_global"] + (not info["lds_indices"])] == LSH.form(g.n, ns, nl, len(g.indices), bool(flags & L.FLAG_LAYERED_VGLOBAL),
+                                                                                 bool(flags & L.FLAG_LAYERED_GLOBAL_IDX))[0], (what, info)
+    forced = {L.FLAG_LAYERED_BLOCK_256: 256, L.FLAG_LAYERED_BLOCK_512: 512, L.FLAG_LAYERED_BLOCK_1024: 1024}
+    assert info["block"] == LSH.block(len(g.indices), nl, sum(v for k, v in forced.items() if flags & k)), (what, info)
     want = model.decode(synd, max_iter=max_iter, alpha_mode=MODEL_ALPHA[alpha_mode][0], alpha=alpha, clip_llr=clip_llr)
     print(f"{what}: {info}; shots {len(synd)}, converged {int(want[1].sum())}, mean iterations {float((want[3] + 1).mean()):.1f}")
     assert_same(got, want, what)

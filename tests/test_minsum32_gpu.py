@@ -14,6 +14,7 @@ import torch  # noqa: F401  (first: the HIP runtime torch loads is the one libql
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import graph_shapes as GS  # noqa: E402
 import minsum32_model as MM  # noqa: E402
+from minsum32_shapes import lds_bytes  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup, sampled  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -38,12 +39,6 @@ def assert_same(got, want, what):
         eq = (a == b) | ((a != a) & (b != b)) if name == "llr" else (a == b)        # equal values, NaN where NaN
         bad = np.flatnonzero(~eq.reshape(len(a), -1).all(axis=1))
         assert bad.size == 0, f"{what}: {name} differs on shots {bad[:8].tolist()} ({bad.size} of {len(a)})"
-
-
-def lds_bytes(m, n):
-    """the header's layout: V f32 | 16-byte records | a byte per row | flags"""
-    up = lambda x: (x + 15) // 16 * 16                                      # noqa: E731
-    return up(up(4 * n) + 16 * m + m) + 16
 
 
 def check(L, g, prior, synd, what, max_iter=50, alpha_mode="dynamical", alpha=1.0, clip_llr=20.0, flags=0):
