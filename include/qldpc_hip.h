@@ -52,6 +52,8 @@
  *        additive, same version: heralded-erasure noise and erasure-aware decoding on a circuit plan, qldpc_erasure_priors[_dev],
  *        qldpc_circuit_plan_use_erasure_noise, _use_erasure_aware and _sample_erasures, QLDPC_ERASURE_H_INF
  *        additive, same version: per-class, biased Pauli noise on a circuit plan, qldpc_noise_model and qldpc_circuit_plan_use_noise_model
+ *        additive, same version: soft-readout noise and soft-information decoding on a circuit plan, qldpc_soft_priors[_dev],
+ *        qldpc_circuit_plan_use_soft_readout, _use_soft_aware and _sample_soft, QLDPC_SOFT_MAX_LEVELS
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -916,6 +918,76 @@ typedef struct {
  * QLDPC_ERR_INVALID while a model is on.  Composing a noise model with heralded erasures is deliberately out of scope: the erasure sampler draws its
  * ordinary faults at one p.  A refused call leaves the plan as it was. */
 int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *plan, const qldpc_noise_model *model);
+
+/* ---- soft-readout noise and soft-information decoding.  New here: the reference has no counterpart.  Circuit plans only. ---------------------------
+ * Every measurement of the plan's sampler is a hard bit.  A real readout is an analog signal: thresholded it gives the bit, and its distance from the
+ * threshold says how far to trust it.  A readout channel has K confidence levels (1 <= K <= QLDPC_SOFT_MAX_LEVELS): the readout of a measurement
+ * lands in level lv on the WRONG side with probability proportional to flip_mass[lv] and on the right side with keep_mass[lv].  The masses are
+ * non-negative and finite and their sum is positive.  A decoder that reads the levels gives every measurement its own flip probability.
+ *
+ * Cuts: S_b = the running f64 sum of the 2K masses in bin order -- the flipped bins 0 .. K-1 first, then the kept bins K .. 2K-1 --
+ *     cut[b] = (uint64) floor(ldexp(S_b / S_{2K-1}, 32)) for b <= 2K-2, cut[-1] = 0, cut[2K-1] = 2^32
+ *   (the law qldpc_noise_model uses for weighted Paulis; compares are 64-bit: a cut may be 2^32, which no word reaches).
+ * Level flip probabilities, from the integers, so that the decoder's belief is exactly the sampler's law:
+ *     q_lv = (cut[lv] - cut[lv-1]) / ((cut[lv] - cut[lv-1]) + (cut[K+lv] - cut[K+lv-1]));
+ *   a level whose two integer masses are both 0 is refused.  Marginal flip rate: qbar = cut[K-1] / 2^32.
+ *
+ * Readout draws, a pure function of (seed, global trial index g = trial_begin + t): the plan's ordinary faults (domains 1 and 2) are drawn first,
+ * word for word as without soft readout.  On top of them every location l of class MeasX or MeasZ reads
+ *     u = word (l & 3) of Philox4x32-10(counter = (lo32(g), hi32(g), l >> 2, 7), key = (lo32(seed), hi32(seed)))        (domain 7 is new)
+ *     bin = #{ i <= 2K-2 : u >= cut[i] };   bin < K: flipped at level bin;   else: kept at level bin - K.
+ * A flipped readout XORs the location's slot-0 signature exactly as that class's measurement fault does (component 4 for MeasX, 1 for MeasZ).
+ * Level record: uint8[B][n_meas], entry k = the level of the k-th MeasX / MeasZ location in ascending l.  It holds the level only, never whether
+ * the readout flipped.  With soft readout off the samples are the plain sampler's bit for bit.
+ *
+ * Decoder tables, per sector (simulation/soft.py builds them on the host), for a sector with n columns:
+ *   meas_col int32[n_meas]: the column measurement k's readout flip lands on, -1 = it touches no column of this sector;
+ *   meas_w int32[n_meas]: for a column with measurements k_0 < ... < k_{c-1}, meas_w[k_r] = K^r (mixed radix; not read where meas_col is -1);
+ *   lut_ptr int32[n + 1], lut f64[lut_ptr[n]]: column j's run has K^c entries, 1 for a column without measurements and at most 65536;
+ *     entry (lv_0 .. lv_{c-1}) is the prior LLR of (1 - (1 - 2 p_j) prod_r (1 - 2 q_{lv_r})) / 2.  Every entry is finite.
+ * Per-shot prior: I_j = sum of level[b][k] * meas_w[k] over the measurements k with meas_col[k] = j;  prior[b][j] = lut[lut_ptr[j] + I_j].
+ *   I_j is an integer sum: the value does not depend on the order in which the measurements are met, and the device takes no logarithm. */
+#define QLDPC_SOFT_MAX_LEVELS 16
+/* The prior kernel alone: level uint8[B][n_meas] and one sector's tables -> prior f64[B][n].  Host pointers, staged on the calling thread's current
+ * device.  QLDPC_ERR_INVALID for a table that breaks a rule above (the error text names the offending index) and for a level that is not below
+ * `levels` (the text names the shot and the measurement); QLDPC_ERR_UNSUPPORTED when a 16-bit counter per column does not fit in 160 KB of LDS:
+ * the bound is n <= 81920. */
+int qldpc_soft_priors(int64_t B, int32_t levels, int32_t n_meas, const uint8_t *level, const int32_t *meas_col, const int32_t *meas_w, int32_t n,
+                      const int32_t *lut_ptr, const double *lut, double *prior);
+/* same on device pointers of the current device; only enqueues on `stream`.  Precondition: tables and levels that keep the rules above (a level is
+ * clamped to levels - 1, a column outside 0 .. n - 1 is skipped and I_j is held inside the column's run, so nothing outside the arrays is addressed
+ * either way). */
+int qldpc_soft_priors_dev(int64_t B, int32_t levels, int32_t n_meas, const uint8_t *d_levels, const int32_t *d_meas_col, const int32_t *d_meas_w,
+                          int32_t n, const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, void *stream);
+/* The sampler axis of a plan a fourth time (beside qldpc_circuit_plan_use_fixed_weight, _use_erasure_noise and _use_noise_model): from now on the
+ * plan's sampler draws the readouts above on top of its ordinary faults; flip_mass == NULL switches them off again.  Two-way, any number of times;
+ * not a decode switch, so it goes with every path and OSD stage in either call order.  _run, _run_outcomes, _sample, _sample_erasures (whose herald
+ * record stays all zero) and _sample_soft honour it; a plan that is not on the soft-aware path decodes the syndromes as it always does (it does not
+ * read the levels).  A plan that is never switched, or is switched off again, enqueues exactly what it enqueued before.
+ * QLDPC_ERR_INVALID, plan unchanged: levels outside 1..16; a mass that is negative or not finite, a sum of 0, a level without mass (the text names
+ * the index); a plan created from a detector error model; a plan on the soft-aware path whose tables were built for another number of levels; a
+ * fixed weight, erasure noise or a noise model in force -- and qldpc_circuit_plan_use_fixed_weight(w >= 0), _use_erasure_noise(non-NULL) and
+ * _use_noise_model(non-NULL) return QLDPC_ERR_INVALID while soft readout is on.  Composing them is deliberately out of scope. */
+int qldpc_circuit_plan_use_soft_readout(qldpc_circuit_plan *plan, int32_t levels, const double *flip_mass, const double *keep_mass);
+/* A decode path, "soft-aware decoding": the BP launch of both sectors becomes qldpc_shotprior_decode_batch's kernel with the constant `alpha`, the
+ * plan's max_iter and clip_llr, no link tables, and prior[batch][n] (stride n) computed per batch, inside the QLDPC_PHASE_SAMPLE bracket, from the
+ * sampler's level record and the sector's tables given here (host pointers, copied; the rules above for `levels` levels).  While soft readout is
+ * off -- and for recorded events, which carry no levels -- the path decodes with the plan's prior (stride 0): the same answers as
+ * qldpc_circuit_plan_use_correlated with no links.  So the lut entry of every run of length 1 must equal the plan's prior of that column bit for
+ * bit; the plan's prior of a column with measurements is the caller's (the marginal one, say), and OSD-CS keeps scoring its candidates with the
+ * plan's sector prior, not the per-shot one.  The rules of the erasure-aware path apply: a circuit plan, damping = 1, OSD-0, OSD-CS or LSD may
+ * follow in either call order, no other path, a second call replaces the arguments.  QLDPC_ERR_INVALID for these, for `levels` other than the
+ * levels of the soft readout in force, for arguments qldpc_shotprior_decode_batch refuses and for tables that break a rule (the text names the
+ * sector and the index); QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_shotprior_decode_batch or qldpc_soft_priors refuses.  A refused
+ * call leaves the plan as it was. */
+int qldpc_circuit_plan_use_soft_aware(qldpc_circuit_plan *plan, double alpha, int32_t levels, const int32_t *meas_col_z, const int32_t *meas_w_z,
+                                      const int32_t *lut_ptr_z, const double *lut_z, const int32_t *meas_col_x, const int32_t *meas_w_x,
+                                      const int32_t *lut_ptr_x, const double *lut_x);
+/* qldpc_circuit_plan_sample plus level uint8[count][n_meas] (all zero while soft readout is off) and, where prior_z / prior_x are not NULL (both or
+ * neither; needs the soft-aware path), the per-shot priors f64[count][n_z] / f64[count][n_x] the plan would decode those levels with.  n_meas
+ * is the number of MeasX / MeasZ locations of the plan's base circuit. */
+int qldpc_circuit_plan_sample_soft(qldpc_circuit_plan *plan, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z, int8_t *true_z,
+                                   int8_t *sparse_x, int8_t *true_x, uint8_t *level, double *prior_z, double *prior_x);
 
 /* ---- recorded detection events in place of the sampler: events -> decode -> OSD -> predict.  New here: the reference has no counterpart. ---------
  * The second front door of a circuit plan, for plans of qldpc_circuit_plan_create and _create_dem alike: the syndromes come from the caller's records

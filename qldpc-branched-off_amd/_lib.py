@@ -699,6 +699,49 @@ def erasure_priors(erased, tables):
     return prior
 
 
+def soft_table_args(tables, n=None, n_meas=None):
+    """One sector's soft tables -- an object with meas_col / meas_w / lut_ptr / lut / levels (simulation.soft.SoftTables) or that 5-tuple ->
+    (contiguous meas_col int32[>= 1], meas_w int32[>= 1], lut_ptr int32, lut f64[>= 1], levels, n_meas).  The shapes are checked here (the library
+    reads n_meas, n + 1 and lut_ptr[n] entries), the rules themselves by the library."""
+    t = tables
+    mc, mw, up, lu, K = (t.meas_col, t.meas_w, t.lut_ptr, t.lut, t.levels) if hasattr(t, "meas_col") else t
+    mc, mw, up, lu = i32(mc).ravel(), i32(mw).ravel(), i32(up).ravel(), f64(lu).ravel()
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f"soft tables: levels must be an integer, got {K!r}")
+    if mc.size != mw.size or (n_meas is not None and mc.size != n_meas):
+        raise ValueError(f"soft tables: meas_col has {mc.size} entries and meas_w {mw.size}" + (f", the plan has {n_meas} measurements" if n_meas is not None else ""))
+    if up.size < 2 or (n is not None and up.size != n + 1):
+        raise ValueError(f"soft tables: lut_ptr has {up.size} entries" + (f", the sector has {n} columns (n + 1 expected)" if n is not None else ""))
+    if lu.size < max(int(up[-1]), 0):
+        raise ValueError(f"soft tables: lut_ptr ends at {int(up[-1])}, lut holds {lu.size} entries")
+    nm = mc.size
+    if nm == 0:
+        mc, mw = np.full(1, -1, np.int32), np.ones(1, np.int32)
+    if lu.size == 0:
+        lu = np.zeros(1, np.float64)
+    return mc, mw, up, lu, int(K), nm
+
+
+def _soft_table_ptrs(t):
+    return ptr(t[0], C.c_int32), ptr(t[1], C.c_int32), ptr(t[2], C.c_int32), ptr(t[3], C.c_double)
+
+
+def soft_priors(levels, tables):
+    """qldpc_soft_priors on host arrays: the level record uint8[B, n_meas] and one sector's tables (soft_table_args) -> the per-shot prior f64[B, n]."""
+    mc, mw, up, lu, K, nm = t = soft_table_args(tables)
+    n = up.size - 1
+    levels = np.ascontiguousarray(levels, np.uint8)
+    if levels.ndim != 2 or levels.shape[1] != nm:
+        raise ValueError(f"levels must be uint8[B, {nm}], got shape {levels.shape}")
+    B = levels.shape[0]
+    prior = np.zeros((B, n), np.float64)
+    if levels.size == 0:
+        levels = np.zeros(1, np.uint8)
+    p = _soft_table_ptrs(t)
+    check(lib().qldpc_soft_priors(C.c_int64(B), C.c_int32(K), C.c_int32(nm), ptr(levels, C.c_uint8), *p[:2], C.c_int32(n), *p[2:], ptr(prior, C.c_double)))
+    return prior
+
+
 def check_window_args(layer_rows, window, commit, m=None):
     """ValueError unless window >= 1, 1 <= commit <= window and layer_rows >= 1 (dividing m when m is given) -> the three as ints."""
     for name, v in (("layer_rows", layer_rows), ("window", window), ("commit", commit)):
@@ -1089,6 +1132,10 @@ class CircuitPlan(Owner):
         self.fixed_weight = None                            # the sampler axis: None = the independent draws, else the weight in force
         self.erasure_rates = None                           # ... and None = no erasure noise, else the rates in force (f64[7] by op code)
         self.noise_model = None                             # ... and None = the plan's own p and uniform Paulis, else the NoiseModel in force
+        self.soft_readout = None                            # ... and None = hard measurements, else the simulation.soft.SoftReadout in force
+        from .noise.constants import GATE_TO_OPCODE as OP
+        base_ops = np.asarray(compiled.base_ops if hasattr(compiled, "base_ops") else compiled["base_ops"])
+        self.n_meas = int(np.isin(base_ops, (OP["MeasX"], OP["MeasZ"])).sum())      # what the level record of sample_soft counts
         self.graph_z, self.graph_x = graph_z, graph_x
         self.flags = flags
         self._h = C.c_void_p()
@@ -1229,6 +1276,49 @@ class CircuitPlan(Owner):
         check(lib().qldpc_circuit_plan_use_erasure_aware(self._h, alpha, *_erasure_table_ptrs(keep[0]), *_erasure_table_ptrs(keep[1])))
         self.erasure_aware = {"alpha": alpha}
 
+    def use_soft_readout(self, readout):
+        """Draw a soft readout per measurement on top of the plan's ordinary faults from now on (qldpc_circuit_plan_use_soft_readout): `readout` is a
+        simulation.soft.SoftReadout; None: hard measurements again.  The sampler axis, beside use_fixed_weight, use_erasure_noise and use_noise_model
+        (soft readout refuses all three, and they refuse it): two-way, and it goes with every other use_* in either order.  Circuit plans only."""
+        if readout is None:
+            check(lib().qldpc_circuit_plan_use_soft_readout(self._h, C.c_int32(0), None, None))
+            self.soft_readout = None
+            return
+        from .simulation.soft import SoftReadout
+        if not isinstance(readout, SoftReadout):
+            raise ValueError(f"use_soft_readout takes a simulation.soft.SoftReadout (or None), got {readout!r}")
+        f, k = f64(readout.flip_mass), f64(readout.keep_mass)
+        check(lib().qldpc_circuit_plan_use_soft_readout(self._h, C.c_int32(readout.levels), ptr(f, C.c_double), ptr(k, C.c_double)))
+        self.soft_readout = readout
+
+    def use_soft_aware(self, alpha=1.0, tables=None):
+        """Decode both sectors with the readout levels from now on (qldpc_circuit_plan_use_soft_aware): constant-alpha min-sum whose prior is computed
+        per shot from the sampler's level record.  tables: (sector Z, sector X), each a simulation.soft.SoftTables or its 5-tuple -- what
+        soft_tables_from_circuit returns.  The plan's max_iter and clip_llr apply, its alpha table does not.  Goes with OSD-0, OSD-CS (which still
+        scores with the shared prior) and LSD; with no other path; circuit plans only.  Again with new arguments is allowed."""
+        alpha = shotprior_params(alpha)[0]
+        if tables is None or len(tables) != 2:
+            raise ValueError("use_soft_aware needs the tables of both sectors (simulation.soft.soft_tables_from_circuit)")
+        ns = [g.n if g is not None else None for g in (self.graph_z, self.graph_x)]
+        keep = [soft_table_args(t, n, self.n_meas) for t, n in zip(tables, ns)]
+        if keep[0][4] != keep[1][4]:
+            raise ValueError(f"use_soft_aware: the tables of sector Z have {keep[0][4]} levels, those of sector X {keep[1][4]}")
+        check(lib().qldpc_circuit_plan_use_soft_aware(self._h, alpha, C.c_int32(keep[0][4]), *_soft_table_ptrs(keep[0]), *_soft_table_ptrs(keep[1])))
+        self.soft_aware = {"alpha": alpha, "levels": keep[0][4]}
+
+    def sample_soft(self, seed, trial_begin, count, want_priors=False):
+        """sample() plus the level record -> (sparse_z, true_z, sparse_x, true_x, levels uint8[count, n_meas]) and, with want_priors (the soft-aware
+        path), the per-shot priors f64[count, n_z], f64[count, n_x] the plan decodes those trials with (qldpc_circuit_plan_sample_soft)."""
+        spz, spx = np.zeros((count, self.nsx), np.int8), np.zeros((count, self.nsz), np.int8)
+        tz, tx = np.zeros((count, self.k), np.int8), np.zeros((count, self.k), np.int8)
+        levels = np.zeros((count, self.n_meas), np.uint8)
+        pz = np.zeros((count, self.graph_z.n), np.float64) if want_priors else None
+        px = np.zeros((count, self.graph_x.n), np.float64) if want_priors else None
+        check(lib().qldpc_circuit_plan_sample_soft(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), ptr(spz, C.c_int8),
+                                                   ptr(tz, C.c_int8), ptr(spx, C.c_int8), ptr(tx, C.c_int8), ptr(levels, C.c_uint8),
+                                                   ptr(pz, C.c_double) if want_priors else None, ptr(px, C.c_double) if want_priors else None))
+        return (spz, tz, spx, tx, levels, pz, px) if want_priors else (spz, tz, spx, tx, levels)
+
     def sample_erasures(self, seed, trial_begin, count, want_priors=False):
         """sample() plus the herald record -> (sparse_z, true_z, sparse_x, true_x, erased uint32[count, ceil(n_locs / 32)]) and, with want_priors (the
         erasure-aware path), the per-shot priors f64[count, n_z], f64[count, n_x] the plan decodes those trials with (qldpc_circuit_plan_sample_erasures)."""
@@ -1364,6 +1454,8 @@ class DemPlan(CircuitPlan):
         self.fixed_weight = None
         self.erasure_rates = None
         self.noise_model = None
+        self.soft_readout = None
+        self.n_meas = 0
         self.graph_z, self.graph_x = g[0], g[1]
         self.flags = flags
         opt = lambda a, t: ptr(a, t) if a is not None else None

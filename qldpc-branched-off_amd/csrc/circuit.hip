@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace qldpc {
@@ -142,7 +143,7 @@ __global__ void collect_failed2_kernel(int64_t B, const uint8_t *__restrict__ co
 using namespace qldpc;
 
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
-enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED, ERASURE };      // who fills the BP bracket and its follow-up
+enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED, ERASURE, SOFT };      // who fills the BP bracket and its follow-up
 enum class Osd { OSD0, CS, LSD };                                     // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
 
 struct qldpc_circuit_plan {
@@ -162,6 +163,8 @@ struct qldpc_circuit_plan {
         DevBuf d_evtab, d_pred;
         // Path::ERASURE (erasure.hip): the sector's tables location -> (column, h) and column -> lut run; the per-shot prior f64[batch][n] of a batch
         DevBuf d_er_ptr, d_er_col, d_er_h, d_er_lutptr, d_er_lut, d_eprior;
+        // Path::SOFT (soft.hip): the sector's tables measurement -> (column, weight) and column -> lut run; its per-shot prior shares d_eprior
+        DevBuf d_so_col, d_so_w, d_so_lutptr, d_so_lut;
         bool ev_tab = false;
         int ev_base = 0;
         // the decoder objects of a path, below the buffers they write so that they go first (each waits for what it has in flight)
@@ -214,6 +217,15 @@ struct qldpc_circuit_plan {
     bool noise_model = false;
     NoiseModelHost nm{};
     DevBuf d_loc_cls;
+    // ... and a fourth, qldpc_circuit_plan_use_soft_readout: a confidence level and a flip per measurement on top of the independent draws (soft.hip);
+    // sr: the checked readout channel; n_meas: the MeasX / MeasZ locations (-1 until soft_prepare counts them); d_meas_rank: a location's rank
+    // among them; d_levels: the level record uint8[batch][n_meas] of a batch.  Soft readout refuses the three other switches of the axis.
+    bool soft = false;
+    SoftReadoutHost sr{};
+    int n_meas = -1;
+    DevBuf d_meas_rank, d_levels;
+    double soft_alpha = 1.0;                       // Path::SOFT: constant alpha
+    int soft_levels = 0;                           // Path::SOFT: the K its tables were built for
     int32_t *fail_count(int sector) { return d_count.as<int32_t>() + 4 * sector; }
     bool osd_stage() const { return use_osd && path != Path::RELAY; }            // the judge then adds d_count to the OSD tally slots
     ~qldpc_circuit_plan() {                        // the events; the sectors' decoder objects and every buffer then release themselves
@@ -519,6 +531,11 @@ static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, i
         return noise_model_sample_launch(B, begin, seed, P->nm, P->n_locs, P->d_loc_cls.as<uint32_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(),
                                          X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
                                          zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
+    if (P->soft)
+        return soft_sample_launch(B, begin, seed, P->thr, P->sr, P->n_locs, P->d_loc_type.as<uint8_t>(), P->d_loc_cls.as<uint32_t>(),
+                                  P->d_meas_rank.as<int32_t>(), P->n_meas, sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(),
+                                  Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(), P->d_levels.as<uint8_t>(),
+                                  zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
     const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
     const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
     const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
@@ -536,8 +553,16 @@ static int launch_erasure_prior(qldpc_circuit_plan *P, int sector, int64_t B, hi
                                 S.g->n, S.d_er_lutptr.as<int32_t>(), S.d_er_lut.as<double>(), S.d_eprior.as<double>(), s);
 }
 
+// Path::SOFT: the per-shot prior of sector `sector` from the level record of the batch in d_levels
+static int launch_soft_prior(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s) {
+    const Sector &S = P->sec[sector];
+    return soft_prior_launch(P->device, B, P->soft_levels, P->n_meas, P->d_levels.as<uint8_t>(), S.d_so_col.as<int32_t>(), S.d_so_w.as<int32_t>(), S.g->n,
+                             S.d_so_lutptr.as<int32_t>(), S.d_so_lut.as<double>(), S.d_eprior.as<double>(), s);
+}
+
 // enqueues the decode of sector `sector` (0 = Z, 1 = X) of a batch on s, inside that sector's phase brackets.  heralds: the batch came from the
-// erasure sampler and d_eprior holds its per-shot priors (Path::ERASURE reads them; without, it decodes with the plan's prior)
+// erasure sampler (or the soft-readout sampler) and d_eprior holds its per-shot priors (Path::ERASURE and Path::SOFT read them; without, they
+// decode with the plan's prior)
 static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream_t s, uint64_t seed, int64_t trial_begin, bool heralds = false) {
     Sector &S = P->sec[sector];
     const qldpc_graph *g = S.g;
@@ -581,11 +606,12 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
                                      S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), nullptr, s);
         break;
     }
-    case Path::ERASURE: {      // the per-shot-prior kernel with no links: prior[B][n] of the batch's heralds, or the plan's prior where there are none
+    case Path::ERASURE:        // the per-shot-prior kernel with no links: prior[B][n] of the batch's heralds, or the plan's prior where there are none
+    case Path::SOFT: {         // ... and the same launch for the batch's readout levels
         const ShotLinks none{0, nullptr, nullptr, nullptr, nullptr};
         std::lock_guard<std::mutex> lk(g->mu);
         rc = shotprior_decode_launch(g, B, S.d_syn.as<int8_t>(), heralds ? S.d_eprior.as<double>() : S.d_prior.as<double>(), heralds ? g->n : 0, none,
-                                     P->era_alpha, P->clip, P->max_iter, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(),
+                                     P->path == Path::SOFT ? P->soft_alpha : P->era_alpha, P->clip, P->max_iter, -1, S.d_det.as<int8_t>(), S.d_llr.as<double>(), S.d_conv.as<uint8_t>(),
                                      S.d_iter.as<int32_t>(), nullptr, s);
         break;
     }
@@ -644,9 +670,10 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         if (P->pending.size() > 256) drain_phases(P, false);         // a caller that never reads phase times: recycle finished brackets (bounded event count)
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, s, true)) != QLDPC_OK) return rc;
-        const bool heralds = P->erasure && P->path == Path::ERASURE;       // (the prior kernels count as sampling: they turn the draws into the decoder's input)
+        const bool levels = P->soft && P->path == Path::SOFT;
+        const bool heralds = (P->erasure && P->path == Path::ERASURE) || levels;       // (the prior kernels count as sampling: they turn the draws into the decoder's input)
         for (int sector = 0; heralds && sector < P->nsec; sector++)
-            if ((rc = launch_erasure_prior(P, sector, B, s)) != QLDPC_OK) return rc;
+            if ((rc = levels ? launch_soft_prior(P, sector, B, s) : launch_erasure_prior(P, sector, B, s)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
         for (int sector = 0; sector < P->nsec; sector++)
             if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off, heralds)) != QLDPC_OK) return rc;
@@ -744,20 +771,20 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 
 // The switch rules, once.  A plan decodes on two axes, and qldpc_circuit_plan_use_* moves it along one of them:
 //   Path: who fills the BP bracket and its follow-up -- flooding min-sum (as created), the layered schedule, guided decimation, single precision (f32),
-//     Relay-BP, sliding windows, correlated two-sector decoding or erasure-aware decoding.  A plan leaves flooding at most once.  Asking again for the
-//     path it is on brings new arguments (Relay-BP, layered, decimation, correlated, erasure-aware), changes nothing (f32) or is refused (windows).
+//     Relay-BP, sliding windows, correlated two-sector decoding, erasure-aware or soft-aware decoding.  A plan leaves flooding at most once.  Asking again for the
+//     path it is on brings new arguments (Relay-BP, layered, decimation, correlated, erasure-aware, soft-aware), changes nothing (f32) or is refused (windows).
 //   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation, f32,
-//     correlated and erasure-aware whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
+//     correlated, erasure-aware and soft-aware whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
 //     refuse each other in either order.
-//   Windows need use_osd as well; Relay-BP, layered, decimation, f32, correlated and erasure-aware do not.  Windows, layered, decimation, f32,
-//   correlated and erasure-aware need damping = 1.
+//   Windows need use_osd as well; Relay-BP, layered, decimation, f32, correlated, erasure-aware and soft-aware do not.  Windows, layered,
+//   decimation, f32, correlated, erasure-aware and soft-aware need damping = 1.
 // Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation, correlated: finite priors and a supported graph;
-// correlated: two sectors; erasure-aware: what correlated's kernel needs, and a circuit plan).
+// correlated: two sectors; erasure-aware and soft-aware: what correlated's kernel needs, and a circuit plan).
 // `to`: the path asked for; Path::FLOOD stands for a request on the other axis, for the OSD stage `stage` (no call asks for flooding).
 // QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
 static int switch_allowed(const qldpc_circuit_plan *P, Path to, Osd stage = Osd::CS) {
     static const char *const path_name[] = {"BP + OSD-0", "the layered schedule", "guided decimation", "single precision (f32)", "Relay-BP", "sliding-window decoding", "correlated decoding",
-                                             "erasure-aware decoding"};
+                                             "erasure-aware decoding", "soft-aware decoding"};
     static const char *const osd_name[] = {"BP + OSD-0", "BP + OSD-CS", "BP + LSD"};
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
     const bool cs = to == Path::FLOOD;                                   // a request on the OSD axis: `stage` says for which of the two
@@ -942,6 +969,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *P, int 
     if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a fixed weight counts the faults of the independent draws alone (switch erasure noise off first)");
     QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the fixed-weight law needs one p for every location (switch the noise model off first)");
+    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: a fixed weight counts the faults of the independent draws alone (switch soft readout off first)");
     QLDPC_REQUIRE(!P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
                   "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
     P->fixed_weight = weight;
@@ -956,6 +984,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *P, con
     QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: erasure noise goes with the independent draws (switch the fixed weight off first)",
                   P->fixed_weight);
     QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the erasure sampler draws its ordinary faults at one p (switch the noise model off first)");
+    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: erasure noise does not compose with readout levels (switch soft readout off first)");
     uint32_t thr[8];
     int rc = erasure_rates_check(rate, thr);
     if (rc != QLDPC_OK || (rc = erasure_sample_supported(P->sec[0].nsyn, P->sec[1].nsyn, P->n_locs)) != QLDPC_OK) return rc;
@@ -974,6 +1003,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *P, const
     QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: that law needs one p for every location (switch the fixed weight off first)",
                   P->fixed_weight);
     QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a noise model does not compose with heralded erasures (switch erasure noise off first)");
+    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: a noise model does not compose with readout levels (switch soft readout off first)");
     NoiseModelHost nm;
     int rc = noise_model_check(model, &nm);
     if (rc != QLDPC_OK) return rc;
@@ -987,6 +1017,143 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *P, const
     }
     P->nm = nm;
     P->noise_model = true;
+    return QLDPC_OK;
+}
+
+// What both soft switches need of a circuit plan, once: the packed classes (as the noise model's sampler reads them), the rank of every MeasX / MeasZ
+// location among them and their number.  All or none.
+static int soft_prepare(qldpc_circuit_plan *P) {
+    if (P->n_meas >= 0) return QLDPC_OK;
+    QLDPC_USE_DEVICE(P->device);
+    std::vector<uint8_t> loc_type((size_t)P->n_locs);
+    if (P->n_locs) QLDPC_HIP_TRY(hipMemcpy(loc_type.data(), P->d_loc_type.p, loc_type.size(), hipMemcpyDeviceToHost));
+    std::vector<int32_t> rank(std::max<size_t>(loc_type.size(), 1), -1);
+    int n_meas = 0;
+    for (size_t l = 0; l < loc_type.size(); l++)
+        if (loc_type[l] == C_OP_MEAS_X || loc_type[l] == C_OP_MEAS_Z) rank[l] = n_meas++;
+    int rc;
+    DevBuf cls, rk;
+    if ((rc = upload(rk, rank)) != QLDPC_OK) return rc;
+    if (!P->d_loc_cls.p) {
+        if ((rc = upload(cls, noise_model_pack_classes(loc_type))) != QLDPC_OK) return rc;
+        P->d_loc_cls = std::move(cls);
+    }
+    P->d_meas_rank = std::move(rk);
+    P->n_meas = n_meas;
+    return QLDPC_OK;
+}
+static size_t levels_bytes(const qldpc_circuit_plan *P) { return (size_t)P->batch * (size_t)P->n_meas + 4; }
+
+// The sampler axis a fourth time: a confidence level and a flip per measurement on top of the independent draws (soft.hip).  flip_mass NULL = off.
+QLDPC_EXPORT int qldpc_circuit_plan_use_soft_readout(qldpc_circuit_plan *P, int32_t levels, const double *flip_mass, const double *keep_mass) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    if (flip_mass == nullptr) { P->soft = false; return QLDPC_OK; }
+    QLDPC_REQUIRE(!P->dem, "soft readout needs a circuit plan: a detector error model has no measurement locations");
+    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: soft readout goes with the independent draws (switch the fixed weight off first)",
+                  P->fixed_weight);
+    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: soft readout does not compose with heralded erasures (switch erasure noise off first)");
+    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the soft-readout sampler draws its ordinary faults at one p (switch the noise model off first)");
+    SoftReadoutHost sr;
+    int rc = soft_readout_check(levels, flip_mass, keep_mass, &sr);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(P->path != Path::SOFT || P->soft_levels == levels, "the plan decodes soft-aware with tables for %d levels: a readout with %d levels does not go with them",
+                  P->soft_levels, levels);
+    if ((rc = soft_prepare(P)) != QLDPC_OK) return rc;
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_levels.ensure(levels_bytes(P))) != QLDPC_OK) return rc;
+    P->sr = sr;
+    P->soft = true;
+    return QLDPC_OK;
+}
+
+// One sector's tables of qldpc_circuit_plan_use_soft_aware (host pointers).
+struct SoftTabIn { const int32_t *meas_col, *meas_w, *lut_ptr; const double *lut; };
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_soft_aware(qldpc_circuit_plan *P, double alpha, int32_t levels, const int32_t *meas_col_z, const int32_t *meas_w_z,
+                                                   const int32_t *lut_ptr_z, const double *lut_z, const int32_t *meas_col_x, const int32_t *meas_w_x,
+                                                   const int32_t *lut_ptr_x, const double *lut_x) {
+    int rc = switch_allowed(P, Path::SOFT);
+    if (rc != QLDPC_OK) return rc;
+    QLDPC_REQUIRE(!P->dem, "soft-aware decoding needs a circuit plan: a detector error model has no measurement locations to read levels from");
+    QLDPC_REQUIRE(!P->soft || P->sr.levels == levels, "the plan samples soft readout with %d levels: tables for %d levels do not go with it", P->sr.levels, levels);
+    if ((rc = soft_prepare(P)) != QLDPC_OK) return rc;
+    const SoftTabIn in[2] = {{meas_col_z, meas_w_z, lut_ptr_z, lut_z}, {meas_col_x, meas_w_x, lut_ptr_x, lut_x}};
+    for (int i = 0; i < 2; i++) {
+        const Sector &S = P->sec[i];
+        QLDPC_REQUIRE(in[i].lut_ptr && in[i].lut && (P->n_meas == 0 || (in[i].meas_col && in[i].meas_w)), "sector %c: meas_col, meas_w, lut_ptr or lut is NULL", "ZX"[i]);
+        if ((rc = soft_check_tables(levels, P->n_meas, in[i].meas_col, in[i].meas_w, S.g->n, in[i].lut_ptr, in[i].lut)) != QLDPC_OK) {
+            const std::string why = qldpc_last_error();
+            set_error("sector %c: %s", "ZX"[i], why.c_str());
+            return rc;
+        }
+        for (int j = 0; j < S.g->n; j++)      // a run of length 1 is the plan's own prior, verbatim: a plan without levels decodes a column without measurements as ever
+            QLDPC_REQUIRE(in[i].lut_ptr[j + 1] - in[i].lut_ptr[j] != 1 || std::memcmp(&in[i].lut[in[i].lut_ptr[j]], &S.h_prior[j], 8) == 0,
+                          "sector %c: lut[lut_ptr[%d]] = %.17g is not the plan's prior %.17g of column %d, which has no measurement", "ZX"[i], j,
+                          in[i].lut[in[i].lut_ptr[j]], S.h_prior[j], j);
+        if ((rc = soft_prior_supported(S.g->n)) != QLDPC_OK) return rc;
+    }
+    if ((rc = inputs_supported(P, shotprior_check_params(alpha, P->clip, P->max_iter),
+                               [](const qldpc_graph *g) { return shotprior_mode(g) ? QLDPC_OK : shotprior_unsupported(g); })) != QLDPC_OK)
+        return rc;
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a decode that is still enqueued reads the tables replaced here
+    DevBuf nb[2][4];                                                     // all or none: a failed upload leaves the plan's tables as they were
+    for (int i = 0; i < 2; i++) {
+        const size_t nm = (size_t)P->n_meas, n = (size_t)P->sec[i].g->n;
+        if ((rc = upload(nb[i][0], nm ? std::vector<int32_t>(in[i].meas_col, in[i].meas_col + nm) : std::vector<int32_t>(1, -1))) ||
+            (rc = upload(nb[i][1], nm ? std::vector<int32_t>(in[i].meas_w, in[i].meas_w + nm) : std::vector<int32_t>(1, 1))) ||
+            (rc = upload(nb[i][2], std::vector<int32_t>(in[i].lut_ptr, in[i].lut_ptr + n + 1))) ||
+            (rc = upload(nb[i][3], std::vector<double>(in[i].lut, in[i].lut + in[i].lut_ptr[n]))))
+            return rc;
+    }
+    for (int i = 0; i < 2; i++)
+        if ((rc = P->sec[i].d_eprior.ensure((size_t)P->batch * (size_t)P->sec[i].g->n * 8)) != QLDPC_OK) return rc;
+    if ((rc = P->d_levels.ensure(levels_bytes(P))) != QLDPC_OK) return rc;
+    for (int i = 0; i < 2; i++) {
+        Sector &S = P->sec[i];
+        S.d_so_col = std::move(nb[i][0]); S.d_so_w = std::move(nb[i][1]); S.d_so_lutptr = std::move(nb[i][2]); S.d_so_lut = std::move(nb[i][3]);
+    }
+    P->soft_alpha = alpha;
+    P->soft_levels = levels;
+    P->path = Path::SOFT;
+    return QLDPC_OK;
+}
+
+// qldpc_circuit_plan_sample plus the level record and, where asked for, the per-shot priors of both sectors (host pointers)
+QLDPC_EXPORT int qldpc_circuit_plan_sample_soft(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z, int8_t *true_z,
+                                                int8_t *sparse_x, int8_t *true_x, uint8_t *level, double *prior_z, double *prior_x) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(!P->dem, "sample_soft needs a circuit plan: a detector error model has no measurement locations");
+    QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
+    QLDPC_REQUIRE((prior_z == nullptr) == (prior_x == nullptr), "prior_z and prior_x are both NULL or both given");
+    QLDPC_REQUIRE(!prior_z || P->path == Path::SOFT, "the per-shot priors need the tables of qldpc_circuit_plan_use_soft_aware");
+    int rc = soft_prepare(P);
+    if (rc != QLDPC_OK) return rc;
+    const size_t nm = (size_t)P->n_meas;
+    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x && (level || nm == 0)), "NULL output");
+    QLDPC_USE_DEVICE(P->device);
+    if ((rc = P->d_levels.ensure(levels_bytes(P))) != QLDPC_OK) return rc;
+    int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
+    double *const prior[2] = {prior_z, prior_x};
+    std::vector<unsigned long long> t;
+    for (int64_t off = 0; off < count; off += P->batch) {
+        const int64_t B = std::min<int64_t>(P->batch, count - off);
+        if (!P->soft) QLDPC_HIP_TRY(hipMemsetAsync(P->d_levels.p, 0, (size_t)B * nm + 4, nullptr));      // the switch is off: every level is 0
+        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
+        for (int i = 0; prior_z && i < 2; i++)
+            if ((rc = launch_soft_prior(P, i, B, nullptr)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(hipDeviceSynchronize());
+        t.resize(B);
+        if (nm) QLDPC_HIP_TRY(hipMemcpy(level + off * nm, P->d_levels.p, (size_t)B * nm, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 2; i++) {
+            const Sector &S = P->sec[i];
+            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
+            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+            for (int64_t b = 0; b < B; b++)
+                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
+            if (prior[i]) QLDPC_HIP_TRY(hipMemcpy(prior[i] + off * S.g->n, S.d_eprior.p, (size_t)B * S.g->n * 8, hipMemcpyDeviceToHost));
+        }
+    }
     return QLDPC_OK;
 }
 

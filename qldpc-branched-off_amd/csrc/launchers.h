@@ -221,6 +221,21 @@ std::vector<uint32_t> noise_model_pack_classes(const std::vector<uint8_t> &loc_t
 int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, const NoiseModelHost &M, int n_locs, const uint32_t *d_loc_cls,
                               const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
                               unsigned long long *d_true_z, unsigned long long *d_true_x, int32_t *d_fail_counts, hipStream_t s);
+// Soft-readout noise of a circuit plan (soft.hip).  SoftReadoutHost: what checked masses become on the host -- K and the 2K cuts of the law (uint64:
+// the last is 2^32).  readout_check: the rules of qldpc_circuit_plan_use_soft_readout on the masses alone, QLDPC_ERR_INVALID with the text naming the
+// index.  sample: circuit_sample_kernel's draws at threshold thr plus the readout bins, the level record uint8[B][n_meas] written to d_levels;
+// d_loc_cls is noise_model_pack_classes' array on the device, d_meas_rank int32[n_locs] the rank of a MeasX / MeasZ location among them.  prior: levels
+// and the tables of one sector (device pointers) -> d_prior f64[B][n].  check_tables: the table rules of qldpc_soft_priors on host arrays,
+// QLDPC_ERR_INVALID with the text naming the offending index.  prior_supported: QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the text set (LDS).
+struct SoftReadoutHost { int levels; uint64_t cut[32]; };
+int soft_readout_check(int levels, const double *flip_mass, const double *keep_mass, SoftReadoutHost *out);
+int soft_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const SoftReadoutHost &R, int n_locs, const uint8_t *d_loc_type,
+                       const uint32_t *d_loc_cls, const int32_t *d_meas_rank, int n_meas, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z,
+                       int8_t *d_syn_x, unsigned long long *d_true_z, unsigned long long *d_true_x, uint8_t *d_levels, int32_t *d_fail_counts, hipStream_t s);
+int soft_check_tables(int levels, int n_meas, const int32_t *meas_col, const int32_t *meas_w, int n, const int32_t *lut_ptr, const double *lut);
+int soft_prior_supported(int n);
+int soft_prior_launch(int device, int64_t B, int levels, int n_meas, const uint8_t *d_levels, const int32_t *d_meas_col, const int32_t *d_meas_w, int n,
+                      const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, hipStream_t s);
 // Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
 // only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
 // predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does

@@ -320,7 +320,7 @@ def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder
 
 def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode=None, alvarado_alpha=None, base_seed=None, target_logical_errors=None,
                        max_trials=None, batch=16384, device=None, devices=None, num_workers=None, flags=0, decoder="bp_osd", relay_params=None, window=None,
-                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None):
+                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, soft=None):
     """``run_simulation`` for a DetectorErrorModel: the same result keys, in-order early stop (``target_logical_errors``), ``num_workers`` / ``devices`` and
     extensions (``decoder`` with ``lsd`` for ``"bp_lsd"``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``, ``correlated`` with the links of
     ``correlated.links_from_dem``) under the same argument rules; sector 0 fills the ``z``
@@ -328,10 +328,12 @@ def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode
 
     Out of scope (ValueError before any device call): the alpha / SCOPT estimators, which draw errors at one error rate -- use ``alpha_mode="dynamical"``
     (the default) or ``"alvarado"`` with an explicit ``alvarado_alpha`` (a number or a pair) -- and ``osd_order > 0`` with ``decoder="bp_osd"`` (the
-    reference's OSD-w pass; ``decoder="bp_osd_cs"`` is the higher-order OSD of the fused pipeline) -- and ``erasure=...``: heralded erasures belong to
-    gate locations, which a detector error model does not have."""
+    reference's OSD-w pass; ``decoder="bp_osd_cs"`` is the higher-order OSD of the fused pipeline) -- and ``erasure=...`` / ``soft=...``: heralded erasures and
+    readout levels belong to gate locations, which a detector error model does not have."""
     if erasure is not None:
         raise ValueError("run_dem_simulation: erasure=... needs a circuit plan (run_simulation): a detector error model has no gate locations to erase")
+    if soft is not None:
+        raise ValueError("run_dem_simulation: soft=... needs a circuit plan (run_simulation): a detector error model has no measurement locations")
     rules, alpha_mode, alphas = _dem_rules("run_dem_simulation", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers,
                                            decimation, precision, num_workers, lsd=lsd, correlated=correlated)
     rank, world, devices = engine._worker_devices(num_workers, devices, device)

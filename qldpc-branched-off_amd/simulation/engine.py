@@ -23,7 +23,7 @@ Differences that are deliberate and documented:
   * ``target_logical_errors`` stops at the exact trial the reference would (in-order prefix cut over per-trial verdicts).
 
 The extensions below choose what a worker's plan decodes with, on the plan's two axes.  The path: at most one of
-``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...``, ``precision="f32"``, ``correlated=...`` and ``erasure={..., "aware": True}`` leaves flooding min-sum, and none of them
+``decoder="relay_bp"``, ``window=...``, ``schedule="layered"``, ``decimation=...``, ``precision="f32"``, ``correlated=...``, ``erasure={..., "aware": True}`` and ``soft={..., "aware": True}`` leaves flooding min-sum, and none of them
 goes with the reference's OSD-w pass (``osd_order > 0`` with ``decoder="bp_osd"``).  The OSD stage: ``decoder="bp_osd_cs"`` puts OSD-CS in the place
 of OSD-0 and ``decoder="bp_lsd"`` puts BP+LSD there; each goes with every path but Relay-BP (which has no OSD stage) and windows.  Anything else raises ValueError before any device call.
 
@@ -81,6 +81,15 @@ is the constant of the dict as for ``correlated``, and OSD-0, OSD-CS (which stil
 ``aware=False`` only the sampler changes -- the sampler axis -- and every path and decoder goes with it: the decoder does not see the heralds.  The result
 also holds ``erasure`` (rates as f64[7] by op code, aware, alpha).  Circuit plans only: ``run_weight_strata`` and ``run_dem_simulation`` raise ValueError.
 
+``soft={"sigma": 0.4, "levels": 8, "aware": True, "alpha": 1.0}`` (an extension; None is today's behaviour; ``levels`` defaults to 8, ``aware`` to True
+and ``alpha`` to 1.0; ``{"readout": SoftReadout(...)}`` gives the channel itself) adds soft-readout noise to the sampler (``simulation/soft.py``,
+``CircuitPlan.use_soft_readout``): every measurement gets a readout flip and a confidence level.  With ``aware=True`` both sectors are decoded with a
+per-shot prior built from the levels (``CircuitPlan.use_soft_aware``, the tables of ``soft_tables_from_circuit``): a decode path under the rules of
+``erasure``'s.  With ``aware=False`` only the sampler changes and every path and decoder goes with it.  With ``matched_priors=True`` (the default) the
+plan's priors are ``marginal_priors`` -- the readout's marginal flip rate folded into the measured columns, what a decoder that does not read the levels
+should believe -- else the plain ones.  It goes with neither ``erasure`` nor ``noise_model``.  The result also holds ``soft`` (readout, aware, alpha) and
+``matched_priors``.
+
 ``noise_model=NoiseModel(...)`` (an extension; None is today's behaviour) replaces the sampler's one rate and uniform Paulis by a rate per location class
 and, optionally, weighted Paulis on faulty IDLEs and CNOTs (``simulation/noise_model.py``, ``CircuitPlan.use_noise_model``): the sampler axis, so every
 path and decoder goes with it.  The decoding matrices are built or loaded at ``error_rate`` as without it -- their columns do not depend on the rates
@@ -123,12 +132,13 @@ def _estimation_trials(requested, n_cols, error_rate):
 
 
 def _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha, use_dynamic_alpha, scopt,
-                     maxIter, num_workers, lsd=None, correlated=None, erasure=None):
+                     maxIter, num_workers, lsd=None, correlated=None, erasure=None, soft=None):
     """The argument rules of the extensions (decoder, window, schedule, layers, decimation, precision, correlated), shared by run_simulation and
     run_dem_simulation: raises ValueError before any device call.  Returns the call on the plan's two axes -- ``path`` ("flooding", "layered",
     "decimation", "f32", "relay", "window", "correlated" or "erasure": who decodes the BP stage) and the OSD stage, ``osd_cs`` (OSD-CS instead of OSD-0) or ``lsd`` (BP+LSD instead of OSD-0: its normalised
     parameters, else None) -- with the normalised parameters of that path (``layers``, ``decimation``, ``relay_params``, ``window``, ``correlated``; None
-    where the path is another) and ``erasure`` (the sampler axis: rates f64[7], aware, alpha; None without erasure noise)."""
+    where the path is another), ``erasure`` (the sampler axis: rates f64[7], aware, alpha; None without erasure noise) and ``soft`` (the sampler axis
+    again: readout, aware, alpha; None without soft readout; "soft" is the path where it is aware)."""
     if osd_order < 0:
         raise ValueError("osd_order must be >= 0")
     if precision not in ("f64", "f32"):
@@ -158,17 +168,34 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
         erasure = {"rates": erasure_rates(erasure["rates"]), "aware": bool(erasure.get("aware", True)),
                    "alpha": _lib.shotprior_params(erasure.get("alpha", 1.0), 20.0, maxIter)[0]}
     aware = erasure is not None and erasure["aware"]
+    if soft is not None:
+        if not isinstance(soft, dict) or ("readout" in soft) == ("sigma" in soft):
+            raise ValueError("soft must be a dict with either sigma (and, optionally, levels and edges) or readout, and, optionally, aware and alpha (or None)")
+        unknown = set(soft) - ({"readout", "aware", "alpha"} if "readout" in soft else {"sigma", "levels", "edges", "aware", "alpha"})
+        if unknown:
+            raise ValueError(f"unknown soft parameter(s): {sorted(unknown)}")
+        if not isinstance(soft.get("aware", True), (bool, np.bool_)):
+            raise ValueError("soft['aware'] must be True or False")
+        if erasure is not None:
+            raise ValueError("soft=... does not go with erasure=... (the two samplers do not compose)")
+        from .soft import SoftReadout
+        readout = soft["readout"] if "readout" in soft else SoftReadout.gaussian(soft["sigma"], soft.get("levels", 8), soft.get("edges"))
+        if not isinstance(readout, SoftReadout):
+            raise ValueError(f"soft['readout'] must be a simulation.soft.SoftReadout, got {readout!r}")
+        soft = {"readout": readout, "aware": bool(soft.get("aware", True)), "alpha": _lib.shotprior_params(soft.get("alpha", 1.0), 20.0, maxIter)[0]}
+    soft_aware = soft is not None and soft["aware"]
     # the path: at most one argument leaves flooding min-sum (the plan's own rule, qldpc_circuit_plan_use_*) ...
     asked = [(path, text) for path, text, given in (("f32", "precision='f32'", precision == "f32"), ("decimation", "decimation=...", decimation is not None),
                                                      ("layered", "schedule='layered'", schedule == "layered"),
                                                      ("window", f"window={window!r}", window is not None), ("relay", "decoder='relay_bp'", decoder == "relay_bp"),
                                                      ("correlated", "correlated=...", correlated is not None),
-                                                     ("erasure", "erasure={..., 'aware': True}", aware))
+                                                     ("erasure", "erasure={..., 'aware': True}", aware),
+                                                     ("soft", "soft={..., 'aware': True}", soft_aware))
              if given]
     if len(asked) > 1:
         (_, one), (_, other) = asked[:2]
         raise ValueError(f"{one} does not go with {other}: {one} goes with none of the others of decoder='relay_bp', window=(W, C), schedule='layered', "
-                         "decimation=..., precision='f32', correlated=... and erasure={..., 'aware': True} (each decodes the BP stage its own way)")
+                         "decimation=..., precision='f32', correlated=..., erasure={..., 'aware': True} and soft={..., 'aware': True} (each decodes the BP stage its own way)")
     path, text = asked[0] if asked else ("flooding", None)
     # ... and none of them goes with the OSD-w pass, which decodes again with flooding min-sum in f64
     if path != "flooding" and decoder == "bp_osd" and osd_order > 0:
@@ -212,6 +239,11 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
                                         ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
         if bad:
             raise ValueError(f"erasure={{..., 'aware': True}} does not use {', '.join(bad)}: its alpha is the constant erasure['alpha']")
+    elif path == "soft":
+        bad = [name for name, given in (("alpha_mode", alpha_mode is not None), ("alvarado_alpha", alvarado_alpha is not None),
+                                        ("use_dynamic_alpha=False", not use_dynamic_alpha), ("scopt", bool(scopt))) if given]
+        if bad:
+            raise ValueError(f"soft={{..., 'aware': True}} does not use {', '.join(bad)}: its alpha is the constant soft['alpha']")
     elif path == "layered":
         mode = alpha_mode if alpha_mode is not None else ("dynamical" if use_dynamic_alpha else "alvarado")
         if mode == "alvarado-autoregressive" or (mode == "alvarado" and alvarado_alpha is None):
@@ -241,13 +273,17 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
     return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window, correlated=correlated,
-                           links=None, erasure=erasure, erasure_tables=None, noise_model=None, matched_priors=True)
+                           links=None, erasure=erasure, erasure_tables=None, noise_model=None, matched_priors=True, soft=soft, soft_tables=None)
 
 
-def _noise_model_rules(who, noise_model, matched_priors, correlated=None, erasure=None):
+def _noise_model_rules(who, noise_model, matched_priors, correlated=None, erasure=None, soft=None):
     """The argument rules of ``noise_model=`` / ``matched_priors=``: raises ValueError before any device call."""
+    if soft is not None and not isinstance(matched_priors, (bool, np.bool_)):
+        raise ValueError(f"{who}: matched_priors must be True or False")
     if noise_model is None:
         return
+    if soft is not None:
+        raise ValueError(f"{who}: noise_model=... does not go with soft=... (the soft-readout sampler draws its ordinary faults at one rate)")
     from .noise_model import NoiseModel
     if not isinstance(noise_model, NoiseModel):
         raise ValueError(f"{who}: noise_model must be a simulation.noise_model.NoiseModel (or None), got {noise_model!r}")
@@ -288,8 +324,8 @@ def _worker_devices(num_workers, devices, device):
 def _plan_switch(rules, csr, osd_order):
     """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
     dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` or LSD in the OSD stage when the rules ask for it, then moves the BP stage to
-    rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links; erasure: with rules.erasure_tables), then
-    switches erasure noise on where rules.erasure asks for it (the sampler axis: last, since it goes with whatever the plan decodes with).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
+    rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links; erasure: with rules.erasure_tables; soft: with
+    rules.soft_tables), then switches erasure noise, a noise model or soft readout on where the rules ask for it (the sampler axis: last, since it goes with whatever the plan decodes with).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
     layers = None
     if rules.path == "layered":
         layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
@@ -297,7 +333,8 @@ def _plan_switch(rules, csr, osd_order):
                "layered": lambda plan: plan.use_layered(*layers), "decimation": lambda plan: plan.use_decimation(**rules.decimation),
                "f32": lambda plan: plan.use_f32(),
                "correlated": lambda plan: plan.use_correlated(rules.correlated["alpha"], rules.links, None if rules.links is None else rules.links.base),
-               "erasure": lambda plan: plan.use_erasure_aware(rules.erasure["alpha"], rules.erasure_tables)}[rules.path]
+               "erasure": lambda plan: plan.use_erasure_aware(rules.erasure["alpha"], rules.erasure_tables),
+               "soft": lambda plan: plan.use_soft_aware(rules.soft["alpha"], rules.soft_tables)}[rules.path]
 
     def switch(plan):
         if rules.osd_cs:
@@ -310,6 +347,8 @@ def _plan_switch(rules, csr, osd_order):
             plan.use_erasure_noise({g: rules.erasure["rates"][i + 1] for i, g in enumerate(GATES)})
         if rules.noise_model is not None:                                        # the sampler axis again
             plan.use_noise_model(rules.noise_model)
+        if rules.soft is not None:                                               # ... and a fourth time
+            plan.use_soft_readout(rules.soft["readout"])
 
     return switch, layers
 
@@ -486,6 +525,8 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         result.update(erasure=dict(rules.erasure))
     if rules.noise_model is not None:
         result.update(noise_model=rules.noise_model, matched_priors=bool(rules.matched_priors))
+    if rules.soft is not None:
+        result.update(soft=dict(rules.soft), matched_priors=bool(rules.matched_priors))
     result["precision"] = precision
     result["tally"] = total
     return result
@@ -524,10 +565,10 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, noise_model=None, matched_priors=True, **bb_params):
-    _noise_model_rules("run_simulation", noise_model, matched_priors, correlated, erasure)
+                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, noise_model=None, matched_priors=True, soft=None, **bb_params):
+    _noise_model_rules("run_simulation", noise_model, matched_priors, correlated, erasure, soft)
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
-                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated, erasure=erasure)
+                             use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated, erasure=erasure, soft=soft)
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:
@@ -554,6 +595,15 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
         rules.noise_model, rules.matched_priors = noise_model, bool(matched_priors)
         if matched_priors:                                                       # the same columns, the model's probabilities
             own_llrs = llrs_z, llrs_x = noise_model.prior_llrs(prob.compiled, Lx, Lz, prob.matrices)
+
+    if rules.soft is not None:
+        from .soft import marginal_priors, soft_tables_from_circuit
+        tables = soft_tables_from_circuit(prob.compiled, Lx, Lz, prob.matrices, rules.soft["readout"])
+        rules.matched_priors = bool(matched_priors)
+        if rules.path == "soft":
+            rules.soft_tables = tables
+        if matched_priors:                                                       # the same columns, the readout's marginal flip rate on the measured ones
+            own_llrs = llrs_z, llrs_x = marginal_priors(prob.matrices, tables, rules.soft["readout"])
 
     # Normalisation factors (engine.py:228-344).  The estimators draw their error patterns from a Generator seeded with
     # base_seed (the reference leaves it unseeded), so every rank of a multi-GPU run derives the same factors.

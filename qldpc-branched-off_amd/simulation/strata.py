@@ -240,10 +240,15 @@ def _refuse_noise_model(who, noise_model):
         raise ValueError(f"{who}: noise_model=... does not go with fixed-weight sampling (the weight strata reweight one rate p for every location)")
 
 
+def _refuse_soft(who, soft):
+    if soft is not None:
+        raise ValueError(f"{who}: soft=... does not go with fixed-weight sampling (a weight stratum counts the faults of the independent draws alone)")
+
+
 def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=None, trials_per_weight=4096, target_failures=None,
                       max_trials_per_weight=None, coverage=1e-9, num_cycles=12, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding",
                       layers=None, decimation=None, precision="f64", relay_params=None, precomputed_matrices=None, device=None, base_seed=0, batch=16384,
-                      flags=0, lsd=None, erasure=None, noise_model=None, **bb_params):
+                      flags=0, lsd=None, erasure=None, noise_model=None, soft=None, **bb_params):
     """One sweep over the number of faults on the circuit plan of ``run_simulation`` -> WeightStrata.
 
     The circuit and decoder arguments are ``run_simulation``'s, under the same rules (``engine._extension_rules``: ValueError before any device call).
@@ -256,9 +261,10 @@ def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=No
     Per weight: ``trials_per_weight`` trials; with ``target_failures``, batches of ``batch`` until that many failures or ``max_trials_per_weight``
     (default ``trials_per_weight``) trials -- whole batches, all counted.
     One plan on a single ``device`` serves the whole sweep; weight w uses the global trial range starting at ``w << 40``.
-    ``erasure=...`` raises ValueError: a weight counts the faults of the independent draws alone, and the plan refuses erasure noise beside it.
+    ``erasure=...`` and ``soft=...`` raise ValueError: a weight counts the faults of the independent draws alone, and the plan refuses both beside it.
     ``noise_model=...`` raises ValueError too: LER(p) is rebuilt from the strata with one rate p for every location, and the plan refuses a model beside a weight."""
     _refuse_erasure("run_weight_strata", erasure)
+    _refuse_soft("run_weight_strata", soft)
     _refuse_noise_model("run_weight_strata", noise_model)
     rules = engine._extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, None, None, True, False, maxIter, None, lsd=lsd)
     if decoder == "bp_osd" and osd_order > 0:
@@ -283,11 +289,12 @@ def run_weight_strata(Hx, Hz, Lx, Lz, prior_error_rate, weights=None, p_range=No
 
 def run_dem_weight_strata(dem, weights=None, p_range=None, trials_per_weight=4096, target_failures=None, max_trials_per_weight=None, coverage=1e-9,
                           maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding", layers=None, decimation=None, precision="f64",
-                          relay_params=None, alpha_mode=None, alvarado_alpha=None, device=None, base_seed=0, batch=16384, flags=0, lsd=None, erasure=None):
+                          relay_params=None, alpha_mode=None, alvarado_alpha=None, device=None, base_seed=0, batch=16384, flags=0, lsd=None, erasure=None, soft=None):
     """``run_weight_strata`` for a DetectorErrorModel whose mechanisms all have ONE probability (N = its mechanisms); the arguments and rules are
     ``run_dem_simulation``'s.  The decoder view -- and with it the priors -- is the model's own, held fixed across the sweep.  A model with two
-    different probabilities raises ValueError before any device call, and so does ``erasure=...``."""
+    different probabilities raises ValueError before any device call, and so do ``erasure=...`` and ``soft=...``."""
     _refuse_erasure("run_dem_weight_strata", erasure)
+    _refuse_soft("run_dem_weight_strata", soft)
     rules, alpha_mode, alphas = dem_mod._dem_rules("run_dem_weight_strata", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window,
                                                    schedule, layers, decimation, precision, lsd=lsd)
     thr = np.floor(dem.prob * 4294967296.0)
