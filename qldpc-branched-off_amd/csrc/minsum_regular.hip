@@ -68,8 +68,8 @@
 //   * class-uniform waves (PLACE; qldpc_set_option("regular_wave_classes", 0) turns them off).  The eight v_cndmask_b32 of the ownership form exist only because
 //     `last` differs from lane to lane.  A placed table is therefore built from the assignment that owns the FEWEST last edges (regular_own.h: min-cost
 //     flow) and deals the (slot, check) items of a workgroup to its threads so that whole waves hold checks that own no last edge (regular_place.h); the
-//     record names the thread's (slot, member) and its wave's class, and in the bare passes such a wave takes, by one scalar branch, the arm that adds
-//     (o1 + own) + o2 without a select.  Why no output word moves:
+//     record names the thread's (slot, member) and its wave's class, and in the bare passes such a wave runs straight through the sums (o1 + own) + o2,
+//     without a select: one forward branch, not taken, and the back-edge; the other waves' sums sit out of line behind that branch.  Why no output word moves:
 //       assignment   every perfect assignment gives the reference's words (regular_own.h, header: the sum is the ascending-order sum whichever of
 //                    the column's three checks owns it);
 //       thread order threads exchange data only through LDS addresses taken from the table, which is built for the order; the leaders of a team are
@@ -481,13 +481,26 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             // so no pass reads Al from LDS; the table A.alpha is never written by a kernel, hence the constant address space
             const __attribute__((address_space(4))) double *alpha_tab = (const __attribute__((address_space(4))) double *)A.alpha;
             double alpha_it = (it < max_iter) ? Al[it] : 0.0;
-            // PLACE: the variable sums of a pass come in two forms, picked per WAVE by one scalar branch (wave_class is wave-uniform, regular_place.h).  A
-            // wave whose team lanes all own no `last` edge adds (o1 + own) + o2 for both columns without a select; every other wave keeps the two selects per
-            // column (a wave of "one" or "both" could have an arm of its own, but they are rare -- none, one and none of eight waves on bb144, bb72 and
-            // bb288 -- and every further copy of the pass, as a loop or as an arm, cost more than it saved: profiles/r27_wave_classes.txt).  Both arms sit
-            // between the same two barriers, so the waves of a workgroup meet at every barrier whichever arm they take.  The empty asm keeps the arm from
-            // being folded back into selects on the class.
+            // PLACE: the variable sums of a pass come in two forms, picked per WAVE (wave_class is wave-uniform, regular_place.h).  A wave whose team lanes
+            // all own no `last` edge adds (o1 + own) + o2 for both columns without a select -- the common wave, seven of eight on bb144; every other wave
+            // keeps the two selects per column.  How it is written decides what the common wave pays.  An if / else on the class comes out of the
+            // compiler's control-flow structurizer as two guarded blocks and a flag, four scalar branches per pass for every wave
+            // (profiles/r27_wave_classes.txt).  An `if` WITHOUT an else survives it as one forward branch: so the select-free sums are written
+            // unconditionally and the form with selects overwrites them under the test.  The sums have no other use, so the code generator sinks them
+            // onto the fall-through edge: the "none" wave runs test, not-taken branch, four adds, and no wave computes a sum twice
+            // (profiles/r30_one_path.txt has the disassembly's counts).  The other arm sits out of line behind the taken branch and jumps back; both arms
+            // lie between the same two barriers.  The test reads a copy of the class that an empty asm makes opaque in every pass: a scalar compare in
+            // the pass itself, where a hoisted comparison is kept as a 64-bit lane mask in two scalar registers.  The empty asm inside the arm keeps it
+            // from being folded into selects on the class.
             if constexpr (PLACE) {
+                // the first alpha from the constant table too (the staged copy is the same words): the loop-carried alpha is then a scalar pair, no pass
+                // moves it into a vector register, and the back-edge is the loop's one branch besides the class test
+                it = __builtin_amdgcn_readfirstlane(it);
+                // a 32-bit byte offset from the table's base: the scalar load takes it as its offset register, no 64-bit address arithmetic per pass
+                auto alpha_at = [&](int i) {
+                    return *reinterpret_cast<const __attribute__((address_space(4))) double *>(reinterpret_cast<const __attribute__((address_space(4))) char *>(alpha_tab) + (unsigned)i * 8u);
+                };
+                if (it < max_iter) alpha_it = alpha_at(it);
                 for (; it < max_iter; it++) {
                     double x[CDEG];
                     unsigned ph = synw;
@@ -504,11 +517,12 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     for (int v = 0; v < 2; v++)
 #pragma unroll
                         for (int d = 0; d < 2; d++) o[v][d] = Rin(v, d);
-                    if (__builtin_expect(wave_class == kRegWaveNone, 1)) {
-                        asm volatile("");
 #pragma unroll
-                        for (int v = 0; v < 2; v++) s[v] = (o[v][0] + Rprev[v]) + o[v][1];         // kernels.py:316 with the own message second or first ("zero")
-                    } else {
+                    for (int v = 0; v < 2; v++) s[v] = (o[v][0] + Rprev[v]) + o[v][1];             // kernels.py:316 with the own message second or first ("zero")
+                    int cls = wave_class;
+                    asm volatile("" : "+s"(cls));
+                    if (__builtin_expect(cls != kRegWaveNone, 0)) {
+                        asm volatile("");
 #pragma unroll
                         for (int v = 0; v < 2; v++) s[v] = (o[v][0] + (vlast[v] ? o[v][1] : Rprev[v])) + (vlast[v] ? Rprev[v] : o[v][1]);
                     }
@@ -521,7 +535,7 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                     }
                     __builtin_amdgcn_s_setprio(0);
                     // the next pass's alpha, clamped (the table has max_iter entries): a uniform address, and the barrier below waits for LDS anyway
-                    alpha_it = alpha_tab[it + 1 < max_iter ? it + 1 : max_iter - 1];
+                    alpha_it = alpha_at(it + 1 < max_iter ? it + 1 : max_iter - 1);
                     __syncthreads();
                 }
             } else {

@@ -333,8 +333,8 @@ _REGULAR = ["minsum_regular.hip", "clocks.h", "mc_common.h", "minsum_common.h", 
 RECORDED = {
     # the seventh argument: OWN, two edges of each check inside its thread (the form bench.py's bb144 graph takes by default)
     # "bare": the loop that holds s_setprio -- the passes a workgroup runs once its shots are frozen.  Under a place table a wave takes one of two paths
-    # through it per pass, by its class (csrc/regular_place.h); the entry holds the mix of the path WITHOUT selects, which seven of the eight waves of a bb144
-    # workgroup take, and lists every path under "paths"
+    # through it per pass, by its class (csrc/regular_place.h); the entry holds the mix of the straight path WITHOUT selects, which seven of the eight waves
+    # of a bb144 workgroup take, and lists every path under "paths"
     "cc_bb144_fixed": ("minsum_regular.hip", "minsum_regular_kernel<6, 3, false, true, true, true, true>", "bare", _REGULAR),
     "cc_bb144_early_exit": ("mc_first.hip", "mc_first_kernel<8, 6, 3>", None, ["mc_first.hip", "clocks.h", "mc_common.h"]),
     "circ144_bp": ("minsum_wg2.hip", "minsum_wg2_kernel<true>", "whole", ["minsum_wg2.hip", "clocks.h", "minsum_f64.h"]),      # <true>: the shipped circ144 matrices have degree-1 checks
@@ -363,15 +363,20 @@ def record(path):
             bare = [l for l in r["loops"] if l["innermost"] and "s_setprio" in l["ops"] and l["paths"]]
             if len(bare) != 1:
                 sys.exit(f"{key}: {len(bare)} innermost loops hold s_setprio and have enumerable paths, expected the one bare loop")
-            # the compiler keeps the arm without selects behind a flag that is constant on that route, so of the static paths two cannot be taken: the one
-            # that skips both arms and the one that runs both.  A wave runs exactly one arm: the longest path without selects, or the shortest with them.
-            plain = max((p for p in bare[0]["paths"] if not p["selects"]), key=lambda p: p["valu"])
-            picked = min((p for p in bare[0]["paths"] if p["selects"]), key=lambda p: p["valu"])
-            r["steady_state"], paths = bare[0], [dict(plain, arm="no last edge in the wave: no select"), dict(picked, arm="any other wave: two selects per owned column")]
+            # one path per arm of the variable sums: the straight one of a "none" wave (no select) and the one with the two selects per owned column,
+            # which leaves the loop's text behind a taken branch and jumps back into it
+            by_selects = {}
+            for p in bare[0]["paths"]:
+                by_selects.setdefault(p["selects"], []).append(p)
+            if sorted(by_selects) != [0, 8] or any(len(v) != 1 for v in by_selects.values()):
+                sys.exit(f"{key}: expected one path without selects and one with 8 round the bare loop, found {sorted((k, len(v)) for k, v in by_selects.items())}")
+            r["steady_state"], paths = bare[0], [dict(by_selects[0][0], arm="no last edge in the wave: no select"),
+                                                 dict(by_selects[8][0], arm="any other wave: two selects per owned column")]
         if paths:
             m = paths[0]["mix"]
             scope = (f"steady-state loop [{r['steady_state']['first']}..{r['steady_state']['last']}], {r['steady_state']['blocks']} blocks (static): the path of a "
-                     f"wave whose checks own no last edge ({paths[0]['selects']} selects; 7 of the 8 waves of a bb144 workgroup); the other path is under 'paths'")
+                     f"wave whose checks own no last edge ({paths[0]['selects']} selects, {paths[0]['branches']} branches; 7 of the 8 waves of a bb144 workgroup); "
+                     f"the other path is under 'paths'")
         elif which == "whole" or "steady_state" not in r:
             m, scope = r["whole"], "whole kernel (static)"
         else:
