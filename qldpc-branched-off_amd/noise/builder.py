@@ -53,19 +53,21 @@ def build_decoding_matrices(circuit_builder, Lx, Lz, error_rate, verbose=True, n
     """Decoding matrices of a circuit-level noise model -> dict with the reference's keys (builder.py:165-176)."""
     cb = circuit_builder
     k = np.asarray(Lx).shape[0]
-    num_syndrome_bits = cb.n2 * (cb.num_cycles + 2)
     compiled = CompiledCircuit(base_circuit=cb.get_full_circuit(), noiseless_suffix=cb.cycle * 2, lin_order=cb.lin_order,
                                data_qubits=cb.data_qubits, Xchecks=cb.Xchecks, Zchecks=cb.Zchecks)
+    # detectors per sector: every measurement of the X checks (sector Z) / of the Z checks (sector X), base circuit and suffix.  A BB circuit has
+    # n / 2 checks of each kind and num_cycles + 2 rounds, the reference's n2 * (num_cycles + 2) for both; a code with unequal check counts does not.
+    rows_z, rows_x = int(compiled.x_syn_ptrs[-1]), int(compiled.z_syn_ptrs[-1])
     if verbose:
         print("Building Z-error decoding matrix...")
-    HZ_full, probsZ = _sector(compiled, Lx, Lz, False, error_rate, num_syndrome_bits, k)
+    HZ_full, probsZ = _sector(compiled, Lx, Lz, False, error_rate, rows_z, k)
     if verbose:
         print("Building X-error decoding matrix...")
-    HX_full, probsX = _sector(compiled, Lx, Lz, True, error_rate, num_syndrome_bits, k)
+    HX_full, probsX = _sector(compiled, Lx, Lz, True, error_rate, rows_x, k)
     return {
-        "HdecZ": HZ_full[:num_syndrome_bits], "HdecX": HX_full[:num_syndrome_bits],
+        "HdecZ": HZ_full[:rows_z], "HdecX": HX_full[:rows_x],
         "channel_probsZ": probsZ, "channel_probsX": probsX,
         "HZ_full": HZ_full, "HX_full": HX_full,
-        "first_logical_rowZ": num_syndrome_bits, "first_logical_rowX": num_syndrome_bits,
+        "first_logical_rowZ": rows_z, "first_logical_rowX": rows_x,
         "num_cycles": cb.num_cycles, "k": k,
     }

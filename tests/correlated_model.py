@@ -81,3 +81,53 @@ def toy_dem():
                [([], 0), ([0, 1], 0)],      # E
                [([], 0), ([1], 0)]]         # F
     return DetectorErrorModel.from_columns(prob, columns, (2, 2), (1, 1))
+
+
+# ---------------------------------------------------------------------------------------- the links of a circuit, restated
+def circuit_links(loc_type, sig_z, sig_x, cols_z, cols_x, n_x, probs_z, p, mode="raise", floor=None):
+    """The rule of qldpc_amd/simulation/correlated.py's module text on a circuit, written a second time: -> (ptr int32[n_x + 1], src int32[links],
+    llr f64[links], base f64[n_x] or None, unmatched).  loc_type: the op code of every location; sig_*: (ptr, idx, logmask), entry 2 * location +
+    slot; cols_*: {(frozenset of detectors, logical mask): column} of the two decoding matrices (of equal columns the first).  The Pauli faults in
+    location order -- a measurement or preparation: its own sector, mass p; an IDLE: Z, X, Y of slot 0, p / 3 each; a CNOT: every product of a Z
+    part and an X part in (none, slot 0, slot 1, both) but the identity, p / 15 each -- map to the column that equals their projection; J[i, j] and
+    U[j] are running f64 sums in that order; llr = prior_llrs(min(J / probs_z[i], 1)), sorted by X column, then Z column."""
+    def parts(sig, l):
+        ptr, idx, lm = sig
+        a = (frozenset(int(v) for v in idx[ptr[2 * l]:ptr[2 * l + 1]]), int(lm[2 * l]))
+        b = (frozenset(int(v) for v in idx[ptr[2 * l + 1]:ptr[2 * l + 2]]), int(lm[2 * l + 1]))
+        return [None] + [s if (s[0] or s[1]) else None for s in (a, b, (a[0] ^ b[0], a[1] ^ b[1]))]
+
+    def llrs(q):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.clip(np.nan_to_num(np.log((1 - q) / q)), -50, 50)
+
+    J, U, unmatched = {}, np.zeros(n_x), 0
+    for l, op in enumerate(np.asarray(loc_type).tolist()):
+        z, x = parts(sig_z, l), parts(sig_x, l)
+        if op in (4, 2):                                                   # MeasX, PrepX
+            faults = [(z[1], None, p)]
+        elif op in (5, 3):                                                 # MeasZ, PrepZ
+            faults = [(None, x[1], p)]
+        elif op == 6:
+            faults = [(z[1], None, p / 3), (None, x[1], p / 3), (z[1], x[1], p / 3)]
+        elif op == 1:
+            faults = [(a, b, p / 15) for ia, a in enumerate(z) for ib, b in enumerate(x) if ia or ib]
+        else:
+            faults = []
+        for kz, kx, mass in faults:
+            i = cols_z.get(kz) if kz is not None else None
+            j = cols_x.get(kx) if kx is not None else None
+            unmatched += (kz is not None and i is None) + (kx is not None and j is None)
+            if j is None:
+                continue
+            if kz is None:
+                U[j] = U[j] + mass
+            elif i is not None:
+                J[(j, i)] = J.get((j, i), 0.0) + mass
+    keys = sorted(J)
+    src = np.array([i for _, i in keys], np.int32)
+    ptr = np.zeros(n_x + 1, np.int32)
+    np.cumsum(np.bincount(np.array([j for j, _ in keys], np.int64), minlength=n_x), out=ptr[1:])
+    ratio = np.minimum(np.array([J[k] for k in keys], np.float64) / np.asarray(probs_z, np.float64)[src], 1.0) if keys else np.zeros(0)
+    base = llrs(np.maximum(U, p / 15 if floor is None else floor)) if mode == "condition" else None
+    return ptr, src, llrs(ratio), base, unmatched

@@ -176,6 +176,30 @@ def verdicts(masks, dets, truths):
     return sum(((logical_bits(d, masks[s]) != truth[s]).astype(np.uint8) << s) for s, d in enumerate(dets)).astype(np.uint8)
 
 
+def aware_chain(L, graphs, synds, shot_priors, alpha, cs=None, max_iter=50):
+    """what a plan on a per-shot-prior path does with a batch, from its parts: per sector shotprior_decode_batch with prior[B][n] (stride n, no links),
+    then on the BP failures OSD-0 or, with cs = (order, the scoring weights per sector), OSD-CS.  -> (corrections per sector, converged per sector)"""
+    dets, convs = [], []
+    for s, (synd, prior) in enumerate(zip(synds, shot_priors)):
+        assert prior.shape == (synd.shape[0], graphs[s].n)
+        det, llr, conv, _ = L.shotprior_decode_batch(graphs[s], synd, prior, alpha, 20.0, max_iter)
+        failed = np.flatnonzero(conv == 0)
+        if failed.size and cs is not None:
+            det[failed] = L.osdcs_batch(graphs[s], synd[failed], llr[failed], det[failed], cs[1][s], cs[0])[0]
+        elif failed.size:
+            det[failed] = L.osd0_batch(graphs[s], synd[failed], llr[failed], det[failed])
+        dets.append(det)
+        convs.append(conv)
+    return dets, convs
+
+
+def assert_aware_tally(L, tally, count, convs):
+    """the slots such a plan fills: every trial, the BP successes per sector, an OSD call per BP failure, no legs"""
+    T = L.TALLY
+    assert tally[T["trials"]] == count and tally[T["bp_conv_z"]] == convs[0].sum() and tally[T["bp_conv_x"]] == convs[1].sum()
+    assert tally[T["osd_z"]] == count - convs[0].sum() and tally[T["osd_x"]] == count - convs[1].sum() and tally[T["legs_z"]] == 0
+
+
 @pytest.mark.parametrize("how", ["aware", "aware+osd_cs", "aware, noise off"])
 def test_the_plan_equals_the_chain_of_its_parts(L, how):
     c, compiled, M, graphs, priors, masks, plan, sigs, model, tables = setup(L)
@@ -189,21 +213,9 @@ def test_the_plan_equals_the_chain_of_its_parts(L, how):
     got = p.run_outcomes(SEED, 0, COUNT)
     tally = p.read(clear=True)
     spz, tz, spx, tx, er, pz, px = p.sample_erasures(SEED, 0, COUNT, want_priors=True)
-    dets, convs = [], []
-    for s, (synd, prior) in enumerate(((spz, pz), (spx, px))):
-        assert prior.shape == (COUNT, graphs[s].n)
-        det, llr, conv, _ = L.shotprior_decode_batch(graphs[s], synd, prior, alpha, 20.0, 50)      # prior[B][n]: stride n, no links
-        failed = np.flatnonzero(conv == 0)
-        if failed.size and how.endswith("osd_cs"):
-            det[failed] = L.osdcs_batch(graphs[s], synd[failed], llr[failed], det[failed], priors[s], 5)[0]      # the shared prior scores: the documented limitation
-        elif failed.size:
-            det[failed] = L.osd0_batch(graphs[s], synd[failed], llr[failed], det[failed])
-        dets.append(det)
-        convs.append(conv)
+    dets, convs = aware_chain(L, graphs, (spz, spx), (pz, px), alpha, (5, priors) if how.endswith("osd_cs") else None)      # the shared prior scores: the documented limitation
     assert np.array_equal(got, verdicts(masks, dets, (tz, tx))), how
-    T = L.TALLY
-    assert tally[T["trials"]] == COUNT and tally[T["bp_conv_z"]] == convs[0].sum() and tally[T["bp_conv_x"]] == convs[1].sum()
-    assert tally[T["osd_z"]] == COUNT - convs[0].sum() and tally[T["osd_x"]] == COUNT - convs[1].sum() and tally[T["legs_z"]] == 0
+    assert_aware_tally(L, tally, COUNT, convs)
     if how.endswith("off"):                                                # no heralds: the plan's prior, which is a correlated plan with no links
         assert 0 < convs[0].sum() < COUNT                                   # both stages took part
         assert not er.any() and np.array_equal(pz, np.tile(priors[0], (COUNT, 1))) and np.array_equal(px, np.tile(priors[1], (COUNT, 1)))

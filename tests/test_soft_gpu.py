@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import correlated_model as CM  # noqa: E402
 import soft_model as SM  # noqa: E402
 from test_correlated_gpu import logical_bits  # noqa: E402
+from test_erasure_gpu import assert_aware_tally, aware_chain  # noqa: E402
 from test_plan_switch_gpu import SWITCHES, refused, run64, BATCH  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup  # noqa: E402
 
@@ -229,23 +230,12 @@ def test_the_plan_equals_the_chain_of_its_parts(L, how):
     got = p.run_outcomes(SEED, 0, COUNT)
     tally = p.read(clear=True)
     spz, tz, spx, tx, lv, pz, px = p.sample_soft(SEED, 0, COUNT, want_priors=True)
-    dets, convs = [], []
-    for s, (synd, prior) in enumerate(((spz, pz), (spx, px))):
-        assert prior.shape == (COUNT, graphs[s].n)
-        if how.endswith("off"):                                            # no levels: the plan decodes with its own prior at stride 0
-            prior = np.tile(mp[s], (COUNT, 1))
-        det, llr, conv, _ = L.shotprior_decode_batch(graphs[s], synd, prior, alpha, 20.0, 50)      # prior[B][n]: stride n, no links
-        failed = np.flatnonzero(conv == 0)
-        if failed.size and how.endswith("osd_cs"):
-            det[failed] = L.osdcs_batch(graphs[s], synd[failed], llr[failed], det[failed], mp[s], 5)[0]      # the plan's prior scores: the documented limitation
-        elif failed.size:
-            det[failed] = L.osd0_batch(graphs[s], synd[failed], llr[failed], det[failed])
-        dets.append(det)
-        convs.append(conv)
+    assert pz.shape == (COUNT, graphs[0].n) and px.shape == (COUNT, graphs[1].n)
+    if how.endswith("off"):                                                # no levels: the plan decodes with its own prior at stride 0
+        pz, px = np.tile(mp[0], (COUNT, 1)), np.tile(mp[1], (COUNT, 1))
+    dets, convs = aware_chain(L, graphs, (spz, spx), (pz, px), alpha, (5, mp) if how.endswith("osd_cs") else None)      # the plan's prior scores: the documented limitation
     assert np.array_equal(got, verdicts(masks, dets, (tz, tx))), how
-    T = L.TALLY
-    assert tally[T["trials"]] == COUNT and tally[T["bp_conv_z"]] == convs[0].sum() and tally[T["bp_conv_x"]] == convs[1].sum()
-    assert tally[T["osd_z"]] == COUNT - convs[0].sum() and tally[T["osd_x"]] == COUNT - convs[1].sum() and tally[T["legs_z"]] == 0
+    assert_aware_tally(L, tally, COUNT, convs)
     assert 0 < convs[0].sum() < COUNT                                       # both stages took part
     if how.endswith("off"):
         assert not lv.any()
