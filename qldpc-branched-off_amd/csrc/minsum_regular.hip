@@ -93,6 +93,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 namespace qldpc {
 
@@ -281,6 +282,23 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
         const int64_t b = base + slot;
         const bool valid = in_team && b < nshots;
         bool csyn = false;
+        // PLACE, Monte-Carlo: the columns of the thread's check, for the syndrome and, the first two, for the logical comparison at the freeze.  The record
+        // is the same for every shot, but 64 VGPRs leave no room to keep it across the bare loop, so a shot reads it again -- here, in front of the sampler,
+        // whose arithmetic hides the latency.  Read where they are used, the loads stood behind a barrier each (the sampler's, and at the freeze the check
+        // phase's) with the whole workgroup waiting for a spilled pointer, the record and then the byte or the mask it names: profiles/r31_opening.txt.
+        // The other forms read the record where they use it: their code objects do not move.
+        constexpr bool EARLY_COLS = MC && PLACE;
+        struct Cols { int c[CDEG]; };
+        struct NoCols { int c[2]; };            // never touched
+        std::conditional_t<EARLY_COLS, Cols, NoCols> ecs;
+        if constexpr (EARLY_COLS) {
+#pragma unroll
+            for (int k = 0; k < CDEG; k++) ecs.c[k] = 0;
+            if (valid && has_check) {
+#pragma unroll
+                for (int k = 0; k < CDEG; k++) ecs.c[k] = ecol(k);
+            }
+        }
         if (MC) {
             // ---- sample e ~ Bernoulli(p)^n (4 bits per Philox block), s = H e ----
             if (valid && member < nq) {
@@ -300,13 +318,19 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
             if (valid && has_check) {
                 int s = 0;
 #pragma unroll
-                for (int k = 0; k < CDEG; k++) s ^= Eb[ecol(k)];
+                for (int k = 0; k < CDEG; k++) {
+                    if constexpr (EARLY_COLS) s ^= Eb[ecs.c[k]];
+                    else s ^= Eb[ecol(k)];
+                }
                 csyn = s & 1;
                 if (csyn) sres[2] = 1;
             }
         } else {
             csyn = (valid && has_check) ? (A.synd[b * m + member] & 1) : false;
         }
+        // the two owned columns for the freeze, in one register across the passes before it (n <= 2 * QLDPC_LB_T: 16 bits each)
+        int cols01 = 0;
+        if constexpr (EARLY_COLS) cols01 = ecs.c[0] | (ecs.c[1] << 16);
         const unsigned synw = csyn ? 0x80000000u : 0u;       // the syndrome bit as the sign bit of a word: sign of 1 - 2 s (kernels.py:252,289)
         double Rprev[CDEG], Qold[CDEG];
 #pragma unroll
@@ -426,8 +450,16 @@ __global__ __launch_bounds__(QLDPC_LB_T, QLDPC_LB_W) void minsum_regular_kernel(
                             const uint8_t *Eb = reinterpret_cast<const uint8_t *>(El);
                             unsigned long long lm = 0ull;
 #pragma unroll
-                            for (int v = 0; v < 2; v++)
-                                if (has_var[v] && ((Eb[vcol(v)] ^ ((it >= 1 && Vmine(v) < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[vcol(v)];   // V still holds values_{it-1}
+                            for (int v = 0; v < 2; v++) {
+                                int col;                                                           // the owned columns are edges 0 and 1 of the check
+                                if constexpr (EARLY_COLS) {
+                                    int packed = cols01;
+                                    asm volatile("" : "+v"(packed));                               // unpacked here: two addresses hoisted out of the loop would cost it a spill
+                                    col = (packed >> (16 * v)) & 0xffff;
+                                }
+                                else col = vcol(v);
+                                if (has_var[v] && ((Eb[col] ^ ((it >= 1 && Vmine(v) < 0.0) ? 1 : 0)) & 1)) lm ^= A.Lmask[col];   // V still holds values_{it-1}
+                            }
                             if (lm) atomicXor(lacc, lm);
                         } else if (member == 0) {
                             active[1] = 1;
