@@ -54,6 +54,8 @@
  *        additive, same version: per-class, biased Pauli noise on a circuit plan, qldpc_noise_model and qldpc_circuit_plan_use_noise_model
  *        additive, same version: soft-readout noise and soft-information decoding on a circuit plan, qldpc_soft_priors[_dev],
  *        qldpc_circuit_plan_use_soft_readout, _use_soft_aware and _sample_soft, QLDPC_SOFT_MAX_LEVELS
+ *        additive, same version: LSD cluster statistics and the confidence of a trial, qldpc_lsd_stats_batch[_dev],
+ *        qldpc_circuit_plan_use_confidence, _confidence_read, _run_scores and _decode_events_scored[_dev], QLDPC_CONF_*
  */
 #ifndef QLDPC_HIP_H
 #define QLDPC_HIP_H
@@ -430,6 +432,23 @@ int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, co
 int qldpc_lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard, int bits_per_step,
                         int max_rows, const int32_t *d_select, const int32_t *d_select_count, int8_t *d_solution, int32_t *d_info,
                         void *stream);
+/* qldpc_lsd_batch, and the statistics of the clusters each shot ends with: the soft output of BP+LSD (Lee et al., "Efficient post-selection for
+ * general quantum LDPC codes", 2025).  New here.  For a shot that ends with flag 0 the clusters are the connected components of (R, A) at
+ * termination.  Cluster i has a_i columns of A, r_i rows, and W_i = the sum of weight[j] over its columns; weight is uint16[n], the same for every
+ * shot, and may be NULL.  stats uint64[B][8] =
+ *   [0] the number of clusters   [1] sum a_i (= info[3])   [2] sum a_i^2   [3] max a_i   [4] sum W_i   [5] sum W_i^2   [6] max W_i   [7] max r_i
+ * A shot with zero residual has eight zeros.  A shot that ends with flag 1 or 2 has all eight words 2^64 - 1: "no statement", which ranks behind
+ * every statement.  With weight == NULL the words 4 .. 6 are 0.  Nothing overflows: n < 65535 and weight <= 65535 give sum W < 2^32, so
+ * sum W_i^2 <= (sum W)^2 < 2^64.  The words are sums and maxima over sets: no thread or lane order enters them (tests/lsd_stats_model.py is the
+ * model).  The default weight of a prior is min(65535, rint(|prior_j| * 256)) with NaN as 65535 (quantise_weights of the Python binding): a
+ * cluster's W is then its prior weight in units of 1 / 256.  solution and info are qldpc_lsd_batch's, and so are the refusals, with stats == NULL
+ * as one more QLDPC_ERR_INVALID. */
+int qldpc_lsd_stats_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
+                          int max_rows, const uint16_t *weight, int8_t *solution, int32_t *info, uint64_t *stats);
+/* same on device pointers; only enqueues on `stream`.  Shots not listed keep whatever d_solution, d_info and d_stats hold. */
+int qldpc_lsd_stats_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
+                              int bits_per_step, int max_rows, const int32_t *d_select, const int32_t *d_select_count, const uint16_t *d_weight,
+                              int8_t *d_solution, int32_t *d_info, uint64_t *d_stats, void *stream);
 
 /* Sliding-window decoding over the row layers of a space-time decoding matrix: min-sum + OSD-0 on W layers at a time, the first C layers
  * of every window committed.  New here (the reference decodes the whole matrix).  The window graphs do not grow with the number of layers,
@@ -706,6 +725,37 @@ int qldpc_circuit_plan_use_lsd(qldpc_circuit_plan *plan, int bits_per_step, int 
  * a one-sector plan; all 0 on a plan that was never switched).  The cluster kernel accumulates them on the device; the three of a sector add up to
  * the sector's OSD tally slot over the same batches.  Synchronises `stream`. */
 int qldpc_circuit_plan_lsd_counts(qldpc_circuit_plan *plan, void *stream, int clear, int64_t *counts);
+/* The confidence of a trial on a plan whose OSD stage is BP+LSD: one uint64 score per trial from the cluster statistics of its two sectors
+ * (qldpc_lsd_stats_batch), small = trustworthy, and a histogram of (score, outcome) for post-selection.  New here.
+ *   kind                   word of the statistics   how the sectors combine
+ *   QLDPC_CONF_COLS_1      1  sum a_i               sum, saturating at 2^64 - 2
+ *   QLDPC_CONF_COLS_2      2  sum a_i^2             sum, saturating at 2^64 - 2 (the squared norm: only the order matters, so no root is taken)
+ *   QLDPC_CONF_COLS_INF    3  max a_i               max
+ *   QLDPC_CONF_LLR_1       4  sum W_i               sum, saturating at 2^64 - 2
+ *   QLDPC_CONF_LLR_2       5  sum W_i^2             sum, saturating at 2^64 - 2
+ *   QLDPC_CONF_LLR_INF     6  max W_i               max
+ * A sector whose BP converged contributes 0; if LSD made no statement in either sector (flag 1 or 2) the score is 2^64 - 1.
+ * edges uint64[nbins - 1], strictly increasing, 1 <= nbins <= QLDPC_CONF_MAX_BINS (NULL with nbins = 1): bin = the number of edges <= score, and every
+ * trial of _run / _run_outcomes / _run_scores adds 1 to hist[bin][outcome], outcome = bit0 z_err | bit1 x_err as in _run_outcomes.  weight_z /
+ * weight_x: uint16[n] of the sector (copied; weight_x is ignored on a one-sector plan); NULL is legal for the COLS kinds only.
+ * Legal once qldpc_circuit_plan_use_lsd has been called, before or after the path switches LSD goes with, and again with new arguments, which clears
+ * the histogram.  QLDPC_ERR_INVALID otherwise (a plan with use_osd = 0, on OSD-0, OSD-CS, Relay-BP or windows), and for a kind, nbins, edges or
+ * weights outside the above.  The tally, the verdicts and the LSD counts of the plan do not change. */
+#define QLDPC_CONF_COLS_1 0
+#define QLDPC_CONF_COLS_2 1
+#define QLDPC_CONF_COLS_INF 2
+#define QLDPC_CONF_LLR_1 3
+#define QLDPC_CONF_LLR_2 4
+#define QLDPC_CONF_LLR_INF 5
+#define QLDPC_CONF_MAX_BINS 4096
+int qldpc_circuit_plan_use_confidence(qldpc_circuit_plan *plan, int kind, int nbins, const uint64_t *edges, const uint16_t *weight_z,
+                                      const uint16_t *weight_x);
+/* hist uint64[nbins][4] (host) of the trials since the last clear.  Synchronises `stream`.  QLDPC_ERR_INVALID on a plan without a confidence. */
+int qldpc_circuit_plan_confidence_read(qldpc_circuit_plan *plan, void *stream, int clear, uint64_t *hist);
+/* qldpc_circuit_plan_run_outcomes, and score[i] of trial trial_begin + i (host, uint64[count]).  A trial's score is a function of (seed, trial index)
+ * alone: it depends neither on the plan's batch nor on how a range is split over calls.  QLDPC_ERR_INVALID on a plan without a confidence. */
+int qldpc_circuit_plan_run_scores(qldpc_circuit_plan *plan, uint64_t seed, int64_t trial_begin, int64_t count, void *stream, uint8_t *outcome,
+                                  uint64_t *score);
 /* Switches the BP + OSD-0 stage of both sectors to sliding-window decoding (one-way): a qldpc_window_decoder per sector with the plan's
  * prior, alpha schedule, max_iter and clip_llr, layer_rows = the sector's number of checks (num_x_checks for sector Z, num_z_checks for
  * sector X: one layer per syndrome cycle).  Sampler, judge and tally are unchanged; bp_conv_* counts the trials in which every window
@@ -1019,6 +1069,14 @@ int qldpc_circuit_plan_decode_events(qldpc_circuit_plan *plan, uint64_t seed, in
 /* The same on device pointers: everything is enqueued on `stream`, nothing is copied and nothing synchronised. */
 int qldpc_circuit_plan_decode_events_dev(qldpc_circuit_plan *plan, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
                                          int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags);
+/* qldpc_circuit_plan_decode_events[_dev] on a plan with a confidence (qldpc_circuit_plan_use_confidence), and score[i] of shot i (uint64[count], host /
+ * device like the other outputs).  Recorded events have no outcome, so the plan's histogram is left alone.  QLDPC_ERR_INVALID on a plan without a
+ * confidence or with score NULL; predictions and flags are those of the unscored call. */
+int qldpc_circuit_plan_decode_events_scored(qldpc_circuit_plan *plan, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events,
+                                            int64_t stride, void *stream, uint64_t *pred0, uint64_t *pred1, uint8_t *flags, uint64_t *score);
+int qldpc_circuit_plan_decode_events_scored_dev(qldpc_circuit_plan *plan, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
+                                                int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags,
+                                                uint64_t *d_score);
 /* The unpacker alone, the counterpart of qldpc_circuit_plan_sample: sparse0 int8[count][rows of g0], sparse1 int8[count][rows of g1] (host; values
  * 0 / 1; sparse1 may be NULL on a one-sector plan). */
 int qldpc_circuit_plan_unpack_events(qldpc_circuit_plan *plan, int64_t count, const uint8_t *events, int64_t stride, int8_t *sparse0, int8_t *sparse1);

@@ -478,6 +478,82 @@ def lsd_batch(graph, syndromes, llr, hard, bits_per_step=1, max_rows=512):
     return sol, info
 
 
+LSD_STATS = ("clusters", "cols_1", "cols_2", "cols_inf", "llr_1", "llr_2", "llr_inf", "rows_inf")      # the eight words of qldpc_lsd_stats_batch
+NO_STATEMENT = np.uint64(0xFFFFFFFFFFFFFFFF)     # every word of a shot LSD ended with flag 1 or 2, and the score of such a trial
+CONF_KINDS = {"cols_1": 0, "cols_2": 1, "cols_inf": 2, "llr_1": 3, "llr_2": 4, "llr_inf": 5}            # QLDPC_CONF_*
+CONF_MAX_BINS = 4096
+
+
+def quantise_weights(prior):
+    """The default weight table of the cluster statistics: uint16[n] = min(65535, rint(|prior_j| * 256)), NaN -> 65535 (a cluster's W is then its
+    prior weight in units of 1 / 256; include/qldpc_hip.h states the same rule at qldpc_lsd_stats_batch)."""
+    a = np.abs(f64(prior).ravel())
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.minimum(np.rint(a * 256.0), 65535.0)
+    w[np.isnan(a)] = 65535.0
+    return w.astype(np.uint16)
+
+
+def _weights(weights, n, what="weights"):
+    """uint16[n] (C order) or None; ValueError for another size or values outside 0..65535"""
+    if weights is None:
+        return None
+    w = np.asarray(weights)
+    if w.size != n:
+        raise ValueError(f"{what} has {w.size} entries, the graph has {n} columns")
+    if w.dtype != np.uint16:
+        if w.dtype.kind not in "iu" or (w.size and (w.min() < 0 or w.max() > 65535)):
+            raise ValueError(f"{what} must be integers in 0..65535 (quantise_weights turns a prior into them)")
+    return np.ascontiguousarray(w.ravel(), np.uint16)
+
+
+def conf_kind(kind):
+    """A confidence kind by name (CONF_KINDS) or number -> the QLDPC_CONF_* number; ValueError otherwise."""
+    if isinstance(kind, str) and kind in CONF_KINDS:
+        return CONF_KINDS[kind]
+    if not isinstance(kind, (bool, np.bool_)) and isinstance(kind, (int, np.integer)) and 0 <= int(kind) < len(CONF_KINDS):
+        return int(kind)
+    raise ValueError(f"unknown confidence kind {kind!r} (expected one of {sorted(CONF_KINDS)})")
+
+
+def conf_edges(edges):
+    """The bin edges of a confidence histogram: uint64[nbins - 1], strictly increasing, at most CONF_MAX_BINS - 1 of them; ValueError otherwise."""
+    if edges is None:
+        edges = []
+    if isinstance(edges, np.ndarray) and edges.ndim != 1:
+        raise ValueError("edges must be a 1-D sequence of integers in 0..2^64 - 1")
+    try:                                                                     # through Python integers: a list that holds 2^64 - 1 stays exact
+        vals = [int(v) if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) else None for v in edges]
+    except TypeError:
+        vals = [None]
+    if any(v is None or not 0 <= v < 1 << 64 for v in vals):
+        raise ValueError("edges must be a 1-D sequence of integers in 0..2^64 - 1")
+    e = np.array(vals, np.uint64)
+    if e.size > CONF_MAX_BINS - 1:
+        raise ValueError(f"at most {CONF_MAX_BINS - 1} edges ({CONF_MAX_BINS} bins), got {e.size}")
+    if e.size > 1 and not (e[1:] > e[:-1]).all():
+        raise ValueError("edges must be strictly increasing")
+    return e
+
+
+def lsd_stats_batch(graph, syndromes, llr, hard, bits_per_step=1, max_rows=512, weights=None):
+    """qldpc_lsd_stats_batch on host arrays: lsd_batch plus the cluster statistics -> (solution int8[B, n], info int32[B, 4], stats uint64[B, 8]);
+    the words of a row are named by LSD_STATS.  weights: uint16[n] (quantise_weights(prior) is the default table) or None (words 4 .. 6 stay 0).
+    A shot with flag 1 or 2 has eight NO_STATEMENT words."""
+    p = lsd_params({"bits_per_step": bits_per_step, "max_rows": max_rows})
+    w = _weights(weights, graph.n)
+    syndromes = i8(syndromes).reshape(-1, graph.m) if graph.m else np.zeros((np.asarray(hard).reshape(-1, graph.n).shape[0], 0), np.int8)
+    B = syndromes.shape[0]
+    llr, hard = f64(llr).reshape(B, graph.n), i8(hard).reshape(B, graph.n)
+    sol = np.zeros((B, graph.n), np.int8)
+    info = np.zeros((B, 4), np.int32)
+    stats = np.zeros((B, 8), np.uint64)
+    check(lib().qldpc_lsd_stats_batch(graph.handle, B, ptr(syndromes, C.c_int8), ptr(llr, C.c_double), ptr(hard, C.c_int8), p["bits_per_step"],
+                                      p["max_rows"], ptr(w, C.c_uint16) if w is not None else None, ptr(sol, C.c_int8), ptr(info, C.c_int32),
+                                      ptr(stats, C.c_uint64)))
+    return sol, info, stats
+
+
 def gf2_spmv_batch(graph, vectors):
     """s = H e over GF(2) for B vectors (qldpc_gf2_spmv_batch, kernels.py:222-231): int8[B, n] -> int8[B, m]."""
     vectors = i8(vectors).reshape(-1, graph.n)
@@ -1169,6 +1245,33 @@ class CircuitPlan(Owner):
         check(lib().qldpc_circuit_plan_use_lsd(self._h, p["bits_per_step"], p["max_rows"]))
         self.lsd = p
 
+    def use_confidence(self, kind, edges=None, weight_z=None, weight_x=None):
+        """Score every trial from the LSD cluster statistics of its sectors and keep a histogram of (score, outcome) (qldpc_circuit_plan_use_confidence):
+        kind by name (CONF_KINDS) or number, edges uint64[nbins - 1] strictly increasing (None: one bin), weights uint16[n] per sector
+        (quantise_weights(prior); None goes with the cols_* kinds only).  After use_lsd; again with new arguments clears the histogram."""
+        k, e = conf_kind(kind), conf_edges(edges)
+        nz, nx = self.graph_z.n, (self.graph_x.n if self.graph_x is not None else 0)
+        wz, wx = _weights(weight_z, nz, "weight_z"), (_weights(weight_x, nx, "weight_x") if self.graph_x is not None else None)
+        opt = lambda a, t: ptr(a, t) if a is not None and a.size else None      # noqa: E731
+        check(lib().qldpc_circuit_plan_use_confidence(self._h, C.c_int(k), C.c_int(e.size + 1), opt(e, C.c_uint64), opt(wz, C.c_uint16), opt(wx, C.c_uint16)))
+        self.confidence = {"kind": k, "edges": e}
+
+    def confidence_hist(self, stream=0, clear=False):
+        """uint64[nbins, 4]: hist[bin, outcome] of the trials since the last clear, bin = #{edges <= score}, outcome = bit0 z_err | bit1 x_err
+        (qldpc_circuit_plan_confidence_read)."""
+        if getattr(self, "confidence", None) is None:
+            raise QldpcError("the plan has no confidence (use_confidence)")
+        hist = np.zeros((self.confidence["edges"].size + 1, 4), np.uint64)
+        check(lib().qldpc_circuit_plan_confidence_read(self._h, C.c_void_p(stream), C.c_int(int(clear)), ptr(hist, C.c_uint64)))
+        return hist
+
+    def run_scores(self, seed, trial_begin, count, stream=0):
+        """run_outcomes() + the score of every trial: (uint8[count], uint64[count]) (qldpc_circuit_plan_run_scores)."""
+        out, score = np.zeros(max(int(count), 0), np.uint8), np.zeros(max(int(count), 0), np.uint64)
+        check(lib().qldpc_circuit_plan_run_scores(self._h, C.c_uint64(seed), C.c_int64(trial_begin), C.c_int64(count), C.c_void_p(stream),
+                                                  ptr(out, C.c_uint8), ptr(score, C.c_uint64)))
+        return out, score
+
     def lsd_counts(self, stream=0, clear=False):
         """int64[2, 3]: the shots per sector that the LSD stage ended with flag 0 (solved in clusters) / 1 (capped) / 2 (no candidates) since the last
         clear (qldpc_circuit_plan_lsd_counts); a row adds up to the sector's OSD tally slot over the same batches."""
@@ -1391,13 +1494,20 @@ class CircuitPlan(Owner):
             raise ValueError(f"events must be uint8[count, stride], got shape {events.shape}")
         return events
 
-    def decode_events(self, events, seed=0, shot_begin=0, stream=0):
+    def decode_events(self, events, seed=0, shot_begin=0, stream=0, scores=False):
         """Bit-packed records uint8[count, stride] (pack_events) -> (pred0 uint64[count], pred1 uint64[count], flags uint8[count]): the predicted observable
         flips per sector (bit r = observable r) and, per shot, bit 0 / 1 = converged, 2 / 3 = correction does not reproduce the syndrome, 4 / 5 = zero
-        syndrome of sector 0 / 1 (qldpc_circuit_plan_decode_events).  A one-sector plan returns zeros for sector 1."""
+        syndrome of sector 0 / 1 (qldpc_circuit_plan_decode_events).  A one-sector plan returns zeros for sector 1.  scores=True (a plan with
+        use_confidence): a fourth array, the score uint64[count] of every shot (qldpc_circuit_plan_decode_events_scored)."""
         events = self._events(events)
         count = events.shape[0]
         pred0, pred1, flags = np.zeros(count, np.uint64), np.zeros(count, np.uint64), np.zeros(count, np.uint8)
+        if scores:
+            score = np.zeros(count, np.uint64)
+            check(lib().qldpc_circuit_plan_decode_events_scored(self._h, C.c_uint64(seed), C.c_int64(shot_begin), C.c_int64(count), ptr(events, C.c_uint8),
+                                                                C.c_int64(events.shape[1]), C.c_void_p(stream), ptr(pred0, C.c_uint64),
+                                                                ptr(pred1, C.c_uint64), ptr(flags, C.c_uint8), ptr(score, C.c_uint64)))
+            return pred0, pred1, flags, score
         check(lib().qldpc_circuit_plan_decode_events(self._h, C.c_uint64(seed), C.c_int64(shot_begin), C.c_int64(count), ptr(events, C.c_uint8),
                                                      C.c_int64(events.shape[1]), C.c_void_p(stream), ptr(pred0, C.c_uint64), ptr(pred1, C.c_uint64),
                                                      ptr(flags, C.c_uint8)))

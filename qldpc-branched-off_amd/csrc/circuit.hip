@@ -159,6 +159,10 @@ struct qldpc_circuit_plan {
         DevBuf d_legs;                             // Path::RELAY: legs per trial; Path::DECIM: rounds per trial
         DevBuf d_flips;                            // Osd::CS: workspace of the sweep
         DevBuf d_lsd_info;                         // Osd::LSD: info of the batch in flight
+        // ... with qldpc_circuit_plan_use_confidence: the cluster statistics uint64[batch][8] of the batch in flight (zeroed, then the unconverged
+        // shots' rows from lsd_kernel), and the weight table uint16[n] of the sector (has_conf_w: one was given)
+        DevBuf d_lsd_stats, d_conf_w;
+        bool has_conf_w = false;
         // decode of recorded events (events.hip): the record bit of every row (ev_tab, else the contiguous run at ev_base); the predictions of a batch
         DevBuf d_evtab, d_pred;
         // Path::ERASURE (erasure.hip): the sector's tables location -> (column, h) and column -> lut run; the per-shot prior f64[batch][n] of a batch
@@ -206,6 +210,10 @@ struct qldpc_circuit_plan {
     int cs_order = 0;                              // Osd::CS (osd_cs.hip)
     int lsd_bits = 0, lsd_rows = 0;                // Osd::LSD (lsd.hip)
     DevBuf d_lsd_counts;                           // ... uint64[2][3]: shots per sector that ended with flag 0 / 1 / 2 (the kernel accumulates)
+    // qldpc_circuit_plan_use_confidence (confidence.hip): conf_kind -1 = off, else QLDPC_CONF_*; d_score: uint64[batch] of the batch in flight; d_edges:
+    // uint64[conf_bins - 1]; d_hist: uint64[conf_bins][4], accumulated by every run until it is read with clear
+    int conf_kind = -1, conf_bins = 0;
+    DevBuf d_score, d_edges, d_hist;
     // hipEvent brackets of the phases of every batch not yet read by qldpc_circuit_plan_phase_times
     struct Bracket { int phase; hipEvent_t a, b; };
     std::vector<Bracket> pending;
@@ -636,9 +644,14 @@ static int decode_sector(qldpc_circuit_plan *P, int sector, int64_t B, hipStream
         if (P->osd == Osd::CS)
             rc = osdcs_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(),
                                      S.d_prior.as<double>(), P->cs_order, S.d_det.as<int8_t>(), S.d_flips.as<int32_t>(), s);
-        else if (P->osd == Osd::LSD)
-            rc = lsd_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), P->lsd_bits,
-                                   P->lsd_rows, S.d_det.as<int8_t>(), S.d_lsd_info.as<int32_t>(), P->d_lsd_counts.as<unsigned long long>() + 3 * sector, s);
+        else if (P->osd == Osd::LSD) {
+            const bool conf = P->conf_kind >= 0;                              // a converged shot has nothing to solve: its row stays zero
+            if (conf && hipMemsetAsync(S.d_lsd_stats.p, 0, (size_t)B * 64, s) != hipSuccess) { set_error("hipMemsetAsync failed"); rc = QLDPC_ERR_HIP; }
+            if (rc == QLDPC_OK)
+                rc = lsd_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), P->lsd_bits,
+                                       P->lsd_rows, S.d_det.as<int8_t>(), S.d_lsd_info.as<int32_t>(), P->d_lsd_counts.as<unsigned long long>() + 3 * sector,
+                                       conf && S.has_conf_w ? S.d_conf_w.as<uint16_t>() : nullptr, conf ? S.d_lsd_stats.as<unsigned long long>() : nullptr, s);
+        }
         else
             rc = osd0_listed_launch(g, S.d_list.as<int32_t>(), count, B, S.d_syn.as<int8_t>(), S.d_llr.as<double>(), S.d_det.as<int8_t>(), nullptr,
                                     S.d_det.as<int8_t>(), P->flags, s);
@@ -655,11 +668,20 @@ static JudgeSector judge_view(const Sector &S) {
             S.d_conv.as<uint8_t>(), S.d_iter.as<int32_t>(), S.d_true.as<unsigned long long>()};
 }
 
-// one pass over [trial_begin, trial_begin + count); `outcome` (host, may be NULL) receives bit0 = z_err, bit1 = x_err per trial
-static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, hipStream_t s, uint8_t *outcome) {
+// the score kernel on the batch in flight (qldpc_circuit_plan_use_confidence): d_score from the sectors' statistics, and with d_outcome the histogram
+static int launch_confidence(qldpc_circuit_plan *P, int64_t B, const uint8_t *d_outcome, hipStream_t s) {
+    return confidence_launch(P->device, B, P->conf_kind, P->sec[0].d_lsd_stats.as<unsigned long long>(),
+                             P->nsec == 2 ? P->sec[1].d_lsd_stats.as<unsigned long long>() : nullptr, d_outcome, P->d_score.as<unsigned long long>(),
+                             d_outcome ? P->conf_bins : 1, P->d_edges.as<unsigned long long>(), d_outcome ? P->d_hist.as<unsigned long long>() : nullptr, s);
+}
+
+// one pass over [trial_begin, trial_begin + count); `outcome` (host, may be NULL) receives bit0 = z_err, bit1 = x_err per trial, `score` (host, may be
+// NULL; a plan with a confidence only) the trial's score.  A plan with a confidence writes the outcome byte of every batch: its histogram reads it.
+static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, hipStream_t s, uint8_t *outcome, uint64_t *score = nullptr) {
     QLDPC_USE_DEVICE(P->device);
     int rc;
-    if (outcome && (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK) return rc;
+    const bool conf = P->conf_kind >= 0, bytes = outcome || conf;
+    if (bytes && (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK) return rc;
     const bool two = P->nsec == 2;
     const JudgeSector Z = judge_view(P->sec[0]), X = two ? judge_view(P->sec[1]) : JudgeSector{};
     const bool sparse = Z.m <= 4096 && Z.colptr && (!two || (X.m <= 4096 && X.colptr));
@@ -679,8 +701,9 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
             if ((rc = decode_sector(P, sector, B, s, seed, trial_begin + off, heralds)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, true)) != QLDPC_OK) return rc;
         hipLaunchKernelGGL(judge, dim3((unsigned)((B + 7) / 8)), dim3(256), 0, s, B, Z, X, P->d_tally.as<unsigned long long>(),
-                           outcome ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
+                           bytes ? P->d_outcome.as<uint8_t>() : (uint8_t *)nullptr, P->osd_stage() ? P->d_count.as<int32_t>() : (const int32_t *)nullptr);
         QLDPC_HIP_TRY(hipGetLastError());
+        if (conf && (rc = launch_confidence(P, B, P->d_outcome.as<uint8_t>(), s)) != QLDPC_OK) return rc;
         if ((P->path == Path::RELAY || P->path == Path::DECIM) &&
             (rc = relay_legs_tally_launch(B, P->sec[0].d_legs.as<int32_t>(), two ? P->sec[1].d_legs.as<int32_t>() : nullptr, P->d_tally.as<unsigned long long>(), s)) != QLDPC_OK)
             return rc;
@@ -688,6 +711,7 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         P->batches++;
         if (outcome) {
             QLDPC_HIP_TRY(hipMemcpyAsync(outcome + off, P->d_outcome.p, (size_t)B, hipMemcpyDeviceToHost, s));
+            if (score) QLDPC_HIP_TRY(hipMemcpyAsync(score + off, P->d_score.p, (size_t)B * 8, hipMemcpyDeviceToHost, s));
             QLDPC_HIP_TRY(hipStreamSynchronize(s));
         }
     }
@@ -706,6 +730,15 @@ QLDPC_EXPORT int qldpc_circuit_plan_run_outcomes(qldpc_circuit_plan *P, uint64_t
     QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
     QLDPC_REQUIRE(count == 0 || outcome != nullptr, "outcome is NULL");
     return circuit_run(P, seed, trial_begin, count, reinterpret_cast<hipStream_t>(stream), outcome);
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_run_scores(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, void *stream, uint8_t *outcome,
+                                               uint64_t *score) {
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
+    QLDPC_REQUIRE(P->conf_kind >= 0, "the plan has no confidence (qldpc_circuit_plan_use_confidence)");
+    QLDPC_REQUIRE(count == 0 || (outcome != nullptr && score != nullptr), "outcome or score is NULL");
+    return circuit_run(P, seed, trial_begin, count, reinterpret_cast<hipStream_t>(stream), outcome, score);
 }
 
 QLDPC_EXPORT int qldpc_circuit_plan_read(qldpc_circuit_plan *P, void *stream, int clear, int64_t *tally) {
@@ -776,6 +809,8 @@ QLDPC_EXPORT int qldpc_circuit_plan_clock(qldpc_circuit_plan *P, void *stream, d
 //   OSD stage: OSD-0 (as created; none with use_osd = 0), OSD-CS or LSD.  OSD-CS and LSD need use_osd, go with flooding, layered, decimation, f32,
 //     correlated, erasure-aware and soft-aware whichever came first, and may be asked for again with new arguments.  They go with neither Relay-BP nor windows, whichever came first, and they
 //     refuse each other in either order.
+//   Confidence (qldpc_circuit_plan_use_confidence) is no axis of its own: it rides on the LSD stage, so it is legal once the OSD stage is LSD, before or
+//     after the path switches that LSD goes with, and again with new arguments; everything that refuses LSD thereby refuses it.
 //   Windows need use_osd as well; Relay-BP, layered, decimation, f32, correlated, erasure-aware and soft-aware do not.  Windows, layered,
 //   decimation, f32, correlated, erasure-aware and soft-aware need damping = 1.
 // Each switch then checks its own arguments and what its kernels need (Relay-BP, OSD-CS, decimation, correlated: finite priors and a supported graph;
@@ -870,6 +905,49 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_lsd(qldpc_circuit_plan *P, int bits_per_
     }
     P->lsd_bits = bits_per_step; P->lsd_rows = max_rows;
     P->osd = Osd::LSD;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_use_confidence(qldpc_circuit_plan *P, int kind, int nbins, const uint64_t *edges, const uint16_t *weight_z,
+                                                  const uint16_t *weight_x) {
+    static const char *const osd_name[] = {"BP + OSD-0", "BP + OSD-CS", "BP + LSD"};
+    static const char *const path_name[] = {"", "", "", "", "Relay-BP", "sliding-window decoding", "", "", ""};
+    QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(P->use_osd, "the plan was created with use_osd = 0: a confidence needs its OSD stage switched to BP + LSD");
+    QLDPC_REQUIRE(P->path != Path::RELAY && P->path != Path::WINDOW, "the plan was switched to %s: a confidence cannot follow (it needs BP + LSD)",
+                  path_name[(int)P->path]);
+    QLDPC_REQUIRE(P->osd == Osd::LSD, "the plan's OSD stage is %s: a confidence needs BP + LSD (qldpc_circuit_plan_use_lsd first)", osd_name[(int)P->osd]);
+    int rc = confidence_check(kind, nbins, edges);
+    if (rc != QLDPC_OK) return rc;
+    const uint16_t *const weight[2] = {weight_z, weight_x};
+    for (int i = 0; i < P->nsec; i++)
+        QLDPC_REQUIRE(weight[i] != nullptr || kind <= QLDPC_CONF_COLS_INF, "weight_%c is NULL: only the QLDPC_CONF_COLS_* kinds go without weights", "zx"[i]);
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipDeviceSynchronize());                              // a run that is still enqueued reads the tables replaced here
+    if ((rc = ensure_each(P, &Sector::d_lsd_stats, (size_t)P->batch * 64)) != QLDPC_OK || (rc = P->d_score.ensure((size_t)P->batch * 8)) != QLDPC_OK ||
+        (rc = P->d_outcome.ensure((size_t)P->batch)) != QLDPC_OK || (rc = P->d_hist.ensure((size_t)nbins * 32)) != QLDPC_OK ||
+        (rc = P->d_edges.ensure((size_t)std::max(nbins - 1, 1) * 8)) != QLDPC_OK)
+        return rc;
+    if (nbins > 1) QLDPC_HIP_TRY(hipMemcpy(P->d_edges.p, edges, (size_t)(nbins - 1) * 8, hipMemcpyHostToDevice));
+    for (int i = 0; i < P->nsec; i++) {
+        Sector &S = P->sec[i];
+        S.has_conf_w = weight[i] != nullptr;
+        if (!S.has_conf_w) continue;
+        if ((rc = S.d_conf_w.ensure((size_t)std::max(S.g->n, 1) * 2)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(hipMemcpy(S.d_conf_w.p, weight[i], (size_t)S.g->n * 2, hipMemcpyHostToDevice));
+    }
+    QLDPC_HIP_TRY(zero_now(P->d_hist.p, (size_t)nbins * 32));
+    P->conf_kind = kind; P->conf_bins = nbins;
+    return QLDPC_OK;
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_confidence_read(qldpc_circuit_plan *P, void *stream, int clear, uint64_t *hist) {
+    QLDPC_REQUIRE(P != nullptr && hist != nullptr, "NULL argument");
+    QLDPC_REQUIRE(P->conf_kind >= 0, "the plan has no confidence (qldpc_circuit_plan_use_confidence)");
+    QLDPC_USE_DEVICE(P->device);
+    QLDPC_HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    QLDPC_HIP_TRY(hipMemcpy(hist, P->d_hist.p, (size_t)P->conf_bins * 32, hipMemcpyDeviceToHost));
+    if (clear) QLDPC_HIP_TRY(zero_now(P->d_hist.p, (size_t)P->conf_bins * 32));
     return QLDPC_OK;
 }
 
@@ -1294,9 +1372,12 @@ static int events_args(const qldpc_circuit_plan *P, const uint8_t *events, int64
 // one pass over the records [0, count): copy (host records) + unpack in the sampler's bracket, the sectors' decode as in a run, predict in the judge's bracket.
 // host = true: events / pred0 / pred1 / flags are host pointers, and every batch is copied back and waited for (as circuit_run does for its outcomes);
 // host = false: device pointers, everything is enqueued on s and nothing is waited for.
+// scored: `score` (uint64[count], host or device like the rest) receives the confidence of every shot; there is no outcome, so the histogram stays as it is.
 static int decode_events(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events, int64_t stride, hipStream_t s,
-                         uint64_t *pred0, uint64_t *pred1, uint8_t *flags, bool host) {
+                         uint64_t *pred0, uint64_t *pred1, uint8_t *flags, bool host, bool scored = false, uint64_t *score = nullptr) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
+    QLDPC_REQUIRE(!scored || P->conf_kind >= 0, "the plan has no confidence (qldpc_circuit_plan_use_confidence)");
+    QLDPC_REQUIRE(!scored || count == 0 || score != nullptr, "score is NULL");
     QLDPC_REQUIRE(count >= 0, "count is negative");
     QLDPC_REQUIRE(shot_begin >= 0, "shot_begin is negative");
     if (count == 0) return QLDPC_OK;
@@ -1335,6 +1416,10 @@ static int decode_events(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begi
         unsigned long long *p1 = !two ? nullptr : host ? P->sec[1].d_pred.as<unsigned long long>() : reinterpret_cast<unsigned long long *>(pred1) + off;
         uint8_t *fl = host ? P->d_evflags.as<uint8_t>() : flags + off;
         if ((rc = events_predict_launch(B, Z, X, two, p0, p1, fl, s)) != QLDPC_OK) return rc;
+        if (scored) {
+            if ((rc = launch_confidence(P, B, nullptr, s)) != QLDPC_OK) return rc;
+            QLDPC_HIP_TRY(hipMemcpyAsync(score + off, P->d_score.p, (size_t)B * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+        }
         if ((rc = phase_mark(P, QLDPC_PHASE_JUDGE, s, false)) != QLDPC_OK) return rc;
         P->batches++;
         if (host) {
@@ -1355,6 +1440,17 @@ QLDPC_EXPORT int qldpc_circuit_plan_decode_events(qldpc_circuit_plan *P, uint64_
 QLDPC_EXPORT int qldpc_circuit_plan_decode_events_dev(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
                                                       int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags) {
     return decode_events(P, seed, shot_begin, count, d_events, stride, reinterpret_cast<hipStream_t>(stream), d_pred0, d_pred1, d_flags, false);
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_decode_events_scored(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *events,
+                                                         int64_t stride, void *stream, uint64_t *pred0, uint64_t *pred1, uint8_t *flags, uint64_t *score) {
+    return decode_events(P, seed, shot_begin, count, events, stride, reinterpret_cast<hipStream_t>(stream), pred0, pred1, flags, true, true, score);
+}
+
+QLDPC_EXPORT int qldpc_circuit_plan_decode_events_scored_dev(qldpc_circuit_plan *P, uint64_t seed, int64_t shot_begin, int64_t count, const uint8_t *d_events,
+                                                             int64_t stride, void *stream, uint64_t *d_pred0, uint64_t *d_pred1, uint8_t *d_flags,
+                                                             uint64_t *d_score) {
+    return decode_events(P, seed, shot_begin, count, d_events, stride, reinterpret_cast<hipStream_t>(stream), d_pred0, d_pred1, d_flags, false, true, d_score);
 }
 
 // the unpacker alone, the counterpart of qldpc_circuit_plan_sample: sparse0 int8[count][nsyn0], sparse1 int8[count][nsyn1] (host; sparse1 may be NULL on one sector)

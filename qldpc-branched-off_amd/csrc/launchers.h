@@ -158,11 +158,19 @@ int osdcs_check_order(int order);
 // BP+LSD (lsd.hip) on the listed shots; the shots that end capped or without candidates go through osd0_listed_launch behind it.  d_info int32[B][4];
 // d_counts (may be NULL): uint64[3], the shots that ended with flag 0 / 1 / 2, accumulated by the kernel.  Callers hold g->mu and have checked the
 // parameters (lsd_check_params) and the graph at that cap (lsd_graph_supported: QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set).
+// d_stats (may be NULL): uint64[B][8], the cluster statistics of the listed shots (qldpc_lsd_stats_batch), with d_weight uint16[n] (may be NULL).
 int lsd_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
                       const int8_t *d_hard, int bits_per_step, int max_rows, int8_t *d_solution, int32_t *d_info, unsigned long long *d_counts,
-                      hipStream_t stream);
+                      const uint16_t *d_weight, unsigned long long *d_stats, hipStream_t stream);
 int lsd_check_params(int bits_per_step, int max_rows);
 int lsd_graph_supported(const qldpc_graph *g, int max_rows);
+// The confidence of B trials (confidence.hip) from the cluster statistics uint64[B][8] of sector Z and of sector X (NULL: one sector): d_score[B], and
+// with d_hist (may be NULL; then nbins = 1) hist[bin][d_outcome[b] & 3] += 1 at bin = #{d_edges <= score}.  kind and the edges have passed
+// confidence_check (QLDPC_OK, or QLDPC_ERR_INVALID with the error text set).
+constexpr int kConfLdsMax = 4096 * 8 + 4096 * 16;      // the edge table and the workgroup's counts at QLDPC_CONF_MAX_BINS
+int confidence_launch(int device, int64_t B, int kind, const unsigned long long *d_stats_z, const unsigned long long *d_stats_x, const uint8_t *d_outcome,
+                      unsigned long long *d_score, int nbins, const unsigned long long *d_edges, unsigned long long *d_hist, hipStream_t stream);
+int confidence_check(int kind, int nbins, const uint64_t *edges);
 // Sliding-window decoding (window.hip) inside a circuit plan.  create_tab: qldpc_window_decoder_create on a ready alpha table.  lock_and_launch enqueues
 // the window loop for B shots; the last window's commit fills the plan's per-trial slots: conv = 1 iff every window converged, iter = iterations - 1 (the
 // judge adds one per trial), *osd_count += 1 per trial with an OSD-0 window.  mark(0 / 1, open) brackets the BP and the OSD + commit part of every window.

@@ -22,6 +22,8 @@
 // The order in which seed rows get their local indices (an LDS atomic) is the one thing that varies between runs; it moves pivot ROWS only.  Which
 // columns pivot (independence of the columns before them in A), the validity of a cluster and the solution on the pivots do not depend on it.
 // A shot that ends capped (flag 1) or without candidates (flag 2) is listed; the caller runs qldpc_osd0_batch's kernels on the list behind this kernel.
+// On request (qldpc_lsd_stats_batch) an epilogue behind the solution turns the final labels into the statistics of the clusters: sums and maxima over
+// sets, by LDS integer atomics, so the order of the local indices does not enter them either; tests/lsd_stats_model.py is their model.
 #include "common.h"
 #include "launchers.h"
 #include "osd_common.h"
@@ -44,6 +46,8 @@ struct LsdArgs {
     int *queue;                    // next list entry (zeroed before the launch)
     int32_t *redo_list, *redo_count;
     unsigned long long *counts;    // [3] shots that ended with flag 0 / 1 / 2, accumulated (may be NULL)
+    const uint16_t *weight;        // [n] weight of a column in the cluster statistics (may be NULL: slots 4 .. 6 stay 0)
+    unsigned long long *stats;     // [B][8] cluster statistics of a shot (may be NULL: no epilogue)
     LsdOffsets o;
 };
 
@@ -307,6 +311,38 @@ __global__ __launch_bounds__(kLsdBlock) void lsd_kernel(LsdArgs P) {
             info[0] = flag; info[1] = flag ? 0 : rounds; info[2] = flag ? 0 : nR; info[3] = flag ? 0 : ib[kIbAdded];
             if (P.counts) atomicAdd(&P.counts[flag], 1ull);
         }
+        // ---- the cluster statistics (qldpc_lsd_stats_batch): per label the columns of A, their weight and the rows, then sums and maxima over the labels.
+        // The accumulators are pieces that are dead once the solution is out: bestJ (columns), bestKey (weight), the first words of U (rows; T b in row MR
+        // stays), the round's key list (the eight slots).  LDS integer atomics only, so neither lane order nor the order of the seed indices enters. ----
+        if (P.stats) {
+            unsigned int *rcnt = reinterpret_cast<unsigned int *>(U);                             // [nR] (nR <= MR < the words of U's rows)
+            unsigned long long *acc = lK;                                                         // [8]
+            const int nC = flag == 0 ? nR : 0;
+            for (int q = tid; q < nC; q += T) { bestKey[q] = 0ull; bestJ[q] = 0u; rcnt[q] = 0u; }
+            if (tid < 8) acc[tid] = 0ull;
+            __syncthreads();
+            if (nC > 0) {
+                for (int q = tid; q < nC; q += T) atomicAdd(&rcnt[label[q]], 1u);
+                for (int t = tid; t < nbw; t += T)
+                    for (uint32_t bits = inA[t]; bits; bits &= bits - 1u) {
+                        const int j = 32 * t + __builtin_ctz(bits);
+                        const int L = label[lidx[P.col_rows[(size_t)j * cd]]];                    // (a column of A has a row, and its rows are in R)
+                        atomicAdd(&bestJ[L], 1u);
+                        if (P.weight) atomicAdd(&bestKey[L], (unsigned long long)P.weight[j]);
+                    }
+                __syncthreads();
+                for (int L = tid; L < nC; L += T) {
+                    if (label[L] != L) continue;
+                    const unsigned long long a = bestJ[L], wt = bestKey[L];
+                    atomicAdd(&acc[0], 1ull);
+                    atomicAdd(&acc[1], a); atomicAdd(&acc[2], a * a); atomicMax(&acc[3], a);
+                    atomicAdd(&acc[4], wt); atomicAdd(&acc[5], wt * wt); atomicMax(&acc[6], wt);
+                    atomicMax(&acc[7], (unsigned long long)rcnt[L]);
+                }
+                __syncthreads();
+            }
+            if (tid < 8) P.stats[shot * 8 + tid] = flag ? ~0ull : acc[tid];                       // (capped or without candidates: no statement)
+        }
         __syncthreads();
     }
 }
@@ -331,7 +367,7 @@ int lsd_check_params(int bits_per_step, int max_rows) {
 // from the OSD-0 kernels, behind this launch on the same stream.
 int lsd_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t *d_count, int64_t max_listed, const int8_t *d_synd, const double *d_llr,
                       const int8_t *d_hard, int bits_per_step, int max_rows, int8_t *d_solution, int32_t *d_info, unsigned long long *d_counts,
-                      hipStream_t stream) {
+                      const uint16_t *d_weight, unsigned long long *d_stats, hipStream_t stream) {
     if (g->m == 0 || g->n == 0 || max_listed == 0) return QLDPC_OK;
     int rc = lsd_graph_supported(g, max_rows);
     if (rc != QLDPC_OK) return rc;
@@ -354,7 +390,7 @@ int lsd_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t
         QLDPC_HIP_TRY(hipMemsetAsync(P.redo_count, 0, 4, stream));
         P.col_rows = g->d_col_rows; P.indptr = g->d_indptr; P.indices = g->d_indices;
         P.list = d_list; P.count = d_count; P.synd = d_synd; P.llr = d_llr; P.hard = d_hard;
-        P.solution = d_solution; P.info = d_info; P.counts = d_counts;
+        P.solution = d_solution; P.info = d_info; P.counts = d_counts; P.weight = d_weight; P.stats = d_stats;
         if ((rcl = ensure_max_lds(g->device, reinterpret_cast<const void *>(lsd_kernel), kLsdLdsMax)) != QLDPC_OK) return rcl;
         hipLaunchKernelGGL(lsd_kernel, dim3(grid), dim3(kLsdBlock), lds, stream, P);
         QLDPC_HIP_TRY(hipGetLastError());
@@ -372,12 +408,14 @@ int lsd_listed_launch(const qldpc_graph *g, const int32_t *d_list, const int32_t
 
 using namespace qldpc;
 
-QLDPC_EXPORT int qldpc_lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
-                                     int bits_per_step, int max_rows, const int32_t *d_select, const int32_t *d_select_count, int8_t *d_solution,
-                                     int32_t *d_info, void *stream) {
+// qldpc_lsd_batch_dev and qldpc_lsd_stats_batch_dev (want_stats: d_stats is an output the caller must give)
+static int lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard, int bits_per_step,
+                         int max_rows, const int32_t *d_select, const int32_t *d_select_count, const uint16_t *d_weight, int8_t *d_solution,
+                         int32_t *d_info, unsigned long long *d_stats, bool want_stats, void *stream) {
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
     QLDPC_REQUIRE((d_select == nullptr) == (d_select_count == nullptr), "d_select and d_select_count go together");
+    QLDPC_REQUIRE(!want_stats || d_stats != nullptr, "stats is NULL");
     int rc = lsd_check_params(bits_per_step, max_rows);
     if (rc != QLDPC_OK) return rc;
     if ((rc = lsd_graph_supported(g, max_rows)) != QLDPC_OK) return rc;
@@ -394,13 +432,16 @@ QLDPC_EXPORT int qldpc_lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8
         iota_list_launch(B, list, cnt, s);
         d_select = list; d_select_count = cnt;
     }
-    return lsd_listed_launch(g, d_select, d_select_count, B, d_syndromes, d_llr, d_hard, bits_per_step, max_rows, d_solution, d_info, nullptr, s);
+    return lsd_listed_launch(g, d_select, d_select_count, B, d_syndromes, d_llr, d_hard, bits_per_step, max_rows, d_solution, d_info, nullptr, d_weight,
+                             d_stats, s);
 }
 
-QLDPC_EXPORT int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
-                                 int max_rows, int8_t *solution, int32_t *info) {
+// qldpc_lsd_batch and qldpc_lsd_stats_batch
+static int lsd_batch_host(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step, int max_rows,
+                          const uint16_t *weight, int8_t *solution, int32_t *info, uint64_t *stats, bool want_stats) {
     QLDPC_REQUIRE(g != nullptr, "graph is NULL");
     QLDPC_REQUIRE(B >= 0 && B < ((int64_t)1 << 31), "batch out of range");
+    QLDPC_REQUIRE(!want_stats || stats != nullptr, "stats is NULL");
     int rc = lsd_check_params(bits_per_step, max_rows);
     if (rc != QLDPC_OK) return rc;
     if ((rc = lsd_graph_supported(g, max_rows)) != QLDPC_OK) return rc;
@@ -411,6 +452,7 @@ QLDPC_EXPORT int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *
     if (m == 0) {                                                            // no checks: the residual is zero
         std::memcpy(solution, hard, (size_t)B * n);
         std::memset(info, 0, (size_t)B * 16);
+        if (stats) std::memset(stats, 0, (size_t)B * 64);
         return QLDPC_OK;
     }
     HostStage S;
@@ -420,11 +462,40 @@ QLDPC_EXPORT int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *
     const auto dsol = S.out(solution, B, n);
     const auto dinf = S.out(info, B, 4);
     const auto dlist = S.scratch<int32_t>(B), dcnt = S.scratch<int32_t>(4);
+    Staged<uint16_t> dw;
+    Staged<uint64_t> dst;
+    if (weight) dw = S.in(weight, n);
+    if (stats) dst = S.out(stats, B, 8);
     if ((rc = S.stage()) != QLDPC_OK) return rc;
     iota_list_launch(B, S[dlist], S[dcnt], nullptr);
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        rc = lsd_listed_launch(g, S[dlist], S[dcnt], B, S[ds], S[dl], S[dh], bits_per_step, max_rows, S[dsol], S[dinf], nullptr, nullptr);
+        rc = lsd_listed_launch(g, S[dlist], S[dcnt], B, S[ds], S[dl], S[dh], bits_per_step, max_rows, S[dsol], S[dinf], nullptr, S[dw],
+                               reinterpret_cast<unsigned long long *>(S[dst]), nullptr);
     }
     return rc != QLDPC_OK ? rc : S.finish("LSD kernel", HostStage::kDevice);
+}
+
+QLDPC_EXPORT int qldpc_lsd_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
+                                     int bits_per_step, int max_rows, const int32_t *d_select, const int32_t *d_select_count, int8_t *d_solution,
+                                     int32_t *d_info, void *stream) {
+    return lsd_batch_dev(g, B, d_syndromes, d_llr, d_hard, bits_per_step, max_rows, d_select, d_select_count, nullptr, d_solution, d_info, nullptr, false,
+                         stream);
+}
+
+QLDPC_EXPORT int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
+                                 int max_rows, int8_t *solution, int32_t *info) {
+    return lsd_batch_host(g, B, syndromes, llr, hard, bits_per_step, max_rows, nullptr, solution, info, nullptr, false);
+}
+
+QLDPC_EXPORT int qldpc_lsd_stats_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndromes, const double *d_llr, const int8_t *d_hard,
+                                           int bits_per_step, int max_rows, const int32_t *d_select, const int32_t *d_select_count,
+                                           const uint16_t *d_weight, int8_t *d_solution, int32_t *d_info, uint64_t *d_stats, void *stream) {
+    return lsd_batch_dev(g, B, d_syndromes, d_llr, d_hard, bits_per_step, max_rows, d_select, d_select_count, d_weight, d_solution, d_info,
+                         reinterpret_cast<unsigned long long *>(d_stats), true, stream);
+}
+
+QLDPC_EXPORT int qldpc_lsd_stats_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
+                                       int max_rows, const uint16_t *weight, int8_t *solution, int32_t *info, uint64_t *stats) {
+    return lsd_batch_host(g, B, syndromes, llr, hard, bits_per_step, max_rows, weight, solution, info, stats, true);
 }

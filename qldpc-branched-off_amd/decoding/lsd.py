@@ -17,6 +17,11 @@ Per shot, with H (m x n), the syndrome s, the BP posteriors ``llr`` and their ha
 ``info`` (int32[B, 4]) holds the flag, the rounds, ``|R|`` and ``|A|`` of a shot (the last three 0 when the flag is not 0).  With
 ``bits_per_step=1`` a flag-0 answer has been OSD-0's on every recorded circuit-level case; larger steps take fewer rounds and may differ.  The C ABI is
 ``qldpc_lsd_batch`` in ``include/qldpc_hip.h``; ``tests/lsd_model.py`` is the model the kernel is tested against.
+
+``decode(..., return_stats=True)`` adds the statistics of the clusters a shot ends with (uint64[B, 8], ``_lib.LSD_STATS`` names the words: the number
+of clusters, the 1-, squared 2- and infinity norm of their column counts and of their weights, the largest row count), the soft output of BP+LSD
+(Lee et al., "Efficient post-selection for general quantum LDPC codes", 2025).  ``weights`` is uint16[n]; ``_lib.quantise_weights(prior)`` is the
+default table.  A shot with flag 1 or 2 has eight words 2^64 - 1: no statement (``qldpc_lsd_stats_batch``; ``tests/lsd_stats_model.py``).
 """
 import numpy as np
 
@@ -26,7 +31,7 @@ from .relay import _csr
 
 class LsdDecoder:
     """BP+LSD post-processor of one parity-check matrix.  ``decode(syndromes, llr, hard)`` returns ``(solution int8[B, n], info int32[B, 4])``
-    (one shot in, one shot out)."""
+    (one shot in, one shot out); with ``return_stats=True`` a third array, the cluster statistics uint64[B, 8] under ``weights`` (uint16[n] or None)."""
 
     def __init__(self, H, bits_per_step=1, max_rows=512, device=0):
         indptr, indices, n = _csr(H)
@@ -34,10 +39,16 @@ class LsdDecoder:
         self.bits_per_step, self.max_rows = p["bits_per_step"], p["max_rows"]
         self.graph = _lib.Graph(indptr, indices, n, device=device)
 
-    def decode(self, syndromes, llr, hard):
+    def decode(self, syndromes, llr, hard, weights=None, return_stats=False):
         syndromes = np.asarray(syndromes, dtype=np.int8)
         single = syndromes.ndim == 1
         n = self.graph.n
+        if weights is not None and not return_stats:
+            raise ValueError("weights are for return_stats=True")
+        if return_stats:
+            out = _lib.lsd_stats_batch(self.graph, syndromes.reshape(-1, self.graph.m), np.asarray(llr, np.float64).reshape(-1, n),
+                                       np.asarray(hard, np.int8).reshape(-1, n), self.bits_per_step, self.max_rows, weights)
+            return tuple(a[0] for a in out) if single else out
         sol, info = _lib.lsd_batch(self.graph, syndromes.reshape(-1, self.graph.m), np.asarray(llr, np.float64).reshape(-1, n),
                                    np.asarray(hard, np.int8).reshape(-1, n), self.bits_per_step, self.max_rows)
         return (sol[0], info[0]) if single else (sol, info)

@@ -320,9 +320,9 @@ def _dem_rules(who, dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder
 
 def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode=None, alvarado_alpha=None, base_seed=None, target_logical_errors=None,
                        max_trials=None, batch=16384, device=None, devices=None, num_workers=None, flags=0, decoder="bp_osd", relay_params=None, window=None,
-                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, soft=None):
+                       schedule="flooding", layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, soft=None, post_select=None):
     """``run_simulation`` for a DetectorErrorModel: the same result keys, in-order early stop (``target_logical_errors``), ``num_workers`` / ``devices`` and
-    extensions (``decoder`` with ``lsd`` for ``"bp_lsd"``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``, ``correlated`` with the links of
+    extensions (``decoder`` with ``lsd`` and ``post_select`` for ``"bp_lsd"``, ``window``, ``schedule`` / ``layers``, ``decimation``, ``precision``, ``correlated`` with the links of
     ``correlated.links_from_dem``) under the same argument rules; sector 0 fills the ``z``
     keys, sector 1 the ``x`` keys (0 for a one-sector model).  ``window=(W, C)`` needs the model's ``layer_rows``.
 
@@ -336,6 +336,8 @@ def run_dem_simulation(dem, num_trials=1000, maxIter=50, osd_order=0, alpha_mode
         raise ValueError("run_dem_simulation: soft=... needs a circuit plan (run_simulation): a detector error model has no measurement locations")
     rules, alpha_mode, alphas = _dem_rules("run_dem_simulation", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window, schedule, layers,
                                            decimation, precision, num_workers, lsd=lsd, correlated=correlated)
+    from .postselect import post_select_rules
+    rules.post_select = post_select_rules("run_dem_simulation", post_select, decoder, target_logical_errors)
     rank, world, devices = engine._worker_devices(num_workers, devices, device)
     if base_seed is None:
         base_seed = int(np.random.randint(0, 2 ** 31))
@@ -393,14 +395,22 @@ class DemDecoder:
 
     Events come in the MODEL's detector numbering (``dem.detector_map``; for ``from_text`` the text's ``D<i>``), ``dem.n_detectors`` per shot.  ``seed`` and
     the global shot index (``shot_begin`` + row) are what Relay-BP draws from; every other decoder ignores them.  So a prediction is a function of
-    (record, seed, shot index) and depends neither on ``batch`` nor on how the shots are split over calls."""
+    (record, seed, shot index) and depends neither on ``batch`` nor on how the shots are split over calls.
+
+    ``confidence`` (with ``decoder="bp_lsd"``; a kind of ``simulation.postselect.KINDS``) makes ``decode_batch(events, return_confidence=True)`` return
+    a score uint64[count] beside the predictions: small = trustworthy, 2^64 - 1 = LSD made no statement (``qldpc_circuit_plan_use_confidence``; the
+    weights are ``_lib.quantise_weights`` of the decoder views' priors)."""
 
     def __init__(self, dem, maxIter=50, decoder="bp_osd", osd_order=0, window=None, schedule="flooding", layers=None, decimation=None, precision="f64",
-                 relay_params=None, alpha_mode=None, alvarado_alpha=None, batch=16384, device=None, seed=0, flags=0, lsd=None, correlated=None):
+                 relay_params=None, alpha_mode=None, alvarado_alpha=None, batch=16384, device=None, seed=0, flags=0, lsd=None, correlated=None,
+                 confidence=None):
         self._rules, self._alpha_mode, self._alphas = _dem_rules("DemDecoder", dem, maxIter, osd_order, alpha_mode, alvarado_alpha, decoder, relay_params, window,
                                                                  schedule, layers, decimation, precision, lsd=lsd, correlated=correlated)
         if int(batch) < 1:
             raise ValueError("batch must be >= 1")
+        if confidence is not None:
+            from .postselect import post_select_rules
+            self._rules.post_select = post_select_rules("DemDecoder", {"kind": confidence, "edges": []}, decoder)
         self.dem, self.seed, self.batch, self.device = dem, int(seed), int(batch), device
         self._max_iter, self._osd_order, self._flags = maxIter, osd_order, flags
         self._plan = self._graphs = None
@@ -410,6 +420,8 @@ class DemDecoder:
             dem = self.dem
             dev = 0 if self.device is None else int(self.device)
             views = [dem.decoder_view(s) for s in range(dem.n_sectors)]
+            if self._rules.post_select is not None:
+                self._rules.post_select["weights"] = [_lib.quantise_weights(v.prior) for v in views]
             switch, _ = engine._plan_switch(self._rules, [(v.indptr, v.indices, v.shape[1]) for v in views], self._osd_order)
             self._graphs = [_lib.Graph(v.indptr, v.indices, v.shape[1], device=dev) for v in views]
             plan = dem.plan(self._graphs, max_iter=self._max_iter, alphas=self._alphas, alpha_mode=self._alpha_mode, batch=self.batch, flags=self._flags)
@@ -422,21 +434,26 @@ class DemDecoder:
             self._plan = plan
         return self._plan
 
-    def decode_to_flags(self, events, bit_packed=None, shot_begin=0):
+    def decode_to_flags(self, events, bit_packed=None, shot_begin=0, return_confidence=False):
         """decode_batch and the flags uint8[count]: bit 0 / 1 = converged, 2 / 3 = the correction does not reproduce the syndrome, 4 / 5 = zero syndrome,
-        of sector 0 / 1."""
+        of sector 0 / 1; with return_confidence a third entry, the score uint64[count]."""
+        if return_confidence and self._rules.post_select is None:
+            raise ValueError("return_confidence=True needs DemDecoder(..., decoder='bp_lsd', confidence=<kind>)")
         packed = _packed_events(events, self.dem.n_detectors, bit_packed)
         if int(shot_begin) < 0:
             raise ValueError("shot_begin must be >= 0")
-        pred = self._ensure_plan().decode_events(packed, seed=self.seed, shot_begin=int(shot_begin))
+        pred = self._ensure_plan().decode_events(packed, seed=self.seed, shot_begin=int(shot_begin), scores=bool(return_confidence))
         out = tuple(((pred[s][:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool) for s, k in enumerate(self.dem.k))
-        return (out[0] if self.dem.n_sectors == 1 else out), pred[2]
+        out = out[0] if self.dem.n_sectors == 1 else out
+        return (out, pred[2], pred[3]) if return_confidence else (out, pred[2])
 
-    def decode_batch(self, events, bit_packed=None, shot_begin=0):
+    def decode_batch(self, events, bit_packed=None, shot_begin=0, return_confidence=False):
         """events: bool or uint8 [count, n_detectors] (0 / 1 per detector), or bit-packed uint8 [count, ceil(n_detectors / 8)] (``_lib.pack_events``,
         ``read_b8``); bit_packed None = told apart by dtype and width.  Returns the predicted observable flips bool[count, k] per sector -- a pair for a
-        two-sector model, the array itself for a one-sector model (column r = ``L<r>`` of the text)."""
-        return self.decode_to_flags(events, bit_packed, shot_begin)[0]
+        two-sector model, the array itself for a one-sector model (column r = ``L<r>`` of the text).  return_confidence=True (a decoder created with
+        ``confidence=``): (predictions, score uint64[count])."""
+        res = self.decode_to_flags(events, bit_packed, shot_begin, return_confidence)
+        return (res[0], res[2]) if return_confidence else res[0]
 
     def close(self):
         if self._plan is not None:

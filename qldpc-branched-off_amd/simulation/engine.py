@@ -273,7 +273,7 @@ def _extension_rules(osd_order, precision, decimation, schedule, layers, window,
     if num_workers is not None and int(num_workers) < 1:
         raise ValueError("num_workers must be >= 1")
     return SimpleNamespace(path=path, osd_cs=osd_cs, lsd=lsd, layers=layers, decimation=decimation, relay_params=relay_params, window=window, correlated=correlated,
-                           links=None, erasure=erasure, erasure_tables=None, noise_model=None, matched_priors=True, soft=soft, soft_tables=None)
+                           links=None, erasure=erasure, erasure_tables=None, noise_model=None, matched_priors=True, soft=soft, soft_tables=None, post_select=None)
 
 
 def _noise_model_rules(who, noise_model, matched_priors, correlated=None, erasure=None, soft=None):
@@ -325,7 +325,8 @@ def _plan_switch(rules, csr, osd_order):
     """How a fresh plan moves to the call's path (qldpc_circuit_plan_use_*; the plan itself holds the rules), shared by _run_trials and
     dem.DemDecoder: (switch, layers).  switch(plan) puts OSD-CS of `osd_order` or LSD in the OSD stage when the rules ask for it, then moves the BP stage to
     rules.path (correlated: with rules.links, the CorrelationLinks the caller built; None = no links; erasure: with rules.erasure_tables; soft: with
-    rules.soft_tables), then switches erasure noise, a noise model or soft readout on where the rules ask for it (the sampler axis: last, since it goes with whatever the plan decodes with).  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
+    rules.soft_tables), then switches erasure noise, a noise model or soft readout on where the rules ask for it (the sampler axis: last, since it goes with whatever the plan decodes with),
+    then the confidence of rules.post_select (kind, edges, and the weights per sector the caller put there) on the LSD stage.  csr: (indptr, indices, n) per sector; layers: the row_layer every plan gets per sector (host code; None off the layered path)."""
     layers = None
     if rules.path == "layered":
         layers = [check_layers(c) if lay is None else validate_layers(c, lay) for c, lay in zip(csr, rules.layers)] + [None] * (2 - len(csr))
@@ -349,6 +350,8 @@ def _plan_switch(rules, csr, osd_order):
             plan.use_noise_model(rules.noise_model)
         if rules.soft is not None:                                               # ... and a fourth time
             plan.use_soft_readout(rules.soft["readout"])
+        if rules.post_select is not None:                                        # rides on the LSD stage (simulation/postselect.py)
+            plan.use_confidence(rules.post_select["kind"], rules.post_select["edges"], *rules.post_select["weights"])
 
     return switch, layers
 
@@ -361,6 +364,10 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
     device = devices[0]
     T = _lib.TALLY
     csr = [(g.indptr, g.indices, g.n) for g in graphs]
+    if rules.post_select is not None:
+        if world > 1:
+            raise ValueError("post_select=... does not run under a torch.distributed world > 1 (the histogram has no multi-rank reduction)")
+        rules.post_select["weights"] = [_lib.quantise_weights(prior) for prior in llrs]       # the priors the plans decode with, in units of 1 / 256
     to_path, layers = _plan_switch(rules, csr, osd_order)
     osdw_pass = osd_order > 0 and not rules.osd_cs    # (OSD-CS answers an unsatisfiable trial with OSD-0, as the fused plan does)
 
@@ -498,6 +505,10 @@ def _run_trials(make_plan, graphs, llrs, masks, alphas, ks, rules, rank, world, 
         pass
     if rules.lsd is not None:                                                    # flag 0 / 1 / 2 per sector over this process's plans (whole rounds, like the tally)
         extra["lsd_counts"] = np.sum([w.plan.lsd_counts(w.stream.ptr) for w in workers], axis=0)
+    if rules.post_select is not None:                                            # the workers' histograms, summed on the host
+        from .postselect import PostSelection
+        hist = np.sum([w.plan.confidence_hist(w.stream.ptr) for w in workers], axis=0, dtype=np.uint64)
+        extra["post_selection"] = PostSelection(hist, rules.post_select["edges"], rules.post_select["kind"])
     for w in workers:
         w.close()
     if stop_on_errors:
@@ -565,10 +576,14 @@ def run_simulation(Hx, Hz, Lx, Lz, error_rate, num_trials=1000, num_cycles=12, m
                    alpha_mode=None, alvarado_alpha=None, alpha_estimation_trials=5000, alpha_estimation_bins=50, precomputed_matrices=None,
                    num_workers=None, base_seed=None, use_jit=True, target_logical_errors=None, max_trials=None, scopt=False,
                    estimation_plot_dir=None, batch=16384, device=None, flags=0, devices=None, decoder="bp_osd", relay_params=None, window=None, schedule="flooding",
-                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, noise_model=None, matched_priors=True, soft=None, **bb_params):
+                   layers=None, decimation=None, precision="f64", lsd=None, correlated=None, erasure=None, noise_model=None, matched_priors=True, soft=None, post_select=None,
+                   **bb_params):
+    from .postselect import post_select_rules
     _noise_model_rules("run_simulation", noise_model, matched_priors, correlated, erasure, soft)
+    post_select = post_select_rules("run_simulation", post_select, decoder, target_logical_errors)
     rules = _extension_rules(osd_order, precision, decimation, schedule, layers, window, decoder, relay_params, alpha_mode, alvarado_alpha,
                              use_dynamic_alpha, scopt, maxIter, num_workers, lsd=lsd, correlated=correlated, erasure=erasure, soft=soft)
+    rules.post_select = post_select
     rank, world, devices = _worker_devices(num_workers, devices, device)
     device = devices[0]
     if base_seed is None:
