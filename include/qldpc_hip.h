@@ -423,8 +423,10 @@ int qldpc_osdcs_batch_dev(const qldpc_graph *g, int64_t B, const int8_t *d_syndr
  *   4. Shots with flag 1 or 2 get exactly qldpc_osd0_batch's answer (the OSD-0 kernels run on them behind the cluster kernel).
  * The outcome is a function of sets and of the (round, key) order only: no thread or lane order enters it (tests/lsd_model.py is the model).
  * With bits_per_step = 1 a flag-0 answer was qldpc_osd0_batch's on every recorded circ144 case; larger steps take fewer rounds and may differ.
- * QLDPC_ERR_INVALID for parameters outside their ranges; QLDPC_ERR_UNSUPPORTED for n >= 65535, m > 65535, or a layout at max_rows beyond
- * 160 KiB of LDS (csrc/lsd_plan.h).  solution int8[B][n]. */
+ * QLDPC_ERR_INVALID for parameters outside their ranges; QLDPC_ERR_UNSUPPORTED for n >= 65535, m > 65535, a layout at max_rows beyond
+ * 160 KiB of LDS (csrc/lsd_plan.h), or a matrix qldpc_osd0_batch refuses (step 4 hands shots over to it: its scratch, 5 m + 8 ceil(n / 64)
+ * + 40 bytes, passes 150 KiB beyond 30 710 rows at n <= 64 and beyond about 29 070 rows at n = 65 534, csrc/osd_plan.h).  The refusal is decided once, before anything is launched, whether or not a shot would have been
+ * handed over: no kernel runs and no output byte is written.  solution int8[B][n]. */
 int qldpc_lsd_batch(const qldpc_graph *g, int64_t B, const int8_t *syndromes, const double *llr, const int8_t *hard, int bits_per_step,
                     int max_rows, int8_t *solution, int32_t *info);
 /* same on device pointers; only enqueues on `stream`.  d_select / d_select_count as in qldpc_osd0_batch_dev: shots not listed keep whatever

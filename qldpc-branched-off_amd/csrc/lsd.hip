@@ -28,6 +28,7 @@
 #include "launchers.h"
 #include "osd_common.h"
 #include "lsd_plan.h"
+#include "osd_plan.h"
 
 #include <algorithm>
 #include <cstring>
@@ -347,9 +348,15 @@ __global__ __launch_bounds__(kLsdBlock) void lsd_kernel(LsdArgs P) {
     }
 }
 
+// the layout (lsd_supported), and the hand-over: flag-1 and flag-2 shots go to osd0_listed_launch, so a matrix OSD-0 refuses is refused here, once, before
+// anything is launched (whether a shot would be listed is not known until the cluster kernel has run)
 int lsd_graph_supported(const qldpc_graph *g, int max_rows) {
     switch (lsd_supported(g->m, g->n, std::max(g->max_col_deg, 1), max_rows)) {
-    case kLsdAccepted: return QLDPC_OK;
+    case kLsdAccepted:
+        if (osd0_plan(g->m, g->n, g->max_col_deg, 0).refused == kOsdAccepted) return QLDPC_OK;
+        set_error("LSD hands the shots it cannot finish over to OSD-0, which refuses a %d x %d matrix (too large for its LDS scratch: m=%d nwords=%d)", g->m,
+                  g->n, g->m, osd_global_nwords(g->n));
+        break;
     case kLsdRefusedColumns: set_error("LSD supports n < 65535 (this matrix has %d columns)", g->n); break;
     case kLsdRefusedRows: set_error("LSD supports m <= 65535 (this matrix has %d rows)", g->m); break;
     case kLsdRefusedLds: set_error("LSD: a %d x %d matrix with max_rows = %d needs more LDS than the 160 KiB of a workgroup", g->m, g->n, max_rows); break;

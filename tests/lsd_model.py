@@ -90,7 +90,8 @@ def span_basis(G, cols):
 
 
 def lsd(G, syndrome, llr, hard, bits_per_step=1, max_rows=512, trace=None, osd0=None):
-    """one shot -> (solution int8[n], info (flag, rounds, |R|, |A|)); trace (a dict, optional) receives A, the pivots and the clusters of every round.
+    """one shot -> (solution int8[n], info (flag, rounds, |R|, |A|)); trace (a dict, optional) receives A, the pivots, the clusters of every round and the size
+    of every round's list N_t.
     osd0(syndrome, llr, hard) answers the shots that end with flag 1 or 2; the default is the sweep of tests/osd_cs_model.py, which is OSD-0's answer
     where s + H hard lies in the column space (a flag-2 shot never does: pass the oracle's or the library's OSD-0 there)."""
     assert 1 <= bits_per_step <= 64 and 1 <= max_rows <= 1024
@@ -130,6 +131,8 @@ def lsd(G, syndrome, llr, hard, bits_per_step=1, max_rows=512, trace=None, osd0=
         grown = R
         for j in picks:
             grown |= G.mask(j)
+        if trace is not None:
+            trace.setdefault("lists", []).append(len(picks))                  # |N_t| of every round that found its candidates (a capped one too)
         if bin(grown).count("1") > max_rows:
             return fail(1)
         A += sorted(picks, key=key.__getitem__)

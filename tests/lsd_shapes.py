@@ -63,26 +63,37 @@ def _shots(synd, llr, hard):
     return SimpleNamespace(synd=np.ascontiguousarray(synd, np.int8), llr=np.ascontiguousarray(llr, np.float64), hard=np.ascontiguousarray(hard, np.int8))
 
 
-def general(key, B=24, seed=0):
-    """a mixed batch: sparse errors of weight 1 .. 6 over a sparse hard decision, a third of them with tied and non-finite |llr|, every eighth shot with
-    zero residual (hard = the error), every eighth a random syndrome (many seeds; it may lie outside the column space)"""
-    f, G = matrix(key)
-    rng = np.random.default_rng([S.SEED, seed, B] + [ord(c) for c in key])
+def general_on(f, G, rng, B, quick=False):
+    """the mixed batch of `general` on any matrix (tests/lsd_domain_shapes.py uses it too).  quick: the columns of the error and of the hard decision are
+    among the least reliable ones and no syndrome is random, so the clusters stay small and the model quick"""
     E, hard = np.zeros((B, f.n), np.int8), np.zeros((B, f.n), np.int8)
     llr = rng.normal(1.0, 3.0, (B, f.n))
+    if quick:
+        llr = 2.0 + np.abs(llr)
     for b in range(B):
         E[b, rng.choice(f.n, min(1 + b % 6, f.n), replace=False)] = 1
         hard[b, rng.choice(f.n, min(b % 4, f.n), replace=False)] = 1
         if b % 3 == 1:
             llr[b] = np.round(llr[b])                                        # many ties, zeros among them
             llr[b, rng.choice(f.n, min(3, f.n), replace=False)] = [np.nan, np.inf, -np.inf][:min(3, f.n)]
+        if quick:
+            low = np.flatnonzero(E[b] | hard[b])
+            llr[b, low] = rng.choice([0.0, 0.25, 0.5, 0.5, 1.0], low.size)
+            llr[b] *= rng.choice([-1.0, 1.0], f.n)
     synd = np.stack([G.parity(e) for e in E])
     for b in range(B):
         if b % 8 == 7:
             hard[b] = E[b]
-        elif b % 8 == 3:
+        elif b % 8 == 3 and not quick:
             synd[b] = rng.random(f.m) < 0.5
     return _shots(synd, llr, hard)
+
+
+def general(key, B=24, seed=0):
+    """a mixed batch: sparse errors of weight 1 .. 6 over a sparse hard decision, a third of them with tied and non-finite |llr|, every eighth shot with
+    zero residual (hard = the error), every eighth a random syndrome (many seeds; it may lie outside the column space)"""
+    f, G = matrix(key)
+    return general_on(f, G, np.random.default_rng([S.SEED, seed, B] + [ord(c) for c in key]), B)
 
 
 def single_seed(key="ident"):
