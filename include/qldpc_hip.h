@@ -718,8 +718,9 @@ int qldpc_circuit_plan_use_relay(qldpc_circuit_plan *plan, double alpha, double 
  * outside the range of qldpc_osdcs_batch. */
 int qldpc_circuit_plan_use_osd_cs(qldpc_circuit_plan *plan, int order);
 /* Switches the plan's OSD stage to BP+LSD (qldpc_lsd_batch with these parameters): the same unconverged trials, the same phase brackets, the
- * same tally slots.  It goes with flooding, the layered schedule, guided decimation and f32 in either order, and may be called again with new
- * parameters.  QLDPC_ERR_INVALID on a plan created with use_osd = 0, switched to Relay-BP, to windows or to OSD-CS (and
+ * same tally slots.  It goes with flooding, the layered schedule, guided decimation, f32, correlated decoding, erasure-aware decoding and
+ * soft-aware decoding in either order (it reads the posteriors and the hard decision as that path left them; behind correlated decoding sector X's
+ * links are read against sector Z's correction as this stage left it), and may be called again with new parameters.  QLDPC_ERR_INVALID on a plan created with use_osd = 0, switched to Relay-BP, to windows or to OSD-CS (and
  * qldpc_circuit_plan_use_relay / _use_window / _use_osd_cs after this call return QLDPC_ERR_INVALID), or for parameters outside their ranges;
  * QLDPC_ERR_UNSUPPORTED when a sector's matrix is one qldpc_lsd_batch refuses at this max_rows. */
 int qldpc_circuit_plan_use_lsd(qldpc_circuit_plan *plan, int bits_per_step, int max_rows);

@@ -1240,7 +1240,7 @@ class CircuitPlan(Owner):
 
     def use_lsd(self, bits_per_step=1, max_rows=512):
         """Run BP+LSD in the OSD stage from now on (qldpc_circuit_plan_use_lsd; again with new parameters is allowed).  Goes with flooding, the layered
-        schedule, guided decimation and f32; not with Relay-BP, windows or OSD-CS."""
+        schedule, guided decimation, f32, correlated, erasure-aware and soft-aware decoding; not with Relay-BP, windows or OSD-CS."""
         p = lsd_params({"bits_per_step": bits_per_step, "max_rows": max_rows})
         check(lib().qldpc_circuit_plan_use_lsd(self._h, p["bits_per_step"], p["max_rows"]))
         self.lsd = p

@@ -10,7 +10,7 @@ import torch  # noqa: F401  (first: the HIP runtime torch loads is the one libql
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import correlated_model as CM  # noqa: E402
-from test_plan_switch_gpu import SWITCHES, refused, run64, BATCH  # noqa: E402
+from test_plan_switch_gpu import BASE_SWITCHES as SWITCHES, refused, run64, BATCH  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup  # noqa: E402
 
 pytestmark = pytest.mark.gpu

@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import correlated_model as CM  # noqa: E402
 import erasure_model as EM  # noqa: E402
 from test_correlated_gpu import logical_bits  # noqa: E402
-from test_plan_switch_gpu import SWITCHES, refused, run64, BATCH  # noqa: E402
+from test_plan_switch_gpu import BASE_SWITCHES as SWITCHES, refused, run64, BATCH  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup  # noqa: E402
 
 pytestmark = pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""The circuit plan's switch rules as one table: every qldpc_circuit_plan_use_* on a fresh plan, every ordered pair of them and every one applied
+"""The circuit plan's switch rules as one table: every decode switch qldpc_circuit_plan_use_* (all ten) on a fresh plan, every ordered pair of them and every one applied
 twice, on circ72 with batch 64.  An accepted switch leaves a plan that runs; a refused one answers QLDPC_ERR_INVALID, names the plan's state before
 the requested one, and leaves the plan decoding exactly as before.  Then the two creation arguments the rules read: use_osd = 0 and damping != 1."""
 import os
@@ -15,8 +15,18 @@ pytestmark = pytest.mark.gpu
 
 BATCH = 64
 
+def _tables(which):
+    """the erasure tables or the gaussian soft tables of circ72, from the feature modules' setup (imported late: they import this module)"""
+    from qldpc_amd import _lib
+    if which == "erasure":
+        import test_erasure_gpu
+        return test_erasure_gpu.setup(_lib)[9]
+    import test_soft_gpu
+    return test_soft_gpu.setup(_lib)[9]["gaussian"]
+
+
 # switch -> (display name in the library's messages, the call, the call with other arguments for a re-application)
-SWITCHES = {
+BASE_SWITCHES = {
     "relay": ("Relay-BP", lambda p: p.use_relay(), lambda p: p.use_relay(t0=40, max_legs=100)),
     "osd_cs": ("BP + OSD-CS", lambda p: p.use_osd_cs(5), lambda p: p.use_osd_cs(3)),
     "window": ("sliding-window decoding", lambda p: p.use_window(4, 2), lambda p: p.use_window(3, 1)),
@@ -24,18 +34,26 @@ SWITCHES = {
     "decimation": ("guided decimation", lambda p: p.use_decimation(), lambda p: p.use_decimation(per_round=4)),
     "f32": ("single precision (f32)", lambda p: p.use_f32(), lambda p: p.use_f32()),
 }
+# ... and the four that came later.  The feature modules build their "new row and column" tests on BASE_SWITCHES, as they did when they were written.
+SWITCHES = dict(
+    BASE_SWITCHES,
+    lsd=("BP + LSD", lambda p: p.use_lsd(), lambda p: p.use_lsd(max_rows=128)),
+    correlated=("correlated decoding", lambda p: p.use_correlated(), lambda p: p.use_correlated(0.875)),
+    erasure_aware=("erasure-aware decoding", lambda p: p.use_erasure_aware(1.0, _tables("erasure")), lambda p: p.use_erasure_aware(0.875, _tables("erasure"))),
+    soft_aware=("soft-aware decoding", lambda p: p.use_soft_aware(1.0, _tables("soft")), lambda p: p.use_soft_aware(0.875, _tables("soft"))),
+)
 
 # ACCEPTED[first] = the switches a plan takes after `first` (every switch is accepted on a fresh plan); everything else is refused.
-# Two axes: the path (relay, window, layered, decimation, f32: left at most once, re-applied except window) and the OSD stage (osd_cs: goes with
-# layered, decimation and f32 in either order, with neither relay nor window).
-ACCEPTED = {
-    "relay": {"relay"},
-    "osd_cs": {"osd_cs", "layered", "decimation", "f32"},
-    "window": set(),
-    "layered": {"layered", "osd_cs"},
-    "decimation": {"decimation", "osd_cs"},
-    "f32": {"f32", "osd_cs"},
-}
+# Two axes: the path (relay, window, layered, decimation, f32, correlated, erasure_aware, soft_aware: left at most once, re-applied except window) and
+# the OSD stage (osd_cs, lsd: each goes with layered, decimation, f32, correlated, erasure_aware and soft_aware in either order, with neither relay nor
+# window, and they refuse each other).
+STAGE_SWITCHES = ("osd_cs", "lsd")
+WITH_A_STAGE = ("layered", "decimation", "f32", "correlated", "erasure_aware", "soft_aware")
+ACCEPTED = {"relay": {"relay"}, "window": set()}
+ACCEPTED.update({path: {path, *STAGE_SWITCHES} for path in WITH_A_STAGE})
+ACCEPTED.update({stage: {stage, *WITH_A_STAGE} for stage in STAGE_SWITCHES})
+assert set(ACCEPTED) == set(SWITCHES) and ACCEPTED["osd_cs"] == {"osd_cs", "layered", "decimation", "f32", "correlated", "erasure_aware", "soft_aware"}
+assert all(ACCEPTED[k] == {k, "osd_cs", "lsd"} for k in ("layered", "decimation", "f32"))
 
 
 @pytest.fixture(scope="module")
@@ -94,7 +112,7 @@ def test_a_plan_without_osd_stage(L):
     plan = circuit_setup(L, "circ72")[6]
     for name, (requested, call, _) in SWITCHES.items():
         p = plan(batch=BATCH, use_osd=False)
-        if name in ("osd_cs", "window"):
+        if name in ("osd_cs", "window", "lsd"):
             refused(L, p, call, "use_osd = 0", requested, reason="OSD stage")
         else:
             call(p)
@@ -106,7 +124,7 @@ def test_a_damped_plan(L):
     plan = circuit_setup(L, "circ72")[6]
     for name, (requested, call, _) in SWITCHES.items():
         p = plan(batch=BATCH, damping=0.5)
-        if name in ("relay", "osd_cs"):                                    # neither reads the damping: only their own argument checks apply
+        if name in ("relay", "osd_cs", "lsd"):                             # none of them reads the damping: only their own argument checks apply
             call(p)
             run64(L, p)
         else:

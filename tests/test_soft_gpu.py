@@ -14,7 +14,7 @@ import correlated_model as CM  # noqa: E402
 import soft_model as SM  # noqa: E402
 from test_correlated_gpu import logical_bits  # noqa: E402
 from test_erasure_gpu import assert_aware_tally, aware_chain  # noqa: E402
-from test_plan_switch_gpu import SWITCHES, refused, run64, BATCH  # noqa: E402
+from test_plan_switch_gpu import BASE_SWITCHES as SWITCHES, refused, run64, BATCH  # noqa: E402
 from test_relay_gpu import _bb_params, circuit_setup  # noqa: E402
 
 pytestmark = pytest.mark.gpu
