@@ -1012,7 +1012,7 @@ int qldpc_soft_priors(int64_t B, int32_t levels, int32_t n_meas, const uint8_t *
  * either way). */
 int qldpc_soft_priors_dev(int64_t B, int32_t levels, int32_t n_meas, const uint8_t *d_levels, const int32_t *d_meas_col, const int32_t *d_meas_w,
                           int32_t n, const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, void *stream);
-/* The sampler axis of a plan a fourth time (beside qldpc_circuit_plan_use_fixed_weight, _use_erasure_noise and _use_noise_model): from now on the
+/* The sampler axis of a plan (beside qldpc_circuit_plan_use_fixed_weight, _use_erasure_noise and _use_noise_model): from now on the
  * plan's sampler draws the readouts above on top of its ordinary faults; flip_mass == NULL switches them off again.  Two-way, any number of times;
  * not a decode switch, so it goes with every path and OSD stage in either call order.  _run, _run_outcomes, _sample, _sample_erasures (whose herald
  * record stays all zero) and _sample_soft honour it; a plan that is not on the soft-aware path decodes the syndromes as it always does (it does not

@@ -51,40 +51,22 @@ __global__ void fault_signature_kernel(int nl, const int32_t *__restrict__ lane_
     }
 }
 
-// SigTab, the component masks, xor_signature and fire_location: sampler_common.h (shared with fixed_weight.hip)
-
-// one workgroup per trial (grid-stride): draw faults, accumulate both sectors' detector bit-sets in LDS, write them out
+// the independent draws in the frame of sampler_common.h: a lane per Philox block = four locations, a faulty one fires its components
 __global__ __launch_bounds__(256) void circuit_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, uint32_t thr,
-                                                             int n_locs, const uint8_t *__restrict__ loc_type, SigTab Z, SigTab X, int nsx,
-                                                             int nsz, int8_t *__restrict__ syn_z, int8_t *__restrict__ syn_x,
-                                                             unsigned long long *__restrict__ true_z, unsigned long long *__restrict__ true_x,
-                                                             int32_t *__restrict__ fail_counts) {
+                                                             int n_locs, const uint8_t *__restrict__ loc_type, SigTab Z, SigTab X, SampleOut O) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // [0] Z, [4] X BP failures of this batch (no memset launches)
-    const int wz = (nsx + 31) >> 5, wx = (nsz + 31) >> 5;
-    uint32_t *bz = sm, *bx = sm + wz;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + ((wz + wx + 1) & ~1));
     const int nblk = (n_locs + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int w = threadIdx.x; w < wz + wx; w += blockDim.x) sm[w] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        __syncthreads();
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    sample_trials<true>(sm, B, trial_begin, O, 0, nullptr, [&](int64_t, uint64_t g, const SampleLds &L) {
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             uint32_t o[4];
             philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)blk, 1u, seed_lo, seed_hi, o);
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
-                if (l < n_locs && o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, bz, bx, lacc);
+                if (l < n_locs && o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, L.b0, L.b1, L.lacc);
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < nsx; i += blockDim.x) syn_z[t * nsx + i] = (bz[i >> 5] >> (i & 31)) & 1;
-        for (int i = threadIdx.x; i < nsz; i += blockDim.x) syn_x[t * nsz + i] = (bx[i >> 5] >> (i & 31)) & 1;
-        if (threadIdx.x == 0) { true_z[t] = lacc[0]; true_x[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
 // per trial (32 lanes): decoded logical action H_logical @ det (engine.py:99,119) (judge.h) vs the true logical flips, both sectors
@@ -145,6 +127,13 @@ using namespace qldpc;
 // What both sectors decode with, on two axes; a plan is created as FLOOD + OSD0 and qldpc_circuit_plan_use_* moves it (switch_allowed holds the rules).
 enum class Path { FLOOD, LAYERED, DECIM, F32, RELAY, WINDOW, CORRELATED, ERASURE, SOFT };      // who fills the BP bracket and its follow-up
 enum class Osd { OSD0, CS, LSD };                                     // the OSD stage of a plan that has one (use_osd, and a path other than RELAY)
+// What a trial is drawn with, the third axis (sampler_switch_allowed holds its rules; only launch_sampler and the two record exports read it).  A plan is
+// created on INDEPENDENT: every location of a circuit at the plan's p (circuit.hip), or every mechanism of a detector error model at its own probability
+// (dem.hip; `dem` is a property of the plan, the source of its tables, and no switch).  FIXED_WEIGHT: exactly `fixed_weight` faults per trial
+// (fixed_weight.hip).  ERASURE: heralded erasures at `ethr` on top of the independent draws (erasure.hip).  NOISE_MODEL: a threshold per location
+// class and weighted Paulis, `nm`, in place of p and r % K (noise_model.hip).  SOFT: a confidence level and a flip per measurement, `sr`, on top of the
+// independent draws (soft.hip).  A sampler's parameters and buffers outlive a switch away from it; they are read only while the plan is on it.
+enum class Sampler { INDEPENDENT, FIXED_WEIGHT, ERASURE, NOISE_MODEL, SOFT };
 
 struct qldpc_circuit_plan {
     // Everything that exists once per sector: sec[0] = Z, sec[1] = X.  A batch decodes Z, then X, on the caller's stream.
@@ -182,13 +171,11 @@ struct qldpc_circuit_plan {
     // projection onto it, and d_thr their thresholds (uint32, zero-padded to a multiple of four).
     bool dem = false;
     DevBuf d_thr;
-    // the sampler axis (qldpc_circuit_plan_use_fixed_weight): -1 = the independent draws above, w >= 0 = exactly w faults per trial (fixed_weight.hip).
-    // dem_odd: the first mechanism whose threshold differs from mechanism 0's (-1: none), which refuses the switch
-    int fixed_weight = -1;
+    Sampler sampler = Sampler::INDEPENDENT;
+    // Sampler::FIXED_WEIGHT: faults per trial.  dem_odd: the first mechanism whose threshold differs from mechanism 0's (-1: none), which refuses the switch
+    int fixed_weight = 0;
     int64_t dem_odd = -1;
-    // ... and qldpc_circuit_plan_use_erasure_noise: heralded erasures on top of the independent draws (erasure.hip); ethr: the threshold per op code;
-    // d_erased: the herald record uint32[batch][ceil(n_locs / 32)] of a batch.  Erasure noise and a fixed weight refuse each other.
-    bool erasure = false;
+    // Sampler::ERASURE: the threshold per op code; d_erased: the herald record uint32[batch][ceil(n_locs / 32)] of a batch
     uint32_t ethr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf d_erased;
     double era_alpha = 1.0;                        // Path::ERASURE: constant alpha
@@ -220,15 +207,11 @@ struct qldpc_circuit_plan {
     std::vector<hipEvent_t> pool;
     double phase_ms[QLDPC_CIRCUIT_PHASES] = {0, 0, 0, 0, 0, 0};
     int64_t batches = 0;
-    // the sampler axis a third time, qldpc_circuit_plan_use_noise_model: a threshold per location class and weighted Paulis in place of thr and r % K (noise_model.hip); nm: the
-    // checked model; d_loc_cls: the op codes of d_loc_type, four to a word (uploaded at the first switch).  A model refuses a fixed weight and erasure noise.
-    bool noise_model = false;
+    // Sampler::NOISE_MODEL: the checked model; d_loc_cls: the op codes of d_loc_type, four to a word (uploaded at the first switch that reads them)
     NoiseModelHost nm{};
     DevBuf d_loc_cls;
-    // ... and a fourth, qldpc_circuit_plan_use_soft_readout: a confidence level and a flip per measurement on top of the independent draws (soft.hip);
-    // sr: the checked readout channel; n_meas: the MeasX / MeasZ locations (-1 until soft_prepare counts them); d_meas_rank: a location's rank
-    // among them; d_levels: the level record uint8[batch][n_meas] of a batch.  Soft readout refuses the three other switches of the axis.
-    bool soft = false;
+    // Sampler::SOFT: the checked readout channel; n_meas: the MeasX / MeasZ locations (-1 until soft_prepare counts them); d_meas_rank: a location's rank
+    // among them; d_levels: the level record uint8[batch][n_meas] of a batch
     SoftReadoutHost sr{};
     int n_meas = -1;
     DevBuf d_meas_rank, d_levels;
@@ -518,38 +501,27 @@ QLDPC_EXPORT int qldpc_circuit_plan_create_dem(const qldpc_dem_desc *D, const ql
 
 static int launch_sampler(qldpc_circuit_plan *P, uint64_t seed, int64_t begin, int64_t B, hipStream_t s, bool zero_counts = false) {
     const Sector &Z = P->sec[0], &X = P->sec[1];
-    if (P->fixed_weight >= 0) {
-        const auto tab = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
-        return fixed_weight_sample_launch(P->device, B, begin, seed, P->fixed_weight, P->n_locs, P->dem, P->d_loc_type.as<uint8_t>(), tab(Z), tab(X), Z.nsyn,
-                                          X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(),
-                                          X.d_true.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
-    }
-    if (P->dem) {
-        const auto tab = [](const Sector &S) { return DemTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
-        return dem_sample_launch(B, begin, seed, P->n_locs, P->d_thr.as<uint32_t>(), tab(Z), tab(X), Z.nsyn, X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(),
-                                 X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
-                                 zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
-    }
     const auto sig = [](const Sector &S) { return SigTab{S.d_ptr.as<int32_t>(), S.d_idx.as<uint16_t>(), S.d_log.as<uint64_t>()}; };
-    if (P->erasure)
-        return erasure_sample_launch(P->device, B, begin, seed, P->thr, P->ethr, P->n_locs, P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn,
-                                     Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
-                                     P->d_erased.as<uint32_t>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
-    if (P->noise_model)
-        return noise_model_sample_launch(B, begin, seed, P->nm, P->n_locs, P->d_loc_cls.as<uint32_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(),
-                                         X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(),
-                                         zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
-    if (P->soft)
+    const SampleOut out{Z.nsyn, X.nsyn, P->nsec == 2, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(), Z.d_true.as<unsigned long long>(),
+                        X.d_true.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr};
+    switch (P->sampler) {
+    case Sampler::FIXED_WEIGHT:
+        return fixed_weight_sample_launch(P->device, B, begin, seed, P->fixed_weight, P->n_locs, P->dem, P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), out, s);
+    case Sampler::ERASURE:
+        return erasure_sample_launch(P->device, B, begin, seed, P->thr, P->ethr, P->n_locs, P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), out,
+                                     P->d_erased.as<uint32_t>(), s);
+    case Sampler::NOISE_MODEL:
+        return noise_model_sample_launch(B, begin, seed, P->nm, P->n_locs, P->d_loc_cls.as<uint32_t>(), sig(Z), sig(X), out, s);
+    case Sampler::SOFT:
         return soft_sample_launch(B, begin, seed, P->thr, P->sr, P->n_locs, P->d_loc_type.as<uint8_t>(), P->d_loc_cls.as<uint32_t>(),
-                                  P->d_meas_rank.as<int32_t>(), P->n_meas, sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(),
-                                  Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(), P->d_levels.as<uint8_t>(),
-                                  zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr, s);
-    const int wz = (Z.nsyn + 31) / 32, wx = (X.nsyn + 31) / 32;
-    const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(circuit_sample_kernel, dim3(grid), dim3(256), lds, s, B, begin, (uint32_t)seed, (uint32_t)(seed >> 32), P->thr, P->n_locs,
-                       P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), Z.nsyn, X.nsyn, Z.d_syn.as<int8_t>(), X.d_syn.as<int8_t>(),
-                       Z.d_true.as<unsigned long long>(), X.d_true.as<unsigned long long>(), zero_counts ? P->d_count.as<int32_t>() : (int32_t *)nullptr);
+                                  P->d_meas_rank.as<int32_t>(), P->n_meas, sig(Z), sig(X), out, P->d_levels.as<uint8_t>(), s);
+    case Sampler::INDEPENDENT:
+        break;
+    }
+    if (P->dem) return dem_sample_launch(B, begin, seed, P->n_locs, P->d_thr.as<uint32_t>(), sig(Z), sig(X), out, s);
+    const SampleShape shape = sample_shape(out.n0, out.n1, true, B);
+    hipLaunchKernelGGL(circuit_sample_kernel, dim3(shape.grid), dim3(256), shape.words * 4, s, B, begin, (uint32_t)seed, (uint32_t)(seed >> 32), P->thr, P->n_locs,
+                       P->d_loc_type.as<uint8_t>(), sig(Z), sig(X), out);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }
@@ -692,8 +664,8 @@ static int circuit_run(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin
         if (P->pending.size() > 256) drain_phases(P, false);         // a caller that never reads phase times: recycle finished brackets (bounded event count)
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, true)) != QLDPC_OK) return rc;
         if ((rc = launch_sampler(P, seed, trial_begin + off, B, s, true)) != QLDPC_OK) return rc;
-        const bool levels = P->soft && P->path == Path::SOFT;
-        const bool heralds = (P->erasure && P->path == Path::ERASURE) || levels;       // (the prior kernels count as sampling: they turn the draws into the decoder's input)
+        const bool levels = P->sampler == Sampler::SOFT && P->path == Path::SOFT;
+        const bool heralds = (P->sampler == Sampler::ERASURE && P->path == Path::ERASURE) || levels;       // (the prior kernels count as sampling: they turn the draws into the decoder's input)
         for (int sector = 0; heralds && sector < P->nsec; sector++)
             if ((rc = levels ? launch_soft_prior(P, sector, B, s) : launch_erasure_prior(P, sector, B, s)) != QLDPC_OK) return rc;
         if ((rc = phase_mark(P, QLDPC_PHASE_SAMPLE, s, false)) != QLDPC_OK) return rc;
@@ -751,6 +723,38 @@ QLDPC_EXPORT int qldpc_circuit_plan_read(qldpc_circuit_plan *P, void *stream, in
     return QLDPC_OK;
 }
 
+// The batch loop of the three sample exports, everything to host pointers: per batch the sampler and, where priors are asked for, every sector's prior
+// kernel; a wait; then per sector in use the syndromes int8[count][nsyn], the truth bits unpacked to int8[count][k] and the priors f64[count][n] out of
+// d_eprior, and the batch's rows of the record.  A one-sector plan touches nothing of sector 1.
+// SampleRecord: what a sampler writes per trial besides the syndromes (the herald words, the levels): `bytes` per trial from dev to host; zero: the
+// plan is not on that sampler, which then writes no record, so it reads as zeros.
+struct SampleRecord { void *dev; size_t bytes; void *host; bool zero; };
+using PriorLaunch = int (*)(qldpc_circuit_plan *, int, int64_t, hipStream_t);
+static int sample_readback(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *const sparse[2], int8_t *const truth[2],
+                           const SampleRecord &rec = {}, PriorLaunch launch_prior = nullptr, double *const prior[2] = nullptr) {
+    int rc;
+    std::vector<unsigned long long> t;
+    for (int64_t off = 0; off < count; off += P->batch) {
+        const int64_t B = std::min<int64_t>(P->batch, count - off);
+        if (rec.zero && rec.bytes) QLDPC_HIP_TRY(hipMemsetAsync(rec.dev, 0, (size_t)B * rec.bytes, nullptr));
+        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
+        for (int i = 0; launch_prior && i < P->nsec; i++)
+            if ((rc = launch_prior(P, i, B, nullptr)) != QLDPC_OK) return rc;
+        QLDPC_HIP_TRY(hipDeviceSynchronize());
+        t.resize(B);
+        if (rec.bytes) QLDPC_HIP_TRY(hipMemcpy(static_cast<uint8_t *>(rec.host) + off * rec.bytes, rec.dev, (size_t)B * rec.bytes, hipMemcpyDeviceToHost));
+        for (int i = 0; i < P->nsec; i++) {
+            const Sector &S = P->sec[i];
+            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
+            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+            for (int64_t b = 0; b < B; b++)
+                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
+            if (launch_prior) QLDPC_HIP_TRY(hipMemcpy(prior[i] + off * S.g->n, S.d_eprior.p, (size_t)B * S.g->n * 8, hipMemcpyDeviceToHost));
+        }
+    }
+    return QLDPC_OK;
+}
+
 // batched run_trial_fast: sparse_z int8[count][nsx], true_z int8[count][k], sparse_x int8[count][nsz], true_x int8[count][k] (host)
 QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed, int64_t trial_begin, int64_t count, int8_t *sparse_z,
                                            int8_t *true_z, int8_t *sparse_x, int8_t *true_x) {
@@ -758,23 +762,8 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample(qldpc_circuit_plan *P, uint64_t seed,
     QLDPC_REQUIRE(count >= 0 && trial_begin >= 0, "negative trial range");
     QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && (P->nsec == 1 || (sparse_x && true_x))), "NULL output");
     QLDPC_USE_DEVICE(P->device);
-    int rc;
     int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
-    std::vector<unsigned long long> t;
-    for (int64_t off = 0; off < count; off += P->batch) {
-        const int64_t B = std::min<int64_t>(P->batch, count - off);
-        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
-        QLDPC_HIP_TRY(hipDeviceSynchronize());
-        t.resize(B);
-        for (int i = 0; i < P->nsec; i++) {
-            const Sector &S = P->sec[i];
-            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
-            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-            for (int64_t b = 0; b < B; b++)
-                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
-        }
-    }
-    return QLDPC_OK;
+    return sample_readback(P, seed, trial_begin, count, sparse, truth);
 }
 
 // Sums (ms) of the hipEvent brackets of each phase over the batches enqueued since the last call, and the number of batches.  The phases of
@@ -1038,53 +1027,69 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_f32(qldpc_circuit_plan *P) {
     return rc;
 }
 
-// The sampler axis: not a decode switch (switch_allowed is not asked), two-way, and only read by launch_sampler.  Launch arguments travel by value,
-// so batches already enqueued keep the sampler they were enqueued with.
+// The rules of the sampler axis, once.  qldpc_circuit_plan_use_fixed_weight, _use_erasure_noise, _use_noise_model and _use_soft_readout move a plan
+// along it, and unlike the decode axes it is two-way: each of them also switches its sampler off again.
+//   It asks no decode-path rule (switch_allowed is not consulted): what a trial is drawn with and what decodes it are independent.
+//   Every sampler other than the independent draws refuses every other such sampler until it is switched off.  Asking again for the sampler the plan
+//     is on brings new arguments.
+//   Erasure noise, a noise model and soft readout need a circuit plan: a detector error model has no gate locations.
+//   A fixed weight on a detector error model needs one probability for all mechanisms (dem_odd < 0).
+// Launch arguments travel by value, so batches already enqueued keep the sampler they were enqueued with.
+// QLDPC_OK, or QLDPC_ERR_INVALID with the error text set.
+static int sampler_switch_allowed(const qldpc_circuit_plan *P, Sampler to) {
+    static const char *const name[] = {"the independent draws", "a fixed weight", "erasure noise", "a noise model", "soft readout"};
+    static const char *const the[] = {"", "the fixed weight", "erasure noise", "the noise model", "soft readout"};
+    QLDPC_REQUIRE(!P->dem || to == Sampler::FIXED_WEIGHT, "%s needs a circuit plan: a detector error model has no gate locations", name[(int)to]);
+    QLDPC_REQUIRE(P->sampler == Sampler::INDEPENDENT || P->sampler == to, "the plan samples %s: %s goes with the independent draws alone (switch %s off first)",
+                  name[(int)P->sampler], name[(int)to], the[(int)P->sampler]);
+    QLDPC_REQUIRE(to != Sampler::FIXED_WEIGHT || !P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
+                  "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
+    return QLDPC_OK;
+}
+// Switching off a sampler the plan is not on changes nothing and is no error: only the plan's own sampler falls back to the independent draws, so
+// "erasure noise off" leaves a plan on a noise model on its noise model.
+static int sampler_off(qldpc_circuit_plan *P, Sampler which) {
+    if (P->sampler == which) P->sampler = Sampler::INDEPENDENT;
+    return QLDPC_OK;
+}
+// The order in which errors win inside an entry is part of its contract: a fixed weight checks its argument before the axis rules; the other three ask
+// the axis rules (a circuit plan, then the refusals) before their arguments.  Every entry sets the plan's state after its last check, so a refused call
+// leaves the plan sampling exactly what it sampled before.
+
+// weight -1 = off
 QLDPC_EXPORT int qldpc_circuit_plan_use_fixed_weight(qldpc_circuit_plan *P, int weight) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    if (weight == -1) { P->fixed_weight = -1; return QLDPC_OK; }
-    const int rc = fixed_weight_check(P->n_locs, weight);
-    if (rc != QLDPC_OK) return rc;
-    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a fixed weight counts the faults of the independent draws alone (switch erasure noise off first)");
-    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the fixed-weight law needs one p for every location (switch the noise model off first)");
-    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: a fixed weight counts the faults of the independent draws alone (switch soft readout off first)");
-    QLDPC_REQUIRE(!P->dem || P->dem_odd < 0, "mechanism %lld of the detector error model does not have the probability of mechanism 0: fixed-weight "
-                  "sampling needs one probability for all mechanisms (a non-uniform model has no weight strata)", (long long)P->dem_odd);
+    if (weight == -1) return sampler_off(P, Sampler::FIXED_WEIGHT);
+    int rc = fixed_weight_check(P->n_locs, weight);
+    if (rc != QLDPC_OK || (rc = sampler_switch_allowed(P, Sampler::FIXED_WEIGHT)) != QLDPC_OK) return rc;
     P->fixed_weight = weight;
+    P->sampler = Sampler::FIXED_WEIGHT;
     return QLDPC_OK;
 }
 
-// The sampler axis again: heralded erasures on top of the independent draws (erasure.hip).  rate[op code], NULL = off.
+// rate[op code], NULL = off
 QLDPC_EXPORT int qldpc_circuit_plan_use_erasure_noise(qldpc_circuit_plan *P, const double rate[7]) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    if (rate == nullptr) { P->erasure = false; return QLDPC_OK; }
-    QLDPC_REQUIRE(!P->dem, "erasure noise needs a circuit plan: a detector error model has no gate locations to erase");
-    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: erasure noise goes with the independent draws (switch the fixed weight off first)",
-                  P->fixed_weight);
-    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the erasure sampler draws its ordinary faults at one p (switch the noise model off first)");
-    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: erasure noise does not compose with readout levels (switch soft readout off first)");
+    if (rate == nullptr) return sampler_off(P, Sampler::ERASURE);
+    int rc = sampler_switch_allowed(P, Sampler::ERASURE);
+    if (rc != QLDPC_OK) return rc;
     uint32_t thr[8];
-    int rc = erasure_rates_check(rate, thr);
-    if (rc != QLDPC_OK || (rc = erasure_sample_supported(P->sec[0].nsyn, P->sec[1].nsyn, P->n_locs)) != QLDPC_OK) return rc;
+    if ((rc = erasure_rates_check(rate, thr)) != QLDPC_OK || (rc = erasure_sample_supported(P->sec[0].nsyn, P->sec[1].nsyn, P->n_locs)) != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(P->device);
     if ((rc = P->d_erased.ensure((size_t)P->batch * ((size_t)(P->n_locs + 31) / 32) * 4 + 4)) != QLDPC_OK) return rc;
     std::copy(thr, thr + 8, P->ethr);
-    P->erasure = true;
+    P->sampler = Sampler::ERASURE;
     return QLDPC_OK;
 }
 
-// The sampler axis a third time: a rate per location class and weighted Paulis in place of the plan's p and r % K (noise_model.hip).  NULL = off.
+// NULL = off
 QLDPC_EXPORT int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *P, const qldpc_noise_model *model) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    if (model == nullptr) { P->noise_model = false; return QLDPC_OK; }
-    QLDPC_REQUIRE(!P->dem, "a noise model needs a circuit plan: a detector error model has no gate locations (give its mechanisms their probabilities)");
-    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: that law needs one p for every location (switch the fixed weight off first)",
-                  P->fixed_weight);
-    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: a noise model does not compose with heralded erasures (switch erasure noise off first)");
-    QLDPC_REQUIRE(!P->soft, "the plan samples soft readout: a noise model does not compose with readout levels (switch soft readout off first)");
-    NoiseModelHost nm;
-    int rc = noise_model_check(model, &nm);
+    if (model == nullptr) return sampler_off(P, Sampler::NOISE_MODEL);
+    int rc = sampler_switch_allowed(P, Sampler::NOISE_MODEL);
     if (rc != QLDPC_OK) return rc;
+    NoiseModelHost nm;
+    if ((rc = noise_model_check(model, &nm)) != QLDPC_OK) return rc;
     if (!P->d_loc_cls.p) {                                               // the first switch: pack the classes the plan already holds on the device
         QLDPC_USE_DEVICE(P->device);
         std::vector<uint8_t> loc_type((size_t)P->n_locs);
@@ -1094,7 +1099,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_noise_model(qldpc_circuit_plan *P, const
         P->d_loc_cls = std::move(cls);
     }
     P->nm = nm;
-    P->noise_model = true;
+    P->sampler = Sampler::NOISE_MODEL;
     return QLDPC_OK;
 }
 
@@ -1122,25 +1127,21 @@ static int soft_prepare(qldpc_circuit_plan *P) {
 }
 static size_t levels_bytes(const qldpc_circuit_plan *P) { return (size_t)P->batch * (size_t)P->n_meas + 4; }
 
-// The sampler axis a fourth time: a confidence level and a flip per measurement on top of the independent draws (soft.hip).  flip_mass NULL = off.
+// flip_mass NULL = off
 QLDPC_EXPORT int qldpc_circuit_plan_use_soft_readout(qldpc_circuit_plan *P, int32_t levels, const double *flip_mass, const double *keep_mass) {
     QLDPC_REQUIRE(P != nullptr, "plan is NULL");
-    if (flip_mass == nullptr) { P->soft = false; return QLDPC_OK; }
-    QLDPC_REQUIRE(!P->dem, "soft readout needs a circuit plan: a detector error model has no measurement locations");
-    QLDPC_REQUIRE(P->fixed_weight < 0, "the plan draws a fixed weight of %d faults: soft readout goes with the independent draws (switch the fixed weight off first)",
-                  P->fixed_weight);
-    QLDPC_REQUIRE(!P->erasure, "the plan samples erasure noise: soft readout does not compose with heralded erasures (switch erasure noise off first)");
-    QLDPC_REQUIRE(!P->noise_model, "the plan samples a noise model: the soft-readout sampler draws its ordinary faults at one p (switch the noise model off first)");
-    SoftReadoutHost sr;
-    int rc = soft_readout_check(levels, flip_mass, keep_mass, &sr);
+    if (flip_mass == nullptr) return sampler_off(P, Sampler::SOFT);
+    int rc = sampler_switch_allowed(P, Sampler::SOFT);
     if (rc != QLDPC_OK) return rc;
+    SoftReadoutHost sr;
+    if ((rc = soft_readout_check(levels, flip_mass, keep_mass, &sr)) != QLDPC_OK) return rc;
     QLDPC_REQUIRE(P->path != Path::SOFT || P->soft_levels == levels, "the plan decodes soft-aware with tables for %d levels: a readout with %d levels does not go with them",
                   P->soft_levels, levels);
     if ((rc = soft_prepare(P)) != QLDPC_OK) return rc;
     QLDPC_USE_DEVICE(P->device);
     if ((rc = P->d_levels.ensure(levels_bytes(P))) != QLDPC_OK) return rc;
     P->sr = sr;
-    P->soft = true;
+    P->sampler = Sampler::SOFT;
     return QLDPC_OK;
 }
 
@@ -1153,7 +1154,7 @@ QLDPC_EXPORT int qldpc_circuit_plan_use_soft_aware(qldpc_circuit_plan *P, double
     int rc = switch_allowed(P, Path::SOFT);
     if (rc != QLDPC_OK) return rc;
     QLDPC_REQUIRE(!P->dem, "soft-aware decoding needs a circuit plan: a detector error model has no measurement locations to read levels from");
-    QLDPC_REQUIRE(!P->soft || P->sr.levels == levels, "the plan samples soft readout with %d levels: tables for %d levels do not go with it", P->sr.levels, levels);
+    QLDPC_REQUIRE(P->sampler != Sampler::SOFT || P->sr.levels == levels, "the plan samples soft readout with %d levels: tables for %d levels do not go with it", P->sr.levels, levels);
     if ((rc = soft_prepare(P)) != QLDPC_OK) return rc;
     const SoftTabIn in[2] = {{meas_col_z, meas_w_z, lut_ptr_z, lut_z}, {meas_col_x, meas_w_x, lut_ptr_x, lut_x}};
     for (int i = 0; i < 2; i++) {
@@ -1207,32 +1208,13 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample_soft(qldpc_circuit_plan *P, uint64_t 
     QLDPC_REQUIRE(!prior_z || P->path == Path::SOFT, "the per-shot priors need the tables of qldpc_circuit_plan_use_soft_aware");
     int rc = soft_prepare(P);
     if (rc != QLDPC_OK) return rc;
-    const size_t nm = (size_t)P->n_meas;
-    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x && (level || nm == 0)), "NULL output");
+    QLDPC_REQUIRE(count == 0 || (sparse_z && true_z && sparse_x && true_x && (level || P->n_meas == 0)), "NULL output");
     QLDPC_USE_DEVICE(P->device);
     if ((rc = P->d_levels.ensure(levels_bytes(P))) != QLDPC_OK) return rc;
     int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
     double *const prior[2] = {prior_z, prior_x};
-    std::vector<unsigned long long> t;
-    for (int64_t off = 0; off < count; off += P->batch) {
-        const int64_t B = std::min<int64_t>(P->batch, count - off);
-        if (!P->soft) QLDPC_HIP_TRY(hipMemsetAsync(P->d_levels.p, 0, (size_t)B * nm + 4, nullptr));      // the switch is off: every level is 0
-        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
-        for (int i = 0; prior_z && i < 2; i++)
-            if ((rc = launch_soft_prior(P, i, B, nullptr)) != QLDPC_OK) return rc;
-        QLDPC_HIP_TRY(hipDeviceSynchronize());
-        t.resize(B);
-        if (nm) QLDPC_HIP_TRY(hipMemcpy(level + off * nm, P->d_levels.p, (size_t)B * nm, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 2; i++) {
-            const Sector &S = P->sec[i];
-            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
-            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-            for (int64_t b = 0; b < B; b++)
-                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
-            if (prior[i]) QLDPC_HIP_TRY(hipMemcpy(prior[i] + off * S.g->n, S.d_eprior.p, (size_t)B * S.g->n * 8, hipMemcpyDeviceToHost));
-        }
-    }
-    return QLDPC_OK;
+    return sample_readback(P, seed, trial_begin, count, sparse, truth, {P->d_levels.p, (size_t)P->n_meas, level, P->sampler != Sampler::SOFT},
+                           prior_z ? launch_soft_prior : nullptr, prior);
 }
 
 // One sector's tables of qldpc_circuit_plan_use_erasure_aware (host pointers).
@@ -1292,31 +1274,12 @@ QLDPC_EXPORT int qldpc_circuit_plan_sample_erasures(qldpc_circuit_plan *P, uint6
     QLDPC_REQUIRE((prior_z == nullptr) == (prior_x == nullptr), "prior_z and prior_x are both NULL or both given");
     QLDPC_REQUIRE(!prior_z || P->path == Path::ERASURE, "the per-shot priors need the tables of qldpc_circuit_plan_use_erasure_aware");
     QLDPC_USE_DEVICE(P->device);
-    int rc;
     const size_t nw = (size_t)(P->n_locs + 31) / 32;
-    if ((rc = P->d_erased.ensure((size_t)P->batch * nw * 4 + 4)) != QLDPC_OK) return rc;
+    if (const int rc = P->d_erased.ensure((size_t)P->batch * nw * 4 + 4); rc != QLDPC_OK) return rc;
     int8_t *const sparse[2] = {sparse_z, sparse_x}, *const truth[2] = {true_z, true_x};
     double *const prior[2] = {prior_z, prior_x};
-    std::vector<unsigned long long> t;
-    for (int64_t off = 0; off < count; off += P->batch) {
-        const int64_t B = std::min<int64_t>(P->batch, count - off);
-        if (!P->erasure) QLDPC_HIP_TRY(hipMemsetAsync(P->d_erased.p, 0, (size_t)B * nw * 4, nullptr));      // the switch is off: no location is erased
-        if ((rc = launch_sampler(P, seed, trial_begin + off, B, nullptr)) != QLDPC_OK) return rc;
-        for (int i = 0; prior_z && i < 2; i++)
-            if ((rc = launch_erasure_prior(P, i, B, nullptr)) != QLDPC_OK) return rc;
-        QLDPC_HIP_TRY(hipDeviceSynchronize());
-        t.resize(B);
-        if (nw) QLDPC_HIP_TRY(hipMemcpy(erased + off * nw, P->d_erased.p, (size_t)B * nw * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 2; i++) {
-            const Sector &S = P->sec[i];
-            QLDPC_HIP_TRY(hipMemcpy(sparse[i] + off * S.nsyn, S.d_syn.p, (size_t)B * S.nsyn, hipMemcpyDeviceToHost));
-            QLDPC_HIP_TRY(hipMemcpy(t.data(), S.d_true.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-            for (int64_t b = 0; b < B; b++)
-                for (int r = 0; r < P->ks[i]; r++) truth[i][(off + b) * P->ks[i] + r] = (int8_t)((t[b] >> r) & 1);
-            if (prior[i]) QLDPC_HIP_TRY(hipMemcpy(prior[i] + off * S.g->n, S.d_eprior.p, (size_t)B * S.g->n * 8, hipMemcpyDeviceToHost));
-        }
-    }
-    return QLDPC_OK;
+    return sample_readback(P, seed, trial_begin, count, sparse, truth, {P->d_erased.p, nw * 4, erased, P->sampler != Sampler::ERASURE},
+                           prior_z ? launch_erasure_prior : nullptr, prior);
 }
 
 // ---- recorded detection events in place of the sampler (kernels: events.hip) ----

@@ -7,27 +7,17 @@
 // sets and its logical masks into the sectors' accumulators, so the result does not depend on grid, block size or lane mapping.
 #include "common.h"
 #include "launchers.h"
-#include "mc_common.h"
+#include "sampler_common.h"
 
 namespace qldpc {
 
-// one workgroup per trial (grid-stride); one lane per Philox block = four mechanisms.  thr is padded with zeros to a multiple of four (a padded
-// entry never fires: no word is < 0), so a lane reads its four thresholds as one 16-byte load; l < n_mech still bounds every table access.
+// The frame of sampler_common.h; one lane per Philox block = four mechanisms.  thr is padded with zeros to a multiple of four (a padded entry never
+// fires: no word is < 0), so a lane reads its four thresholds as one 16-byte load; l < n_mech still bounds every table access.
 __global__ __launch_bounds__(256) void dem_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, int n_mech,
-                                                         const uint4 *__restrict__ thr4, DemTab T0, DemTab T1, int n0, int n1, int two,
-                                                         int8_t *__restrict__ syn0, int8_t *__restrict__ syn1, unsigned long long *__restrict__ true0,
-                                                         unsigned long long *__restrict__ true1, int32_t *__restrict__ fail_counts) {
+                                                         const uint4 *__restrict__ thr4, SigTab T0, SigTab T1, SampleOut O) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
-    const int w0 = (n0 + 31) >> 5, w1 = two ? (n1 + 31) >> 5 : 0;
-    uint32_t *b0 = sm, *b1 = sm + w0;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + ((w0 + w1 + 1) & ~1));
     const int nblk = (n_mech + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int w = threadIdx.x; w < w0 + w1; w += blockDim.x) sm[w] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        __syncthreads();
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    sample_trials<false>(sm, B, trial_begin, O, 0, nullptr, [&](int64_t, uint64_t g, const SampleLds &L) {
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             const uint4 th = thr4[blk];
             if ((th.x | th.y | th.z | th.w) == 0u) continue;                                   // four mechanisms with p = 0 (or padding): nothing to draw
@@ -38,35 +28,20 @@ __global__ __launch_bounds__(256) void dem_sample_kernel(int64_t B, int64_t tria
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
                 if (l < n_mech && o[w] < tw[w]) {
-                    for (int k = T0.ptr[l]; k < T0.ptr[l + 1]; k++) { const int d = T0.idx[k]; atomicXor(&b0[d >> 5], 1u << (d & 31)); }
-                    const unsigned long long l0 = T0.log[l];
-                    if (l0) atomicXor(&lacc[0], l0);
-                    if (two) {
-                        for (int k = T1.ptr[l]; k < T1.ptr[l + 1]; k++) { const int d = T1.idx[k]; atomicXor(&b1[d >> 5], 1u << (d & 31)); }
-                        const unsigned long long l1 = T1.log[l];
-                        if (l1) atomicXor(&lacc[1], l1);
-                    }
+                    xor_signature(T0, l, L.b0, &L.lacc[0]);
+                    if (O.two) xor_signature(T1, l, L.b1, &L.lacc[1]);
                 }
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < n0; i += blockDim.x) syn0[t * n0 + i] = (b0[i >> 5] >> (i & 31)) & 1;
-        if (two)
-            for (int i = threadIdx.x; i < n1; i += blockDim.x) syn1[t * n1 + i] = (b1[i >> 5] >> (i & 31)) & 1;
-        if (threadIdx.x == 0) { true0[t] = lacc[0]; if (two) true1[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
-int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const DemTab &T0, const DemTab &T1, int n0, int n1,
-                      bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
+int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const SigTab &T0, const SigTab &T1, const SampleOut &O,
                       hipStream_t s) {
     if (B <= 0) return QLDPC_OK;
-    const int w0 = (n0 + 31) / 32, w1 = two ? (n1 + 31) / 32 : 0;
-    const size_t lds = (size_t)((w0 + w1 + 1) & ~1) * 4 + 16;                                 // n_det < 65536 per sector: at most 16 KiB + 16 B
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(dem_sample_kernel, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), n_mech,
-                       reinterpret_cast<const uint4 *>(d_thr), T0, T1, n0, n1, two ? 1 : 0, d_syn0, d_syn1, d_true0, d_true1, d_fail_counts);
+    const SampleShape shape = sample_shape(O.n0, O.n1, O.two, B);
+    hipLaunchKernelGGL(dem_sample_kernel, dim3(shape.grid), dim3(256), shape.words * 4, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), n_mech,
+                       reinterpret_cast<const uint4 *>(d_thr), T0, T1, O);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }

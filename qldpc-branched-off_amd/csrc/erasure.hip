@@ -30,26 +30,14 @@ __device__ __forceinline__ int erased_components(int ty, uint64_t g, int l, uint
     return (r[0] & 1u) ? 1 : 0;                                                                         // MeasZ / PrepZ
 }
 
-// One workgroup per trial (grid-stride), shaped like circuit_sample_kernel.  LDS (uint32 words): both sectors' detector bit sets, the two logical
-// accumulators, the erased bit set (ceil(n_locs / 32) words).  Every index is bounded by n_locs or a signature run; the host bounds the LDS request.
+// The frame of sampler_common.h.  LDS behind the frame's words: the erased bit set (ceil(n_locs / 32) words), which the frame zeroes per trial and
+// stores as the trial's herald row.  Every index is bounded by n_locs or a signature run; the host bounds the LDS request.
 __global__ __launch_bounds__(256) void erasure_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, uint32_t thr, ErasureThr E,
-                                                             int n_locs, const uint8_t *__restrict__ loc_type, SigTab Z, SigTab X, int nsx, int nsz,
-                                                             int8_t *__restrict__ syn_z, int8_t *__restrict__ syn_x, unsigned long long *__restrict__ true_z,
-                                                             unsigned long long *__restrict__ true_x, uint32_t *__restrict__ erased,
-                                                             int32_t *__restrict__ fail_counts) {
+                                                             int n_locs, const uint8_t *__restrict__ loc_type, SigTab Z, SigTab X, SampleOut O,
+                                                             uint32_t *__restrict__ erased) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
-    const int wz = (nsx + 31) >> 5, wx = (nsz + 31) >> 5, nbits = (wz + wx + 1) & ~1, nw = (n_locs + 31) >> 5;
-    uint32_t *bz = sm, *bx = sm + wz;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + nbits);
-    uint32_t *er = sm + nbits + 4;
     const int nblk = (n_locs + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int w = threadIdx.x; w < wz + wx; w += blockDim.x) sm[w] = 0;
-        for (int w = threadIdx.x; w < nw; w += blockDim.x) er[w] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        __syncthreads();
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    sample_trials<true>(sm, B, trial_begin, O, (n_locs + 31) >> 5, erased, [&](int64_t, uint64_t g, const SampleLds &L) {
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             uint32_t o[4], e[4];
             philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)blk, 1u, seed_lo, seed_hi, o);
@@ -58,25 +46,15 @@ __global__ __launch_bounds__(256) void erasure_sample_kernel(int64_t B, int64_t 
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
                 if (l >= n_locs) continue;
-                if (o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, bz, bx, lacc);
+                if (o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, L.b0, L.b1, L.lacc);
                 const int ty = loc_type[l];
                 if (e[w] < E.t[ty & 7]) {
-                    atomicOr(&er[l >> 5], 1u << (l & 31));
-                    const int comp = erased_components(ty, g, l, seed_lo, seed_hi);
-                    if (comp & 1) xor_signature(X, 2 * l, bx, &lacc[1]);
-                    if (comp & 2) xor_signature(X, 2 * l + 1, bx, &lacc[1]);
-                    if (comp & 4) xor_signature(Z, 2 * l, bz, &lacc[0]);
-                    if (comp & 8) xor_signature(Z, 2 * l + 1, bz, &lacc[0]);
+                    atomicOr(&L.more[l >> 5], 1u << (l & 31));
+                    fire_components(Z, X, erased_components(ty, g, l, seed_lo, seed_hi), l, L.b0, L.b1, L.lacc);
                 }
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < nsx; i += blockDim.x) syn_z[t * nsx + i] = (bz[i >> 5] >> (i & 31)) & 1;
-        for (int i = threadIdx.x; i < nsz; i += blockDim.x) syn_x[t * nsz + i] = (bx[i >> 5] >> (i & 31)) & 1;
-        for (int w = threadIdx.x; w < nw; w += blockDim.x) erased[t * nw + w] = er[w];
-        if (threadIdx.x == 0) { true_z[t] = lacc[0]; true_x[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
 // One workgroup per shot (grid-stride).  LDS (uint32 words): ceil(n / 2) words of 16-bit counters (column j in half j & 1 of word j >> 1; the host
@@ -124,7 +102,7 @@ __global__ __launch_bounds__(256) void erasure_prior_kernel(int64_t B, int n_loc
 }
 
 static size_t sample_lds_bytes(int nsx, int nsz, int n_locs) {
-    return ((size_t)((((nsx + 31) / 32) + ((nsz + 31) / 32) + 1) & ~1) + 4 + (size_t)(n_locs + 31) / 32) * 4;
+    return (sample_shape(nsx, nsz, true, 1).words + (size_t)(n_locs + 31) / 32) * 4;
 }
 static size_t prior_lds_bytes(int n) { return ((size_t)(n + 1) / 2 + (size_t)(n + 31) / 32) * 4; }
 static const size_t kMaxLds = 160 * 1024;
@@ -147,18 +125,16 @@ int erasure_rates_check(const double *rate, uint32_t thr[8]) {
 }
 
 int erasure_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const uint32_t ethr[8], int n_locs,
-                          const uint8_t *d_loc_type, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
-                          unsigned long long *d_true_z, unsigned long long *d_true_x, uint32_t *d_erased, int32_t *d_fail_counts, hipStream_t s) {
+                          const uint8_t *d_loc_type, const SigTab &Z, const SigTab &X, const SampleOut &O, uint32_t *d_erased, hipStream_t s) {
     if (B <= 0) return QLDPC_OK;
-    int rc = erasure_sample_supported(nsx, nsz, n_locs);
+    int rc = erasure_sample_supported(O.n0, O.n1, n_locs);
     if (rc != QLDPC_OK) return rc;
     ErasureThr E;
     for (int i = 0; i < 8; i++) E.t[i] = ethr[i];
-    const size_t lds = sample_lds_bytes(nsx, nsz, n_locs);
+    const size_t lds = sample_lds_bytes(O.n0, O.n1, n_locs);
     if (lds > 48 * 1024 && (rc = ensure_max_lds(device, reinterpret_cast<const void *>(erasure_sample_kernel), (int)kMaxLds)) != QLDPC_OK) return rc;
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(erasure_sample_kernel, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), thr, E, n_locs, d_loc_type,
-                       Z, X, nsx, nsz, d_syn_z, d_syn_x, d_true_z, d_true_x, d_erased, d_fail_counts);
+    hipLaunchKernelGGL(erasure_sample_kernel, dim3(sample_shape(O.n0, O.n1, O.two, B).grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), thr, E, n_locs,
+                       d_loc_type, Z, X, O, d_erased);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }

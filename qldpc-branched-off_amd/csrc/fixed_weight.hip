@@ -13,31 +13,22 @@
 
 namespace qldpc {
 
-// One workgroup per trial (grid-stride), as circuit_sample_kernel.  LDS (uint32 words): both sectors' bit sets, the two logical accumulators, the
-// membership bit set of S (ceil(N / 32) words) and the list of S (w words).  Per trial:
+// The frame of sampler_common.h.  LDS behind the frame's words: the membership bit set of S (ceil(N / 32) words) and the list of S (w words).  Per trial:
 //   draw     lanes compute t_i for all i in parallel, one Philox block per four steps, into the list;
 //   resolve  lane 0 walks the list once against the membership bit set ("taken -> j"): w dependent LDS test-and-set steps.  Step i needs the set
 //            after steps 0 .. i-1, so this is the one sequential part; at w ~ 100 it is microseconds per trial beside a decode of milliseconds per batch;
 //   fire     lanes take the list entries in parallel, clear the entry's membership word (the set is empty again for the next trial) and XOR the
 //            location's signatures (DEM = false) or the mechanism's detector lists and logical masks (DEM = true).
+// The membership set is zeroed once (the frame's first barrier comes before anything reads it); the list is written before it is read, never zeroed.
 // Every index is bounded on the host: w <= min(N, 4096), t_i <= j < N, and the tables hold 2 N (circuit) or N (DEM) entries.
 template <bool DEM>
 __global__ __launch_bounds__(256) void fixed_weight_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, int weight, int n_locs,
-                                                                  const uint8_t *__restrict__ loc_type, SigTab T0, SigTab T1, int n0, int n1, int two,
-                                                                  int8_t *__restrict__ syn0, int8_t *__restrict__ syn1, unsigned long long *__restrict__ true0,
-                                                                  unsigned long long *__restrict__ true1, int32_t *__restrict__ fail_counts) {
+                                                                  const uint8_t *__restrict__ loc_type, SigTab T0, SigTab T1, SampleOut O) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
-    const int w0 = (n0 + 31) >> 5, w1 = two ? (n1 + 31) >> 5 : 0, nbits = (w0 + w1 + 1) & ~1, nmem = (n_locs + 31) >> 5;
-    uint32_t *b0 = sm, *b1 = sm + w0;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + nbits);
-    uint32_t *member = sm + nbits + 4, *list = member + nmem;
-    for (int i = threadIdx.x; i < nmem; i += blockDim.x) member[i] = 0;                       // once: every trial leaves it empty
-    const int nblk = (weight + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int i = threadIdx.x; i < w0 + w1; i += blockDim.x) sm[i] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    const int nmem = (n_locs + 31) >> 5, nblk = (weight + 3) >> 2;
+    uint32_t *member = sample_carve<false>(sm, O).more, *list = member + nmem;
+    for (int i = threadIdx.x; i < nmem; i += blockDim.x) member[i] = 0;
+    sample_trials<false>(sm, B, trial_begin, O, 0, nullptr, [&](int64_t, uint64_t g, const SampleLds &L) {
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             uint32_t o[4];
             philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)blk, 4u, seed_lo, seed_hi, o);
@@ -59,19 +50,13 @@ __global__ __launch_bounds__(256) void fixed_weight_sample_kernel(int64_t B, int
             const int l = (int)list[i];
             member[l >> 5] = 0;                                                                // (several lanes may store the same zero)
             if (DEM) {
-                xor_signature(T0, l, b0, &lacc[0]);
-                if (two) xor_signature(T1, l, b1, &lacc[1]);
+                xor_signature(T0, l, L.b0, &L.lacc[0]);
+                if (O.two) xor_signature(T1, l, L.b1, &L.lacc[1]);
             } else {
-                fire_location(T0, T1, loc_type, g, l, seed_lo, seed_hi, b0, b1, lacc);
+                fire_location(T0, T1, loc_type, g, l, seed_lo, seed_hi, L.b0, L.b1, L.lacc);
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < n0; i += blockDim.x) syn0[t * n0 + i] = (b0[i >> 5] >> (i & 31)) & 1;
-        if (two)
-            for (int i = threadIdx.x; i < n1; i += blockDim.x) syn1[t * n1 + i] = (b1[i >> 5] >> (i & 31)) & 1;
-        if (threadIdx.x == 0) { true0[t] = lacc[0]; if (two) true1[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
 int fixed_weight_check(int64_t n_locs, int weight) {
@@ -87,21 +72,18 @@ int fixed_weight_check(int64_t n_locs, int weight) {
 }
 
 int fixed_weight_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, int weight, int n_locs, bool dem, const uint8_t *d_loc_type,
-                               const SigTab &T0, const SigTab &T1, int n0, int n1, bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0,
-                               unsigned long long *d_true1, int32_t *d_fail_counts, hipStream_t s) {
+                               const SigTab &T0, const SigTab &T1, const SampleOut &O, hipStream_t s) {
     if (B <= 0) return QLDPC_OK;
     int rc = fixed_weight_check(n_locs, weight);
     if (rc != QLDPC_OK) return rc;
-    const int w0 = (n0 + 31) / 32, w1 = two ? (n1 + 31) / 32 : 0;
-    // bit sets (n_det < 65536 per sector: at most 16 KiB) + 16 B + membership (at most 64 KiB) + list (at most 16 KiB)
-    const size_t lds = ((size_t)((w0 + w1 + 1) & ~1) + 4 + (size_t)(n_locs + 31) / 32 + (size_t)weight) * 4;
+    const SampleShape shape = sample_shape(O.n0, O.n1, O.two, B);
+    // the frame (at most 16 KiB + 16 B) + membership (at most 64 KiB) + list (at most 16 KiB)
+    const size_t lds = (shape.words + (size_t)(n_locs + 31) / 32 + (size_t)weight) * 4;
     const auto kern = dem ? fixed_weight_sample_kernel<true> : fixed_weight_sample_kernel<false>;
     // (the attribute is set once per kernel: the largest request the limits allow, 96 KiB + 16 B)
     const int lds_max = (2 * 2048 + 4 + QLDPC_FIXED_WEIGHT_MAX_LOCS / 32 + QLDPC_FIXED_WEIGHT_MAX) * 4;
     if (lds > 48 * 1024 && (rc = ensure_max_lds(device, reinterpret_cast<const void *>(kern), lds_max)) != QLDPC_OK) return rc;
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), weight, n_locs, d_loc_type, T0, T1, n0, n1,
-                       two ? 1 : 0, d_syn0, d_syn1, d_true0, d_true1, d_fail_counts);
+    hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), weight, n_locs, d_loc_type, T0, T1, O);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }

@@ -14,8 +14,8 @@ namespace qldpc {
 
 struct OsdLaunch;      // osd_plan.h
 struct OsdGjArgs;      // osd_gj.h
-struct DemTab;         // mc_common.h
 struct SigTab;         // sampler_common.h
+struct SampleOut;      // sampler_common.h
 struct JudgeSector;    // judge.h
 struct EventsSector;   // judge.h
 
@@ -192,19 +192,19 @@ int minsum32_decoder_create_tab(const qldpc_graph *g, const double *prior, int m
 int minsum32_lock_and_launch(qldpc_minsum32_decoder *D, int64_t B, const int8_t *d_synd, int8_t *d_err, double *d_llr, uint8_t *d_conv, int32_t *d_iter,
                              hipStream_t s);
 int osdcs_supported(const qldpc_graph *g);      // QLDPC_OK, or QLDPC_ERR_UNSUPPORTED with the error text set
-// Detector-error-model sampler of a circuit plan (dem.hip).  DemTab (mc_common.h): one sector's projection of the mechanisms (device pointers): ptr int32[n_mech + 1],
-// idx detector indices, log the logical masks.  d_thr: uint32 thresholds, zero-padded to a multiple of four.  two = false: sector 1 is not touched.
-int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const DemTab &T0, const DemTab &T1, int n0, int n1,
-                      bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0, unsigned long long *d_true1, int32_t *d_fail_counts,
+// The samplers of a circuit plan.  Every *_sample_launch takes (B, trial_begin, seed, its own parameters, the two sectors' SigTab, SampleOut, stream);
+// SigTab and SampleOut (sampler_common.h) hold device pointers and travel to the kernel by value.
+// Detector-error-model sampler (dem.hip).  T0 / T1: the sectors' projections of the mechanisms: ptr int32[n_mech + 1], idx detector indices, log the logical
+// masks.  d_thr: uint32 thresholds, zero-padded to a multiple of four.
+int dem_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, int n_mech, const uint32_t *d_thr, const SigTab &T0, const SigTab &T1, const SampleOut &O,
                       hipStream_t s);
 int dem_validate(const qldpc_dem_desc *D);      // QLDPC_OK, or QLDPC_ERR_INVALID with the error text naming the sector or the mechanism
 // Fixed-weight sampler of a circuit plan (fixed_weight.hip): exactly `weight` members of 0 .. n_locs - 1 per trial.  dem = false: T0 / T1 are the fault signatures
 // of sectors Z / X (entry 2 * location + slot) and d_loc_type the locations' op types; dem = true: the mechanisms' projections (entry = mechanism), d_loc_type
-// unused.  The other arguments as in dem_sample_launch.  fixed_weight_check: the limits of (n_locs, weight), QLDPC_ERR_INVALID / _UNSUPPORTED with the text set.
+// unused.  fixed_weight_check: the limits of (n_locs, weight), QLDPC_ERR_INVALID / _UNSUPPORTED with the text set.
 int fixed_weight_check(int64_t n_locs, int weight);
 int fixed_weight_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, int weight, int n_locs, bool dem, const uint8_t *d_loc_type,
-                               const SigTab &T0, const SigTab &T1, int n0, int n1, bool two, int8_t *d_syn0, int8_t *d_syn1, unsigned long long *d_true0,
-                               unsigned long long *d_true1, int32_t *d_fail_counts, hipStream_t s);
+                               const SigTab &T0, const SigTab &T1, const SampleOut &O, hipStream_t s);
 // Heralded-erasure noise of a circuit plan (erasure.hip).  sample: circuit_sample_kernel's draws at threshold thr plus the erasures at ethr[op code]
 // (erasure_rates_check turns rate[7] into them: QLDPC_ERR_INVALID naming the class), the herald record uint32[B][ceil(n_locs / 32)] written to d_erased.
 // prior: heralds and the tables of one sector (device pointers) -> d_prior f64[B][n].  check_tables: the table rules of qldpc_erasure_priors on host
@@ -212,8 +212,7 @@ int fixed_weight_sample_launch(int device, int64_t B, int64_t trial_begin, uint6
 int erasure_rates_check(const double *rate, uint32_t thr[8]);
 int erasure_sample_supported(int nsx, int nsz, int64_t n_locs);
 int erasure_sample_launch(int device, int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const uint32_t ethr[8], int n_locs,
-                          const uint8_t *d_loc_type, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
-                          unsigned long long *d_true_z, unsigned long long *d_true_x, uint32_t *d_erased, int32_t *d_fail_counts, hipStream_t s);
+                          const uint8_t *d_loc_type, const SigTab &Z, const SigTab &X, const SampleOut &O, uint32_t *d_erased, hipStream_t s);
 int erasure_check_tables(int n_locs, const int32_t *loc_ptr, const int32_t *loc_col, const uint8_t *loc_h, int n, const int32_t *lut_ptr, const double *lut);
 int erasure_prior_supported(int n);
 int erasure_prior_launch(int device, int64_t B, int n_locs, const uint32_t *d_erased, const int32_t *d_loc_ptr, const int32_t *d_loc_col,
@@ -222,13 +221,12 @@ int erasure_prior_launch(int device, int64_t B, int n_locs, const uint32_t *d_er
 // threshold per op code, whether a weight table was given and its cuts (uint64: a cut may be 2^32).  check: the rules of
 // qldpc_circuit_plan_use_noise_model on the model alone, QLDPC_ERR_INVALID with the text naming the class or the index.  pack_classes: the op codes
 // of the four locations of Philox block b as the four bytes of word b (zero padding: class 0 has threshold 0).  sample: circuit_sample_kernel with a
-// threshold per class and the cut-based Pauli choice; d_loc_cls is pack_classes' array on the device, the other arguments as in erasure_sample_launch.
+// threshold per class and the cut-based Pauli choice; d_loc_cls is pack_classes' array on the device.
 struct NoiseModelHost { uint32_t thr[8]; bool idle_weighted, cnot_weighted; uint64_t idle_cut[2], cnot_cut[14]; };
 int noise_model_check(const qldpc_noise_model *M, NoiseModelHost *out);
 std::vector<uint32_t> noise_model_pack_classes(const std::vector<uint8_t> &loc_type);
-int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, const NoiseModelHost &M, int n_locs, const uint32_t *d_loc_cls,
-                              const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x,
-                              unsigned long long *d_true_z, unsigned long long *d_true_x, int32_t *d_fail_counts, hipStream_t s);
+int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, const NoiseModelHost &M, int n_locs, const uint32_t *d_loc_cls, const SigTab &Z,
+                              const SigTab &X, const SampleOut &O, hipStream_t s);
 // Soft-readout noise of a circuit plan (soft.hip).  SoftReadoutHost: what checked masses become on the host -- K and the 2K cuts of the law (uint64:
 // the last is 2^32).  readout_check: the rules of qldpc_circuit_plan_use_soft_readout on the masses alone, QLDPC_ERR_INVALID with the text naming the
 // index.  sample: circuit_sample_kernel's draws at threshold thr plus the readout bins, the level record uint8[B][n_meas] written to d_levels;
@@ -238,14 +236,14 @@ int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, con
 struct SoftReadoutHost { int levels; uint64_t cut[32]; };
 int soft_readout_check(int levels, const double *flip_mass, const double *keep_mass, SoftReadoutHost *out);
 int soft_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const SoftReadoutHost &R, int n_locs, const uint8_t *d_loc_type,
-                       const uint32_t *d_loc_cls, const int32_t *d_meas_rank, int n_meas, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z,
-                       int8_t *d_syn_x, unsigned long long *d_true_z, unsigned long long *d_true_x, uint8_t *d_levels, int32_t *d_fail_counts, hipStream_t s);
+                       const uint32_t *d_loc_cls, const int32_t *d_meas_rank, int n_meas, const SigTab &Z, const SigTab &X, const SampleOut &O, uint8_t *d_levels,
+                       hipStream_t s);
 int soft_check_tables(int levels, int n_meas, const int32_t *meas_col, const int32_t *meas_w, int n, const int32_t *lut_ptr, const double *lut);
 int soft_prior_supported(int n);
 int soft_prior_launch(int device, int64_t B, int levels, int n_meas, const uint8_t *d_levels, const int32_t *d_meas_col, const int32_t *d_meas_w, int n,
                       const int32_t *d_lut_ptr, const double *d_lut, double *d_prior, hipStream_t s);
 // Recorded detection events in place of a sampler (events.hip).  unpack: B bit-packed records (shot i at d_events + i * stride, bit d = (rec[d >> 3] >> (d & 7)) & 1;
-// only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as in dem_sample_launch (may be NULL).
+// only the first ceil(n_bits / 8) bytes of a record are read) -> the sectors' syndromes int8[B][nsyn]; d_fail_counts as SampleOut's fail_counts (may be NULL).
 // predict: the judge without a truth -- pred[b] = XOR of the logical masks of the correction's ones; flags[b] bit 0 / 1 = converged, 2 / 3 = the correction does
 // not reproduce the syndrome, 4 / 5 = zero syndrome, of sector 0 / 1.  two = false: sector 1 is not touched and its bits stay 0.
 int events_unpack_launch(int64_t B, const uint8_t *d_events, int64_t stride, int n_bits, const EventsSector &S0, const EventsSector &S1, bool two,

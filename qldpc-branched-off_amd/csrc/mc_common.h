@@ -56,8 +56,4 @@ inline uint32_t bernoulli_threshold(double p) {
     return (uint32_t)std::floor(p * 4294967296.0);
 }
 
-// one sector's projection of a detector error model's mechanisms (device pointers), an argument of the sampler kernel (dem.hip): ptr int32[n_mech + 1],
-// idx detector indices, log the logical masks
-struct DemTab { const int32_t *ptr; const uint16_t *idx; const uint64_t *log; };
-
 }  // namespace qldpc

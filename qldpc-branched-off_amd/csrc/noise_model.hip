@@ -51,23 +51,12 @@ __device__ __forceinline__ int model_components(const NoiseModelArgs &A, uint32_
     return c_cnot_comp[i];                           // i <= 14, likewise
 }
 
-// One workgroup per trial (grid-stride), shaped like circuit_sample_kernel.  LDS (uint32 words): both sectors' detector bit sets, the two logical
-// accumulators.  loc_cls holds ceil(n_locs / 4) words; every signature index is bounded by l < n_locs.
+// The frame of sampler_common.h with nothing behind its words.  loc_cls holds ceil(n_locs / 4) words; every signature index is bounded by l < n_locs.
 __global__ __launch_bounds__(256) void noise_model_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, NoiseModelArgs A, int n_locs,
-                                                                 const uint32_t *__restrict__ loc_cls, SigTab Z, SigTab X, int nsx, int nsz,
-                                                                 int8_t *__restrict__ syn_z, int8_t *__restrict__ syn_x, unsigned long long *__restrict__ true_z,
-                                                                 unsigned long long *__restrict__ true_x, int32_t *__restrict__ fail_counts) {
+                                                                 const uint32_t *__restrict__ loc_cls, SigTab Z, SigTab X, SampleOut O) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
-    const int wz = (nsx + 31) >> 5, wx = (nsz + 31) >> 5;
-    uint32_t *bz = sm, *bx = sm + wz;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + ((wz + wx + 1) & ~1));
     const int nblk = (n_locs + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int w = threadIdx.x; w < wz + wx; w += blockDim.x) sm[w] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        __syncthreads();
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    sample_trials<true>(sm, B, trial_begin, O, 0, nullptr, [&](int64_t, uint64_t g, const SampleLds &L) {
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             uint32_t o[4];
             const uint32_t cls = loc_cls[blk];
@@ -76,21 +65,11 @@ __global__ __launch_bounds__(256) void noise_model_sample_kernel(int64_t B, int6
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
                 const uint32_t ty = (cls >> (8 * w)) & 0xFFu;
-                if (l < n_locs && o[w] < class_threshold(A, ty)) {
-                    const int comp = model_components(A, ty, g, l, seed_lo, seed_hi);
-                    if (comp & 1) xor_signature(X, 2 * l, bx, &lacc[1]);
-                    if (comp & 2) xor_signature(X, 2 * l + 1, bx, &lacc[1]);
-                    if (comp & 4) xor_signature(Z, 2 * l, bz, &lacc[0]);
-                    if (comp & 8) xor_signature(Z, 2 * l + 1, bz, &lacc[0]);
-                }
+                if (l < n_locs && o[w] < class_threshold(A, ty))
+                    fire_components(Z, X, model_components(A, ty, g, l, seed_lo, seed_hi), l, L.b0, L.b1, L.lacc);
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < nsx; i += blockDim.x) syn_z[t * nsx + i] = (bz[i >> 5] >> (i & 31)) & 1;
-        for (int i = threadIdx.x; i < nsz; i += blockDim.x) syn_x[t * nsz + i] = (bx[i >> 5] >> (i & 31)) & 1;
-        if (threadIdx.x == 0) { true_z[t] = lacc[0]; true_x[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
 // cut[j] of the law for j = 0 .. K - 2; QLDPC_ERR_INVALID naming the table and the index
@@ -130,19 +109,16 @@ std::vector<uint32_t> noise_model_pack_classes(const std::vector<uint8_t> &loc_t
 }
 
 int noise_model_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, const NoiseModelHost &M, int n_locs, const uint32_t *d_loc_cls, const SigTab &Z,
-                              const SigTab &X, int nsx, int nsz, int8_t *d_syn_z, int8_t *d_syn_x, unsigned long long *d_true_z, unsigned long long *d_true_x,
-                              int32_t *d_fail_counts, hipStream_t s) {
+                              const SigTab &X, const SampleOut &O, hipStream_t s) {
     if (B <= 0) return QLDPC_OK;
     NoiseModelArgs A{};
     for (int ty = C_OP_CNOT; ty <= C_OP_IDLE; ty++) A.thr[ty] = M.thr[ty];
     A.weighted = (M.idle_weighted ? 1u : 0u) | (M.cnot_weighted ? 2u : 0u);
     for (int j = 0; j < 2; j++) { A.idle_zero += M.idle_cut[j] == 0; A.idle_cm1[j] = (uint32_t)(M.idle_cut[j] - 1); }        // (0 - 1 wraps to 0xFFFFFFFF)
     for (int j = 0; j < 14; j++) { A.cnot_zero += M.cnot_cut[j] == 0; A.cnot_cm1[j] = (uint32_t)(M.cnot_cut[j] - 1); }
-    const int wz = (nsx + 31) / 32, wx = (nsz + 31) / 32;
-    const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;      // as circuit_sample_kernel's launch: 16 KiB at the 65535 detectors a sector may have
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(noise_model_sample_kernel, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), A, n_locs, d_loc_cls, Z, X,
-                       nsx, nsz, d_syn_z, d_syn_x, d_true_z, d_true_x, d_fail_counts);
+    const SampleShape shape = sample_shape(O.n0, O.n1, O.two, B);
+    hipLaunchKernelGGL(noise_model_sample_kernel, dim3(shape.grid), dim3(256), shape.words * 4, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), A, n_locs,
+                       d_loc_cls, Z, X, O);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }

@@ -35,26 +35,16 @@ __device__ __forceinline__ uint32_t soft_bin(const SoftArgs &A, uint32_t u) {
     return b;                  // <= 2K - 1: a slot counts in `zero` or in a compare, never both
 }
 
-// One workgroup per trial (grid-stride), shaped like circuit_sample_kernel.  LDS (uint32 words): both sectors' detector bit sets, the two logical
-// accumulators.  loc_cls holds ceil(n_locs / 4) words (the op codes of a Philox block, zero padded); meas_rank[l] is read for MeasX / MeasZ
-// locations only and is their rank 0 .. n_meas - 1, so a level lands inside its row; every signature index is bounded by l < n_locs.
+// The frame of sampler_common.h with nothing behind its words.  loc_cls holds ceil(n_locs / 4) words (the op codes of a Philox block, zero padded);
+// meas_rank[l] is read for MeasX / MeasZ locations only and is their rank 0 .. n_meas - 1, so a level lands inside its row; every signature index is
+// bounded by l < n_locs.
 __global__ __launch_bounds__(256) void soft_sample_kernel(int64_t B, int64_t trial_begin, uint32_t seed_lo, uint32_t seed_hi, uint32_t thr, SoftArgs A, int n_locs,
                                                           const uint8_t *__restrict__ loc_type, const uint32_t *__restrict__ loc_cls,
-                                                          const int32_t *__restrict__ meas_rank, int n_meas, SigTab Z, SigTab X, int nsx, int nsz,
-                                                          int8_t *__restrict__ syn_z, int8_t *__restrict__ syn_x, unsigned long long *__restrict__ true_z,
-                                                          unsigned long long *__restrict__ true_x, uint8_t *__restrict__ levels,
-                                                          int32_t *__restrict__ fail_counts) {
+                                                          const int32_t *__restrict__ meas_rank, int n_meas, SigTab Z, SigTab X, SampleOut O,
+                                                          uint8_t *__restrict__ levels) {
     extern __shared__ uint32_t sm[];
-    if (fail_counts && blockIdx.x == 0 && threadIdx.x < 8) fail_counts[threadIdx.x] = 0;      // as circuit_sample_kernel: the batch's BP failure counters
-    const int wz = (nsx + 31) >> 5, wx = (nsz + 31) >> 5;
-    uint32_t *bz = sm, *bx = sm + wz;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(sm + ((wz + wx + 1) & ~1));
     const int nblk = (n_locs + 3) >> 2;
-    for (int64_t t = blockIdx.x; t < B; t += gridDim.x) {
-        for (int w = threadIdx.x; w < wz + wx; w += blockDim.x) sm[w] = 0;
-        if (threadIdx.x < 2) lacc[threadIdx.x] = 0ull;
-        __syncthreads();
-        const uint64_t g = (uint64_t)(trial_begin + t);
+    sample_trials<true>(sm, B, trial_begin, O, 0, nullptr, [&](int64_t t, uint64_t g, const SampleLds &L) {
         uint8_t *rec = levels + t * (int64_t)n_meas;
         for (int blk = threadIdx.x; blk < nblk; blk += blockDim.x) {
             uint32_t o[4];
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(256) void soft_sample_kernel(int64_t B, int64_t tri
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 const int l = 4 * blk + w;
-                if (l < n_locs && o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, bz, bx, lacc);
+                if (l < n_locs && o[w] < thr) fire_location(Z, X, loc_type, g, l, seed_lo, seed_hi, L.b0, L.b1, L.lacc);
             }
             const uint32_t cls = loc_cls[blk];
             // a byte is MeasX (4) or MeasZ (5) iff byte >> 1 == 2; most blocks hold no measurement and draw no second Philox
@@ -82,17 +72,12 @@ __global__ __launch_bounds__(256) void soft_sample_kernel(int64_t B, int64_t tri
                 const int k = meas_rank[l];
                 if ((unsigned)k < (unsigned)n_meas) rec[k] = (uint8_t)(flipped ? bin : bin - A.levels);
                 if (flipped) {
-                    if (ty == C_OP_MEAS_X) xor_signature(Z, 2 * l, bz, &lacc[0]);          // component 4: Z on slot 0
-                    else xor_signature(X, 2 * l, bx, &lacc[1]);                            // component 1: X on slot 0
+                    if (ty == C_OP_MEAS_X) xor_signature(Z, 2 * l, L.b0, &L.lacc[0]);      // component 4: Z on slot 0
+                    else xor_signature(X, 2 * l, L.b1, &L.lacc[1]);                        // component 1: X on slot 0
                 }
             }
         }
-        __syncthreads();
-        for (int i = threadIdx.x; i < nsx; i += blockDim.x) syn_z[t * nsx + i] = (bz[i >> 5] >> (i & 31)) & 1;
-        for (int i = threadIdx.x; i < nsz; i += blockDim.x) syn_x[t * nsz + i] = (bx[i >> 5] >> (i & 31)) & 1;
-        if (threadIdx.x == 0) { true_z[t] = lacc[0]; true_x[t] = lacc[1]; }
-        __syncthreads();
-    }
+    });
 }
 
 // One workgroup per shot (grid-stride).  LDS: ceil(n / 2) uint32 words of 16-bit counters, column j in half j & 1 of word j >> 1 (the host checks
@@ -161,8 +146,8 @@ int soft_readout_check(int levels, const double *flip_mass, const double *keep_m
 }
 
 int soft_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, uint32_t thr, const SoftReadoutHost &R, int n_locs, const uint8_t *d_loc_type,
-                       const uint32_t *d_loc_cls, const int32_t *d_meas_rank, int n_meas, const SigTab &Z, const SigTab &X, int nsx, int nsz, int8_t *d_syn_z,
-                       int8_t *d_syn_x, unsigned long long *d_true_z, unsigned long long *d_true_x, uint8_t *d_levels, int32_t *d_fail_counts, hipStream_t s) {
+                       const uint32_t *d_loc_cls, const int32_t *d_meas_rank, int n_meas, const SigTab &Z, const SigTab &X, const SampleOut &O, uint8_t *d_levels,
+                       hipStream_t s) {
     if (B <= 0) return QLDPC_OK;
     SoftArgs A{};
     A.levels = (uint32_t)R.levels;
@@ -171,11 +156,9 @@ int soft_sample_launch(int64_t B, int64_t trial_begin, uint64_t seed, uint32_t t
         A.zero += cut == 0;
         A.cm1[i] = (uint32_t)(cut - 1);                          // (0 - 1 wraps to 0xFFFFFFFF; 2^32 - 1 is 0xFFFFFFFF too)
     }
-    const int wz = (nsx + 31) / 32, wx = (nsz + 31) / 32;
-    const size_t lds = (size_t)((wz + wx + 1) & ~1) * 4 + 16;      // as circuit_sample_kernel's launch
-    const unsigned grid = (unsigned)std::min<int64_t>(B, 256 * 16);
-    hipLaunchKernelGGL(soft_sample_kernel, dim3(grid), dim3(256), lds, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), thr, A, n_locs, d_loc_type,
-                       d_loc_cls, d_meas_rank, n_meas, Z, X, nsx, nsz, d_syn_z, d_syn_x, d_true_z, d_true_x, d_levels, d_fail_counts);
+    const SampleShape shape = sample_shape(O.n0, O.n1, O.two, B);
+    hipLaunchKernelGGL(soft_sample_kernel, dim3(shape.grid), dim3(256), shape.words * 4, s, B, trial_begin, (uint32_t)seed, (uint32_t)(seed >> 32), thr, A, n_locs,
+                       d_loc_type, d_loc_cls, d_meas_rank, n_meas, Z, X, O, d_levels);
     QLDPC_HIP_TRY(hipGetLastError());
     return QLDPC_OK;
 }

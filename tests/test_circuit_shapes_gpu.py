@@ -238,6 +238,48 @@ def test_batch_size_does_not_matter(L):
         q.close()
 
 
+SEVERAL = 2 * 4096 + 37               # a launch has at most 4096 workgroups: in one batch of this size they run three trials each, some two
+
+
+@pytest.mark.parametrize("which", ["plain", "erasure", "noise", "soft"])
+def test_workgroup_runs_several_trials(L, which):
+    """shor (1 + 2 words of detector bits: the pad before the accumulators is in play), the four samplers the tests above pin with one trial per
+    workgroup only: one batch of SEVERAL trials, where a workgroup zeroes its LDS between its trials, against batches of 1024, where none has to --
+    every output bit for bit, the herald words and the levels included; the first 40 trials against the expected output of the tests above"""
+    from qldpc_amd.simulation.noise_model import NoiseModel
+    name = "shor"
+    S, sigs, M, graphs, priors, masks, plan = setup(L, name)
+
+    def draw(batch):
+        q = plan(TC.P_LOW if which in ("plain", "noise") else TC.P_HIGH[name], batch=batch)
+        if which == "erasure":
+            q.use_erasure_noise(TC.ERASURE_RATES)
+            out = q.sample_erasures(SEED, 0, SEVERAL)
+        elif which == "soft":
+            q.use_soft_readout(channels()["gaussian"])
+            out = q.sample_soft(SEED, 0, SEVERAL)
+        else:
+            if which == "noise":
+                q.use_noise_model(NoiseModel(TC.NOISE_RATES, idle_weights=TC.NOISE_IDLE_W, cnot_weights=TC.NOISE_CNOT_W))
+            out = q.sample(SEED, 0, SEVERAL)
+        q.close()
+        return tuple(out)
+
+    one_batch = draw(SEVERAL)
+    assert_same(one_batch, draw(1024), f"{which}: one batch of {SEVERAL} against batches of 1024")
+    if which == "plain":
+        want = TC.literal_samples(name, TC.P_LOW, 0)
+    elif which == "erasure":
+        *want, werased = TC.expected(name, "erasure")
+        want.append(EM.pack_heralds(werased))
+    elif which == "noise":
+        want = TC.expected(name, "noise")[0]
+    else:
+        want = TC.expected(name, "soft", "gaussian")[:5]
+    assert_same(tuple(a[:40] for a in one_batch), tuple(w[:40] for w in want), f"{which}: the first 40 trials")
+    assert all(a[4096:].any() for a in one_batch), which                   # the second and third trials of the workgroups are not all zeros
+
+
 # ---------------------------------------------------------------------------------------- 4. host table builders and the aware paths
 def aware_setup(L, name):
     """setup plus, once: the erasure tables, the soft tables and marginal priors of the gaussian channel, the links of both modes -- all from the
